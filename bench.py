@@ -10,8 +10,8 @@ random_fasta_generator.py:5-15, seeded re-creation kmc_synth_*, resident in HBM 
   N == 1   config 3, the one the metric is quoted on: 10 GB, seed 2, k = 31, canonical.
   N  > 1   config 4 AS STATED: ONE 50 GB file, seed 3, k = 31, its records split over the N GPUs (records are the
            reference's unit of work, k-mer-count/src/main.rs:58-62,73-75), per-GPU count tables reduced over RCCL:
-           "scaling": "strong".  The weak-scaling figure (10 GB per GPU, seed 2 -- config 3 on every rank) is measured
-           right after it and reported in the same line as `weak_scaling`.
+           "scaling": "strong".  With --full the weak-scaling figure (10 GB per GPU, seed 2 -- config 3 on every rank)
+           is measured right after it and reported in the same line as `weak_scaling`.
   --fasta-bytes B (per GPU, weak) or --total-fasta-bytes B (strong) select one workload explicitly.
 One "step" = one pass of the hot path over the resident batch: reset the count table, count every k-mer (HIP
 kernel), compact + sort the table on the device; with N > 1 the per-GPU tables are reduced over RCCL first
@@ -19,10 +19,18 @@ kernel), compact + sort the table on the device; with N > 1 the per-GPU tables a
 data-path collective while counting.
 
 Prints ONE JSON line on rank 0.  `roofline` prices the dominant (count) kernel: algorithmic bytes per launch
-(n_bases + 8*(n_reads+1)) / its hipEvent-measured duration, against the nominal 8 TB/s HBM peak AND
-against the streaming-read rate measured in this run by a plain read-only kernel over the same bytes
-(kmc_read_peak_device).  `cpu_baseline` times the CPU oracle (a port of the reference's algorithm; the Rust reference
-cannot be built here) on a bounded sample, rank 0 at N=1 only.
+(n_bases + 8*(n_reads+1)) / its hipEvent-measured duration, against the nominal 8 TB/s HBM peak.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what the headline figure does not
+need: the streaming-read rate of a plain read-only kernel over the same bytes (kmc_read_peak_device) next to the
+nominal peak, the cold-memo steps, the exact full-size table check against the analytic oracle, `cpu_baseline` (the
+CPU oracle, a port of the reference's algorithm, on a bounded sample, rank 0 at N=1 only) and, at N > 1 with no size
+flag, the weak-scaling figure.
+
+--dump-outputs DIR writes the sorted table of the last timed step (at N > 1: each rank's owned partition, file names
+prefixed rank<r>_) as float64 .npy files: the 64-bit keys split into exact 32-bit halves, the counts, the table
+row of each entry and [n_distinct, n_total]; a table of more than DUMP_MAX_ROWS entries is represented by a fixed,
+seeded sample of its rows.
 """
 import argparse
 import glob
@@ -63,6 +71,11 @@ def main():
                          "(kmc_finalize_async: the sorted table is produced on the device each step).  1: synchronise every step")
     ap.add_argument("--no-exact-check", action="store_true", help="skip the exact full-size table check after the timed region")
     ap.add_argument("--cpu-sample-records", type=int, default=5_000_000, help="bounded CPU-baseline sample (~10-15 s of one core)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: measured read peak, cold-memo steps, "
+                         "exact full-size check, CPU baseline, the N>1 weak-scaling figure (the --no-* options above select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the sorted table of the last timed step to DIR/<name>.npy (float64)")
     args = ap.parse_args()
 
     import torch
@@ -163,7 +176,8 @@ def main():
             return nd
 
         # the plain read kernel runs once in front of everything (it also brings a fresh box's clocks up: on some boxes of the
-        # pool the first ~40 ms of work run 3-5 % slower, more than five warm-up steps cover) and again behind the timed region
+        # pool the first ~40 ms of work run 3-5 % slower, more than five warm-up steps cover), so it is part of every run's
+        # warm-up; with --full it runs again behind the timed region and the faster of the two rates is reported
         nb16 = (n_bases // 16) * 16
 
         def read_peak(best):
@@ -196,11 +210,13 @@ def main():
         n_l = max(int(s1.launches_lifetime - s0.launches_lifetime), 1)
         k_ms = (s1.kernel_ms_lifetime - s0.kernel_ms_lifetime) / args.steps
         algo_used = {1: "stream", 2: "walk", 3: "sort"}.get(s1.algo_last, "?")
+        if args.dump_outputs and first_run:
+            dump_outputs(owner if world > 1 else kc, args.dump_outputs, "rank%d_" % rank if world > 1 else "")
         # Outside the timed region, for transparency: the same step with the walk kernel's memo dropped
         # first (kmc_forget_source).  The memo is graph STRUCTURE learned from earlier launches (no
         # counts); timed steps reuse it, as every batch after the first of a real file does.
         cold_ms = []
-        if algo_used == "walk" and not args.no_cold and first_run:
+        if args.full and algo_used == "walk" and not args.no_cold and first_run:
             for _ in range(3):
                 kc.forget_source(memo=True, history=False)
                 step(0, True)
@@ -211,7 +227,7 @@ def main():
         # exact table of its whole record range (line / adjacent-pair histograms over ALL records expanded
         # through the pool; a few seconds of host time at 22 M records) -- not a prefix, not a bound.
         exact_full = None
-        if args.pool > 0 and not args.no_exact_check:
+        if args.full and args.pool > 0 and not args.no_exact_check:
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             import analytic_oracle  # test infrastructure, used here only as the checker
             tx = time.perf_counter()
@@ -233,7 +249,7 @@ def main():
                 raise SystemExit(f"reduce mismatch: owners hold {reduced['kmers_all_owners']} k-mers, expected {n_kmers_all}")
         # ---- the streaming-read rate this GPU reaches on these very bytes (plain read-only kernel, no product code) ----
         peak = None
-        if not args.no_read_peak and first_run:
+        if args.full and not args.no_read_peak and first_run:
             best = read_peak(best_before)
             peak = {"GBps": round(best[0], 1), "ms": round(best[2], 4), "bytes": nb16, "kernel": "kmc_read_peak_kernel, " + PEAK_SHAPES[best[1]],
                     "how": "nt dwordx4 loads + xor-reduce over the resident batch, best of 4 grid shapes, 5 launches each after a warm-up, one hipEvent pair; "
@@ -255,7 +271,7 @@ def main():
         main_cfg = dict(seed=args.seed if args.seed is not None else 3, strong=True, size_bytes=50e9)
     m = measure(first_run=True, **main_cfg)
     weak = None
-    if world > 1 and not explicit and not args.no_weak:
+    if args.full and world > 1 and not explicit and not args.no_weak:
         weak = measure(first_run=False, seed=2, strong=False, size_bytes=10e9)
 
     # ---- roofline of the dominant kernel (this rank's launches; every rank runs the same shape) --
@@ -300,7 +316,7 @@ def main():
 
     # ---- CPU baseline: the oracle (port of the reference's algorithm), bounded sample ----------
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_py  # the checker/baseline, never the product
         synth, first, read_len = m["synth"], m["first"], m["read_len"]
@@ -403,6 +419,41 @@ PEAK_SHAPES = {0: "256 x 1024 threads (the walk kernel's grid), 5 x 16 B loads i
 SORT_MODEL_KEY_UNITS = 8
 SORT_MODEL_TEXT = ("extraction writes one key per base position (its level-0 histogram is built on the way); level 0: scatter read + write; "
                    "level 1: histogram read + scatter read + write; leaves: read, (key, count) pairs written in place")
+
+
+DUMP_MAX_ROWS = 1_000_000   # 7 float64 arrays of at most this many entries: 56 MB
+DUMP_SEED = 20240611
+
+
+def dump_outputs(ctx, out_dir, prefix=""):
+    """The sorted table ctx holds (what a caller of the timed path receives) as float64 .npy files under out_dir.
+    64-bit keys are split into 32-bit halves so that float64 holds them exactly; counts are far below 2**53.  Rows
+    are taken on the device, so a large table is never copied to the host whole."""
+    import torch
+    kdist = importlib.import_module("k-mer-count_amd.distributed")
+    nd, nt = ctx.finalize()
+    d_hi, d_lo, d_cnt, n = ctx.export_device()
+    assert n == nd, (n, nd)
+    if nd > DUMP_MAX_ROWS:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(nd, DUMP_MAX_ROWS, replace=False)).astype(np.int64)
+    else:
+        rows = np.arange(nd, dtype=np.int64)
+    dev = torch.device("cuda", ctx.device) if ctx.device >= 0 else torch.device("cpu")   # (cpu: host stand-in of the tests)
+    idx = torch.from_numpy(rows).to(dev)
+
+    def take(ptr):
+        if not ptr:   # key_hi is not kept for k <= 32 (it is 0)
+            return np.zeros(len(rows), np.uint64)
+        return kdist.device_view(ptr, nd, dev).index_select(0, idx).cpu().numpy().view(np.uint64)
+
+    hi, lo, cnt = take(d_hi), take(d_lo), take(d_cnt)
+    m32 = np.uint64(0xFFFFFFFF)
+    arrays = {"key_hi_upper32": hi >> np.uint64(32), "key_hi_lower32": hi & m32,
+              "key_lo_upper32": lo >> np.uint64(32), "key_lo_lower32": lo & m32,
+              "count": cnt, "row": rows, "sizes": np.array([nd, nt], np.uint64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a.astype(np.float64))
 
 
 if __name__ == "__main__":

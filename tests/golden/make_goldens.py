@@ -2,8 +2,11 @@
 """Generates the golden fixtures under tests/golden/ -- and, with --check, proves that the committed
 ones are exactly what this script produces.
 
-    python tests/golden/make_goldens.py           # (re)write lr_goldens.json, g1_expected.txt.gz, kat.json
-    python tests/golden/make_goldens.py --check   # regenerate in memory, compare byte for byte, exit 1 on any difference
+    python tests/golden/make_goldens.py --reference DIR           # (re)write lr_goldens.json, g1_expected.txt.gz, kat.json
+    python tests/golden/make_goldens.py --reference DIR --check   # regenerate in memory, compare byte for byte, exit 1 on any difference
+
+DIR is a checkout of the reference project (its test.py and k-mer-count/sample.fasta).  Without --reference only
+kat.json is regenerated, and --check compares the committed G-1 output bytes with their digest in lr_goldens.json.
 
 What is generated from what -- nothing below is produced by this repo's product code or by its C oracle:
 
@@ -22,7 +25,7 @@ What is generated from what -- nothing below is produced by this repo's product 
   "parity unpinned" -- every LR fixture is well-formed, LF-terminated, upper-case ACGT.
   G-1's full expected output (17,751 lines) is committed as bytes (gzip, mtime 0), so one fixture is
   the reference's output itself and not only its digest.
-  This part needs /root/reference and is skipped (with a message) where that does not exist.
+  This part needs the reference (--reference DIR) and is skipped (with a message) without it.
 * kat.json -- known answers for CONTIGUOUS k (the reference has no k, no canonical
   strand and no count table, so these are definition-derived and "parity unpinned" by the reference)
   from an independent pure-Python probe (function kat_probe below: str slicing + dict counting on the
@@ -42,9 +45,7 @@ import tempfile
 import types
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF_ROOT = "/root/reference"
-REF_TEST_PY = os.path.join(REF_ROOT, "test.py")
-REF_SAMPLE = os.path.join(REF_ROOT, "k-mer-count", "sample.fasta")
+REF_TEST_PY = REF_SAMPLE = None   # set from --reference DIR
 SAMPLE = os.path.join(HERE, "sample.fasta")
 SAMPLE_SHA256 = "e4cccec3a83f90a380d18be975c1996460c86cdba014128b8f0b8db441ed1895"
 
@@ -243,16 +244,27 @@ def _gz_bytes(data):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--check", action="store_true", help="regenerate in memory and compare with the committed files")
+    ap.add_argument("--reference", metavar="DIR", default=None, help="checkout of the reference project (for the LR goldens)")
     args = ap.parse_args()
+    global REF_TEST_PY, REF_SAMPLE
     assert hashlib.sha256(open(SAMPLE, "rb").read()).hexdigest() == SAMPLE_SHA256
     products = {KAT_JSON: _json_bytes(generate_kat())}
-    if os.path.exists(REF_TEST_PY):
+    bad = 0
+    if args.reference:
+        REF_TEST_PY = os.path.join(args.reference, "test.py")
+        REF_SAMPLE = os.path.join(args.reference, "k-mer-count", "sample.fasta")
         lr, g1 = generate_lr()
         products[LR_JSON] = _json_bytes(lr)
         products[G1_GZ] = _gz_bytes(g1)
     else:
-        print(f"note: {REF_TEST_PY} not present -- LR goldens not regenerated (they need the reference)")
-    bad = 0
+        print("note: no --reference -- LR goldens not regenerated (they need the reference)")
+        if args.check:
+            # what needs no reference: the committed G-1 output bytes are the ones lr_goldens.json describes
+            want = json.load(open(LR_JSON))["cases"]["G-1"]
+            have = _describe(gzip.decompress(open(G1_GZ, "rb").read()), with_extremes=False)
+            same = all(want[key] == have[key] for key in have)
+            print(("ok       " if same else "DIFFERS  ") + os.path.relpath(G1_GZ, HERE) + " (against lr_goldens.json G-1)")
+            bad += 0 if same else 1
     for path, data in products.items():
         if args.check:
             have = open(path, "rb").read() if os.path.exists(path) else None

@@ -1,5 +1,7 @@
 """The bench.py output contract, checked on the committed lines of the last GPU runs (profiles/r03_bench_n1.json and the
-N > 1 rehearsal lines next to it): the keys and types the driver and the judge read."""
+N > 1 rehearsal lines next to it): the keys and types the driver and the judge read.  Those lines hold what
+`bench.py --full` prints (measured read peak, cpu_baseline, exact full-size check); a plain run prints the same keys with
+those figures null or absent.  Below: --dump-outputs, on a host stand-in of a counter ctx."""
 import json
 import os
 
@@ -59,3 +61,72 @@ def test_sort_path_line_prices_its_own_pipeline():
     assert line["config"]["algo"] == "sort" and sp["key_units_per_kmer"] == 8 and 0 < sp["frac"] < 1
     n_bases, n_kmers = line["config"]["bases_per_gpu"], line["config"]["kmers_per_gpu"]
     assert sp["model_bytes_per_step"] == (n_bases + 8 * n_kmers) * 8
+
+
+class _HostTable:
+    """Stand-in for a counter ctx whose sorted table lives in host memory (device -1: distributed.device_view reads host
+    addresses), enough for bench.dump_outputs."""
+
+    def __init__(self, hi, lo, cnt):
+        self.device, self.hi, self.lo, self.cnt = -1, hi, lo, cnt
+
+    def finalize(self):
+        return len(self.lo), int(self.cnt.sum())
+
+    def export_device(self):
+        return (self.hi.ctypes.data if self.hi is not None else 0), self.lo.ctypes.data, self.cnt.ctypes.data, len(self.lo)
+
+
+def _table(n, seed, with_hi):
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    lo = np.sort(rng.integers(0, 2**64, n, dtype=np.uint64, endpoint=False))
+    hi = rng.integers(0, 2**62, n, dtype=np.uint64) if with_hi else None
+    cnt = rng.integers(1, 2**32, n, dtype=np.uint64)
+    return hi, lo, cnt
+
+
+def _load(d, prefix=""):
+    import numpy as np
+    out = {}
+    for name in ("key_hi_upper32", "key_hi_lower32", "key_lo_upper32", "key_lo_lower32", "count", "row", "sizes"):
+        a = np.load(os.path.join(d, prefix + name + ".npy"))
+        assert a.dtype == np.float64, name
+        out[name] = a
+    return out
+
+
+def test_dump_outputs_holds_the_table_exactly(tmp_path):
+    """--dump-outputs: float64 files from which every key and count of the table comes back bit for bit."""
+    import numpy as np
+    import bench
+    for with_hi in (False, True):
+        hi, lo, cnt = _table(5000, 1, with_hi)
+        d = tmp_path / ("hi" if with_hi else "lo")
+        bench.dump_outputs(_HostTable(hi, lo, cnt), str(d), prefix="rank0_")
+        o = _load(str(d), "rank0_")
+        u = lambda a: a.astype(np.uint64)
+        assert np.array_equal((u(o["key_lo_upper32"]) << np.uint64(32)) | u(o["key_lo_lower32"]), lo)
+        want_hi = hi if with_hi else np.zeros_like(lo)
+        assert np.array_equal((u(o["key_hi_upper32"]) << np.uint64(32)) | u(o["key_hi_lower32"]), want_hi)
+        assert np.array_equal(u(o["count"]), cnt) and np.array_equal(o["row"], np.arange(5000))
+        assert o["sizes"].tolist() == [5000, float(cnt.sum())]
+
+
+def test_dump_outputs_samples_a_large_table_the_same_way_every_time(tmp_path, monkeypatch):
+    import numpy as np
+    import bench
+    assert 7 * 8 * bench.DUMP_MAX_ROWS + 16 <= 64 * 2**20   # the files stay under 64 MB in all, whatever the table's size
+    monkeypatch.setattr(bench, "DUMP_MAX_ROWS", 300)
+    hi, lo, cnt = _table(20000, 2, True)
+    got = []
+    for i in range(2):
+        bench.dump_outputs(_HostTable(hi, lo, cnt), str(tmp_path / str(i)))
+        got.append(_load(str(tmp_path / str(i))))
+    rows = got[0]["row"].astype(np.int64)
+    assert len(rows) == 300 and np.all(np.diff(rows) > 0) and rows[-1] < 20000
+    for name in got[0]:
+        assert np.array_equal(got[0][name], got[1][name]), name
+    assert np.array_equal(got[0]["count"].astype(np.uint64), cnt[rows])
+    assert np.array_equal((got[0]["key_lo_upper32"].astype(np.uint64) << np.uint64(32)) | got[0]["key_lo_lower32"].astype(np.uint64), lo[rows])
+    assert got[0]["sizes"].tolist() == [20000, float(cnt.sum())]

@@ -121,16 +121,15 @@ def test_parser_semantics(oracle, tmp_path):
 
 
 def test_goldens_are_regenerated_byte_identically():
-    """tests/golden/make_goldens.py --check: the committed lr_goldens.json / g1_expected.txt.gz are what
-    the reference's own test.py prints when executed in place (needs /root/reference: present in the
-    build container, absent on the GPU box -- there only kat.json, which needs nothing but the
-    committed fixture, is regenerated and compared)."""
+    """tests/golden/make_goldens.py --check with nothing but the repository: kat.json, which needs only the
+    committed fixture, is regenerated and compared byte for byte, and the committed G-1 output bytes are
+    the ones lr_goldens.json describes.  (Regenerating the LR goldens themselves needs a checkout of the
+    reference: make_goldens.py --reference DIR --check.)"""
     import sys
     r = subprocess.run([sys.executable, os.path.join(GOLDEN, "make_goldens.py"), "--check"], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "ok       kat.json" in r.stdout
-    if os.path.exists("/root/reference/test.py"):
-        assert "ok       lr_goldens.json" in r.stdout and "ok       g1_expected.txt.gz" in r.stdout
+    assert "ok       g1_expected.txt.gz (against lr_goldens.json G-1)" in r.stdout
 
 
 def test_lr_mode_reproduces_the_references_g1_output_bytes(oracle, tmp_path):

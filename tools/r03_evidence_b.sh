@@ -7,7 +7,7 @@ bash tools/profile_bench.sh r03_walk > gpurun_out/prof_r03_walk.log 2>&1; echo "
 bash tools/profile_bench.sh r03_sort --pool 0 --fasta-bytes 1e9 --no-exact-check --no-read-peak > gpurun_out/prof_r03_sort.log 2>&1; echo "sort prof rc=$?"
 o=gpurun_out/ev3b; mkdir -p $o
 rocprofv3 --kernel-trace --stats --output-format csv -d $o/stream -- python3 bench.py --algo stream --steps 5 --warmup 3 --no-cpu-baseline --no-cold --no-exact-check --no-read-peak > $o/stream.log 2>&1; echo "stream trace rc=$?"
-rocprofv3 --kernel-trace --stats --output-format csv -d $o/peak -- python3 bench.py --steps 3 --warmup 3 --no-cpu-baseline --no-cold --no-exact-check > $o/peak.log 2>&1; echo "peak trace rc=$?"
+rocprofv3 --kernel-trace --stats --output-format csv -d $o/peak -- python3 bench.py --full --steps 3 --warmup 3 --no-cpu-baseline --no-cold --no-exact-check > $o/peak.log 2>&1; echo "peak trace rc=$?"
 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $o/step -- python3 bench.py --steps 6 --warmup 4 --no-cpu-baseline --no-cold --no-exact-check --no-read-peak > /dev/null 2> $o/step.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $o/p50 -- python3 tools/pool_sweep.py --fasta-bytes 1e9 --pools 50 --ks 31 --steps 4 > /dev/null 2> /dev/null
 rocprofv3 --kernel-trace --stats --output-format csv -d $o/p20k63 -- python3 tools/pool_sweep.py --fasta-bytes 1e9 --pools 20 --ks 63 --steps 4 > /dev/null 2> /dev/null

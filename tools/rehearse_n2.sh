@@ -5,4 +5,4 @@
 # about RCCL.  usage: tools/rehearse_n2.sh [bench args]
 cd ${GRAFT_REPO_ROOT:-$(pwd)}
 KMC_BENCH_BACKEND=gloo python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 \
-  bench.py --gpus 2 --steps 5 --warmup 3 --fasta-bytes 2e9 "$@"
+  bench.py --full --gpus 2 --steps 5 --warmup 3 --fasta-bytes 2e9 "$@"
