@@ -16,6 +16,8 @@
  *   iteration over the sorted result, main.rs:88-90       kmc_export (sorted ascending)
  *   File::open + Reader + loop, main.rs:44-46,58-62       kmc_count_file (convenience; host parser)
  *   random_fasta_generator.py:5-15                        kmc_synth_* (seeded, sized re-creation)
+ *   (addition: no equivalent in the reference)             kmc_histogram (abundance histogram of the view)
+ *   (addition: no equivalent in the reference)             kmc_filter_device / kmc_export_filtered (count range)
  *
  * Conventions
  *   - Every function returns 0 (KMC_OK) or a negative kmc_status; no exception or abort crosses
@@ -188,6 +190,30 @@ int kmc_export_device(kmc_ctx* ctx, const void** d_key_hi, const void** d_key_lo
 int kmc_partition_device(kmc_ctx* ctx, uint32_t n_parts, uint64_t* part_begin,
                          const void** d_key_hi, const void** d_key_lo, const void** d_count);
 uint32_t kmc_owner_of(uint64_t key_hi, uint64_t key_lo, uint32_t n_parts);
+
+/* ---- what comes after counting (additions: the reference prints its whole table, main.rs:88-90) ----
+ * All three read the sorted view of the last kmc_finalize (a view queued by kmc_finalize_async counts as one) and
+ * change neither it nor a kmc_partition_device result.  A NULL ctx is KMC_ERR_ARG, no view KMC_ERR_STATE, a non-zero
+ * max_count below min_count KMC_ERR_ARG; an empty view gives zeros. */
+
+/* Abundance histogram of the sorted view (after kmc_finalize): for 0 <= c < n_bins-1, hist[c] = number of keys with
+ * count == c; hist[n_bins-1] = number with count >= n_bins-1 (hist[0] is always 0).  Only keys with
+ * min_count <= count <= max_count are counted (max_count 0 = no upper bound).  *max_seen (may be NULL) = largest
+ * count in range, 0 if none.  2 <= n_bins <= 2^24. */
+int kmc_histogram(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, uint32_t n_bins, uint64_t* hist, uint64_t* max_seen);
+
+/* Keys of the sorted view with min_count <= count <= max_count (max_count 0 = no upper bound), in view order, in
+ * ctx-owned device arrays valid until the next kmc_filter_device / kmc_export_filtered / finalize / reset / destroy
+ * (same ordering contract as kmc_export_device; d_key_hi is NULL when keys fit one word).  A filter that keeps
+ * everything (min_count <= 1, max_count 0) launches nothing and returns the kmc_export_device pointers.
+ * *n_kept / *kept_total (may be NULL) = entries kept and the sum of their counts. */
+int kmc_filter_device(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, const void** d_key_hi,
+                      const void** d_key_lo, const void** d_count, uint64_t* n_kept, uint64_t* kept_total);
+
+/* The same, copied to caller arrays of `cap` entries (key_hi may be NULL if the caller knows k <= 32).  *n_kept is
+ * always set; cap < *n_kept -> KMC_ERR_ARG and nothing is copied (call with cap 0 and NULL arrays to size the buffers). */
+int kmc_export_filtered(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, uint64_t* key_hi, uint64_t* key_lo,
+                        uint64_t* count, uint64_t cap, uint64_t* n_kept);
 
 /* Multi-GPU reduce for small tables: ONE fixed-size all-gather instead of size exchange +
  * all-to-all (the reduce of main.rs:87's grouping across GPUs; for the generator's input a table is

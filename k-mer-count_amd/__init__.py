@@ -84,6 +84,7 @@ ABI_SYMBOLS = [
     "kmc_slab_words", "kmc_pack_slab_device", "kmc_merge_slabs_device", "kmc_forget_source",
     "kmc_fasta_stream_open", "kmc_fasta_stream_next", "kmc_fasta_stream_close", "kmc_poll",
     "kmc_count_file_multi", "kmc_read_pieces", "kmc_sync", "kmc_read_peak_device", "kmc_finalize_async",
+    "kmc_histogram", "kmc_filter_device", "kmc_export_filtered",
 ]
 
 _lib = None
@@ -135,6 +136,9 @@ def lib() -> C.CDLL:
     L.kmc_export.argtypes = [vp, vp, vp, vp, u64]
     L.kmc_export_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), pu64]
     L.kmc_partition_device.argtypes = [vp, u32, pu64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.kmc_histogram.argtypes = [vp, u64, u64, u32, vp, pu64]
+    L.kmc_filter_device.argtypes = [vp, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), pu64, pu64]
+    L.kmc_export_filtered.argtypes = [vp, u64, u64, vp, vp, vp, u64, pu64]
     L.kmc_owner_of.argtypes = [u64, u64, u32]
     L.kmc_owner_of.restype = u32
     L.kmc_get_stats.argtypes = [vp, C.POINTER(Stats)]
@@ -388,6 +392,36 @@ class KmerCounter:
         a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
         self._chk(self._L.kmc_partition_device(self._h, n_parts, pb, C.byref(a), C.byref(b), C.byref(c)))
         return list(pb), a.value or 0, b.value or 0, c.value or 0
+
+    # -- after counting: abundance histogram, count-range filter (of the sorted view) --
+    def histogram(self, n_bins: int = 10001, min_count: int = 1, max_count: int = 0, return_max: bool = False):
+        """Abundance histogram of the sorted view (finalize() first): uint64[n_bins], hist[c] = keys with count c for
+        c < n_bins-1, hist[n_bins-1] = keys with count >= n_bins-1; only counts in [min_count, max_count] (max_count 0:
+        no upper bound).  return_max=True: (hist, largest count in range)."""
+        h = np.zeros(int(n_bins), np.uint64)
+        mx = C.c_uint64()
+        self._chk(self._L.kmc_histogram(self._h, int(min_count), int(max_count), int(n_bins), h.ctypes.data, C.byref(mx)))
+        return (h, mx.value) if return_max else h
+
+    def filter_device(self, min_count: int, max_count: int = 0) -> Tuple[int, int, int, int, int]:
+        """(d_key_hi or 0, d_key_lo, d_count, n_kept, kept_total): the keys of the sorted view with count in
+        [min_count, max_count], in view order, in ctx-owned device arrays (kmc_filter_device)."""
+        a, b, c, n, t = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        self._chk(self._L.kmc_filter_device(self._h, int(min_count), int(max_count), C.byref(a), C.byref(b), C.byref(c), C.byref(n), C.byref(t)))
+        return a.value or 0, b.value or 0, c.value or 0, n.value, t.value
+
+    def export_filtered(self, min_count: int, max_count: int = 0) -> Table:
+        """The sorted view restricted to counts in [min_count, max_count] (max_count 0: no upper bound), on the host."""
+        n = C.c_uint64()
+        rc = self._L.kmc_export_filtered(self._h, int(min_count), int(max_count), None, None, None, 0, C.byref(n))
+        if rc not in (OK, ERR_ARG) or (rc == ERR_ARG and n.value == 0):
+            self._chk(rc)
+        nk = n.value
+        hi, lo, cnt = np.zeros(nk, np.uint64), np.zeros(nk, np.uint64), np.zeros(nk, np.uint64)
+        if nk:
+            self._chk(self._L.kmc_export_filtered(self._h, int(min_count), int(max_count), hi.ctypes.data, lo.ctypes.data,
+                                                  cnt.ctypes.data, nk, C.byref(n)))
+        return Table(hi, lo, cnt, self.k)
 
     # -- multi-GPU reduce, small tables (one fixed-size all-gather; distributed.py) --
     def slab_words(self, slab_entries: int) -> int:

@@ -34,6 +34,7 @@
 #include "kmc_msd.hip.h"
 #include "kmc_extract.hip.h"
 #include "kmc_peak.hip.h"
+#include "kmc_spectrum.hip.h"
 #include "kmc_ingest.h"
 
 namespace {
@@ -171,6 +172,9 @@ struct kmc_ctx {
     bool sk_fixed = false;   // its size was set by KMC_SK_SLOTS (tests): never re-allocated
     bool sk_grow = false;    // a poll found it more than half full: re-allocate larger when it is next empty
     DevBuf rx_hi, rx_lo, rx_cnt;  // receive buffers of the one-process multi-GPU reduce (a peer's sorted table)
+    // kmc_filter_device's result (its own buffers: a filter leaves the view and a partition the caller holds alone), the
+    // per-tile kept counts and their scan, [n_kept | kept_total]; kmc_histogram's device histogram + max
+    DevBuf f_hi, f_lo, f_cnt, f_tile, f_tpos, f_bsum, f_ctl, h_hist;
 };
 
 namespace {
@@ -1655,7 +1659,8 @@ extern "C" void kmc_destroy(kmc_ctx* c) {
                       &c->lg_rec, &c->lg_count, &c->lg_bins, &c->lg_cursor,
                       &c->m_hist, &c->m_stot, &c->m_bsum, &c->m_rmin, &c->m_rmax, &c->m_seg[0], &c->m_seg[1], &c->m_first, &c->m_cbase, &c->m_skip, &c->m_term, &c->m_ord,
                       &c->m_bitmap, &c->m_rank, &c->m_nd, &c->m_base, &c->m_ctl, &c->m_clist, &c->m_w[0], &c->m_w[1],
-                      &c->snap_hi, &c->snap_lo, &c->snap_cnt, &c->snap_n, &c->snap_occ, &c->rx_hi, &c->rx_lo, &c->rx_cnt};
+                      &c->snap_hi, &c->snap_lo, &c->snap_cnt, &c->snap_n, &c->snap_occ, &c->rx_hi, &c->rx_lo, &c->rx_cnt,
+                      &c->f_hi, &c->f_lo, &c->f_cnt, &c->f_tile, &c->f_tpos, &c->f_bsum, &c->f_ctl, &c->h_hist};
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
     sk_free(c);
     try { free_runs(c, true); } catch (...) { /* (only the pool bookkeeping can throw; the buffers it could not list leak with the process) */ }
@@ -2094,6 +2099,165 @@ static int kmc_partition_device_impl(kmc_ctx* c, uint32_t n_parts, uint64_t* par
     if (d_key_hi) *d_key_hi = c->KW == 2 ? c->p_hi.p : nullptr;
     if (d_key_lo) *d_key_lo = c->p_lo.p;
     if (d_count) *d_count = c->p_cnt.p;
+    return KMC_OK;
+}
+
+// ---- abundance histogram and count-range filter of the sorted view (kmc_spectrum.hip.h) ----
+// What the three calls share: a queued finalize counts as one (resolve_async), a sane range, a view to read.
+static int spectrum_begin(kmc_ctx* c, const char* what, uint64_t min_count, uint64_t max_count) {
+    int rc = resolve_async(c);
+    if (rc) return rc;
+    if (max_count && min_count > max_count)
+        return fail(c, KMC_ERR_ARG, "%s: min_count %llu > max_count %llu", what, (unsigned long long)min_count, (unsigned long long)max_count);
+    if (!c->sorted_valid) return fail(c, KMC_ERR_STATE, "%s before kmc_finalize", what);
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    return KMC_OK;
+}
+
+static bool filter_is_identity(uint64_t min_count, uint64_t max_count) { return min_count <= 1 && max_count == 0; }
+
+static int kmc_histogram_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint32_t n_bins, uint64_t* hist, uint64_t* max_seen) {
+    if (!c) return KMC_ERR_ARG;
+    int rc = spectrum_begin(c, "kmc_histogram", min_count, max_count);
+    if (rc) return rc;
+    if (n_bins < 2 || n_bins > (1u << 24)) return fail(c, KMC_ERR_ARG, "kmc_histogram: n_bins %u outside 2..2^24", n_bins);
+    if (!hist) return fail(c, KMC_ERR_ARG, "kmc_histogram: null histogram");
+    const u64 n = c->n_sorted;
+    if (!n) {
+        memset(hist, 0, (size_t)n_bins * sizeof(u64));
+        if (max_seen) *max_seen = 0;
+        return KMC_OK;
+    }
+    rc = ensure(c, c->h_hist, ((size_t)n_bins + 1) * sizeof(u64));   // [hist | max]
+    if (rc) return rc;
+    kmc_ull* d = (kmc_ull*)c->h_hist.p;
+    HIPCHK(c, hipMemsetAsync(d, 0, ((size_t)n_bins + 1) * sizeof(u64), c->stream));
+    const u32 lds_bins = std::min<u32>(n_bins, KMC_SPEC_LDS_BINS);
+    const u32 head = ((uintptr_t)c->v_cnt & 15) ? 1u : 0u;
+    const u64 n_pairs = (n - head) / 2;
+    // 64 KiB of LDS: two workgroups per CU (160 KiB); smaller histograms four.  No more workgroups than there are
+    // pairs for: each one clears and flushes its whole LDS part.
+    const u64 per_cu = (u64)lds_bins * sizeof(u32) > 40960 ? 2 : 4;
+    const u64 grid = std::max<u64>(1, std::min<u64>((u64)c->n_cu * per_cu, (n_pairs + 2 * KMC_SPEC_THREADS - 1) / (2 * KMC_SPEC_THREADS)));
+    hipLaunchKernelGGL(kmc_histogram_kernel, dim3((u32)grid), dim3(KMC_SPEC_THREADS), (size_t)lds_bins * sizeof(u32), c->stream,
+                       c->v_cnt, n, head, (u64)min_count, max_count ? (u64)max_count : ~0ull, n_bins, lds_bins, d, d + n_bins);
+    HIPCHK(c, hipGetLastError());
+    u64 mx = 0;
+    HIPCHK(c, hipMemcpyAsync(hist, d, (size_t)n_bins * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&mx, d + n_bins, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (max_seen) *max_seen = mx;
+    return KMC_OK;
+}
+
+// reduce half of the filter: kept entries per tile, their exclusive scan (f_tpos), n_kept and the sum of kept counts
+static int filter_count(kmc_ctx* c, u64 lo_c, u64 hi_c, u64* n_kept, u64* kept_total) {
+    const u64 n = c->n_sorted;
+    *n_kept = 0;
+    *kept_total = 0;
+    if (!n) return KMC_OK;
+    if (((uintptr_t)c->v_cnt | (uintptr_t)c->v_lo | (uintptr_t)(c->KW == 2 ? c->v_hi : nullptr)) & 15)
+        return fail(c, KMC_ERR_HIP, "internal error: sorted view not 16-byte aligned");
+    const u64 n_tiles = (n + KMC_FILT_TILE - 1) / KMC_FILT_TILE;   // (n < 2^32: at most 2^21 tiles)
+    const u32 nb = (u32)((n_tiles + KMC_SCAN_PER_BLOCK - 1) / KMC_SCAN_PER_BLOCK);
+    int rc = ensure(c, c->f_tile, (size_t)n_tiles * sizeof(u32)); if (rc) return rc;
+    rc = ensure(c, c->f_tpos, (size_t)n_tiles * sizeof(u32)); if (rc) return rc;
+    rc = ensure(c, c->f_bsum, ((size_t)nb + 2) * sizeof(u32)); if (rc) return rc;
+    rc = ensure(c, c->f_ctl, 2 * sizeof(u64)); if (rc) return rc;
+    u64* ctl = (u64*)c->f_ctl.p;   // [n_kept (u32 written by the scan, high half stays 0) | kept_total]
+    HIPCHK(c, hipMemsetAsync(ctl, 0, 2 * sizeof(u64), c->stream));
+    const u32 cgrid = (u32)std::min<u64>(n_tiles, (u64)c->n_cu * 8);
+    hipLaunchKernelGGL(kmc_filter_count_kernel, dim3(cgrid), dim3(KMC_FILT_THREADS), 0, c->stream, c->v_cnt, n, n_tiles, lo_c, hi_c,
+                       (u32*)c->f_tile.p, (kmc_ull*)(ctl + 1));
+    hipLaunchKernelGGL(kmc_scan_sums_kernel<0>, dim3(nb), dim3(256), 0, c->stream, (const void*)c->f_tile.p, (u32)n_tiles, (u32*)c->f_bsum.p);
+    hipLaunchKernelGGL(kmc_scan_top_kernel, dim3(1), dim3(1024), 0, c->stream, (u32*)c->f_bsum.p, nb, (u32*)ctl);
+    hipLaunchKernelGGL(kmc_scan_final_kernel<0>, dim3(nb), dim3(256), 0, c->stream, (const void*)c->f_tile.p, (u32)n_tiles,
+                       (const u32*)c->f_bsum.p, (u32*)c->f_tpos.p);
+    HIPCHK(c, hipGetLastError());
+    u64 h[2] = {0, 0};
+    HIPCHK(c, hipMemcpyAsync(h, ctl, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *n_kept = h[0];
+    *kept_total = h[1];
+    return KMC_OK;
+}
+
+// scatter half: the kept entries into f_hi / f_lo / f_cnt at tile base + wave offset + lane prefix (filter_count ran first);
+// finished when it returns (kmc_export_device's ordering contract)
+static int filter_scatter(kmc_ctx* c, u64 lo_c, u64 hi_c, u64 n_kept) {
+    const size_t nb = (size_t)std::max<u64>(n_kept, 1) * sizeof(u64);
+    int rc = ensure(c, c->f_lo, nb); if (rc) return rc;
+    rc = ensure(c, c->f_cnt, nb); if (rc) return rc;
+    if (c->KW == 2) { rc = ensure(c, c->f_hi, nb); if (rc) return rc; }
+    if (!n_kept) return KMC_OK;
+    const u64 n = c->n_sorted;
+    const u64 n_tiles = (n + KMC_FILT_TILE - 1) / KMC_FILT_TILE;
+    if (c->KW == 1)
+        hipLaunchKernelGGL(kmc_filter_scatter_kernel<1>, dim3((u32)n_tiles), dim3(KMC_FILT_THREADS), 0, c->stream, (const u64*)nullptr, c->v_lo, c->v_cnt,
+                           n, lo_c, hi_c, (const u32*)c->f_tpos.p, (u64*)nullptr, (u64*)c->f_lo.p, (u64*)c->f_cnt.p);
+    else
+        hipLaunchKernelGGL(kmc_filter_scatter_kernel<2>, dim3((u32)n_tiles), dim3(KMC_FILT_THREADS), 0, c->stream, c->v_hi, c->v_lo, c->v_cnt,
+                           n, lo_c, hi_c, (const u32*)c->f_tpos.p, (u64*)c->f_hi.p, (u64*)c->f_lo.p, (u64*)c->f_cnt.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return KMC_OK;
+}
+
+static int kmc_filter_device_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, const void** d_key_hi, const void** d_key_lo,
+                                  const void** d_count, uint64_t* n_kept, uint64_t* kept_total) {
+    if (!c) return KMC_ERR_ARG;
+    int rc = spectrum_begin(c, "kmc_filter_device", min_count, max_count);
+    if (rc) return rc;
+    if (filter_is_identity(min_count, max_count)) {   // keeps everything: the view itself, nothing launched
+        const void *h = nullptr, *l = nullptr, *k = nullptr;
+        uint64_t nd = 0;
+        rc = kmc_export_device_impl(c, &h, &l, &k, &nd);
+        if (rc) return rc;
+        if (d_key_hi) *d_key_hi = h;
+        if (d_key_lo) *d_key_lo = l;
+        if (d_count) *d_count = k;
+        if (n_kept) *n_kept = nd;
+        if (kept_total) *kept_total = nd ? c->st.n_kmers : 0;
+        return KMC_OK;
+    }
+    const u64 hi_c = max_count ? (u64)max_count : ~0ull;
+    u64 nk = 0, kt = 0;
+    rc = filter_count(c, min_count, hi_c, &nk, &kt);
+    if (rc) return rc;
+    rc = filter_scatter(c, min_count, hi_c, nk);
+    if (rc) return rc;
+    if (d_key_hi) *d_key_hi = c->KW == 2 ? c->f_hi.p : nullptr;
+    if (d_key_lo) *d_key_lo = c->f_lo.p;
+    if (d_count) *d_count = c->f_cnt.p;
+    if (n_kept) *n_kept = nk;
+    if (kept_total) *kept_total = kt;
+    return KMC_OK;
+}
+
+static int kmc_export_filtered_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t* key_hi, uint64_t* key_lo,
+                                    uint64_t* count, uint64_t cap, uint64_t* n_kept) {
+    if (!c) return KMC_ERR_ARG;
+    if (n_kept) *n_kept = 0;
+    int rc = spectrum_begin(c, "kmc_export_filtered", min_count, max_count);
+    if (rc) return rc;
+    const bool ident = filter_is_identity(min_count, max_count);
+    const u64 hi_c = max_count ? (u64)max_count : ~0ull;
+    u64 nk = c->n_sorted, kt = 0;
+    if (!ident) { rc = filter_count(c, min_count, hi_c, &nk, &kt); if (rc) return rc; }
+    if (n_kept) *n_kept = nk;
+    if (cap < nk) return fail(c, KMC_ERR_ARG, "kmc_export_filtered: capacity %llu < %llu kept keys", (unsigned long long)cap, (unsigned long long)nk);
+    if (!nk) return KMC_OK;
+    if (!key_lo || !count) return fail(c, KMC_ERR_ARG, "null buffer");
+    if (ident) return kmc_export_impl(c, key_hi, key_lo, count, cap);
+    rc = filter_scatter(c, min_count, hi_c, nk);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(key_lo, c->f_lo.p, nk * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(count, c->f_cnt.p, nk * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    if (key_hi) {
+        if (c->KW == 2) HIPCHK(c, hipMemcpyAsync(key_hi, c->f_hi.p, nk * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+        else memset(key_hi, 0, nk * sizeof(u64));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return KMC_OK;
 }
 
@@ -2608,6 +2772,17 @@ extern "C" int kmc_export(kmc_ctx* c, uint64_t* key_hi, uint64_t* key_lo, uint64
 }
 extern "C" int kmc_export_device(kmc_ctx* c, const void** d_key_hi, const void** d_key_lo, const void** d_count, uint64_t* n_distinct) {
     return guarded(c, [&]() -> int { return kmc_export_device_impl(c, d_key_hi, d_key_lo, d_count, n_distinct); });
+}
+extern "C" int kmc_histogram(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint32_t n_bins, uint64_t* hist, uint64_t* max_seen) {
+    return guarded(c, [&]() -> int { return kmc_histogram_impl(c, min_count, max_count, n_bins, hist, max_seen); });
+}
+extern "C" int kmc_filter_device(kmc_ctx* c, uint64_t min_count, uint64_t max_count, const void** d_key_hi, const void** d_key_lo,
+                                 const void** d_count, uint64_t* n_kept, uint64_t* kept_total) {
+    return guarded(c, [&]() -> int { return kmc_filter_device_impl(c, min_count, max_count, d_key_hi, d_key_lo, d_count, n_kept, kept_total); });
+}
+extern "C" int kmc_export_filtered(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t* key_hi, uint64_t* key_lo,
+                                   uint64_t* count, uint64_t cap, uint64_t* n_kept) {
+    return guarded(c, [&]() -> int { return kmc_export_filtered_impl(c, min_count, max_count, key_hi, key_lo, count, cap, n_kept); });
 }
 extern "C" int kmc_partition_device(kmc_ctx* c, uint32_t n_parts, uint64_t* part_begin, const void** d_key_hi,
                                     const void** d_key_lo, const void** d_count) {

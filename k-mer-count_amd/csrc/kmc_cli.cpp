@@ -5,6 +5,7 @@
 // test.py:15-18 takes the FASTA path as its only positional argument.  This tool keeps both:
 //
 //   k-mer-count [FASTA] [-k K] [--forward] [--expand] [--device N | --gpus N] [--algo auto|stream|walk|sort] [--stats]
+//               [--min-count N] [--max-count N] [--histo H]
 //
 //   --gpus N  the file's chunks go round-robin to GPUs 0..N-1 of this process, tables reduced on GPU 0
 //             (there is no CPU backend: SURVEY.md's "--backend cpu" is deliberately absent)
@@ -13,8 +14,14 @@
 //           byte-identical to main.rs:87-90
 //   -k K    count-table mode: contiguous canonical K-mers, "KMER<TAB>COUNT" lines sorted by KMER
 //
+//   --min-count N / --max-count N   only keys seen N times or more / at most N times (table mode: the lines printed;
+//                                   reference mode: the keys expanded).  Additions: the reference has no such option.
+//   --histo H   instead of the table, the abundance histogram: "COUNT<TAB>KEYS" lines, ascending, non-zero only; the line
+//               for H counts the keys seen H times or more.  The count filters apply to it too.
+//
 // Errors: message on stderr, exit code 101 (what a Rust panic exits with), never partial stdout.
 #include <errno.h>
+#include <limits.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -43,9 +50,23 @@ static bool parse_int(const char* opt, const char* text, long lo, long hi, int* 
     return true;
 }
 
+// the same for a 64-bit count (--min-count / --max-count)
+static bool parse_count(const char* opt, const char* text, long long lo, long long hi, long long* out) {
+    char* end = nullptr;
+    errno = 0;
+    const long long v = strtoll(text, &end, 10);
+    if (errno || end == text || *end != '\0' || v < lo || v > hi) {
+        fprintf(stderr, "k-mer-count: %s needs a whole number in %lld..%lld (got '%s')\n", opt, lo, hi, text);
+        return false;
+    }
+    *out = v;
+    return true;
+}
+
 int main(int argc, char** argv) {
     const char* path = "sample.fasta";  // main.rs:44
-    int k = 0, canonical = 1, expand = 0, device = 0, algo = KMC_ALGO_AUTO, stats = 0, gpus = 1;
+    int k = 0, canonical = 1, expand = 0, device = 0, algo = KMC_ALGO_AUTO, stats = 0, gpus = 1, histo = 0;
+    long long min_count = 1, max_count = 0;   // (max_count 0: no upper bound)
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         if (a == "-k" && i + 1 < argc) { if (!parse_int("-k", argv[++i], 1, 63, &k)) return 2; }
@@ -54,18 +75,27 @@ int main(int argc, char** argv) {
         else if (a == "--stats") stats = 1;
         else if (a == "--device" && i + 1 < argc) { if (!parse_int("--device", argv[++i], 0, 1023, &device)) return 2; }
         else if (a == "--gpus" && i + 1 < argc) { if (!parse_int("--gpus", argv[++i], 1, 64, &gpus)) return 2; }
+        else if (a == "--min-count" && i + 1 < argc) { if (!parse_count("--min-count", argv[++i], 1, LLONG_MAX, &min_count)) return 2; }
+        else if (a == "--max-count" && i + 1 < argc) { if (!parse_count("--max-count", argv[++i], 1, LLONG_MAX, &max_count)) return 2; }
+        else if (a == "--histo" && i + 1 < argc) { if (!parse_int("--histo", argv[++i], 1, (1 << 24) - 1, &histo)) return 2; }
         else if (a == "--algo" && i + 1 < argc) {
             std::string v = argv[++i];
             algo = v == "stream" ? KMC_ALGO_STREAM : v == "walk" ? KMC_ALGO_WALK : v == "sort" ? KMC_ALGO_SORT : KMC_ALGO_AUTO;
         } else if (a == "-h" || a == "--help") {
-            fprintf(stderr, "usage: k-mer-count [FASTA] [-k K] [--forward] [--expand] [--device N | --gpus N] [--algo auto|stream|walk|sort] [--stats]\n");
+            fprintf(stderr, "usage: k-mer-count [FASTA] [-k K] [--forward] [--expand] [--device N | --gpus N] [--algo auto|stream|walk|sort] [--stats]\n"
+                            "                   [--min-count N] [--max-count N] [--histo H]\n");
             return 0;
-        } else if (a == "-k" || a == "--device" || a == "--gpus" || a == "--algo") {
+        } else if (a == "-k" || a == "--device" || a == "--gpus" || a == "--algo" || a == "--min-count" || a == "--max-count" || a == "--histo") {
             fprintf(stderr, "k-mer-count: %s needs a value\n", a.c_str());
             return 2;
         } else if (!a.empty() && a[0] != '-') path = argv[i];
         else { fprintf(stderr, "k-mer-count: unknown option %s\n", a.c_str()); return 2; }
     }
+    if (max_count && min_count > max_count) {
+        fprintf(stderr, "k-mer-count: --min-count %lld is above --max-count %lld\n", min_count, max_count);
+        return 2;
+    }
+    const bool filtered = min_count > 1 || max_count != 0;
     kmc_config cfg;
     memset(&cfg, 0, sizeof(cfg));
     cfg.struct_size = sizeof(cfg);
@@ -92,11 +122,27 @@ int main(int argc, char** argv) {
     uint64_t nd = 0, nt = 0;
     rc = gpus == 1 ? kmc_count_file(ctx, path, &nd, &nt) : kmc_count_file_multi(ctxs.data(), (uint32_t)ctxs.size(), path, &nd, &nt);
     if (rc) { int r = die(path, kmc_last_error(ctx)); destroy_all(); return r; }
-    std::vector<uint64_t> hi(nd ? nd : 1), lo(nd ? nd : 1), cnt(nd ? nd : 1);
-    rc = kmc_export(ctx, hi.data(), lo.data(), cnt.data(), nd);
-    if (rc) { int r = die("kmc_export", kmc_last_error(ctx)); destroy_all(); return r; }
-    const int klen = k ? k : 54;
     std::vector<char> obuf(1 << 22);
+    if (histo) {
+        std::vector<uint64_t> h((size_t)histo + 1);
+        rc = kmc_histogram(ctx, (uint64_t)min_count, (uint64_t)max_count, (uint32_t)histo + 1, h.data(), nullptr);
+        if (rc) { int r = die("kmc_histogram", kmc_last_error(ctx)); destroy_all(); return r; }
+        setvbuf(stdout, obuf.data(), _IOFBF, obuf.size());
+        for (int c = 1; c <= histo; ++c)
+            if (h[(size_t)c]) printf("%d\t%llu\n", c, (unsigned long long)h[(size_t)c]);
+        fflush(stdout);
+        destroy_all();
+        return 0;
+    }
+    if (filtered) {   // the kept keys only: size, then copy
+        rc = kmc_export_filtered(ctx, (uint64_t)min_count, (uint64_t)max_count, nullptr, nullptr, nullptr, 0, &nd);
+        if (rc && !(rc == KMC_ERR_ARG && nd)) { int r = die("kmc_export_filtered", kmc_last_error(ctx)); destroy_all(); return r; }
+    }
+    std::vector<uint64_t> hi(nd ? nd : 1), lo(nd ? nd : 1), cnt(nd ? nd : 1);
+    rc = filtered ? kmc_export_filtered(ctx, (uint64_t)min_count, (uint64_t)max_count, hi.data(), lo.data(), cnt.data(), nd, &nd)
+                  : kmc_export(ctx, hi.data(), lo.data(), cnt.data(), nd);
+    if (rc) { int r = die(filtered ? "kmc_export_filtered" : "kmc_export", kmc_last_error(ctx)); destroy_all(); return r; }
+    const int klen = k ? k : 54;
     setvbuf(stdout, obuf.data(), _IOFBF, obuf.size());
     char line[96];
     for (uint64_t i = 0; i < nd; ++i) {

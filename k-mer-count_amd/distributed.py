@@ -263,3 +263,21 @@ def _reduce_tables_a2a(local, owner, group=None, send: bool = True):
         got += m
     got_total, _ = owner.finalize()
     return n, got_total
+
+
+def global_histogram(owner, n_bins: int, min_count: int = 1, max_count: int = 0, group=None) -> Tuple[np.ndarray, int]:
+    """Abundance histogram of the global table after reduce_tables.  Every key then lives on exactly one owner rank,
+    so the global spectrum is the elementwise sum of the owners' histograms: one all_reduce(SUM) of n_bins int64,
+    and the largest count in range one all_reduce(MAX).  `owner`: anything with a
+    histogram(n_bins, min_count, max_count, return_max=True) method (a finalized KmerCounter).
+    Returns (uint64[n_bins], max_seen) on every rank."""
+    h, mx = owner.histogram(n_bins, min_count, max_count, return_max=True)
+    if dist.get_backend(group) == "nccl":
+        dev = torch.device("cuda", getattr(owner, "device", torch.cuda.current_device()))
+    else:
+        dev = torch.device("cpu")
+    t = torch.from_numpy(np.asarray(h, dtype=np.uint64).view(np.int64).copy()).to(dev)
+    m = torch.tensor([int(mx)], dtype=torch.int64, device=dev)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    dist.all_reduce(m, op=dist.ReduceOp.MAX, group=group)
+    return t.cpu().numpy().view(np.uint64).copy(), int(m.item())

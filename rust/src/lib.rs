@@ -94,6 +94,11 @@ extern "C" {
     pub fn kmc_partition_device(ctx: *mut KmcCtx, n_parts: u32, part_begin: *mut u64, d_key_hi: *mut *const c_void,
                                 d_key_lo: *mut *const c_void, d_count: *mut *const c_void) -> c_int;
     pub fn kmc_owner_of(key_hi: u64, key_lo: u64, n_parts: u32) -> u32;
+    pub fn kmc_histogram(ctx: *mut KmcCtx, min_count: u64, max_count: u64, n_bins: u32, hist: *mut u64, max_seen: *mut u64) -> c_int;
+    pub fn kmc_filter_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, d_key_hi: *mut *const c_void, d_key_lo: *mut *const c_void,
+                             d_count: *mut *const c_void, n_kept: *mut u64, kept_total: *mut u64) -> c_int;
+    pub fn kmc_export_filtered(ctx: *mut KmcCtx, min_count: u64, max_count: u64, key_hi: *mut u64, key_lo: *mut u64, count: *mut u64,
+                               cap: u64, n_kept: *mut u64) -> c_int;
     // multi-GPU reduce (one process per GPU; the collective itself is the host program's, e.g. RCCL)
     pub fn kmc_slab_words(ctx: *const KmcCtx, slab_entries: u64) -> u64;
     pub fn kmc_pack_slab_device(ctx: *mut KmcCtx, d_slab: *mut c_void, slab_entries: u64) -> c_int;
@@ -188,6 +193,42 @@ impl Counter {
         let mut buf = vec![0u8; self.klen as usize];
         let mut out = Vec::with_capacity(n);
         for i in 0..n {
+            unsafe { kmc_decode_key(hi[i], lo[i], self.klen, buf.as_mut_ptr() as *mut c_char) };
+            out.push((String::from_utf8_lossy(&buf).into_owned(), cnt[i]));
+        }
+        Ok(out)
+    }
+
+    /// Abundance histogram of the table (`hist[c]` = keys seen `c` times, the last bin `>= n_bins - 1`), counting only
+    /// keys with `min_count <= count <= max_count` (`max_count` 0: no upper bound), and the largest such count.
+    pub fn histogram(&mut self, n_bins: u32, min_count: u64, max_count: u64) -> Result<(Vec<u64>, u64), KmcError> {
+        let (mut nd, mut nt) = (0u64, 0u64);
+        self.check(unsafe { kmc_finalize(self.ctx, &mut nd, &mut nt) })?;
+        let mut hist = vec![0u64; n_bins as usize];
+        let mut max_seen = 0u64;
+        self.check(unsafe { kmc_histogram(self.ctx, min_count, max_count, n_bins, hist.as_mut_ptr(), &mut max_seen) })?;
+        Ok((hist, max_seen))
+    }
+
+    /// `table()` restricted to keys with `min_count <= count <= max_count` (`max_count` 0: no upper bound), same order.
+    pub fn table_filtered(&mut self, min_count: u64, max_count: u64) -> Result<Vec<(String, u64)>, KmcError> {
+        let (mut nd, mut nt) = (0u64, 0u64);
+        self.check(unsafe { kmc_finalize(self.ctx, &mut nd, &mut nt) })?;
+        let mut n = 0u64;
+        let rc = unsafe {
+            kmc_export_filtered(self.ctx, min_count, max_count, std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), 0, &mut n)
+        };
+        if rc != 0 && n == 0 {
+            self.check(rc)?;
+        }
+        let k = n as usize;
+        let (mut hi, mut lo, mut cnt) = (vec![0u64; k], vec![0u64; k], vec![0u64; k]);
+        if k > 0 {
+            self.check(unsafe { kmc_export_filtered(self.ctx, min_count, max_count, hi.as_mut_ptr(), lo.as_mut_ptr(), cnt.as_mut_ptr(), n, &mut n) })?;
+        }
+        let mut buf = vec![0u8; self.klen as usize];
+        let mut out = Vec::with_capacity(k);
+        for i in 0..k {
             unsafe { kmc_decode_key(hi[i], lo[i], self.klen, buf.as_mut_ptr() as *mut c_char) };
             out.push((String::from_utf8_lossy(&buf).into_owned(), cnt[i]));
         }
