@@ -162,8 +162,10 @@ int kmc_finalize(kmc_ctx* ctx, uint64_t* n_distinct, uint64_t* n_total);
  * keys, nothing spilled: every table of generator-style input) is queued on the ctx stream and the call returns.  Behind
  * it in stream order the sorted view is in place (the pointers kmc_export_device last returned stay valid for small
  * tables) and the table is empty; kmc_reset after it launches one small kernel and does not wait either.  The next call
- * that needs the outcome on the host (kmc_finalize, kmc_export*, kmc_add_batch*, ...) synchronises once and takes it from
- * there -- kmc_finalize then returns the sizes of the view this call produced.  A caller that queues many steps
+ * that needs the outcome on the host (kmc_finalize, kmc_export*, kmc_add_batch*, kmc_merge_pairs_device, kmc_count_file,
+ * kmc_poll, the spectrum calls, ...) synchronises once and takes it from there -- kmc_finalize then returns the sizes of
+ * the view this call produced; a call that reads the view gets it also when the device found the table too large, by
+ * the ordinary finalize; an addition puts the view's counts back into the table first.  A caller that queues many steps
  * (count -> kmc_finalize_async -> kmc_reset -> ...) checks afterwards that every step delivered:
  * kmc_stats.n_async_ok grows by one per finalize that produced its view, n_async_slabs_skipped by the oversize slabs
  * those finalizes saw (both valid after a synchronising call).  Larger tables are finalized synchronously, as by kmc_finalize. */

@@ -67,7 +67,10 @@ struct kmc_ctx {
     u64* occ_list = nullptr;        // first KMC_OCC_LIST_CAP claimed slots (fast finalize of small tables)
     u64 *occ_key_lo = nullptr, *occ_key_hi = nullptr;   // ... and their keys, dense (GTable::occ_key_*)
     u32* fin_rank = nullptr;        // ticket counter of kmc_small_finalize_kernel (zero between launches)
-    u64* d_mirror = nullptr;        // h_counters as the device sees it (the finalize kernel publishes the counters there)
+    u64* h_pub = nullptr;           // pinned, 2 * KMC_CTR_N: where kmc_small_finalize_kernel publishes its outcome + the counters.  Its
+                                    // own block: a kernel queued by kmc_finalize_async may publish after the host has reset or
+                                    // polled h_counters; poll_fin copies what the awaited launch published into h_counters
+    u64* d_mirror = nullptr;        // h_pub as the device sees it
     u64* h_restore = nullptr;       // pinned: the counters to put back when a drained table is filled again (undrain)
     // planner invariant (kmc_stats.n_planner_stale): every kernel queued OUTSIDE the count launches' own accounting that
     // changes the table -- the (k+16)-mer unfold, merges -- bumps table_epoch; a poll records the epoch it has seen; a
@@ -428,9 +431,17 @@ auto kw_dispatch(int KW, F1 f1, F2 f2) { return KW == 1 ? f1() : f2(); }
 // what a poll learns from fresh h_counters
 int poll_book(kmc_ctx* c);
 // read the device counters (synchronises the stream)
+int resolve_async(kmc_ctx* c);
 int poll(kmc_ctx* c) {
+    // A finalize queued by kmc_finalize_async may have drained the table: the device counters then read zero and the
+    // totals are in what it published.  Its outcome is this poll (resolve_async clears async_fin first: no recursion).
+    if (c->async_fin) return resolve_async(c);
     HIPCHK(c, hipMemcpyAsync(c->h_counters, c->d_counters, (c->sk.lo ? 2 : 1) * KMC_CTR_N * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    // (every finalize kernel has ended: what the last one published is the ctx's cumulative count -- also of one queued
+    // in front of a kmc_reset, whose outcome nobody resolved)
+    c->st.n_async_ok = c->h_pub[KMC_CTR_FINOK];
+    c->st.n_async_slabs_skipped = c->h_pub[KMC_CTR_FINSKIP];
     return poll_book(c);
 }
 // The poll right behind a speculative kmc_small_finalize_kernel: when the kernel succeeded it has PUBLISHED the
@@ -441,7 +452,7 @@ int poll(kmc_ctx* c) {
 // A kernel that never publishes (a fault) is found by the synchronisation this falls back to.
 int poll_fin(kmc_ctx* c) {
     {
-        const volatile u64* seqw = (const volatile u64*)&c->h_counters[KMC_CTR_FINSEQ];
+        const volatile u64* seqw = (const volatile u64*)&c->h_pub[KMC_CTR_FINSEQ];
         static const bool no_spin = getenv("KMC_NO_MIRROR_SPIN") != nullptr;
         bool seen = false;
         if (!no_spin) {
@@ -455,14 +466,14 @@ int poll_fin(kmc_ctx* c) {
         if (!seen) HIPCHK(c, hipStreamSynchronize(c->stream));
         c->view_unsynced = seen;   // (the kernel may still be running: kmc_export_device waits for its end before it hands out pointers)
     }
-    c->st.n_async_ok = c->h_counters[KMC_CTR_FINOK];
-    c->st.n_async_slabs_skipped = c->h_counters[KMC_CTR_FINSKIP];
-    if (c->h_counters[KMC_CTR_FASTFIN] != 1 || c->h_counters[KMC_CTR_FINSEQ] != c->fin_seq) {   // it gave up: read the counters the usual way
-        c->h_counters[KMC_CTR_FASTFIN] = 0;
+    c->st.n_async_ok = c->h_pub[KMC_CTR_FINOK];
+    c->st.n_async_slabs_skipped = c->h_pub[KMC_CTR_FINSKIP];
+    if (c->h_pub[KMC_CTR_FASTFIN] != 1 || c->h_pub[KMC_CTR_FINSEQ] != c->fin_seq) {   // it gave up: read the counters the usual way
         int rc = poll(c);
         c->h_counters[KMC_CTR_FASTFIN] = 0;   // (the device word is never written; whatever the copy brought is not a verdict)
         return rc;
     }
+    memcpy(c->h_counters, c->h_pub, 2 * KMC_CTR_N * sizeof(u64));   // (all of it: [count table | (k+16)-mer table], FASTFIN = 1)
     c->drained = true;
     c->fin_parity = 0;
     return poll_book(c);
@@ -570,6 +581,7 @@ int settle(kmc_ctx* c) {
 int launch_begin(kmc_ctx* c);
 int launch_end(kmc_ctx* c);
 int poll_and_settle(kmc_ctx* c) {
+    if (c->async_fin) return resolve_async(c);   // (it settles a table the kernel gave up on; a drained one is settled)
     int rc = poll(c);
     if (rc) return rc;
     return settle(c);
@@ -640,6 +652,15 @@ int resolve_async(kmc_ctx* c) {
         return KMC_OK;
     }
     return settle(c);
+}
+
+// What the calls that read the view do first: a finalize queued by kmc_finalize_async counts as one -- also when its
+// kernel gave up (a table it does not take): then the ordinary finalize makes the view here.
+int resolve_view(kmc_ctx* c) {
+    const bool queued = c->async_fin;
+    int rc = resolve_async(c);
+    if (rc || !queued || c->sorted_valid) return rc;
+    return kmc_finalize(c, nullptr, nullptr);
 }
 
 // Give the counts of the (k+16)-mer table to their k-mers (kmc_sk_unfold_kernel).  What the last poll
@@ -1646,6 +1667,7 @@ extern "C" void kmc_destroy(kmc_ctx* c) {
     if (c->d_counters) (void)hipFree(c->d_counters);
     if (c->h_counters) (void)hipHostFree(c->h_counters);
     if (c->h_restore) (void)hipHostFree(c->h_restore);
+    if (c->h_pub) (void)hipHostFree(c->h_pub);
     if (c->occ_list) (void)hipFree(c->occ_list);
     if (c->occ_key_lo) (void)hipFree(c->occ_key_lo);
     if (c->occ_key_hi) (void)hipFree(c->occ_key_hi);
@@ -1700,7 +1722,9 @@ static int kmc_create_impl(kmc_ctx** out, const kmc_config* cfg) {
         HIPCHK(c, hipMemsetAsync(c->d_counters, 0, 2 * KMC_CTR_N * sizeof(u64), c->stream));
         HIPCHK(c, hipHostMalloc((void**)&c->h_counters, 2 * KMC_CTR_N * sizeof(u64)));
         memset(c->h_counters, 0, 2 * KMC_CTR_N * sizeof(u64));
-        HIPCHK(c, hipHostGetDevicePointer((void**)&c->d_mirror, c->h_counters, 0));
+        HIPCHK(c, hipHostMalloc((void**)&c->h_pub, 2 * KMC_CTR_N * sizeof(u64)));
+        memset(c->h_pub, 0, 2 * KMC_CTR_N * sizeof(u64));
+        HIPCHK(c, hipHostGetDevicePointer((void**)&c->d_mirror, c->h_pub, 0));
         HIPCHK(c, hipHostMalloc((void**)&c->h_restore, KMC_CTR_N * sizeof(u64)));
         u64 cap = next_pow2(std::max<u64>(cfg->capacity_hint * 2, 1ull << 20));
         c->spill_cap = std::max<u64>(cap / 4, 1ull << 18);
@@ -2024,7 +2048,7 @@ static int kmc_finalize_async_impl(kmc_ctx* c) {
 
 static int kmc_export_impl(kmc_ctx* c, uint64_t* key_hi, uint64_t* key_lo, uint64_t* count, uint64_t cap) {
     if (!c) return KMC_ERR_ARG;
-    { int rc = resolve_async(c); if (rc) return rc; }
+    { int rc = resolve_view(c); if (rc) return rc; }
     if (!c->sorted_valid) return fail(c, KMC_ERR_STATE, "kmc_export before kmc_finalize");
     const u64 n = c->n_sorted;
     if (cap < n) return fail(c, KMC_ERR_ARG, "export capacity %llu < %llu distinct keys", (unsigned long long)cap, (unsigned long long)n);
@@ -2043,7 +2067,7 @@ static int kmc_export_impl(kmc_ctx* c, uint64_t* key_hi, uint64_t* key_lo, uint6
 
 static int kmc_export_device_impl(kmc_ctx* c, const void** d_key_hi, const void** d_key_lo, const void** d_count, uint64_t* n_distinct) {
     if (!c) return KMC_ERR_ARG;
-    { int rc = resolve_async(c); if (rc) return rc; }
+    { int rc = resolve_view(c); if (rc) return rc; }
     if (!c->sorted_valid) return fail(c, KMC_ERR_STATE, "kmc_export_device before kmc_finalize");
     if (c->view_unsynced) {   // (see poll_fin: the finalize kernel told the host it was done before it ended)
         HIPCHK(c, hipSetDevice(c->cfg.device));
@@ -2062,7 +2086,7 @@ extern "C" uint32_t kmc_owner_of(uint64_t key_hi, uint64_t key_lo, uint32_t n_pa
 static int kmc_partition_device_impl(kmc_ctx* c, uint32_t n_parts, uint64_t* part_begin, const void** d_key_hi,
                                     const void** d_key_lo, const void** d_count) {
     if (!c || !n_parts || !part_begin) return KMC_ERR_ARG;
-    { int rc = resolve_async(c); if (rc) return rc; }
+    { int rc = resolve_view(c); if (rc) return rc; }
     if (!c->sorted_valid) return fail(c, KMC_ERR_STATE, "kmc_partition_device before kmc_finalize");
     HIPCHK(c, hipSetDevice(c->cfg.device));
     const u64 n = c->n_sorted;
@@ -2103,9 +2127,9 @@ static int kmc_partition_device_impl(kmc_ctx* c, uint32_t n_parts, uint64_t* par
 }
 
 // ---- abundance histogram and count-range filter of the sorted view (kmc_spectrum.hip.h) ----
-// What the three calls share: a queued finalize counts as one (resolve_async), a sane range, a view to read.
+// What the three calls share: a queued finalize counts as one (resolve_view), a sane range, a view to read.
 static int spectrum_begin(kmc_ctx* c, const char* what, uint64_t min_count, uint64_t max_count) {
-    int rc = resolve_async(c);
+    int rc = resolve_view(c);
     if (rc) return rc;
     if (max_count && min_count > max_count)
         return fail(c, KMC_ERR_ARG, "%s: min_count %llu > max_count %llu", what, (unsigned long long)min_count, (unsigned long long)max_count);

@@ -1209,10 +1209,19 @@ def test_finalize_async_small_tables(kmc, oracle):
             assert kc.export().equals(want)
             st = kc.stats()
             assert st.n_async_ok - ok0 == 6 and st.n_async_slabs_skipped == 0
-            kc.finalize_async()                       # nothing new: a no-op
-            kc.add_batch(hb, ho)                      # adding behind an unobserved finalize: the view goes back into the table
+            kc.finalize_async()                       # nothing new: a no-op (the export above already resolved the finalize)
+            kc.add_batch(hb, ho)                      # adding behind a drained, finalized table: the view goes back into the table
             t = kc.export()
             assert np.array_equal(t.key_lo, want.key_lo) and np.array_equal(t.count, want.count * 2)
+            kc.reset()                                # adding behind an unobserved finalize (queued, nobody has looked):
+            kc.add_batch(hb, ho)                      # its drained counts go back into the table first
+            ok1 = kc.stats().n_async_ok
+            kc.finalize_async()
+            kc.add_batch(hb, ho)
+            assert kc.stats().n_async_ok == ok1 + 1
+            t = kc.export()
+            assert np.array_equal(t.key_lo, want.key_lo) and np.array_equal(t.count, want.count * 2)
+            # (every other call ordering around kmc_finalize_async: tests/test_async_finalize_gpu.py)
             kc.finalize_async()
             kc.reset()                                # reset behind an unobserved finalize (drained or not: decided on the device)
             kc.add_batch(hb, ho)
