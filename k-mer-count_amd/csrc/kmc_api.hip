@@ -425,8 +425,21 @@ int reset_grid(const kmc_ctx* c) {
     return c->tab.cap <= (16ull << 20) ? 256 : (int)std::min<u64>(c->tab.cap >> 14, 2048);
 }
 
-template <typename F1, typename F2>
-auto kw_dispatch(int KW, F1 f1, F2 f2) { return KW == 1 ? f1() : f2(); }
+// The only launches of kmc_reset_kernel and kmc_merge_pairs_kernel (the callers check hipGetLastError).  Clear the
+// count table and the (k+16)-mer table:
+void launch_reset_table(kmc_ctx* c) {
+    const GTable g = gtable_of(c, c->tab);
+    const int grid = reset_grid(c);
+    if (c->KW == 1) hipLaunchKernelGGL(kmc_reset_kernel<1>, dim3(grid), dim3(256), 0, c->stream, g, sk_table_of(c), c->fin_rank + 3);
+    else hipLaunchKernelGGL(kmc_reset_kernel<2>, dim3(grid), dim3(256), 0, c->stream, g, sk_table_of(c), c->fin_rank + 3);
+}
+// add n (key, count) pairs to the count table (hi: not read for one-word keys):
+void launch_merge_pairs(kmc_ctx* c, const u64* hi, const u64* lo, const u64* cnt, u64 n) {
+    const GTable g = gtable_of(c, c->tab);
+    const int grid = grid_for(c, n, 256);
+    if (c->KW == 1) hipLaunchKernelGGL(kmc_merge_pairs_kernel<1>, dim3(grid), dim3(256), 0, c->stream, g, (const u64*)nullptr, lo, cnt, n);
+    else hipLaunchKernelGGL(kmc_merge_pairs_kernel<2>, dim3(grid), dim3(256), 0, c->stream, g, hi, lo, cnt, n);
+}
 
 // what a poll learns from fresh h_counters
 int poll_book(kmc_ctx* c);
@@ -451,21 +464,16 @@ int poll(kmc_ctx* c) {
 // 1.4 ms step, and what the kernel still does after the word -- clearing slots -- is device work in stream order).
 // A kernel that never publishes (a fault) is found by the synchronisation this falls back to.
 int poll_fin(kmc_ctx* c) {
-    {
-        const volatile u64* seqw = (const volatile u64*)&c->h_pub[KMC_CTR_FINSEQ];
-        static const bool no_spin = getenv("KMC_NO_MIRROR_SPIN") != nullptr;
-        bool seen = false;
-        if (!no_spin) {
-            const auto t0 = std::chrono::steady_clock::now();
-            for (u32 it = 1; !(seen = (*seqw == c->fin_seq)); ++it) {
-                __builtin_ia32_pause();
-                if ((it & 0xfffu) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) break;
-            }
-            std::atomic_thread_fence(std::memory_order_acquire);
-        }
-        if (!seen) HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->view_unsynced = seen;   // (the kernel may still be running: kmc_export_device waits for its end before it hands out pointers)
+    const volatile u64* seqw = (const volatile u64*)&c->h_pub[KMC_CTR_FINSEQ];
+    bool seen = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (u32 it = 1; !(seen = (*seqw == c->fin_seq)); ++it) {
+        __builtin_ia32_pause();
+        if ((it & 0xfffu) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) break;
     }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    if (!seen) HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->view_unsynced = seen;   // (the kernel may still be running: kmc_export_device waits for its end before it hands out pointers)
     c->st.n_async_ok = c->h_pub[KMC_CTR_FINOK];
     c->st.n_async_slabs_skipped = c->h_pub[KMC_CTR_FINSKIP];
     if (c->h_pub[KMC_CTR_FASTFIN] != 1 || c->h_pub[KMC_CTR_FINSEQ] != c->fin_seq) {   // it gave up: read the counters the usual way
@@ -555,7 +563,6 @@ int settle(kmc_ctx* c) {
             // move the spill entries aside conceptually: merge them, then clear the counter
             u64 n = spill;
             c->st.n_spilled += n;
-            GTable g = gtable_of(c, c->tab);
             // the merge may itself spill (appends after position n); handled by the next iteration
             u64 *sh = nullptr, *sl = nullptr, *sc = nullptr;
             HIPCHK(c, hipMalloc((void**)&sl, n * sizeof(u64)));
@@ -565,9 +572,7 @@ int settle(kmc_ctx* c) {
             HIPCHK(c, hipMemcpyAsync(sc, c->spill_cnt, n * sizeof(u64), hipMemcpyDeviceToDevice, c->stream));
             if (sh) HIPCHK(c, hipMemcpyAsync(sh, c->spill_hi, n * sizeof(u64), hipMemcpyDeviceToDevice, c->stream));
             HIPCHK(c, hipMemsetAsync(&c->d_counters[KMC_CTR_SPILL], 0, sizeof(u64), c->stream));
-            int grid = grid_for(c, n, 256);
-            if (c->KW == 1) hipLaunchKernelGGL(kmc_merge_pairs_kernel<1>, dim3(grid), dim3(256), 0, c->stream, g, (const u64*)sh, (const u64*)sl, (const u64*)sc, n);
-            else hipLaunchKernelGGL(kmc_merge_pairs_kernel<2>, dim3(grid), dim3(256), 0, c->stream, g, (const u64*)sh, (const u64*)sl, (const u64*)sc, n);
+            launch_merge_pairs(c, sh, sl, sc, n);
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, hipStreamSynchronize(c->stream));
             (void)hipFree(sl); (void)hipFree(sc); if (sh) (void)hipFree(sh);
@@ -583,11 +588,6 @@ int launch_end(kmc_ctx* c);
 int poll_and_settle(kmc_ctx* c) {
     if (c->async_fin) return resolve_async(c);   // (it settles a table the kernel gave up on; a drained one is settled)
     int rc = poll(c);
-    if (rc) return rc;
-    return settle(c);
-}
-int poll_fin_and_settle(kmc_ctx* c) {
-    int rc = poll_fin(c);
     if (rc) return rc;
     return settle(c);
 }
@@ -622,11 +622,8 @@ int undrain(kmc_ctx* c) {
     for (int i : zero) c->h_restore[i] = 0;   // (the merge claims the slots again and counts them)
     HIPCHK(c, hipMemcpyAsync(c->d_counters, c->h_restore, KMC_CTR_N * sizeof(u64), hipMemcpyHostToDevice, c->stream));
     c->fin_parity = 0;
-    const u64 n = c->n_sorted;
-    if (n) {
-        GTable g = gtable_of(c, c->tab);
-        if (c->KW == 1) hipLaunchKernelGGL(kmc_merge_pairs_kernel<1>, dim3(grid_for(c, n, 256)), dim3(256), 0, c->stream, g, (const u64*)nullptr, (const u64*)c->o_lo.p, (const u64*)c->o_cnt.p, n);
-        else hipLaunchKernelGGL(kmc_merge_pairs_kernel<2>, dim3(grid_for(c, n, 256)), dim3(256), 0, c->stream, g, (const u64*)c->o_hi.p, (const u64*)c->o_lo.p, (const u64*)c->o_cnt.p, n);
+    if (c->n_sorted) {
+        launch_merge_pairs(c, (const u64*)c->o_hi.p, (const u64*)c->o_lo.p, (const u64*)c->o_cnt.p, c->n_sorted);
         HIPCHK(c, hipGetLastError());
     }
     return KMC_OK;
@@ -781,6 +778,33 @@ int launch_extract(kmc_ctx* c, const uint8_t* d_bases, const u64* d_offsets, u64
 }
 
 // ---- hand-written MSD radix sort + run-length (kmc_msd.hip.h) ------------------------------------------
+// the scratch buffers of msd_sort_to_run and the pinned mirror of its counters
+int msd_scratch(kmc_ctx* c, u64 max_ranges, u64 max_seg, u64 term_cap, u64 n_words) {
+    int rc;
+#define MSD_ENSURE(buf, bytes) do { rc = ensure(c, (buf), (size_t)(bytes)); if (rc) return rc; } while (0)
+    MSD_ENSURE(c->m_hist, msd_hist_words(max_ranges) * sizeof(u32));
+    MSD_ENSURE(c->m_rmin, max_ranges * 2 * sizeof(u64));
+    MSD_ENSURE(c->m_rmax, max_ranges * 2 * sizeof(u64));
+    MSD_ENSURE(c->m_seg[0], max_seg * sizeof(MsdSeg));
+    MSD_ENSURE(c->m_seg[1], max_seg * sizeof(MsdSeg));
+    MSD_ENSURE(c->m_first, (max_seg + 1) * sizeof(u32));
+    MSD_ENSURE(c->m_cbase, max_seg * KMC_MSD_NB * sizeof(u32));
+    MSD_ENSURE(c->m_stot, max_seg * KMC_MSD_NB * sizeof(u32));
+    MSD_ENSURE(c->m_skip, max_seg * sizeof(u32));
+    MSD_ENSURE(c->m_term, term_cap * sizeof(MsdTerm));
+    MSD_ENSURE(c->m_ord, term_cap * sizeof(MsdTerm));
+    MSD_ENSURE(c->m_bitmap, n_words * sizeof(u64));
+    MSD_ENSURE(c->m_rank, n_words * sizeof(u32));
+    MSD_ENSURE(c->m_nd, term_cap * sizeof(u32));
+    MSD_ENSURE(c->m_clist, max_seg * sizeof(u32));   // (kind-2 terminals hold more than leaf_cap keys each)
+    MSD_ENSURE(c->m_base, term_cap * sizeof(u32));
+    MSD_ENSURE(c->m_ctl, sizeof(MsdCtl));
+    MSD_ENSURE(c->m_bsum, (std::max<u64>(n_words, term_cap) / KMC_SCAN_PER_BLOCK + 2) * sizeof(u32));
+#undef MSD_ENSURE
+    if (!c->h_ctl) HIPCHK(c, hipHostMalloc((void**)&c->h_ctl, sizeof(MsdCtl)));
+    return KMC_OK;
+}
+
 // Sorts the n keys in lo[0] (hi[0] for two-word keys; w[0] = weights to sum, or null: every key counts
 // once), dropping all-ones filler keys, and appends the resulting sorted (key, count) run to c->runs.
 // lo[1] / hi[1] / w[1] are scratch of the same size.  One host synchronisation per level (the number
@@ -807,27 +831,8 @@ int msd_sort_to_run(kmc_ctx* c, u64* const hi[2], u64* const lo[2], u64* const w
     const u64 term_cap = 16 * (n / leaf_cap) + 65536;
     const u64 n_words = (n + 63) / 64;
     int rc;
-#define MSD_ENSURE(buf, bytes) do { rc = ensure(c, (buf), (size_t)(bytes)); if (rc) return rc; } while (0)
-    MSD_ENSURE(c->m_hist, msd_hist_words(max_ranges) * sizeof(u32));
-    MSD_ENSURE(c->m_rmin, max_ranges * 2 * sizeof(u64));
-    MSD_ENSURE(c->m_rmax, max_ranges * 2 * sizeof(u64));
-    MSD_ENSURE(c->m_seg[0], max_seg * sizeof(MsdSeg));
-    MSD_ENSURE(c->m_seg[1], max_seg * sizeof(MsdSeg));
-    MSD_ENSURE(c->m_first, (max_seg + 1) * sizeof(u32));
-    MSD_ENSURE(c->m_cbase, max_seg * KMC_MSD_NB * sizeof(u32));
-    MSD_ENSURE(c->m_stot, max_seg * KMC_MSD_NB * sizeof(u32));
-    MSD_ENSURE(c->m_skip, max_seg * sizeof(u32));
-    MSD_ENSURE(c->m_term, term_cap * sizeof(MsdTerm));
-    MSD_ENSURE(c->m_ord, term_cap * sizeof(MsdTerm));
-    MSD_ENSURE(c->m_bitmap, n_words * sizeof(u64));
-    MSD_ENSURE(c->m_rank, n_words * sizeof(u32));
-    MSD_ENSURE(c->m_nd, term_cap * sizeof(u32));
-    MSD_ENSURE(c->m_clist, max_seg * sizeof(u32));   // (kind-2 terminals hold more than leaf_cap keys each)
-    MSD_ENSURE(c->m_base, term_cap * sizeof(u32));
-    MSD_ENSURE(c->m_ctl, sizeof(MsdCtl));
-    MSD_ENSURE(c->m_bsum, (std::max<u64>(n_words, term_cap) / KMC_SCAN_PER_BLOCK + 2) * sizeof(u32));
-#undef MSD_ENSURE
-    if (!c->h_ctl) HIPCHK(c, hipHostMalloc((void**)&c->h_ctl, sizeof(MsdCtl)));
+    rc = msd_scratch(c, max_ranges, max_seg, term_cap, n_words);
+    if (rc) return rc;
     MsdCtl* ctl = (MsdCtl*)c->m_ctl.p;
     HIPCHK(c, hipMemsetAsync(ctl, 0, sizeof(MsdCtl), c->stream));
     HIPCHK(c, hipMemsetAsync(c->m_bitmap.p, 0, n_words * sizeof(u64), c->stream));
@@ -1068,7 +1073,6 @@ bool arm_risky(kmc_ctx* c, const uint8_t* d_bases, const u64* d_offsets, u64 n_r
 int recover_overflow(kmc_ctx* c) {
     kmc_ctx::Risky r = c->risky;
     c->risky.armed = false;
-    GTable g = gtable_of(c, c->tab);
     u64 ctr[KMC_CTR_N];
     memcpy(ctr, r.ctr, sizeof(ctr));
     ctr[KMC_CTR_ERR] = 0;
@@ -1081,15 +1085,10 @@ int recover_overflow(kmc_ctx* c) {
             HIPCHK(c, hipStreamSynchronize(c->stream));
         }
         if (n_snap == ~0ull) return fail(c, KMC_ERR_CAPACITY, "count table and spill area exhausted and the table could not be restored; raise capacity_hint");
-        const int grid = reset_grid(c);
-        if (c->KW == 1) hipLaunchKernelGGL(kmc_reset_kernel<1>, dim3(grid), dim3(256), 0, c->stream, g, sk_table_of(c), c->fin_rank + 3);
-        else hipLaunchKernelGGL(kmc_reset_kernel<2>, dim3(grid), dim3(256), 0, c->stream, g, sk_table_of(c), c->fin_rank + 3);
+        launch_reset_table(c);
         ctr[KMC_CTR_OCCUPIED] = 0;  // (the merge below claims the slots again and counts them)
         HIPCHK(c, hipMemcpyAsync(c->d_counters, ctr, sizeof(ctr), hipMemcpyHostToDevice, c->stream));
-        if (n_snap) {
-            if (c->KW == 1) hipLaunchKernelGGL(kmc_merge_pairs_kernel<1>, dim3(grid_for(c, n_snap, 256)), dim3(256), 0, c->stream, g, (const u64*)nullptr, (const u64*)c->snap_lo.p, (const u64*)c->snap_cnt.p, n_snap);
-            else hipLaunchKernelGGL(kmc_merge_pairs_kernel<2>, dim3(grid_for(c, n_snap, 256)), dim3(256), 0, c->stream, g, (const u64*)c->snap_hi.p, (const u64*)c->snap_lo.p, (const u64*)c->snap_cnt.p, n_snap);
-        }
+        if (n_snap) launch_merge_pairs(c, (const u64*)c->snap_hi.p, (const u64*)c->snap_lo.p, (const u64*)c->snap_cnt.p, n_snap);
         HIPCHK(c, hipGetLastError());
     } else {
         const size_t nb = (size_t)c->tab.cap * sizeof(u64);
@@ -1127,10 +1126,7 @@ int recover_overflow(kmc_ctx* c) {
 // a 745 M-entry run by one more sort of everything (first step on 1 GB of random 63-mers: 100 ms of kernels
 // and 60 GB of buffers less).  ctr0 = the device counters at the start of the batch.
 int drop_batch_from_table(kmc_ctx* c, const u64* ctr0) {
-    GTable g = gtable_of(c, c->tab);
-    const int grid = reset_grid(c);
-    if (c->KW == 1) hipLaunchKernelGGL(kmc_reset_kernel<1>, dim3(grid), dim3(256), 0, c->stream, g, sk_table_of(c), c->fin_rank + 3);
-    else hipLaunchKernelGGL(kmc_reset_kernel<2>, dim3(grid), dim3(256), 0, c->stream, g, sk_table_of(c), c->fin_rank + 3);
+    launch_reset_table(c);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(c->d_counters, ctr0, KMC_CTR_N * sizeof(u64), hipMemcpyHostToDevice, c->stream));
     { int rs = sk_clear(c); if (rs) return rs; }
@@ -1213,42 +1209,100 @@ int launch_sklog(kmc_ctx* c, const SkLog& lg, u32 wgrid) {
 // the prior of KMC_ALGO_AUTO's cost comparison until the ctx has sorted something itself
 #define KMC_SORT_MS_PER_BASE_1 2.9e-8
 #define KMC_SORT_MS_PER_BASE_2 5.0e-8
-int count_batch_device_body(kmc_ctx* c, const uint8_t* d_bases, const u64* d_offsets, u64 n_reads, u64 n_bases, u64 max_read_len);
-int count_batch_device(kmc_ctx* c, const uint8_t* d_bases, const u64* d_offsets, u64 n_reads, u64 n_bases, u64 max_read_len) {
-    const int rc = count_batch_device_body(c, d_bases, d_offsets, n_reads, n_bases, max_read_len);
-    // the events of finished batches are read here, BEHIND this batch's launches (or in kmc_get_stats / kmc_poll): in front of
-    // them the microseconds would lie between a step's synchronisation and its successor's first launch
-    if (c->tb.size() >= 4) harvest_timing(c);
-    return rc;
-}
-int count_batch_device_body(kmc_ctx* c, const uint8_t* d_bases, const u64* d_offsets, u64 n_reads, u64 n_bases, u64 max_read_len) {
+
+// The launch plan of a batch, shared by its walk and stream loops.  A launch over n k-mers can add at most n new keys, so without history the first launch is sized to
+// what the table and spill area absorb for certain and later ones ramp up (x16 at most) using the observed ratio
+// rho = new keys per k-mer.  With history (the previous batch on this ctx, kept across kmc_reset) the batch goes out in
+// as few launches as 8 x the predicted number of new keys allows -- one for the benchmark input.
+// A launch larger than what is certain to fit is "risky": the table is saved in front of it (arm_risky) and, should the
+// prediction be wrong enough to exhaust table AND spill area, the next poll puts the table back and counts the rest of
+// the batch by sorting (recover_overflow): nothing is dropped and nothing fails.  The caller's device buffers must
+// therefore stay valid until the next call on the ctx that synchronises (kmc.h, kmc_add_batch_device).
+struct BatchPlan {
+    u64 ctr0[KMC_CTR_N];          // the counters at the start of the batch (as of a poll) ...
+    bool on_empty_table = false;  // ... and whether the table was empty then (drop_batch_from_table)
+    u64 safe = 0;                 // units of the last plan() that fit for certain
+    double rho_max = 0.0;         // largest new keys per k-mer over one of the batch's launches
+    double observed_kmers = 0.0;  // k-mers of the launches observe() has seen
+    u64 sk_seen = 0;              // (k+16)-mer table entries as of the last observe()
+    bool run_sort = false;        // the sort path counts the windows ending at or after sort_from
+    bool mixed = false;           // the batch changed path in the middle: not a rate sample of either
+    u64 sort_from = 0;
+
+    // units (tiles, chunks) of the next launch
+    u64 plan(const kmc_ctx* c, u64 units_left, u64 kmers_per_unit, u64 prev) {
+        u64 occ = c->h_counters[KMC_CTR_OCCUPIED];
+        u64 freeslots = (c->tab.cap * 7 / 10 > occ ? c->tab.cap * 7 / 10 - occ : 0) + c->spill_cap / 2;
+        safe = std::max<u64>(freeslots / kmers_per_unit, 1);
+        u64 take = safe;
+        if (prev) {
+            double opt = (double)freeslots / (4.0 * std::max(c->rho_last, 1e-9)) / (double)kmers_per_unit;
+            take = std::max<u64>(safe, (u64)std::min<double>(opt, (double)prev * 16.0));
+        } else if (c->rho_hist >= 0.0) {
+            // history says rho_hist new keys per k-mer.  A launch may bring 8 x that -- 3 x when the table is known to be
+            // empty: then "saving" it costs nothing, a whole batch of the same source brings what the last one brought
+            // (rho_hist is a whole-batch ratio), and a table with room for 3 x of it takes the batch in ONE launch
+            // (pool 100 of the cardinality sweep went out in four launches with a host poll behind each: 2.9 ms per GB)
+            const bool empty = occ == 0 && c->h_counters[KMC_CTR_SPILL] == 0 && !c->pending;
+            double opt = (double)freeslots / ((empty ? 3.0 : 8.0) * std::max(c->rho_hist, 1e-9)) / (double)kmers_per_unit;
+            take = std::max<u64>(safe, (u64)std::min<double>(opt, 1e18));
+        }
+        return std::min<u64>(take, units_left);
+    }
+    // the poll behind a launch of `units` units that started on occ_before table entries: what it added
+    int observe(kmc_ctx* c, u64 occ_before, u64 units, u64 kmers_per_unit) {
+        int r = poll_and_settle(c);
+        if (r) return r;
+        if (c->recovered) return KMC_OK;
+        u64 occ_after = c->h_counters[KMC_CTR_OCCUPIED];
+        // keys still waiting in the (k+16)-mer table count as well: each entry becomes up to 16 k-mers at the unfold
+        const u64 sk_after = c->sk.lo ? c->h_sk_counters[KMC_CTR_OCCUPIED] + c->h_sk_counters[KMC_CTR_SPILL] : 0;
+        const u64 sk_new = sk_after > sk_seen ? sk_after - sk_seen : 0;
+        sk_seen = sk_after;
+        double rho = ((double)(occ_after > occ_before ? occ_after - occ_before : 0) + 16.0 * (double)sk_new) / ((double)units * (double)kmers_per_unit);
+        c->rho_last = rho;
+        c->rho_max = std::max(c->rho_max, rho);
+        rho_max = std::max(rho_max, rho);
+        // history for later batches from what has been observed of this one so far; the poll after
+        // the batch's last launch (kmc_finalize) replaces it with the whole batch's ratio -- but a
+        // caller that never finalizes this ctx (multi-GPU reduce: the live table is packed and the
+        // ctx reset) must not start every batch without history
+        observed_kmers += (double)units * (double)kmers_per_unit;
+        u64 occ_all = occ_after + c->h_counters[KMC_CTR_SPILL];
+        c->rho_hist = (double)(occ_all > c->b_occ0 ? occ_all - c->b_occ0 : 0) / std::max(observed_kmers, 1.0);
+        return KMC_OK;
+    }
+    // AUTO: the rest of the batch -- the windows ending at or after base position `from` -- goes to the sort path
+    void to_sort_path(kmc_ctx* c, u64 from) {
+        sort_from = from;
+        run_sort = true;
+        mixed = true;
+        c->prefer_sort = true;
+        c->st.algo_last = KMC_ALGO_SORT;
+    }
+};
+
+// What a batch settles first: a queued finalize, a drained table, the previous batch's counters and (k+16)-mer counts
+int begin_batch(kmc_ctx* c) {
     { int rc = resolve_async(c); if (rc) return rc; }
     { int rc = undrain(c); if (rc) return rc; }
     if (c->pending) { int rc = poll_and_settle(c); if (rc) return rc; }
     // the previous batch's (k+16)-mer counts, if it left any: the counters are as of a poll that came after
     // its last launch (every launch sets `pending`), so an empty table is known to be empty
-    {
-        const bool unfolds = c->sk_dirty && c->h_sk_counters && c->h_sk_counters[KMC_CTR_KMERS] != 0;
-        int rc = settle_sk_polled(c);
-        if (rc) return rc;
-        // the unfold just queued changes the table: the launch planner (and the table it saves in front of a risky
-        // launch) must see the table as it will be, not as the poll above found it.  (Without this second poll a
-        // second high-cardinality batch under KMC_ALGO_WALK saved "a small table" that held millions of entries by
-        // the time the snapshot ran: counts of the first batch were lost or KMC_ERR_CAPACITY raised --
-        // tools/stress_sort_lr.py found it, test_walk_two_high_cardinality_batches pins it.)
-        if (unfolds) { rc = poll_and_settle(c); if (rc) return rc; }
-    }
-    c->recovered = false;
-    c->sorted_valid = false;
-    // (for drop_batch_from_table: did this batch start on an empty table?  The counters are as of a poll.)
-    const bool batch_on_empty_table = !c->pending && c->h_counters[KMC_CTR_OCCUPIED] == 0 && c->h_counters[KMC_CTR_SPILL] == 0;
-    u64 ctr0[KMC_CTR_N];
-    memcpy(ctr0, c->h_counters, sizeof(ctr0));
-    c->st.n_reads += n_reads;
-    c->st.n_bases += n_bases;
-    c->st.n_batches += 1;
-    if (!n_reads || !n_bases) return KMC_OK;
+    const bool unfolds = c->sk_dirty && c->h_sk_counters && c->h_sk_counters[KMC_CTR_KMERS] != 0;
+    int rc = settle_sk_polled(c);
+    if (rc) return rc;
+    // the unfold just queued changes the table: the launch planner (and the table it saves in front of a risky
+    // launch) must see the table as it will be, not as the poll above found it.  (Without this second poll a
+    // second high-cardinality batch under KMC_ALGO_WALK saved "a small table" that held millions of entries by
+    // the time the snapshot ran: counts of the first batch were lost or KMC_ERR_CAPACITY raised --
+    // tools/stress_sort_lr.py found it, test_walk_two_high_cardinality_batches pins it.)
+    if (unfolds) { rc = poll_and_settle(c); if (rc) return rc; }
+    return KMC_OK;
+}
 
+// The path of a batch: the configured one, or AUTO's choice.  Finds *max_read_len when the caller did not give it.
+int choose_algo(kmc_ctx* c, const u64* d_offsets, u64 n_reads, u64* max_read_len, int* algo_out) {
     int algo = c->cfg.algo;
     if (c->cfg.mode == KMC_MODE_LR) algo = KMC_ALGO_STREAM;  // LR runs its own kernel (kmc_lr.hip.h)
     if (algo == KMC_ALGO_AUTO && !c->prefer_sort && c->walk_ms_per_base > 0) {
@@ -1261,339 +1315,305 @@ int count_batch_device_body(kmc_ctx* c, const uint8_t* d_bases, const u64* d_off
     }
     if (algo == KMC_ALGO_AUTO && (c->prefer_sort || c->sort_by_cost)) algo = KMC_ALGO_SORT;
     if (algo == KMC_ALGO_AUTO || algo == KMC_ALGO_WALK) {
-        if (!max_read_len) {
+        if (!*max_read_len) {
             HIPCHK(c, hipMemsetAsync(&c->d_counters[KMC_CTR_MAXLEN], 0, sizeof(u64), c->stream));
             hipLaunchKernelGGL(kmc_maxlen_kernel, dim3(grid_for(c, n_reads, 256)), dim3(256), 0, c->stream, d_offsets, n_reads, c->d_counters);
             HIPCHK(c, hipGetLastError());
             int rc = poll(c);
             if (rc) return rc;
-            max_read_len = c->h_counters[KMC_CTR_MAXLEN];
+            *max_read_len = c->h_counters[KMC_CTR_MAXLEN];
         }
-        bool walk_ok = kmc_walk_supported(c->cfg.k, c->cfg.mode, max_read_len) && n_reads < (1ull << 32);
+        bool walk_ok = kmc_walk_supported(c->cfg.k, c->cfg.mode, *max_read_len) && n_reads < (1ull << 32);
         if (algo == KMC_ALGO_AUTO && c->walk_overflowed) walk_ok = false;  // high-cardinality input: memo tables do not help
         if (algo == KMC_ALGO_WALK && !walk_ok)
             return fail(c, KMC_ERR_ARG, "KMC_ALGO_WALK needs contiguous-k mode, k <= %d and fewer than 2^32 reads", KMC_WALK_MAX_K);
         algo = walk_ok ? KMC_ALGO_WALK : KMC_ALGO_STREAM;
     }
+    *algo_out = algo;
+    return KMC_OK;
+}
+
+// Reference mode (main.rs:63-81): every window start contributes up to 61 keys (27 + gap + 27 for
+// sizes 80..=140), and almost every key is new (1.08 M distinct of 3.55 M on the fixture): the keys
+// are FORMED and grouped by the radix sort + run-length, like the reference's own push + sort()
+// (main.rs:79,87) -- no hash table, no per-occurrence atomics -- as pairs of 27-mer ranks
+// (kmc_lr.hip.h): sort the batch's 27-mers once, then sort one-word rank pairs.
+// Sub-batches of 2^25 window starts (61 x 8 B x 2 buffers = 32 GiB of keys in flight at most).
+int count_lr(kmc_ctx* c, const uint8_t* d_bases, const u64* d_offsets, u64 n_reads, u64 n_bases) {
+    const u64 per = KMC_LRX_NS;
+    const u64 SB = 1ull << 25;
+    int rc;
+    for (u64 p0 = 0; p0 < n_bases; p0 += SB) {
+        const u64 p1 = std::min(n_bases, p0 + SB);
+        const u64 n = (p1 - p0) * per;
+        const u64 q0 = p0, q1 = std::min(n_bases, p1 + KMC_LRX_DMAX);
+        const u64 nq = q1 - q0;
+        for (int i = 0; i < 2; ++i) {
+            rc = ensure(c, c->s_lo[i], (size_t)std::max(n, nq) * sizeof(u64)); if (rc) return rc;
+        }
+        rc = ensure(c, c->lr_rank, (size_t)nq * sizeof(u32)); if (rc) return rc;
+        rc = launch_begin(c);
+        if (rc) return rc;
+        u64* const khi[2] = {(u64*)c->s_hi[0].p, (u64*)c->s_hi[1].p};
+        u64* const klo[2] = {(u64*)c->s_lo[0].p, (u64*)c->s_lo[1].p};
+        u64* const kwt[2] = {nullptr, nullptr};
+        // 1. the batch's distinct 27-mers, ordered: the dictionary
+        const unsigned mer_grid = (unsigned)((nq + KMC_LRX_POS - 1) / KMC_LRX_POS);
+        hipLaunchKernelGGL(kmc_lr_mer_kernel<0>, dim3(mer_grid), dim3(KMC_LRX_THREADS), 0, c->stream,
+                           d_bases, n_bases, q0, q1, klo[0], (const u64*)nullptr, 0u, (u32*)nullptr);
+        HIPCHK(c, hipGetLastError());
+        kmc_ctx::Run mers;
+        rc = msd_sort_to_run(c, khi, klo, kwt, nq, 2u * KMC_LR_L, 1, &mers, true);
+        if (rc) return rc;
+        const u64 n_distinct = mers.n;
+        if (n_distinct) {  // 2. every position's rank in it
+            hipLaunchKernelGGL(kmc_lr_mer_kernel<1>, dim3(mer_grid), dim3(KMC_LRX_THREADS), 0, c->stream,
+                               d_bases, n_bases, q0, q1, (u64*)nullptr, (const u64*)mers.lo, (u32)n_distinct, (u32*)c->lr_rank.p);
+            HIPCHK(c, hipGetLastError());
+            // 3. every key as a pair of ranks, sorted and run-length counted; 4. back to 108-bit keys
+            int B = 1;
+            while ((1ull << B) < n_distinct) ++B;
+            hipLaunchKernelGGL(kmc_lr_pair_kernel, dim3((unsigned)((p1 - p0 + KMC_LRX_POS - 1) / KMC_LRX_POS)), dim3(KMC_LRX_THREADS), 0, c->stream,
+                               d_offsets, n_reads, p0, p1, q0, nq, (const u32*)c->lr_rank.p, B, klo[0], c->d_counters);
+            HIPCHK(c, hipGetLastError());
+            kmc_ctx::Run run;
+            rc = msd_sort_to_run(c, khi, klo, kwt, n, 2u * (unsigned)B, 1, &run, true);
+            if (rc) { c->run_pool.push_back(mers); return rc; }
+            hipLaunchKernelGGL(kmc_lr_addcount_kernel, dim3(1), dim3(64), 0, c->stream, (const u32*)&((const MsdCtl*)c->m_ctl.p)->n_valid, c->d_counters);
+            if (run.n) {
+                hipLaunchKernelGGL(kmc_lr_compose_kernel, dim3(grid_for(c, run.n, 256)), dim3(256), 0, c->stream, run.hi, run.lo, run.n, (const u64*)mers.lo, B);
+                HIPCHK(c, hipGetLastError());
+                c->runs.push_back(run);
+            } else if (run.lo) c->run_pool.push_back(run);
+        }
+        if (mers.lo) c->run_pool.push_back(mers);  // (stream order: the compose kernel is queued before any later use)
+        rc = launch_end(c);
+        if (rc) return rc;
+        c->pending = true;
+    }
+    return KMC_OK;
+}
+
+// the (k+16)-mer counts of the launches so far into the count table, and a poll behind them
+int unfold_and_poll(kmc_ctx* c) {
+    int rc = flush_sk(c);
+    if (rc) return rc;
+    return poll_and_settle(c);
+}
+
+// the log of the steps that fall off the LDS memo (kmc_sklog.hip.h), sized for the worst case -- every step of the
+// launch -- up to 12 GiB; a workgroup whose span is full goes on with (k+16)-mer table updates
+int walk_log(kmc_ctx* c, u64 take, int wgrid, u64 max_read_len, SkLog* lg) {
+    const u32 words = c->cfg.k > KMC_SK_MAX_K ? 3u : 2u;
+    const u64 steps_per_read = std::min<u64>(std::max<u64>(max_read_len, 1), KMC_WALK_MAX_READ) / KMC_WALK_STRIDE + 1;
+    u64 cap = ((take + wgrid - 1) / wgrid + 1) * 64ull * steps_per_read;
+    cap = std::min<u64>(cap, (12ull << 30) / ((u64)wgrid * words * sizeof(u64)));
+    cap = std::max<u64>(cap, 1024);
+    // (the binned copy holds exactly the logged records: the same room as the log; fewer than 2^32 records)
+    if ((u64)wgrid * cap < (1ull << 32) &&
+        !ensure(c, c->lg_rec, (size_t)wgrid * cap * words * sizeof(u64)) && !ensure(c, c->lg_bins, (size_t)wgrid * cap * words * sizeof(u64)) &&
+        !ensure(c, c->lg_count, ((size_t)c->n_cu + (size_t)c->n_cu * KMC_SKLOG_BINS) * sizeof(u32)) && !ensure(c, c->lg_cursor, 2 * KMC_SKLOG_BINS * sizeof(u32))) {
+        HIPCHK(c, hipMemsetAsync(c->lg_count.p, 0, (size_t)c->n_cu * sizeof(u32), c->stream));
+        HIPCHK(c, hipMemsetAsync(c->lg_cursor.p, 0, 2 * KMC_SKLOG_BINS * sizeof(u32), c->stream));
+        *lg = SkLog{(u64*)c->lg_rec.p, (u32*)c->lg_count.p, (u32)cap, words};
+    } else {
+        c->err[0] = 0;   // (no memory for a log: the launch runs with table updates, as before)
+    }
+    return KMC_OK;
+}
+
+// The batch by the walk kernel (kmc_walk.hip.h) in planned launches; AUTO may hand the rest to the sort path
+int count_walk(kmc_ctx* c, BatchPlan& bp, const uint8_t* d_bases, const u64* d_offsets, u64 n_reads, u64 n_bases, u64 max_read_len) {
+    int rc;
+    if (!c->walk_memo.p || c->walk_overflowed) {
+        // (re)start from an empty memo: first use, or the last batch overflowed it (its entries
+        // were not representative; keeping them would only hold the tables full)
+        rc = ensure(c, c->walk_memo, kmc_walk_memo_bytes(c->n_cu, c->KW));
+        if (rc) return rc;
+        HIPCHK(c, hipMemsetAsync(c->walk_memo.p, 0, kmc_walk_memo_bytes(c->n_cu, c->KW), c->stream));
+        c->memo_parity = 0;
+        c->walk_overflowed = false;
+    }
+    // the reads the kernel walks: the batch's own, or pieces of <= KMC_WALK_MAX_READ bases
+    const u64 *d_vs = d_offsets, *d_ve = d_offsets + 1;
+    u64 n_v = n_reads;
+    if (max_read_len > KMC_WALK_MAX_READ) {
+        rc = build_vreads(c, d_offsets, n_reads, &n_v);
+        if (rc) return rc;
+        d_vs = (const u64*)c->vr_reads.p;
+        d_ve = d_vs + n_v;
+    }
+    rc = sk_ensure(c);
+    if (rc) return rc;
+    if (n_v >= (1ull << 32)) return fail(c, KMC_ERR_ARG, "batch too large for one walk pass: %llu read pieces; feed smaller batches", (unsigned long long)n_v);
+    {
+        void* before = c->walk_ws.p;
+        rc = ensure(c, c->walk_ws, kmc_walk_workspace_bytes(n_v));
+        if (rc) return rc;
+        if (c->walk_ws.p != before) c->walk_ws_clean = false;  // fresh memory: the host clears header + counters once
+    }
+    const u64 n_tiles = (n_v + 63) / 64;
+    const u64 kpt = 64 * std::min<u64>(std::max<u64>(max_read_len, 1), KMC_WALK_MAX_READ);  // k-mers per tile, upper bound
+    u64 done = 0, prev = 0;
+    while (done < n_tiles) {
+        u64 occ = c->h_counters[KMC_CTR_OCCUPIED];
+        const u64* d_from = done ? d_ve + (done * 64 - 1) : nullptr;   // (where a recovery starts: the end of the last piece walked)
+        u64 take = bp.plan(c, n_tiles - done, kpt, prev);
+        if (c->sk_dirty && take > bp.safe) {
+            // A launch that rests on a prediction is about to save the table: the (k+16)-mer counts of
+            // the launches before it must be IN that table first (a recovery drops the (k+16)-mer
+            // table's counts together with the failed launch's).  This is a poll point: the unfold is
+            // sized exactly, and one more poll tells the planner what the table looks like now.
+            rc = unfold_and_poll(c);
+            if (rc) return rc;
+            if (c->recovered) break;
+            take = bp.plan(c, n_tiles - done, kpt, prev);
+        }
+        if (take > bp.safe && !arm_risky(c, d_bases, d_offsets, n_reads, n_bases, 0, d_from))
+            take = bp.safe;  // (the table cannot be saved cheaply: stay within what fits for certain)
+        // the (k+16)-mer table takes one entry per step at most: a launch that could fill it is risky too;
+        // if the count table cannot be saved, this launch runs without the second-level memo
+        GTable skt = sk_table_of(c);
+        if (skt.key_lo && !c->risky.armed) {
+            const u64 max_adds = take * 64ull * (KMC_WALK_MAX_READ / KMC_WALK_STRIDE + 1);
+            if ((c->h_sk_counters[KMC_CTR_OCCUPIED] + max_adds) * 4 > c->sk.cap * 3 && c->sk_dirty) {
+                rc = unfold_and_poll(c);   // (as above: nothing of earlier launches may be lost with this one)
+                if (rc) return rc;
+                if (c->recovered) break;
+                skt = sk_table_of(c);  // (the flush may have re-allocated it larger)
+            }
+            if ((c->h_sk_counters[KMC_CTR_OCCUPIED] + max_adds) * 4 > c->sk.cap * 3 && !arm_risky(c, d_bases, d_offsets, n_reads, n_bases, 0, d_from))
+                skt = GTable{};
+        }
+        SkLog lg{};
+        const int wgrid = kmc_walk_grid(take, c->n_cu);
+        if (c->sklog_on && skt.key_lo) { rc = walk_log(c, take, wgrid, max_read_len, &lg); if (rc) return rc; }
+        if (!c->walk_ws_clean) {  // (normally the unfold kernel of the previous launch left it clean)
+            rc = kmc_walk_prepare(c->stream, c->walk_ws.p);
+            if (rc) return fail(c, rc, "walk workspace reset failed");
+        }
+        c->walk_ws_clean = false;
+        hipEvent_t we0 = nullptr, we1 = nullptr;   // the walk kernel's own start / stop timestamps (no event packets in the stream)
+        rc = launch_events(c, &we0, &we1);
+        if (rc) return rc;
+        rc = kmc_walk_launch(c->stream, c->n_cu, c->KW, c->cfg.k, c->cfg.canonical != 0, d_bases, d_vs, d_ve, n_v, n_bases,
+                             done, done + take, c->walk_ws.p, c->walk_memo.p, c->memo_parity, gtable_of(c, c->tab), skt, lg, 0, we0, we1);
+        if (rc) return fail(c, rc, "walk kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+        c->batch_pending = true;
+        if (skt.key_lo) c->sk_dirty = true;
+        rc = kmc_walk_launch(c->stream, c->n_cu, c->KW, c->cfg.k, c->cfg.canonical != 0, d_bases, d_vs, d_ve, n_v, n_bases,
+                             done, done + take, c->walk_ws.p, c->walk_memo.p, c->memo_parity, gtable_of(c, c->tab), skt, lg, 1, nullptr, nullptr);
+        if (rc) return fail(c, rc, "scalar/unfold kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+        if (lg.rec) {   // count what the launch logged: partition by hash, LDS tables, one unfold per distinct (k+16)-mer
+            rc = launch_begin(c);
+            if (!rc) rc = launch_sklog(c, lg, (u32)wgrid);
+            if (!rc) rc = launch_end(c);
+            if (rc) return rc;
+        }
+        c->walk_ws_clean = true;
+        if (!c->tb.empty()) c->tb.back().count_launches++;
+        c->memo_parity ^= 1;
+        c->pending = true;
+        done += take;
+        prev = take;
+        if (done == n_tiles) break;
+        rc = bp.observe(c, occ, take, kpt);
+        if (rc) return rc;
+        if (c->recovered) break;  // (the sort path has counted the rest of the batch)
+        if (c->cfg.algo == KMC_ALGO_AUTO && (c->walk_overflowed || (c->rho_last > 0.5 && (take >= 512 || done * 2 >= n_tiles)))) {
+            // (the new-key rate only counts once a launch was large -- 512 tiles, 13 M k-mers: the third launch of the
+            // ramp used to put another 200 M k-mers into the table before the hand-over -- or half the batch is through: the
+            // first tiles of ANY input are all new)
+            // the memos do not help on this input (both levels overflow, or more than one k-mer in
+            // five is new: per-occurrence table updates are the wrong tool): hand the rest
+            // of the batch to the sort path
+            // ... from the end of the last piece walked: the windows ENDING before it are counted
+            u64 pos = 0;
+            if (bp.on_empty_table) {
+                rc = drop_batch_from_table(c, bp.ctr0);   // (the whole batch goes to the sort path)
+                if (rc) return rc;
+            } else {
+                HIPCHK(c, hipMemcpyAsync(&pos, d_ve + (done * 64 - 1), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(c, hipStreamSynchronize(c->stream));
+            }
+            bp.to_sort_path(c, pos);
+            break;
+        }
+    }
+    return KMC_OK;
+}
+
+// The batch by the stream kernel (kmc_stream.hip.h) in planned launches; AUTO may hand the rest to the sort path
+int count_stream(kmc_ctx* c, BatchPlan& bp, const uint8_t* d_bases, const u64* d_offsets, u64 n_reads, u64 n_bases) {
+    const u64 n_chunks = (n_bases + KMC_CHUNK - 1) / KMC_CHUNK;
+    u64 done = 0, prev = 0;
+    while (done < n_chunks) {
+        u64 occ = c->h_counters[KMC_CTR_OCCUPIED];
+        u64 take = bp.plan(c, n_chunks - done, KMC_CHUNK, prev);
+        if (take > bp.safe && !arm_risky(c, d_bases, d_offsets, n_reads, n_bases, done * KMC_CHUNK, nullptr))
+            take = bp.safe;
+        int rc = launch_stream(c, d_bases, d_offsets, n_reads, n_bases, done, done + take, 0);
+        if (rc) return rc;
+        c->pending = true;
+        done += take;
+        prev = take;
+        if (done == n_chunks) break;
+        rc = bp.observe(c, occ, take, KMC_CHUNK);
+        if (rc) return rc;
+        if (c->recovered) break;
+        if (c->cfg.algo == KMC_ALGO_AUTO && (c->rho_last > 0.2 || c->walk_overflowed)) {
+            // many new keys per k-mer, or the LDS partial tables overflow and most k-mers go to
+            // global atomics anyway: per-occurrence hashing is the wrong tool
+            bp.to_sort_path(c, done * KMC_CHUNK);
+            break;
+        }
+    }
+    return KMC_OK;
+}
+
+// One batch: settle what came before it, choose its path, count it (LR, walk or stream), sort what is left to sorting
+int count_batch_device_body(kmc_ctx* c, const uint8_t* d_bases, const u64* d_offsets, u64 n_reads, u64 n_bases, u64 max_read_len) {
+    int rc = begin_batch(c);
+    if (rc) return rc;
+    c->recovered = false;
+    c->sorted_valid = false;
+    BatchPlan bp;
+    // (for drop_batch_from_table: did this batch start on an empty table?  The counters are as of a poll.)
+    bp.on_empty_table = !c->pending && c->h_counters[KMC_CTR_OCCUPIED] == 0 && c->h_counters[KMC_CTR_SPILL] == 0;
+    memcpy(bp.ctr0, c->h_counters, sizeof(bp.ctr0));
+    c->st.n_reads += n_reads;
+    c->st.n_bases += n_bases;
+    c->st.n_batches += 1;
+    if (!n_reads || !n_bases) return KMC_OK;
+    int algo = KMC_ALGO_AUTO;
+    rc = choose_algo(c, d_offsets, n_reads, &max_read_len, &algo);
+    if (rc) return rc;
     c->st.algo_last = algo;
 
     c->tb.emplace_back();    // this batch's launch events
     c->tb.back().n_bases = n_bases;
-    int rc = KMC_OK;
-    bool batch_mixed = false;   // the batch changed path in the middle: not a rate sample of either
-    {
-        // Sub-batches.  A launch over n k-mers can add at most n new keys, so without history the
-        // first launch is sized to what the table and spill area absorb for certain and later ones
-        // ramp up (x16 at most) using the observed ratio rho = new keys per k-mer.  With history
-        // (the previous batch on this ctx, kept across kmc_reset) the batch goes out in as few
-        // launches as 8 x the predicted number of new keys allows -- one for the benchmark input.
-        // A launch larger than what is certain to fit is "risky": the table is saved in front of it
-        // (arm_risky) and, should the prediction be wrong enough to exhaust table AND spill area, the
-        // next poll puts the table back and counts the rest of the batch by sorting (recover_overflow):
-        // nothing is dropped and nothing fails.  The caller's device buffers must therefore stay valid
-        // until the next call on the ctx that synchronises (kmc.h, kmc_add_batch_device).
-        double batch_rho_max = 0.0;
-        u64 plan_safe = 0;  // units of the last plan() that fit for certain
-        c->b_occ0 = c->h_counters[KMC_CTR_OCCUPIED];
-        c->b_kmers = std::max<u64>(n_bases, 1);
-        auto plan = [&](u64 units_left, u64 kmers_per_unit, u64 prev) -> u64 {
-            u64 occ = c->h_counters[KMC_CTR_OCCUPIED];
-            u64 freeslots = (c->tab.cap * 7 / 10 > occ ? c->tab.cap * 7 / 10 - occ : 0) + c->spill_cap / 2;
-            u64 safe = std::max<u64>(freeslots / kmers_per_unit, 1);
-            plan_safe = safe;
-            u64 take = safe;
-            if (prev) {
-                double opt = (double)freeslots / (4.0 * std::max(c->rho_last, 1e-9)) / (double)kmers_per_unit;
-                take = std::max<u64>(safe, (u64)std::min<double>(opt, (double)prev * 16.0));
-            } else if (c->rho_hist >= 0.0) {
-                // history says rho_hist new keys per k-mer.  A launch may bring 8 x that -- 3 x when the table is known to be
-                // empty: then "saving" it costs nothing, a whole batch of the same source brings what the last one brought
-                // (rho_hist is a whole-batch ratio), and a table with room for 3 x of it takes the batch in ONE launch
-                // (pool 100 of the cardinality sweep went out in four launches with a host poll behind each: 2.9 ms per GB)
-                const bool empty = occ == 0 && c->h_counters[KMC_CTR_SPILL] == 0 && !c->pending;
-                double opt = (double)freeslots / ((empty ? 3.0 : 8.0) * std::max(c->rho_hist, 1e-9)) / (double)kmers_per_unit;
-                take = std::max<u64>(safe, (u64)std::min<double>(opt, 1e18));
-            }
-            return std::min<u64>(take, units_left);
-        };
-        double observed_kmers = 0.0;
-        u64 sk_seen = c->sk.lo ? c->h_sk_counters[KMC_CTR_OCCUPIED] + c->h_sk_counters[KMC_CTR_SPILL] : 0;
-        auto observe = [&](u64 occ_before, u64 units, u64 kmers_per_unit) -> int {
-            int r = poll_and_settle(c);
-            if (r) return r;
-            if (c->recovered) return KMC_OK;
-            u64 occ_after = c->h_counters[KMC_CTR_OCCUPIED];
-            // keys still waiting in the (k+16)-mer table count as well: each entry becomes up to 16 k-mers at the unfold
-            const u64 sk_after = c->sk.lo ? c->h_sk_counters[KMC_CTR_OCCUPIED] + c->h_sk_counters[KMC_CTR_SPILL] : 0;
-            const u64 sk_new = sk_after > sk_seen ? sk_after - sk_seen : 0;
-            sk_seen = sk_after;
-            double rho = ((double)(occ_after > occ_before ? occ_after - occ_before : 0) + 16.0 * (double)sk_new) / ((double)units * (double)kmers_per_unit);
-            c->rho_last = rho;
-            c->rho_max = std::max(c->rho_max, rho);
-            batch_rho_max = std::max(batch_rho_max, rho);
-            // history for later batches from what has been observed of this one so far; the poll after
-            // the batch's last launch (kmc_finalize) replaces it with the whole batch's ratio -- but a
-            // caller that never finalizes this ctx (multi-GPU reduce: the live table is packed and the
-            // ctx reset) must not start every batch without history
-            observed_kmers += (double)units * (double)kmers_per_unit;
-            u64 occ_all = occ_after + c->h_counters[KMC_CTR_SPILL];
-            c->rho_hist = (double)(occ_all > c->b_occ0 ? occ_all - c->b_occ0 : 0) / std::max(observed_kmers, 1.0);
-            return KMC_OK;
-        };
-        const bool lr = c->cfg.mode == KMC_MODE_LR;
-        if (lr) {
-            // Reference mode (main.rs:63-81): every window start contributes up to 61 keys (27 + gap + 27 for
-            // sizes 80..=140), and almost every key is new (1.08 M distinct of 3.55 M on the fixture): the keys
-            // are FORMED and grouped by the radix sort + run-length, like the reference's own push + sort()
-            // (main.rs:79,87) -- no hash table, no per-occurrence atomics -- as pairs of 27-mer ranks
-            // (kmc_lr.hip.h): sort the batch's 27-mers once, then sort one-word rank pairs.
-            // Sub-batches of 2^25 window starts (61 x 8 B x 2 buffers = 32 GiB of keys in flight at most).
-            const u64 per = KMC_LRX_NS;
-            const u64 SB = 1ull << 25;
-            for (u64 p0 = 0; p0 < n_bases; p0 += SB) {
-                const u64 p1 = std::min(n_bases, p0 + SB);
-                const u64 n = (p1 - p0) * per;
-                const u64 q0 = p0, q1 = std::min(n_bases, p1 + KMC_LRX_DMAX);
-                const u64 nq = q1 - q0;
-                for (int i = 0; i < 2; ++i) {
-                    rc = ensure(c, c->s_lo[i], (size_t)std::max(n, nq) * sizeof(u64)); if (rc) return rc;
-                }
-                rc = ensure(c, c->lr_rank, (size_t)nq * sizeof(u32)); if (rc) return rc;
-                rc = launch_begin(c);
-                if (rc) return rc;
-                u64* const khi[2] = {(u64*)c->s_hi[0].p, (u64*)c->s_hi[1].p};
-                u64* const klo[2] = {(u64*)c->s_lo[0].p, (u64*)c->s_lo[1].p};
-                u64* const kwt[2] = {nullptr, nullptr};
-                // 1. the batch's distinct 27-mers, ordered: the dictionary
-                const unsigned mer_grid = (unsigned)((nq + KMC_LRX_POS - 1) / KMC_LRX_POS);
-                hipLaunchKernelGGL(kmc_lr_mer_kernel<0>, dim3(mer_grid), dim3(KMC_LRX_THREADS), 0, c->stream,
-                                   d_bases, n_bases, q0, q1, klo[0], (const u64*)nullptr, 0u, (u32*)nullptr);
-                HIPCHK(c, hipGetLastError());
-                kmc_ctx::Run mers;
-                rc = msd_sort_to_run(c, khi, klo, kwt, nq, 2u * KMC_LR_L, 1, &mers, true);
-                if (rc) return rc;
-                const u64 n_distinct = mers.n;
-                if (n_distinct) {  // 2. every position's rank in it
-                    hipLaunchKernelGGL(kmc_lr_mer_kernel<1>, dim3(mer_grid), dim3(KMC_LRX_THREADS), 0, c->stream,
-                                       d_bases, n_bases, q0, q1, (u64*)nullptr, (const u64*)mers.lo, (u32)n_distinct, (u32*)c->lr_rank.p);
-                    HIPCHK(c, hipGetLastError());
-                }
-                if (n_distinct) {
-                    // 3. every key as a pair of ranks, sorted and run-length counted; 4. back to 108-bit keys
-                    int B = 1;
-                    while ((1ull << B) < n_distinct) ++B;
-                    hipLaunchKernelGGL(kmc_lr_pair_kernel, dim3((unsigned)((p1 - p0 + KMC_LRX_POS - 1) / KMC_LRX_POS)), dim3(KMC_LRX_THREADS), 0, c->stream,
-                                       d_offsets, n_reads, p0, p1, q0, nq, (const u32*)c->lr_rank.p, B, klo[0], c->d_counters);
-                    HIPCHK(c, hipGetLastError());
-                    kmc_ctx::Run run;
-                    rc = msd_sort_to_run(c, khi, klo, kwt, n, 2u * (unsigned)B, 1, &run, true);
-                    if (rc) { c->run_pool.push_back(mers); return rc; }
-                    hipLaunchKernelGGL(kmc_lr_addcount_kernel, dim3(1), dim3(64), 0, c->stream, (const u32*)&((const MsdCtl*)c->m_ctl.p)->n_valid, c->d_counters);
-                    if (run.n) {
-                        hipLaunchKernelGGL(kmc_lr_compose_kernel, dim3(grid_for(c, run.n, 256)), dim3(256), 0, c->stream, run.hi, run.lo, run.n, (const u64*)mers.lo, B);
-                        HIPCHK(c, hipGetLastError());
-                        c->runs.push_back(run);
-                    } else if (run.lo) c->run_pool.push_back(run);
-                }
-                if (mers.lo) c->run_pool.push_back(mers);  // (stream order: the compose kernel is queued before any later use)
-                rc = launch_end(c);
-                if (rc) return rc;
-                c->pending = true;
-            }
-        }
-        u64 stream_from = 0;  // base position from which the stream / sort path takes over
-        bool run_stream = (algo == KMC_ALGO_STREAM) && !lr;
-        bool run_sort = (algo == KMC_ALGO_SORT);
-        const bool is_auto = c->cfg.algo == KMC_ALGO_AUTO;
-        if (algo == KMC_ALGO_WALK) {
-            if (!c->walk_memo.p || c->walk_overflowed) {
-                // (re)start from an empty memo: first use, or the last batch overflowed it (its entries
-                // were not representative; keeping them would only hold the tables full)
-                rc = ensure(c, c->walk_memo, kmc_walk_memo_bytes(c->n_cu, c->KW));
-                if (rc) return rc;
-                HIPCHK(c, hipMemsetAsync(c->walk_memo.p, 0, kmc_walk_memo_bytes(c->n_cu, c->KW), c->stream));
-                c->memo_parity = 0;
-                c->walk_overflowed = false;
-            }
-            // the reads the kernel walks: the batch's own, or pieces of <= KMC_WALK_MAX_READ bases
-            const u64 *d_vs = d_offsets, *d_ve = d_offsets + 1;
-            u64 n_v = n_reads;
-            if (max_read_len > KMC_WALK_MAX_READ) {
-                rc = build_vreads(c, d_offsets, n_reads, &n_v);
-                if (rc) return rc;
-                d_vs = (const u64*)c->vr_reads.p;
-                d_ve = d_vs + n_v;
-            }
-            rc = sk_ensure(c);
-            if (rc) return rc;
-            if (n_v >= (1ull << 32)) return fail(c, KMC_ERR_ARG, "batch too large for one walk pass: %llu read pieces; feed smaller batches", (unsigned long long)n_v);
-            {
-                void* before = c->walk_ws.p;
-                rc = ensure(c, c->walk_ws, kmc_walk_workspace_bytes(n_v));
-                if (rc) return rc;
-                if (c->walk_ws.p != before) c->walk_ws_clean = false;  // fresh memory: the host clears header + counters once
-            }
-            const u64 n_tiles = (n_v + 63) / 64;
-            const u64 kpt = 64 * std::min<u64>(std::max<u64>(max_read_len, 1), KMC_WALK_MAX_READ);  // k-mers per tile, upper bound
-            u64 done = 0, prev = 0;
-            while (done < n_tiles) {
-                u64 occ = c->h_counters[KMC_CTR_OCCUPIED];
-                u64 take = plan(n_tiles - done, kpt, prev);
-                if (c->sk_dirty && take > plan_safe) {
-                    // A launch that rests on a prediction is about to save the table: the (k+16)-mer counts of
-                    // the launches before it must be IN that table first (a recovery drops the (k+16)-mer
-                    // table's counts together with the failed launch's).  This is a poll point: the unfold is
-                    // sized exactly, and one more poll tells the planner what the table looks like now.
-                    rc = flush_sk(c);
-                    if (rc) return rc;
-                    rc = poll_and_settle(c);
-                    if (rc) return rc;
-                    if (c->recovered) break;
-                    take = plan(n_tiles - done, kpt, prev);
-                }
-                if (take > plan_safe && !arm_risky(c, d_bases, d_offsets, n_reads, n_bases, 0, done ? d_ve + (done * 64 - 1) : nullptr))
-                    take = plan_safe;  // (the table cannot be saved cheaply: stay within what fits for certain)
-                // the (k+16)-mer table takes one entry per step at most: a launch that could fill it is risky too;
-                // if the count table cannot be saved, this launch runs without the second-level memo
-                GTable skt = sk_table_of(c);
-                if (skt.key_lo && !c->risky.armed) {
-                    const u64 max_adds = take * 64ull * (KMC_WALK_MAX_READ / KMC_WALK_STRIDE + 1);
-                    if ((c->h_sk_counters[KMC_CTR_OCCUPIED] + max_adds) * 4 > c->sk.cap * 3 && c->sk_dirty) {
-                        rc = flush_sk(c);   // (as above: nothing of earlier launches may be lost with this one)
-                        if (rc) return rc;
-                        rc = poll_and_settle(c);
-                        if (rc) return rc;
-                        if (c->recovered) break;
-                        skt = sk_table_of(c);  // (the flush may have re-allocated it larger)
-                    }
-                    if ((c->h_sk_counters[KMC_CTR_OCCUPIED] + max_adds) * 4 > c->sk.cap * 3 &&
-                        !arm_risky(c, d_bases, d_offsets, n_reads, n_bases, 0, done ? d_ve + (done * 64 - 1) : nullptr))
-                        skt = GTable{};
-                }
-                // the log of the steps that fall off the LDS memo (kmc_sklog.hip.h), sized for the worst case -- every step of the
-                // launch -- up to 12 GiB; a workgroup whose span is full goes on with (k+16)-mer table updates
-                SkLog lg{};
-                const int wgrid = kmc_walk_grid(take, c->n_cu);
-                if (c->sklog_on && skt.key_lo && !getenv("KMC_NO_SKLOG")) {
-                    const u32 words = c->cfg.k > KMC_SK_MAX_K ? 3u : 2u;
-                    const u64 steps_per_read = std::min<u64>(std::max<u64>(max_read_len, 1), KMC_WALK_MAX_READ) / KMC_WALK_STRIDE + 1;
-                    u64 cap = ((take + wgrid - 1) / wgrid + 1) * 64ull * steps_per_read;
-                    cap = std::min<u64>(cap, (12ull << 30) / ((u64)wgrid * words * sizeof(u64)));
-                    cap = std::max<u64>(cap, 1024);
-                    // (the binned copy holds exactly the logged records: the same room as the log; fewer than 2^32 records)
-                    if ((u64)wgrid * cap < (1ull << 32) &&
-                        !ensure(c, c->lg_rec, (size_t)wgrid * cap * words * sizeof(u64)) && !ensure(c, c->lg_bins, (size_t)wgrid * cap * words * sizeof(u64)) &&
-                        !ensure(c, c->lg_count, ((size_t)c->n_cu + (size_t)c->n_cu * KMC_SKLOG_BINS) * sizeof(u32)) && !ensure(c, c->lg_cursor, 2 * KMC_SKLOG_BINS * sizeof(u32))) {
-                        HIPCHK(c, hipMemsetAsync(c->lg_count.p, 0, (size_t)c->n_cu * sizeof(u32), c->stream));
-                        HIPCHK(c, hipMemsetAsync(c->lg_cursor.p, 0, 2 * KMC_SKLOG_BINS * sizeof(u32), c->stream));
-                        lg = SkLog{(u64*)c->lg_rec.p, (u32*)c->lg_count.p, (u32)cap, words};
-                    } else {
-                        c->err[0] = 0;   // (no memory for a log: the launch runs with table updates, as before)
-                    }
-                }
-                if (!c->walk_ws_clean) {  // (normally the unfold kernel of the previous launch left it clean)
-                    rc = kmc_walk_prepare(c->stream, c->walk_ws.p);
-                    if (rc) return fail(c, rc, "walk workspace reset failed");
-                }
-                c->walk_ws_clean = false;
-                hipEvent_t we0 = nullptr, we1 = nullptr;   // the walk kernel's own start / stop timestamps (no event packets in the stream)
-                static const bool ev_records = getenv("KMC_WALK_EVENT_RECORDS") != nullptr;   // (A/B switch: hipEventRecord around the launch instead)
-                if (ev_records) rc = launch_begin(c); else rc = launch_events(c, &we0, &we1);
-                if (rc) return rc;
-                rc = kmc_walk_launch(c->stream, c->n_cu, c->KW, c->cfg.k, c->cfg.canonical != 0, d_bases, d_vs, d_ve, n_v, n_bases,
-                                     done, done + take, c->walk_ws.p, c->walk_memo.p, c->memo_parity, gtable_of(c, c->tab), skt, lg, 0, we0, we1);
-                if (rc) return fail(c, rc, "walk kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
-                if (ev_records) { rc = launch_end(c); if (rc) return rc; }
-                c->batch_pending = true;
-                if (skt.key_lo) c->sk_dirty = true;
-                rc = kmc_walk_launch(c->stream, c->n_cu, c->KW, c->cfg.k, c->cfg.canonical != 0, d_bases, d_vs, d_ve, n_v, n_bases,
-                                     done, done + take, c->walk_ws.p, c->walk_memo.p, c->memo_parity, gtable_of(c, c->tab), skt, lg, 1);
-                if (rc) return fail(c, rc, "scalar/unfold kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
-                if (lg.rec) {   // count what the launch logged: partition by hash, LDS tables, one unfold per distinct (k+16)-mer
-                    rc = launch_begin(c);
-                    if (rc) return rc;
-                    rc = launch_sklog(c, lg, (u32)wgrid);
-                    if (rc) return rc;
-                    rc = launch_end(c);
-                    if (rc) return rc;
-                }
-                c->walk_ws_clean = true;
-                if (!c->tb.empty()) c->tb.back().count_launches++;
-                c->memo_parity ^= 1;
-                c->pending = true;
-                done += take;
-                prev = take;
-                if (done < n_tiles) {
-                    rc = observe(occ, take, kpt);
-                    if (rc) return rc;
-                    if (c->recovered) break;  // (the sort path has counted the rest of the batch)
-                    if (c->cfg.algo == KMC_ALGO_AUTO && (c->walk_overflowed || (c->rho_last > 0.5 && (take >= 512 || done * 2 >= n_tiles)))) {
-                        // (the new-key rate only counts once a launch was large -- 512 tiles, 13 M k-mers: the third launch of the
-                        // ramp used to put another 200 M k-mers into the table before the hand-over -- or half the batch is through: the
-                        // first tiles of ANY input are all new)
-                        // the memos do not help on this input (both levels overflow, or more than one k-mer in
-                        // five is new: per-occurrence table updates are the wrong tool): hand the rest
-                        // of the batch to the sort path
-                        // ... from the end of the last piece walked: the windows ENDING before it are counted
-                        u64 pos = 0;
-                        if (batch_on_empty_table) {
-                            rc = drop_batch_from_table(c, ctr0);   // (the whole batch goes to the sort path)
-                            if (rc) return rc;
-                        } else {
-                            HIPCHK(c, hipMemcpyAsync(&pos, d_ve + (done * 64 - 1), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-                            HIPCHK(c, hipStreamSynchronize(c->stream));
-                        }
-                        stream_from = pos;
-                        run_sort = true;
-                        batch_mixed = true;
-                        c->prefer_sort = true;
-                        c->st.algo_last = KMC_ALGO_SORT;
-                        break;
-                    }
-                }
-            }
-        }
-        if (c->recovered) { run_stream = false; run_sort = false; c->sk_dirty = false; }
-        if (run_stream) {
-            const u64 n_chunks = (n_bases + KMC_CHUNK - 1) / KMC_CHUNK;
-            u64 done = stream_from / KMC_CHUNK, prev = 0;
-            while (done < n_chunks) {
-                u64 occ = c->h_counters[KMC_CTR_OCCUPIED];
-                u64 take = plan(n_chunks - done, KMC_CHUNK, prev);
-                if (take > plan_safe && !arm_risky(c, d_bases, d_offsets, n_reads, n_bases, std::max<u64>(done * KMC_CHUNK, stream_from), nullptr))
-                    take = plan_safe;
-                rc = launch_stream(c, d_bases, d_offsets, n_reads, n_bases, done, done + take, stream_from);
-                if (rc) return rc;
-                c->pending = true;
-                done += take;
-                prev = take;
-                if (done < n_chunks) {
-                    rc = observe(occ, take, KMC_CHUNK);
-                    if (rc) return rc;
-                    if (c->recovered) break;
-                    if (is_auto && (c->rho_last > 0.2 || c->walk_overflowed)) {
-                        // many new keys per k-mer, or the LDS partial tables overflow and most k-mers go to
-                        // global atomics anyway: per-occurrence hashing is the wrong tool
-                        stream_from = done * KMC_CHUNK;
-                        run_sort = true;
-                        batch_mixed = true;
-                        c->prefer_sort = true;
-                        c->st.algo_last = KMC_ALGO_SORT;
-                        break;
-                    }
-                }
-            }
-        }
-        if (c->recovered) run_sort = false;
-        if (run_sort) {
-            rc = run_sort_path(c, d_bases, d_offsets, n_reads, n_bases, stream_from);
-            if (rc) return rc;
-        }
-        c->b_rho_max = batch_rho_max;  // the last launch's share is folded in by the next poll()
-        c->b_open = true;
-    }
-    if (!c->tb.empty()) c->tb.back().algo = ((batch_mixed || c->recovered) ? 0 : c->st.algo_last);
+    c->b_occ0 = c->h_counters[KMC_CTR_OCCUPIED];
+    c->b_kmers = std::max<u64>(n_bases, 1);
+    bp.sk_seen = c->sk.lo ? c->h_sk_counters[KMC_CTR_OCCUPIED] + c->h_sk_counters[KMC_CTR_SPILL] : 0;
+    bp.run_sort = algo == KMC_ALGO_SORT;
+    if (c->cfg.mode == KMC_MODE_LR) rc = count_lr(c, d_bases, d_offsets, n_reads, n_bases);
+    else if (algo == KMC_ALGO_WALK) rc = count_walk(c, bp, d_bases, d_offsets, n_reads, n_bases, max_read_len);
+    else if (algo == KMC_ALGO_STREAM) rc = count_stream(c, bp, d_bases, d_offsets, n_reads, n_bases);
+    if (rc) return rc;
+    if (c->recovered) c->sk_dirty = false;   // (recover_overflow has counted the rest of the batch by sorting)
+    else if (bp.run_sort) rc = run_sort_path(c, d_bases, d_offsets, n_reads, n_bases, bp.sort_from);
+    if (rc) return rc;
+    c->b_rho_max = bp.rho_max;  // the last launch's share is folded in by the next poll()
+    c->b_open = true;
+    if (!c->tb.empty()) c->tb.back().algo = ((bp.mixed || c->recovered) ? 0 : c->st.algo_last);
     return KMC_OK;
+}
+int count_batch_device(kmc_ctx* c, const uint8_t* d_bases, const u64* d_offsets, u64 n_reads, u64 n_bases, u64 max_read_len) {
+    const int rc = count_batch_device_body(c, d_bases, d_offsets, n_reads, n_bases, max_read_len);
+    // the events of finished batches are read here, BEHIND this batch's launches (or in kmc_get_stats / kmc_poll): in front of
+    // them the microseconds would lie between a step's synchronisation and its successor's first launch
+    if (c->tb.size() >= 4) harvest_timing(c);
+    return rc;
 }
 
 // kernel time of the last batch = sum over its count-kernel launches (host polls between sub-batches
@@ -1755,34 +1775,23 @@ static int kmc_create_impl(kmc_ctx** out, const kmc_config* cfg) {
 static int kmc_reset_impl(kmc_ctx* c) {
     if (!c) return KMC_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    if (c->async_fin) {
-        // a finalize is queued whose outcome nobody has looked at (kmc_finalize_async): it has drained the table or left it
-        // as it was -- the reset kernel decides on the device, nothing waits
-        c->async_fin = false;
-        c->drained = false;
-        c->sk_dirty = false;   // (kmc_finalize_async queued the unfold in front of its kernel, or the reset kernel drops what is pending)
-        GTable g = gtable_of(c, c->tab);
-        const int grid = reset_grid(c);
-        if (c->KW == 1) hipLaunchKernelGGL(kmc_reset_kernel<1>, dim3(grid), dim3(256), 0, c->stream, g, sk_table_of(c), c->fin_rank + 3);
-        else hipLaunchKernelGGL(kmc_reset_kernel<2>, dim3(grid), dim3(256), 0, c->stream, g, sk_table_of(c), c->fin_rank + 3);
-        HIPCHK(c, hipGetLastError());
-        c->fin_parity = 0;
-    } else if (c->drained) {
+    if (c->drained && !c->async_fin) {
         // the last kmc_finalize emptied the table into its sorted view (kmc_small_finalize_kernel): table and device
         // counters are already what the reset kernel would leave -- nothing to launch
         c->drained = false;
-        c->fin_parity = 0;
     } else {
-        // (counts pending in the (k+16)-mer table go with the table: the reset kernel clears them, nothing is unfolded first)
+        // A finalize queued by kmc_finalize_async whose outcome nobody has looked at has drained the table or left it as it
+        // was: the reset kernel decides on the device, nothing waits.  (Counts pending in the (k+16)-mer table go with the
+        // table: the reset kernel clears them, nothing is unfolded first.)
+        const bool queued = c->async_fin;
+        c->async_fin = false;
+        c->drained = false;
         c->sk_dirty = false;
-        if (c->sk_grow) { int r = sk_regrow(c); if (r) return r; }
-        GTable g = gtable_of(c, c->tab);
-        const int grid = reset_grid(c);
-        if (c->KW == 1) hipLaunchKernelGGL(kmc_reset_kernel<1>, dim3(grid), dim3(256), 0, c->stream, g, sk_table_of(c), c->fin_rank + 3);
-        else hipLaunchKernelGGL(kmc_reset_kernel<2>, dim3(grid), dim3(256), 0, c->stream, g, sk_table_of(c), c->fin_rank + 3);
+        if (!queued && c->sk_grow) { int r = sk_regrow(c); if (r) return r; }
+        launch_reset_table(c);
         HIPCHK(c, hipGetLastError());
-        c->fin_parity = 0;
     }
+    c->fin_parity = 0;
     memset(c->h_counters, 0, KMC_CTR_N * sizeof(u64));
     c->pending = false;
     c->polled_epoch = c->table_epoch;   // (an empty table is a known state)
@@ -1816,6 +1825,14 @@ static int kmc_add_batch_device_impl(kmc_ctx* c, const void* d_bases, const void
     return count_batch_device(c, (const uint8_t*)d_bases, (const u64*)d_offsets, n_reads, n_bases, max_read_len);
 }
 
+// The staging buffers of a host batch: the previous batch, which may still read them, is polled first
+static int stage_host_batch(kmc_ctx* c, u64 n_reads, u64 n_bases) {
+    if (c->pending) { int rc = poll_and_settle(c); if (rc) return rc; }
+    int rc = ensure(c, c->st_bases, n_bases + 64);
+    if (rc) return rc;
+    return ensure(c, c->st_offsets, (n_reads + 1) * sizeof(u64));
+}
+
 static int kmc_add_batch_impl(kmc_ctx* c, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads) {
     if (!c) return KMC_ERR_ARG;
     if (!n_reads) { c->st.n_batches += 1; return KMC_OK; }
@@ -1828,27 +1845,19 @@ static int kmc_add_batch_impl(kmc_ctx* c, const uint8_t* bases, const uint64_t* 
     }
     const u64 n_bases = offsets[n_reads];
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    if (c->pending) { int rc = poll_and_settle(c); if (rc) return rc; }  // previous batch may still read the staging area
-    int rc = ensure(c, c->st_bases, n_bases + 64);
-    if (rc) return rc;
-    rc = ensure(c, c->st_offsets, (n_reads + 1) * sizeof(u64));
-    if (rc) return rc;
+    { int rc = stage_host_batch(c, n_reads, n_bases); if (rc) return rc; }
     if (n_bases) HIPCHK(c, hipMemcpyAsync(c->st_bases.p, bases, n_bases, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->st_offsets.p, offsets, (n_reads + 1) * sizeof(u64), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));  // caller may reuse its buffers on return
     return count_batch_device(c, (const uint8_t*)c->st_bases.p, (const u64*)c->st_offsets.p, n_reads, n_bases, maxlen);
 }
 
-static int kmc_merge_pairs_device_impl(kmc_ctx* c, const void* d_key_hi, const void* d_key_lo, const void* d_count, uint64_t n) {
-    if (!c) return KMC_ERR_ARG;
-    if (!n) return KMC_OK;
-    if (!d_key_lo || !d_count) return fail(c, KMC_ERR_ARG, "null device pointer");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
+// What a merge of n pairs into the table does first: the outcome of a queued finalize, the view of a drained table back
+// in, and room for the worst case (every pair new).  Merges queued since the last poll are accounted with their upper
+// bound, so a series of merges (one per peer in the multi-GPU reduce) needs no host synchronisation in between.
+static int merge_begin(kmc_ctx* c, u64 n) {
     { int rc = resolve_async(c); if (rc) return rc; }
     { int rc = undrain(c); if (rc) return rc; }
-    // make room for the worst case (every pair new).  Merges queued since the last poll are
-    // accounted with their upper bound, so a series of merges (one per peer in the multi-GPU reduce)
-    // needs no host synchronisation in between.
     if (c->batch_pending || (c->h_counters[KMC_CTR_OCCUPIED] + c->unpolled_adds + n) * 2 > c->tab.cap) {
         if (c->pending) { int rc = poll_and_settle(c); if (rc) return rc; }
         u64 occ = c->h_counters[KMC_CTR_OCCUPIED];
@@ -1859,14 +1868,43 @@ static int kmc_merge_pairs_device_impl(kmc_ctx* c, const void* d_key_hi, const v
     }
     c->unpolled_adds += n;
     c->sorted_valid = false;
-    GTable g = gtable_of(c, c->tab);
-    int grid = grid_for(c, n, 256);
-    if (c->KW == 1) hipLaunchKernelGGL(kmc_merge_pairs_kernel<1>, dim3(grid), dim3(256), 0, c->stream, g, (const u64*)nullptr, (const u64*)d_key_lo, (const u64*)d_count, n);
-    else hipLaunchKernelGGL(kmc_merge_pairs_kernel<2>, dim3(grid), dim3(256), 0, c->stream, g, (const u64*)d_key_hi, (const u64*)d_key_lo, (const u64*)d_count, n);
+    return KMC_OK;
+}
+
+static int kmc_merge_pairs_device_impl(kmc_ctx* c, const void* d_key_hi, const void* d_key_lo, const void* d_count, uint64_t n) {
+    if (!c) return KMC_ERR_ARG;
+    if (!n) return KMC_OK;
+    if (!d_key_lo || !d_count) return fail(c, KMC_ERR_ARG, "null device pointer");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    { int rc = merge_begin(c, n); if (rc) return rc; }
+    launch_merge_pairs(c, (const u64*)d_key_hi, (const u64*)d_key_lo, (const u64*)d_count, n);
     HIPCHK(c, hipGetLastError());
     c->pending = true;
     c->table_epoch++;
     return KMC_OK;
+}
+
+// The view buffers a small-table finalize writes: room for its largest table
+static int ensure_small_view(kmc_ctx* c) {
+    const size_t fb = (size_t)KMC_FIN_KERNEL_MAX * sizeof(u64);
+    int rc = ensure(c, c->o_lo, fb);
+    if (!rc) rc = ensure(c, c->o_cnt, fb);
+    if (!rc && c->KW == 2) rc = ensure(c, c->o_hi, fb);
+    return rc;
+}
+// A poll of kmc_finalize, behind its own small-table finalize (fin) or plain, and settle; then the keys a recovery
+// extracted (the poll may have recovered an overflow by extracting the rest of a batch), sorted into a run
+static int finalize_poll(kmc_ctx* c, bool fin) {
+    int rc = fin ? poll_fin(c) : poll_and_settle(c);
+    if (!rc && fin) rc = settle(c);
+    if (!rc && c->acc_n) rc = flush_acc(c);
+    return rc;
+}
+// The small-table finalize once more, with the grid for the largest table it takes (fin_small_max), and its poll
+static int finalize_full_grid(kmc_ctx* c, int* grid) {
+    *grid = (int)(std::min<u64>(c->fin_small_max + c->fin_small_max / 4, KMC_FIN_KERNEL_MAX) / KMC_FIN_CHUNK + 8);
+    const int rc = launch_small_finalize(c, *grid);
+    return rc ? rc : finalize_poll(c, true);
 }
 
 static int kmc_finalize_impl(kmc_ctx* c, uint64_t* n_distinct, uint64_t* n_total) {
@@ -1886,18 +1924,15 @@ static int kmc_finalize_impl(kmc_ctx* c, uint64_t* n_distinct, uint64_t* n_total
     if (rc) return rc;
     if (c->runs.empty() && c->fin_hint <= c->fin_small_max) {
         // speculative small-table finalize, queued behind whatever is still running
-        const size_t fb = (size_t)KMC_FIN_KERNEL_MAX * sizeof(u64);
-        rc = ensure(c, c->o_lo, fb); if (rc) return rc;
-        rc = ensure(c, c->o_cnt, fb); if (rc) return rc;
-        if (c->KW == 2) { rc = ensure(c, c->o_hi, fb); if (rc) return rc; }
+        rc = ensure_small_view(c);
+        if (rc) return rc;
         fgrid_used = small_finalize_grid(c);
         rc = launch_small_finalize(c, fgrid_used);
         if (rc) return rc;
         tried_fast = true;
         if (c->tb.size() >= 4) harvest_timing(c);   // (older batches' events, while the GPU is busy with this one)
     }
-    rc = tried_fast ? poll_fin_and_settle(c) : poll_and_settle(c);
-    if (!rc && c->acc_n) rc = flush_acc(c);  // (the poll may have recovered an overflow by extracting the rest of a batch)
+    rc = finalize_poll(c, tried_fast);
     if (rc) return rc;
     if (c->sk_dirty) {
         // the last batch's walk launches may have left counts in the (k+16)-mer table: the poll tells
@@ -1907,15 +1942,7 @@ static int kmc_finalize_impl(kmc_ctx* c, uint64_t* n_distinct, uint64_t* n_total
         if (had) {  // the table changed under the speculative finalize: once more
             // (the unfold just queued fills the table: the poll behind it may find it grown or spilled -- settled there;
             // the second finalize kernel sees the (k+16)-mer table empty again and may drain)
-            bool again = false;
-            if (tried_fast && c->runs.empty()) {
-                fgrid_used = (int)(std::min<u64>(c->fin_small_max + c->fin_small_max / 4, KMC_FIN_KERNEL_MAX) / KMC_FIN_CHUNK + 8);
-                rc = launch_small_finalize(c, fgrid_used);
-                if (rc) return rc;
-                again = true;
-            }
-            rc = again ? poll_fin_and_settle(c) : poll_and_settle(c);
-    if (!rc && c->acc_n) rc = flush_acc(c);  // (the poll may have recovered an overflow by extracting the rest of a batch)
+            rc = tried_fast && c->runs.empty() ? finalize_full_grid(c, &fgrid_used) : finalize_poll(c, false);
             if (rc) return rc;
         }
     }
@@ -1923,11 +1950,7 @@ static int kmc_finalize_impl(kmc_ctx* c, uint64_t* n_distinct, uint64_t* n_total
     if (tried_fast && c->runs.empty() && c->h_counters[KMC_CTR_FASTFIN] != 1 && c->h_counters[KMC_CTR_SPILL] == 0 &&
         c->h_counters[KMC_CTR_OCCUPIED] > (u64)fgrid_used * KMC_FIN_CHUNK && c->h_counters[KMC_CTR_OCCUPIED] <= c->fin_small_max) {
         // the table outgrew the speculative grid (first finalize of a larger source): once more, full grid
-        fgrid_used = (int)(std::min<u64>(c->fin_small_max + c->fin_small_max / 4, KMC_FIN_KERNEL_MAX) / KMC_FIN_CHUNK + 8);
-        rc = launch_small_finalize(c, fgrid_used);
-        if (rc) return rc;
-        rc = poll_fin_and_settle(c);
-    if (!rc && c->acc_n) rc = flush_acc(c);  // (the poll may have recovered an overflow by extracting the rest of a batch)
+        rc = finalize_full_grid(c, &fgrid_used);
         if (rc) return rc;
     }
     const bool fast_done = tried_fast && c->h_counters[KMC_CTR_FASTFIN] == 1 && c->runs.empty();  // (the poll may have recovered an overflow: runs exist now)
@@ -2029,10 +2052,8 @@ static int kmc_finalize_async_impl(kmc_ctx* c) {
     HIPCHK(c, hipSetDevice(c->cfg.device));
     if (c->async_fin || (c->drained && c->sorted_valid)) return KMC_OK;   // (queued already / final already)
     if (!c->runs.empty() || c->acc_n) return kmc_finalize(c, nullptr, nullptr);
-    const size_t fb = (size_t)KMC_FIN_KERNEL_MAX * sizeof(u64);
-    int rc = ensure(c, c->o_lo, fb); if (rc) return rc;
-    rc = ensure(c, c->o_cnt, fb); if (rc) return rc;
-    if (c->KW == 2) { rc = ensure(c, c->o_hi, fb); if (rc) return rc; }
+    int rc = ensure_small_view(c);
+    if (rc) return rc;
     // Pending (k+16)-mer counts have to be in the table first.  Only the device knows whether there are any; while no poll has
     // ever seen that table in use on this source (sklog_on), none are expected and nothing is launched for them: the kernel
     // below checks, and gives up if the guess was wrong -- the next synchronising call then finalizes the ordinary way, and a
@@ -2046,29 +2067,42 @@ static int kmc_finalize_async_impl(kmc_ctx* c) {
     return KMC_OK;
 }
 
-static int kmc_export_impl(kmc_ctx* c, uint64_t* key_hi, uint64_t* key_lo, uint64_t* count, uint64_t cap) {
-    if (!c) return KMC_ERR_ARG;
-    { int rc = resolve_view(c); if (rc) return rc; }
-    if (!c->sorted_valid) return fail(c, KMC_ERR_STATE, "kmc_export before kmc_finalize");
-    const u64 n = c->n_sorted;
-    if (cap < n) return fail(c, KMC_ERR_ARG, "export capacity %llu < %llu distinct keys", (unsigned long long)cap, (unsigned long long)n);
-    if (!n) return KMC_OK;
-    if (!key_lo || !count) return fail(c, KMC_ERR_ARG, "null buffer");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    HIPCHK(c, hipMemcpyAsync(key_lo, c->v_lo, n * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(count, c->v_cnt, n * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+// What the calls that read the view check first: resolve_view, the count range (max_count != 0), that there is a view
+static int view_begin(kmc_ctx* c, const char* what, uint64_t min_count = 0, uint64_t max_count = 0) {
+    int rc = resolve_view(c);
+    if (rc) return rc;
+    if (max_count && min_count > max_count)
+        return fail(c, KMC_ERR_ARG, "%s: min_count %llu > max_count %llu", what, (unsigned long long)min_count, (unsigned long long)max_count);
+    if (!c->sorted_valid) return fail(c, KMC_ERR_STATE, "%s before kmc_finalize", what);
+    return KMC_OK;
+}
+
+// n entries of a table on the device into the caller's arrays (key_hi: optional, zeros for one-word keys)
+static int copy_to_host(kmc_ctx* c, const void* hi, const void* lo, const void* cnt, u64 n, uint64_t* key_hi, uint64_t* key_lo, uint64_t* count) {
+    HIPCHK(c, hipMemcpyAsync(key_lo, lo, n * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(count, cnt, n * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     if (key_hi) {
-        if (c->KW == 2) HIPCHK(c, hipMemcpyAsync(key_hi, c->v_hi, n * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+        if (c->KW == 2) HIPCHK(c, hipMemcpyAsync(key_hi, hi, n * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
         else memset(key_hi, 0, n * sizeof(u64));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return KMC_OK;
 }
 
+static int kmc_export_impl(kmc_ctx* c, uint64_t* key_hi, uint64_t* key_lo, uint64_t* count, uint64_t cap) {
+    if (!c) return KMC_ERR_ARG;
+    { int rc = view_begin(c, "kmc_export"); if (rc) return rc; }
+    const u64 n = c->n_sorted;
+    if (cap < n) return fail(c, KMC_ERR_ARG, "export capacity %llu < %llu distinct keys", (unsigned long long)cap, (unsigned long long)n);
+    if (!n) return KMC_OK;
+    if (!key_lo || !count) return fail(c, KMC_ERR_ARG, "null buffer");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    return copy_to_host(c, c->v_hi, c->v_lo, c->v_cnt, n, key_hi, key_lo, count);
+}
+
 static int kmc_export_device_impl(kmc_ctx* c, const void** d_key_hi, const void** d_key_lo, const void** d_count, uint64_t* n_distinct) {
     if (!c) return KMC_ERR_ARG;
-    { int rc = resolve_view(c); if (rc) return rc; }
-    if (!c->sorted_valid) return fail(c, KMC_ERR_STATE, "kmc_export_device before kmc_finalize");
+    { int rc = view_begin(c, "kmc_export_device"); if (rc) return rc; }
     if (c->view_unsynced) {   // (see poll_fin: the finalize kernel told the host it was done before it ended)
         HIPCHK(c, hipSetDevice(c->cfg.device));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2086,8 +2120,7 @@ extern "C" uint32_t kmc_owner_of(uint64_t key_hi, uint64_t key_lo, uint32_t n_pa
 static int kmc_partition_device_impl(kmc_ctx* c, uint32_t n_parts, uint64_t* part_begin, const void** d_key_hi,
                                     const void** d_key_lo, const void** d_count) {
     if (!c || !n_parts || !part_begin) return KMC_ERR_ARG;
-    { int rc = resolve_view(c); if (rc) return rc; }
-    if (!c->sorted_valid) return fail(c, KMC_ERR_STATE, "kmc_partition_device before kmc_finalize");
+    { int rc = view_begin(c, "kmc_partition_device"); if (rc) return rc; }
     HIPCHK(c, hipSetDevice(c->cfg.device));
     const u64 n = c->n_sorted;
     const size_t nb = (size_t)std::max<u64>(n, 1) * sizeof(u64);
@@ -2127,23 +2160,13 @@ static int kmc_partition_device_impl(kmc_ctx* c, uint32_t n_parts, uint64_t* par
 }
 
 // ---- abundance histogram and count-range filter of the sorted view (kmc_spectrum.hip.h) ----
-// What the three calls share: a queued finalize counts as one (resolve_view), a sane range, a view to read.
-static int spectrum_begin(kmc_ctx* c, const char* what, uint64_t min_count, uint64_t max_count) {
-    int rc = resolve_view(c);
-    if (rc) return rc;
-    if (max_count && min_count > max_count)
-        return fail(c, KMC_ERR_ARG, "%s: min_count %llu > max_count %llu", what, (unsigned long long)min_count, (unsigned long long)max_count);
-    if (!c->sorted_valid) return fail(c, KMC_ERR_STATE, "%s before kmc_finalize", what);
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    return KMC_OK;
-}
-
 static bool filter_is_identity(uint64_t min_count, uint64_t max_count) { return min_count <= 1 && max_count == 0; }
 
 static int kmc_histogram_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint32_t n_bins, uint64_t* hist, uint64_t* max_seen) {
     if (!c) return KMC_ERR_ARG;
-    int rc = spectrum_begin(c, "kmc_histogram", min_count, max_count);
+    int rc = view_begin(c, "kmc_histogram", min_count, max_count);
     if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
     if (n_bins < 2 || n_bins > (1u << 24)) return fail(c, KMC_ERR_ARG, "kmc_histogram: n_bins %u outside 2..2^24", n_bins);
     if (!hist) return fail(c, KMC_ERR_ARG, "kmc_histogram: null histogram");
     const u64 n = c->n_sorted;
@@ -2230,16 +2253,13 @@ static int filter_scatter(kmc_ctx* c, u64 lo_c, u64 hi_c, u64 n_kept) {
 static int kmc_filter_device_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, const void** d_key_hi, const void** d_key_lo,
                                   const void** d_count, uint64_t* n_kept, uint64_t* kept_total) {
     if (!c) return KMC_ERR_ARG;
-    int rc = spectrum_begin(c, "kmc_filter_device", min_count, max_count);
+    int rc = view_begin(c, "kmc_filter_device", min_count, max_count);
     if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
     if (filter_is_identity(min_count, max_count)) {   // keeps everything: the view itself, nothing launched
-        const void *h = nullptr, *l = nullptr, *k = nullptr;
         uint64_t nd = 0;
-        rc = kmc_export_device_impl(c, &h, &l, &k, &nd);
+        rc = kmc_export_device_impl(c, d_key_hi, d_key_lo, d_count, &nd);
         if (rc) return rc;
-        if (d_key_hi) *d_key_hi = h;
-        if (d_key_lo) *d_key_lo = l;
-        if (d_count) *d_count = k;
         if (n_kept) *n_kept = nd;
         if (kept_total) *kept_total = nd ? c->st.n_kmers : 0;
         return KMC_OK;
@@ -2262,8 +2282,9 @@ static int kmc_export_filtered_impl(kmc_ctx* c, uint64_t min_count, uint64_t max
                                     uint64_t* count, uint64_t cap, uint64_t* n_kept) {
     if (!c) return KMC_ERR_ARG;
     if (n_kept) *n_kept = 0;
-    int rc = spectrum_begin(c, "kmc_export_filtered", min_count, max_count);
+    int rc = view_begin(c, "kmc_export_filtered", min_count, max_count);
     if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
     const bool ident = filter_is_identity(min_count, max_count);
     const u64 hi_c = max_count ? (u64)max_count : ~0ull;
     u64 nk = c->n_sorted, kt = 0;
@@ -2275,14 +2296,7 @@ static int kmc_export_filtered_impl(kmc_ctx* c, uint64_t min_count, uint64_t max
     if (ident) return kmc_export_impl(c, key_hi, key_lo, count, cap);
     rc = filter_scatter(c, min_count, hi_c, nk);
     if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(key_lo, c->f_lo.p, nk * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(count, c->f_cnt.p, nk * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    if (key_hi) {
-        if (c->KW == 2) HIPCHK(c, hipMemcpyAsync(key_hi, c->f_hi.p, nk * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-        else memset(key_hi, 0, nk * sizeof(u64));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return KMC_OK;
+    return copy_to_host(c, c->f_hi.p, c->f_lo.p, c->f_cnt.p, nk, key_hi, key_lo, count);
 }
 
 extern "C" uint64_t kmc_slab_words(const kmc_ctx* c, uint64_t slab_entries) {
@@ -2320,21 +2334,8 @@ static int kmc_merge_slabs_device_impl(kmc_ctx* c, const void* d_slabs, uint32_t
     if (!d_slabs || !n_slabs || !slab_entries || !n_parts || my_part >= n_parts) return fail(c, KMC_ERR_ARG, "kmc_merge_slabs_device: bad argument");
     if (((uintptr_t)d_slabs & 7) != 0) return fail(c, KMC_ERR_ARG, "d_slabs must be 8-byte aligned");
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    { int rc = resolve_async(c); if (rc) return rc; }
-    { int rc = undrain(c); if (rc) return rc; }
-    // room for the worst case (every pair of every slab new and owned here), accounted like
-    // kmc_merge_pairs_device so that a reset table needs no host synchronisation
-    const u64 n = (u64)n_slabs * slab_entries;
-    if (c->batch_pending || (c->h_counters[KMC_CTR_OCCUPIED] + c->unpolled_adds + n) * 2 > c->tab.cap) {
-        if (c->pending) { int rc = poll_and_settle(c); if (rc) return rc; }
-        u64 occ = c->h_counters[KMC_CTR_OCCUPIED];
-        if ((occ + n) * 2 > c->tab.cap) {
-            int rc = grow_to(c, next_pow2((occ + n) * 2));
-            if (rc) return rc;
-        }
-    }
-    c->unpolled_adds += n;
-    c->sorted_valid = false;
+    const u64 n = (u64)n_slabs * slab_entries;   // (the worst case: every pair of every slab new and owned here)
+    { int rc = merge_begin(c, n); if (rc) return rc; }
     GTable g = gtable_of(c, c->tab);
     const u64 words = KMC_SLAB_HEADER + slab_entries * (u64)(c->KW + 1);
     const int grid = grid_for(c, n, 256);
@@ -2436,6 +2437,82 @@ static int count_file_whole(kmc_ctx* c, const char* path, uint64_t* n_distinct, 
     return kmc_finalize(c, n_distinct, n_total);
 }
 
+// A pinned host pair the FASTA reader parses a chunk into, and the event of its upload
+struct Pinned { uint8_t* bases = nullptr; u64* offs = nullptr; u64 offs_cap = 0; hipEvent_t ev = nullptr; bool busy = false; };
+
+static void free_pinned(Pinned& p) {
+    if (p.bases) (void)hipHostFree(p.bases);
+    if (p.offs) (void)hipHostFree(p.offs);
+    if (p.ev) (void)hipEventDestroy(p.ev);
+}
+
+// A pinned pair ready for the reader: allocated at first use, its upload two rounds ago finished
+static int pinned_ready(kmc_ctx* c, Pinned& p, u64 cap) {
+    if (!p.bases) {
+        HIPCHK(c, hipHostMalloc((void**)&p.bases, (size_t)cap));
+        HIPCHK(c, hipEventCreateWithFlags(&p.ev, hipEventDisableTiming));
+    }
+    if (p.busy) { HIPCHK(c, hipEventSynchronize(p.ev)); p.busy = false; }
+    return KMC_OK;
+}
+
+// Upload a parsed chunk from its pinned pair and count it.  The ctx's previous batch is settled first (it may still read
+// the staging buffers; its kernels finished long ago -- this chunk took longer to parse); upload and count are queued
+// without waiting.
+static int upload_and_count(kmc_ctx* c, Pinned& p, const KmcIngestChunk& ck) {
+    if (p.offs_cap < ck.n_reads + 1) {
+        if (p.offs) { HIPCHK(c, hipHostFree(p.offs)); p.offs = nullptr; }
+        p.offs_cap = (ck.n_reads + 1) * 5 / 4 + 1024;
+        HIPCHK(c, hipHostMalloc((void**)&p.offs, (size_t)p.offs_cap * sizeof(u64)));
+    }
+    memcpy(p.offs, ck.offsets.data(), (size_t)(ck.n_reads + 1) * sizeof(u64));
+    int r = stage_host_batch(c, ck.n_reads, ck.n_bases);
+    if (r) return r;
+    for (const auto& pc : ck.pieces)
+        HIPCHK(c, hipMemcpyAsync((uint8_t*)c->st_bases.p + pc.dst_off, p.bases + pc.src_off, (size_t)pc.n_bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->st_offsets.p, p.offs, (size_t)(ck.n_reads + 1) * sizeof(u64), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(p.ev, c->stream));
+    p.busy = true;
+    return count_batch_device(c, (const uint8_t*)c->st_bases.p, (const u64*)c->st_offsets.p, ck.n_reads, ck.n_bases, ck.max_read_len);
+}
+
+// The tables of kmc_count_file_multi reduced pairwise (a tree of depth log2 N): in round r the contexts i with
+// i % 2^(r+1) == 0 take the sorted table of context i + 2^r over a peer copy (xGMI) into receive buffers they keep, and
+// merge it; the pairs of a round run side by side.  ctxs[0] ends up with everything.  (The first version finalized,
+// allocated and copied every other GPU's table into GPU 0 one after the other.)
+static int reduce_tables(kmc_ctx** ctxs, uint32_t n_ctx) {
+    kmc_ctx* c0 = ctxs[0];
+    for (uint32_t stride = 1; stride < n_ctx; stride *= 2) {
+        for (uint32_t i = 0; i + stride < n_ctx; i += 2 * stride) {
+            kmc_ctx *dst = ctxs[i], *src = ctxs[i + stride];
+            u64 nd = 0, nt = 0;
+            int rc = kmc_finalize(src, &nd, &nt);
+            if (rc) { memcpy(c0->err, src->err, sizeof(c0->err)); return rc; }
+            if (!nd) continue;
+            if (src->view_unsynced) {   // (its view is read on ANOTHER ctx's stream below: poll_fin, kmc_export_device)
+                HIPCHK(c0, hipSetDevice(src->cfg.device));
+                HIPCHK(c0, hipStreamSynchronize(src->stream));
+                src->view_unsynced = false;
+            }
+            HIPCHK(c0, hipSetDevice(dst->cfg.device));
+            const size_t nb = (size_t)nd * sizeof(u64);
+            rc = ensure(dst, dst->rx_lo, nb); if (!rc) rc = ensure(dst, dst->rx_cnt, nb); if (!rc && dst->KW == 2) rc = ensure(dst, dst->rx_hi, nb);
+            if (rc) { if (dst != c0) memcpy(c0->err, dst->err, sizeof(c0->err)); return rc; }
+            hipError_t e = hipMemcpyPeerAsync(dst->rx_lo.p, dst->cfg.device, src->v_lo, src->cfg.device, nb, dst->stream);
+            if (e == hipSuccess) e = hipMemcpyPeerAsync(dst->rx_cnt.p, dst->cfg.device, src->v_cnt, src->cfg.device, nb, dst->stream);
+            if (e == hipSuccess && dst->KW == 2) e = hipMemcpyPeerAsync(dst->rx_hi.p, dst->cfg.device, src->v_hi, src->cfg.device, nb, dst->stream);
+            if (e != hipSuccess) return fail(c0, KMC_ERR_HIP, "peer copy from device %d failed: %s", src->cfg.device, hipGetErrorString(e));
+            rc = kmc_merge_pairs_device(dst, dst->KW == 2 ? dst->rx_hi.p : nullptr, dst->rx_lo.p, dst->rx_cnt.p, nd);
+            if (rc) { if (dst != c0) memcpy(c0->err, dst->err, sizeof(c0->err)); return rc; }
+        }
+        for (uint32_t i = 0; i + stride < n_ctx; i += 2 * stride) {  // the round's copies and merges have finished
+            HIPCHK(c0, hipSetDevice(ctxs[i]->cfg.device));
+            HIPCHK(c0, hipStreamSynchronize(ctxs[i]->stream));
+        }
+    }
+    return KMC_OK;
+}
+
 static int count_file_pipeline(kmc_ctx** ctxs, uint32_t n_ctx, const char* path, uint64_t* n_distinct, uint64_t* n_total) {
     kmc_ctx* c0 = ctxs[0];
     // chunk size: a sixteenth of the file between 32 and 128 MiB (measured on 1 and 4 GB files, 16 host
@@ -2458,15 +2535,10 @@ static int count_file_pipeline(kmc_ctx** ctxs, uint32_t n_ctx, const char* path,
     if (rc == KMC_ERR_IO && err != "Error during opening the file" && n_ctx == 1) return count_file_whole(c0, path, n_distinct, n_total);  // (not mappable)
     if (rc) return fail(c0, rc, "%s: %s", path, err.c_str());
     const u64 cap = ing.chunk_capacity();
-    struct Pinned { uint8_t* bases = nullptr; u64* offs = nullptr; u64 offs_cap = 0; hipEvent_t ev = nullptr; bool busy = false; };
     std::vector<Pinned> pin((size_t)n_ctx * 2);  // two per ctx
     auto cleanup = [&]() {
         for (uint32_t i = 0; i < n_ctx; ++i) { (void)hipSetDevice(ctxs[i]->cfg.device); (void)hipStreamSynchronize(ctxs[i]->stream); }
-        for (auto& p : pin) {
-            if (p.bases) (void)hipHostFree(p.bases);
-            if (p.offs) (void)hipHostFree(p.offs);
-            if (p.ev) (void)hipEventDestroy(p.ev);
-        }
+        for (auto& p : pin) free_pinned(p);
     };
     auto body = [&]() -> int {
         KmcIngestChunk ck;
@@ -2474,36 +2546,13 @@ static int count_file_pipeline(kmc_ctx** ctxs, uint32_t n_ctx, const char* path,
             kmc_ctx* c = ctxs[j % n_ctx];  // chunks go round-robin over the GPUs
             Pinned& p = pin[(size_t)(j % n_ctx) * 2 + ((j / n_ctx) & 1)];
             HIPCHK(c, hipSetDevice(c->cfg.device));
-            if (!p.bases) {
-                HIPCHK(c, hipHostMalloc((void**)&p.bases, (size_t)cap));
-                HIPCHK(c, hipEventCreateWithFlags(&p.ev, hipEventDisableTiming));
-            }
-            if (p.busy) { HIPCHK(c, hipEventSynchronize(p.ev)); p.busy = false; }  // its upload two rounds ago has finished
-            int r;
+            int r = pinned_ready(c, p, cap);
+            if (r) return r;
             try { r = ing.next(p.bases, false, &ck, &err); } catch (const std::bad_alloc&) { return fail(c0, KMC_ERR_NOMEM, "out of memory while parsing %s", path); }
             if (r) return fail(c0, r, "%s: %s", path, err.c_str());
             if (ck.n_reads) {
-                if (p.offs_cap < ck.n_reads + 1) {
-                    if (p.offs) { HIPCHK(c, hipHostFree(p.offs)); p.offs = nullptr; }
-                    p.offs_cap = (ck.n_reads + 1) * 5 / 4 + 1024;
-                    HIPCHK(c, hipHostMalloc((void**)&p.offs, (size_t)p.offs_cap * sizeof(u64)));
-                }
-                memcpy(p.offs, ck.offsets.data(), (size_t)(ck.n_reads + 1) * sizeof(u64));
-                // settle the ctx's previous batch first (it may still read the staging buffers; its kernels
-                // finished long ago -- this chunk took longer to parse), then queue upload + count without waiting
-                auto fwd = [&](int code) { if (c != c0) memcpy(c0->err, c->err, sizeof(c0->err)); return code; };
-                if (c->pending) { r = poll_and_settle(c); if (r) return fwd(r); }
-                r = ensure(c, c->st_bases, ck.n_bases + 64);
-                if (r) return fwd(r);
-                r = ensure(c, c->st_offsets, (ck.n_reads + 1) * sizeof(u64));
-                if (r) return fwd(r);
-                for (const auto& pc : ck.pieces)
-                    HIPCHK(c, hipMemcpyAsync((uint8_t*)c->st_bases.p + pc.dst_off, p.bases + pc.src_off, (size_t)pc.n_bytes, hipMemcpyHostToDevice, c->stream));
-                HIPCHK(c, hipMemcpyAsync(c->st_offsets.p, p.offs, (size_t)(ck.n_reads + 1) * sizeof(u64), hipMemcpyHostToDevice, c->stream));
-                HIPCHK(c, hipEventRecord(p.ev, c->stream));
-                p.busy = true;
-                r = count_batch_device(c, (const uint8_t*)c->st_bases.p, (const u64*)c->st_offsets.p, ck.n_reads, ck.n_bases, ck.max_read_len);
-                if (r) return fwd(r);
+                r = upload_and_count(c, p, ck);
+                if (r) { if (c != c0) memcpy(c0->err, c->err, sizeof(c0->err)); return r; }
             }
             if (ck.eof) break;
         }
@@ -2529,7 +2578,7 @@ static int count_file_pipeline(kmc_ctx** ctxs, uint32_t n_ctx, const char* path,
             Pinned pp[2];
             auto fin = [&]() {
                 (void)hipStreamSynchronize(c->stream);
-                for (auto& p : pp) { if (p.bases) (void)hipHostFree(p.bases); if (p.offs) (void)hipHostFree(p.offs); if (p.ev) (void)hipEventDestroy(p.ev); }
+                for (auto& p : pp) free_pinned(p);
             };
             auto run = [&]() -> int {
                 HIPCHK(c, hipSetDevice(c->cfg.device));
@@ -2539,34 +2588,14 @@ static int count_file_pipeline(kmc_ctx** ctxs, uint32_t n_ctx, const char* path,
                 for (size_t j = i; j < n_chunks; j += n_ctx, ++it) {
                     if ((long long)j > stop_at.load()) break;
                     Pinned& p = pp[it & 1];
-                    if (!p.bases) {
-                        HIPCHK(c, hipHostMalloc((void**)&p.bases, (size_t)cap));
-                        HIPCHK(c, hipEventCreateWithFlags(&p.ev, hipEventDisableTiming));
-                    }
-                    if (p.busy) { HIPCHK(c, hipEventSynchronize(p.ev)); p.busy = false; }
-                    int r;
+                    int r = pinned_ready(c, p, cap);
+                    if (r) return r;
                     try { r = ing.parse_chunk(j, per, p.bases, false, &ck, &e2); } catch (const std::bad_alloc&) { return fail(c, KMC_ERR_NOMEM, "out of memory while parsing %s", path); }
                     if (r) return fail(c, r, "%s: %s", path, e2.c_str());
                     if (ck.terminated) { long long cur = stop_at.load(); while ((long long)j < cur && !stop_at.compare_exchange_weak(cur, (long long)j)) {} }
                     if ((long long)j > stop_at.load()) break;
                     if (!ck.n_reads) continue;
-                    if (p.offs_cap < ck.n_reads + 1) {
-                        if (p.offs) { HIPCHK(c, hipHostFree(p.offs)); p.offs = nullptr; }
-                        p.offs_cap = (ck.n_reads + 1) * 5 / 4 + 1024;
-                        HIPCHK(c, hipHostMalloc((void**)&p.offs, (size_t)p.offs_cap * sizeof(u64)));
-                    }
-                    memcpy(p.offs, ck.offsets.data(), (size_t)(ck.n_reads + 1) * sizeof(u64));
-                    if (c->pending) { r = poll_and_settle(c); if (r) return r; }
-                    r = ensure(c, c->st_bases, ck.n_bases + 64);
-                    if (r) return r;
-                    r = ensure(c, c->st_offsets, (ck.n_reads + 1) * sizeof(u64));
-                    if (r) return r;
-                    for (const auto& pc : ck.pieces)
-                        HIPCHK(c, hipMemcpyAsync((uint8_t*)c->st_bases.p + pc.dst_off, p.bases + pc.src_off, (size_t)pc.n_bytes, hipMemcpyHostToDevice, c->stream));
-                    HIPCHK(c, hipMemcpyAsync(c->st_offsets.p, p.offs, (size_t)(ck.n_reads + 1) * sizeof(u64), hipMemcpyHostToDevice, c->stream));
-                    HIPCHK(c, hipEventRecord(p.ev, c->stream));
-                    p.busy = true;
-                    r = count_batch_device(c, (const uint8_t*)c->st_bases.p, (const u64*)c->st_offsets.p, ck.n_reads, ck.n_bases, ck.max_read_len);
+                    r = upload_and_count(c, p, ck);
                     if (r) return r;
                     queued_max[i] = (long long)j;
                 }
@@ -2611,38 +2640,8 @@ static int count_file_pipeline(kmc_ctx** ctxs, uint32_t n_ctx, const char* path,
             }
         }
     }
-    // reduce: pairwise (a tree of depth log2 N): in round r the contexts i with i % 2^(r+1) == 0 take the sorted
-    // table of context i + 2^r over a peer copy (xGMI) into receive buffers they keep, and merge it; the pairs
-    // of a round run side by side.  ctxs[0] ends up with everything.  (The first version finalized, allocated
-    // and copied every other GPU's table into GPU 0 one after the other.)
-    for (uint32_t stride = 1; stride < n_ctx; stride *= 2) {
-        for (uint32_t i = 0; i + stride < n_ctx; i += 2 * stride) {
-            kmc_ctx *dst = ctxs[i], *src = ctxs[i + stride];
-            u64 nd = 0, nt = 0;
-            rc = kmc_finalize(src, &nd, &nt);
-            if (rc) { memcpy(c0->err, src->err, sizeof(c0->err)); return rc; }
-            if (!nd) continue;
-            if (src->view_unsynced) {   // (its view is read on ANOTHER ctx's stream below: poll_fin, kmc_export_device)
-                HIPCHK(c0, hipSetDevice(src->cfg.device));
-                HIPCHK(c0, hipStreamSynchronize(src->stream));
-                src->view_unsynced = false;
-            }
-            HIPCHK(c0, hipSetDevice(dst->cfg.device));
-            const size_t nb = (size_t)nd * sizeof(u64);
-            rc = ensure(dst, dst->rx_lo, nb); if (!rc) rc = ensure(dst, dst->rx_cnt, nb); if (!rc && dst->KW == 2) rc = ensure(dst, dst->rx_hi, nb);
-            if (rc) { if (dst != c0) memcpy(c0->err, dst->err, sizeof(c0->err)); return rc; }
-            hipError_t e = hipMemcpyPeerAsync(dst->rx_lo.p, dst->cfg.device, src->v_lo, src->cfg.device, nb, dst->stream);
-            if (e == hipSuccess) e = hipMemcpyPeerAsync(dst->rx_cnt.p, dst->cfg.device, src->v_cnt, src->cfg.device, nb, dst->stream);
-            if (e == hipSuccess && dst->KW == 2) e = hipMemcpyPeerAsync(dst->rx_hi.p, dst->cfg.device, src->v_hi, src->cfg.device, nb, dst->stream);
-            if (e != hipSuccess) return fail(c0, KMC_ERR_HIP, "peer copy from device %d failed: %s", src->cfg.device, hipGetErrorString(e));
-            rc = kmc_merge_pairs_device(dst, dst->KW == 2 ? dst->rx_hi.p : nullptr, dst->rx_lo.p, dst->rx_cnt.p, nd);
-            if (rc) { if (dst != c0) memcpy(c0->err, dst->err, sizeof(c0->err)); return rc; }
-        }
-        for (uint32_t i = 0; i + stride < n_ctx; i += 2 * stride) {  // the round's copies and merges have finished
-            HIPCHK(c0, hipSetDevice(ctxs[i]->cfg.device));
-            HIPCHK(c0, hipStreamSynchronize(ctxs[i]->stream));
-        }
-    }
+    rc = reduce_tables(ctxs, n_ctx);
+    if (rc) return rc;
     HIPCHK(c0, hipSetDevice(c0->cfg.device));
     return kmc_finalize(c0, n_distinct, n_total);
 }

@@ -1013,12 +1013,8 @@ static inline void kmc_walk_launch_t(hipStream_t st, int grid, int n_cu, const u
     if (phase == 0) {
         // the launch's own start / stop timestamps go to e0 / e1 (hipExtLaunchKernelGGL): what hipEventRecord in front of and
         // behind the launch measured too, without two more packets in the stream per step
-        if (e0 && e1)
-            hipExtLaunchKernelGGL((kmc_walk_kernel<KW, CANON>), dim3(grid), dim3(KMC_WALK_THREADS), (uint32_t)smem, st, e0, e1, 0u, d_bases, n_bases, d_vstart, d_vend, n_reads, k, tile_begin, tile_end, hdr, list,
-                                  (const WalkMemoSlot<KW>*)&slots[parity], &slots[parity ^ 1], gcnt, g, sk, lg);
-        else
-            hipLaunchKernelGGL((kmc_walk_kernel<KW, CANON>), dim3(grid), dim3(KMC_WALK_THREADS), smem, st, d_bases, n_bases, d_vstart, d_vend, n_reads, k, tile_begin, tile_end, hdr, list,
-                               (const WalkMemoSlot<KW>*)&slots[parity], &slots[parity ^ 1], gcnt, g, sk, lg);
+        hipExtLaunchKernelGGL((kmc_walk_kernel<KW, CANON>), dim3(grid), dim3(KMC_WALK_THREADS), (uint32_t)smem, st, e0, e1, 0u, d_bases, n_bases, d_vstart, d_vend, n_reads, k, tile_begin, tile_end, hdr, list,
+                              (const WalkMemoSlot<KW>*)&slots[parity], &slots[parity ^ 1], gcnt, g, sk, lg);
     } else {
         static_assert(((KMC_WALK_NCAP + KMC_WALK_ECAP) * KMC_WALK_STRIDE) % 256 == 0 && 256 % KMC_WALK_STRIDE == 0, "unfold grid must cover the items exactly");
         hipLaunchKernelGGL((kmc_walk_tail_kernel<KW, CANON>), dim3(KMC_WALK_UNFOLD_BLOCKS + n_cu), dim3(256), 0, st,
@@ -1044,6 +1040,7 @@ static inline int kmc_sk_unfold_launch(hipStream_t st, int n_cu, int KW, int k, 
 // phase 0: the walk kernel over tiles [tile_begin, tile_end); phase 1: the scalar kernel for the reads
 // it diverted + the unfold of the dense snapshot counters.  `parity` selects the snapshot slot read
 // by this launch (the other one is written); the caller flips it after phase 1.  The caller clears the workspace header (kmc_walk_prepare) before phase 0.
+// e0 / e1: the events phase 0 records its start and stop in (phase 1 ignores them).
 static inline int kmc_walk_prepare(hipStream_t st, void* ws) {
     return hipMemsetAsync(ws, 0, KMC_WALK_WS_PREFIX, st) == hipSuccess ? KMC_OK : KMC_ERR_HIP;
 }
@@ -1055,7 +1052,7 @@ static inline int kmc_walk_grid(u64 n_tiles, int n_cu) {
 }
 static inline int kmc_walk_launch(hipStream_t st, int n_cu, int KW, int k, bool canon, const uint8_t* d_bases,
                                   const u64* d_vstart, const u64* d_vend, u64 n_reads, u64 n_bases, u64 tile_begin, u64 tile_end, void* ws, void* memo, int parity, GTable g, GTable sk, SkLog lg, int phase,
-                                  hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
+                                  hipEvent_t e0, hipEvent_t e1) {
     if (n_reads >= (1ull << 32) || tile_end <= tile_begin) return KMC_ERR_ARG;
     WalkWs* hdr = (WalkWs*)ws;
     u32* list = (u32*)((char*)ws + KMC_WALK_WS_PREFIX);
