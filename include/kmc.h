@@ -18,6 +18,9 @@
  *   random_fasta_generator.py:5-15                        kmc_synth_* (seeded, sized re-creation)
  *   (addition: no equivalent in the reference)             kmc_histogram (abundance histogram of the view)
  *   (addition: no equivalent in the reference)             kmc_filter_device / kmc_export_filtered (count range)
+ *   (addition: no equivalent in the reference)             kmc_encode_key (ASCII k-mer -> packed key)
+ *   (addition: no equivalent in the reference)             kmc_query / kmc_query_device (count of given keys)
+ *   (addition: no equivalent in the reference)             kmc_profile / kmc_profile_device (per-read k-mer profile)
  *
  * Conventions
  *   - Every function returns 0 (KMC_OK) or a negative kmc_status; no exception or abort crosses
@@ -216,6 +219,39 @@ int kmc_filter_device(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, cons
  * always set; cap < *n_kept -> KMC_ERR_ARG and nothing is copied (call with cap 0 and NULL arrays to size the buffers). */
 int kmc_export_filtered(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, uint64_t* key_hi, uint64_t* key_lo,
                         uint64_t* count, uint64_t cap, uint64_t* n_kept);
+
+/* ---- asking the table: key lookups and per-read profiles (additions, as above: they read the sorted view of the last
+ * kmc_finalize -- a view queued by kmc_finalize_async counts as one -- and change neither the table, the view, a
+ * kmc_partition_device result nor a kmc_filter_device result).  A NULL ctx is KMC_ERR_ARG, no view KMC_ERR_STATE (exactly
+ * where kmc_export says so), an empty view gives zeros.  The first query of a view builds a prefix index over it on the
+ * device (kept by the ctx until its next view); a view of 2^32 keys or more is KMC_ERR_CAPACITY. ---- */
+
+/* ASCII k-mer -> packed key (inverse of kmc_decode_key).  canonical != 0: min(fwd, revcomp).  Host only, no ctx.
+ * klen outside 1..63 or a null pointer: KMC_ERR_ARG; a byte outside upper-case ACGT: KMC_ERR_ALPHABET. */
+int kmc_encode_key(const char* kmer, int klen, int canonical, uint64_t* key_hi, uint64_t* key_lo);
+
+/* count[i] = count of key i in the sorted view of the last finalize, 0 if absent.  Keys are looked up AS GIVEN
+ * (in a canonical ctx a non-canonical key is simply absent).  key_hi may be NULL when keys fit one word.
+ * Any order, duplicates allowed, n_keys == 0 is fine. */
+int kmc_query(kmc_ctx* ctx, const uint64_t* key_hi, const uint64_t* key_lo, uint64_t n_keys, uint64_t* count);
+/* Same on device arrays of this ctx's GPU (8-byte aligned; 16-byte aligned arrays are read and written 16 bytes per lane);
+ * asynchronous on the ctx stream, no host synchronisation of its own beyond what resolving the view needs. */
+int kmc_query_device(kmc_ctx* ctx, const void* d_key_hi, const void* d_key_lo, uint64_t n_keys, void* d_count);
+
+#define KMC_PROFILE_WORDS 5
+/* Per-read k-mer profile of a batch (same bases/offsets layout as kmc_add_batch) against the view; the batch is NOT
+ * counted.  KMC_MODE_CONTIG only (LR: KMC_ERR_ARG).  Uses the ctx's k and canonical setting.
+ *   window_count[n_bases] (may be NULL): entry offsets[r] + j = count of the window that STARTS at base j of read r,
+ *     saturated at 0xFFFFFFFF; 0 for an absent key, for a window containing a byte outside ACGT, and for the last
+ *     k-1 positions of a read (all positions of a read shorter than k).
+ *   read_stats[n_reads * KMC_PROFILE_WORDS] (may be NULL), per read: [0] valid windows (no non-ACGT byte),
+ *     [1] of those, windows with count >= max(min_count, 1), [2] smallest and [3] largest count over the valid
+ *     windows (absent = 0; both 0 when there is no valid window), [4] sum of counts.  [2..4] are exact u64. */
+int kmc_profile(kmc_ctx* ctx, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads, uint64_t min_count,
+                uint32_t* window_count, uint64_t* read_stats);
+/* Device form: alignment / padding rules of kmc_add_batch_device for d_bases; asynchronous on the ctx stream. */
+int kmc_profile_device(kmc_ctx* ctx, const void* d_bases, const void* d_offsets, uint64_t n_reads, uint64_t n_bases,
+                       uint64_t min_count, void* d_window_count, void* d_read_stats);
 
 /* Multi-GPU reduce for small tables: ONE fixed-size all-gather instead of size exchange +
  * all-to-all (the reduce of main.rs:87's grouping across GPUs; for the generator's input a table is

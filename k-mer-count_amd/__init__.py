@@ -85,7 +85,10 @@ ABI_SYMBOLS = [
     "kmc_fasta_stream_open", "kmc_fasta_stream_next", "kmc_fasta_stream_close", "kmc_poll",
     "kmc_count_file_multi", "kmc_read_pieces", "kmc_sync", "kmc_read_peak_device", "kmc_finalize_async",
     "kmc_histogram", "kmc_filter_device", "kmc_export_filtered",
+    "kmc_encode_key", "kmc_query", "kmc_query_device", "kmc_profile", "kmc_profile_device",
 ]
+
+PROFILE_WORDS = 5  # KMC_PROFILE_WORDS: valid windows, present windows, min, max, sum
 
 _lib = None
 
@@ -139,6 +142,11 @@ def lib() -> C.CDLL:
     L.kmc_histogram.argtypes = [vp, u64, u64, u32, vp, pu64]
     L.kmc_filter_device.argtypes = [vp, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), pu64, pu64]
     L.kmc_export_filtered.argtypes = [vp, u64, u64, vp, vp, vp, u64, pu64]
+    L.kmc_encode_key.argtypes = [C.c_char_p, i32, i32, pu64, pu64]
+    L.kmc_query.argtypes = [vp, vp, vp, u64, vp]
+    L.kmc_query_device.argtypes = [vp, vp, vp, u64, vp]
+    L.kmc_profile.argtypes = [vp, vp, vp, u64, u64, vp, vp]
+    L.kmc_profile_device.argtypes = [vp, vp, vp, u64, u64, u64, vp, vp]
     L.kmc_owner_of.argtypes = [u64, u64, u32]
     L.kmc_owner_of.restype = u32
     L.kmc_get_stats.argtypes = [vp, C.POINTER(Stats)]
@@ -310,6 +318,7 @@ class KmerCounter:
         self.stream = int(stream) if stream else 0  # hipStream_t the ctx runs on (0: its own stream)
         self.k = 54 if mode == MODE_LR else int(k)
         self.mode = mode
+        self.canonical = bool(canonical)
         self.device = int(device)
 
     # -- lifetime --
@@ -423,6 +432,59 @@ class KmerCounter:
                                                   cnt.ctypes.data, nk, C.byref(n)))
         return Table(hi, lo, cnt, self.k)
 
+    # -- asking the table: key lookups and per-read profiles (of the sorted view; finalize() first) --
+    def query(self, key_lo, key_hi=None) -> np.ndarray:
+        """uint64 counts of the given packed keys (0 = absent), looked up as given; key_hi None: high words zero."""
+        lo = np.ascontiguousarray(key_lo, dtype=np.uint64).ravel()
+        hi = None if key_hi is None else np.ascontiguousarray(key_hi, dtype=np.uint64).ravel()
+        if hi is not None and hi.shape != lo.shape:
+            raise ValueError("key_hi and key_lo differ in length")
+        out = np.zeros(lo.shape[0], np.uint64)
+        self._chk(self._L.kmc_query(self._h, hi.ctypes.data if hi is not None else None, lo.ctypes.data, lo.shape[0], out.ctypes.data))
+        return out
+
+    def query_kmers(self, kmers: Iterable) -> np.ndarray:
+        """Counts of ASCII k-mers (str or bytes, each of this ctx's key length), encoded with the ctx's canonical setting."""
+        keys = [encode_key(km, self.canonical) for km in kmers]
+        hi = np.array([h for h, _ in keys], np.uint64)
+        lo = np.array([l for _, l in keys], np.uint64)
+        return self.query(lo, hi)
+
+    def query_device(self, d_key_hi: int, d_key_lo: int, n_keys: int, d_count: int):
+        """Device arrays given as raw addresses (d_key_hi 0: high words zero); asynchronous on the ctx stream."""
+        self._chk(self._L.kmc_query_device(self._h, d_key_hi or None, d_key_lo or None, int(n_keys), d_count or None))
+
+    def profile(self, bases: np.ndarray, offsets: np.ndarray, min_count: int = 1, windows: bool = True, stats: bool = True):
+        """Per-read k-mer profile of a host batch against the view (kmc_profile; the batch is not counted):
+        (window_count uint32[n_bases] or None, read_stats uint64[n_reads, 5] or None)."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n_reads = max(int(offsets.shape[0]) - 1, 0)
+        win = np.zeros(bases.shape[0], np.uint32) if windows else None
+        rs = np.zeros((n_reads, PROFILE_WORDS), np.uint64) if stats else None
+        self._chk(self._L.kmc_profile(self._h, bases.ctypes.data, offsets.ctypes.data, n_reads, int(min_count),
+                                      win.ctypes.data if windows else None, rs.ctypes.data if stats else None))
+        return win, rs
+
+    def profile_device(self, d_bases: int, d_offsets: int, n_reads: int, n_bases: int, min_count: int, d_window_count: int, d_read_stats: int):
+        self._chk(self._L.kmc_profile_device(self._h, d_bases or None, d_offsets or None, int(n_reads), int(n_bases), int(min_count),
+                                             d_window_count or None, d_read_stats or None))
+
+    def profile_tensors(self, bases, offsets, min_count: int = 1, windows: bool = True, stats: bool = True):
+        """torch tensors on this ctx's GPU (bases uint8[n_bases], padded as for add_batch_tensors; offsets int64[n_reads+1]):
+        (window_count int32 tensor holding the uint32 bit patterns or None, read_stats int64[n_reads, 5] tensor or None).
+        Asynchronous on the ctx stream: call sync() (or order the consumer behind the ctx stream) before reading."""
+        import torch
+        assert bases.is_cuda and offsets.is_cuda and bases.is_contiguous() and offsets.is_contiguous()
+        n_reads, n_bases = max(offsets.numel() - 1, 0), bases.numel()
+        win = torch.zeros(n_bases, dtype=torch.int32, device=bases.device) if windows else None
+        rs = torch.zeros((n_reads, PROFILE_WORDS), dtype=torch.int64, device=bases.device) if stats else None
+        if windows or stats:
+            torch.cuda.synchronize(bases.device)  # (the zero fills ran on torch's stream, the profile runs on the ctx's)
+        self.profile_device(bases.data_ptr(), offsets.data_ptr(), n_reads, n_bases, min_count,
+                            win.data_ptr() if windows and n_bases else 0, rs.data_ptr() if stats and n_reads else 0)
+        return win, rs
+
     # -- multi-GPU reduce, small tables (one fixed-size all-gather; distributed.py) --
     def slab_words(self, slab_entries: int) -> int:
         return int(self._L.kmc_slab_words(self._h, int(slab_entries)))
@@ -467,6 +529,16 @@ def count_file_multi(counters, path: str) -> Tuple[int, int]:
 
 def owner_of(key_hi: int, key_lo: int, n_parts: int) -> int:
     return int(lib().kmc_owner_of(int(key_hi), int(key_lo), int(n_parts)))
+
+
+def encode_key(kmer, canonical: bool = True) -> Tuple[int, int]:
+    """(key_hi, key_lo) of an ASCII k-mer of 1..63 upper-case ACGT characters (kmc_encode_key)."""
+    b = kmer.encode() if isinstance(kmer, str) else bytes(kmer)
+    hi, lo = C.c_uint64(), C.c_uint64()
+    rc = lib().kmc_encode_key(b, len(b), 1 if canonical else 0, C.byref(hi), C.byref(lo))
+    if rc:
+        raise KmcError(rc, lib().kmc_status_string(rc).decode())
+    return hi.value, lo.value
 
 
 def count_file(path: str, k: Optional[int] = None, canonical: bool = True, device: int = 0, algo: int = ALGO_AUTO) -> Table:

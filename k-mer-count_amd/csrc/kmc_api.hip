@@ -35,6 +35,7 @@
 #include "kmc_extract.hip.h"
 #include "kmc_peak.hip.h"
 #include "kmc_spectrum.hip.h"
+#include "kmc_query.hip.h"
 #include "kmc_ingest.h"
 
 namespace {
@@ -178,6 +179,11 @@ struct kmc_ctx {
     // kmc_filter_device's result (its own buffers: a filter leaves the view and a partition the caller holds alone), the
     // per-tile kept counts and their scan, [n_kept | kept_total]; kmc_histogram's device histogram + max
     DevBuf f_hi, f_lo, f_cnt, f_tile, f_tpos, f_bsum, f_ctl, h_hist;
+    // kmc_query / kmc_profile (kmc_query.hip.h): the prefix index of the view numbered q_gen (view_gen counts the views this
+    // ctx has produced: every place that publishes one bumps it, so an index can never outlive its view), staging of the
+    // host forms: query keys and counts, a batch's bases and offsets, its window counts and read statistics
+    u64 view_gen = 0, q_gen = ~0ull;
+    DevBuf q_idx, q_khi, q_klo, q_cnt, q_bases, q_offs, q_win, q_stats;
 };
 
 namespace {
@@ -643,6 +649,7 @@ int resolve_async(kmc_ctx* c) {
         c->v_cnt = (const u64*)c->o_cnt.p;
         c->n_sorted = n;
         c->sorted_valid = true;
+        c->view_gen += 1;
         c->fin_hint = n;
         c->st.n_distinct = n;
         c->st.n_kmers = n ? c->h_counters[KMC_CTR_SUM2] : 0;
@@ -1702,7 +1709,8 @@ extern "C" void kmc_destroy(kmc_ctx* c) {
                       &c->m_hist, &c->m_stot, &c->m_bsum, &c->m_rmin, &c->m_rmax, &c->m_seg[0], &c->m_seg[1], &c->m_first, &c->m_cbase, &c->m_skip, &c->m_term, &c->m_ord,
                       &c->m_bitmap, &c->m_rank, &c->m_nd, &c->m_base, &c->m_ctl, &c->m_clist, &c->m_w[0], &c->m_w[1],
                       &c->snap_hi, &c->snap_lo, &c->snap_cnt, &c->snap_n, &c->snap_occ, &c->rx_hi, &c->rx_lo, &c->rx_cnt,
-                      &c->f_hi, &c->f_lo, &c->f_cnt, &c->f_tile, &c->f_tpos, &c->f_bsum, &c->f_ctl, &c->h_hist};
+                      &c->f_hi, &c->f_lo, &c->f_cnt, &c->f_tile, &c->f_tpos, &c->f_bsum, &c->f_ctl, &c->h_hist,
+                      &c->q_idx, &c->q_khi, &c->q_klo, &c->q_cnt, &c->q_bases, &c->q_offs, &c->q_win, &c->q_stats};
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
     sk_free(c);
     try { free_runs(c, true); } catch (...) { /* (only the pool bookkeeping can throw; the buffers it could not list leak with the process) */ }
@@ -2036,6 +2044,7 @@ static int kmc_finalize_impl(kmc_ctx* c, uint64_t* n_distinct, uint64_t* n_total
     }
     c->n_sorted = n;
     c->sorted_valid = true;
+    c->view_gen += 1;
     c->st.n_distinct = n;
     c->st.n_kmers = n ? n_kmers : 0;
     if (!fast_done && c->tb.size() >= 4) harvest_timing(c);
@@ -2297,6 +2306,157 @@ static int kmc_export_filtered_impl(kmc_ctx* c, uint64_t min_count, uint64_t max
     rc = filter_scatter(c, min_count, hi_c, nk);
     if (rc) return rc;
     return copy_to_host(c, c->f_hi.p, c->f_lo.p, c->f_cnt.p, nk, key_hi, key_lo, count);
+}
+
+// ---- key lookups and per-read profiles against the sorted view (kmc_query.hip.h) ----
+// The view as the query kernels see it, its prefix index built first if this view has none yet (one launch; kept until the
+// ctx publishes another view).  An empty view gets an index of one empty bucket, so the kernels need no special case.
+static int query_view(kmc_ctx* c, const char* what, QView* out) {
+    const u64 n = c->n_sorted;
+    if (n >= (1ull << 32)) return fail(c, KMC_ERR_CAPACITY, "%s: a view of 2^32 keys or more cannot be indexed", what);
+    const int kb = 2 * c->klen;
+    const int P = kmc_query_index_bits(n, kb);
+    QView v;
+    v.hi = c->KW == 2 ? c->v_hi : nullptr;
+    v.lo = c->v_lo;
+    v.cnt = c->v_cnt;
+    v.n = n;
+    v.sh = kb - P;
+    v.max_lo = kb >= 64 ? ~0ull : (1ull << kb) - 1;
+    v.max_hi = kb <= 64 ? 0ull : (1ull << (kb - 64)) - 1;
+    if (c->q_gen != c->view_gen || !c->q_idx.p) {
+        int rc = ensure(c, c->q_idx, (((size_t)1 << P) + 2) * sizeof(u32));
+        if (rc) return rc;
+        v.idx = (u32*)c->q_idx.p;
+        const u32 grid = (u32)((n + 1 + 255) / 256);
+        if (c->KW == 1) hipLaunchKernelGGL(kmc_query_index_kernel<1>, dim3(grid), dim3(256), 0, c->stream, v, 1u << P);
+        else hipLaunchKernelGGL(kmc_query_index_kernel<2>, dim3(grid), dim3(256), 0, c->stream, v, 1u << P);
+        HIPCHK(c, hipGetLastError());
+        c->q_gen = c->view_gen;
+    }
+    v.idx = (u32*)c->q_idx.p;
+    *out = v;
+    return KMC_OK;
+}
+
+// the lookup launch (device arrays; d_hi may be null: high words zero)
+static int query_launch(kmc_ctx* c, const u64* d_hi, const u64* d_lo, u64 n_keys, u64* d_cnt) {
+    QView v;
+    int rc = query_view(c, "kmc_query", &v);
+    if (rc) return rc;
+    const int al16 = (((uintptr_t)d_hi | (uintptr_t)d_lo | (uintptr_t)d_cnt) & 15) == 0;
+    const u64 per_wg = (u64)KMC_Q_THREADS * KMC_Q_U;
+    const u64 grid = (n_keys + per_wg - 1) / per_wg;
+    if (grid > 0x7FFFFFFFull) return fail(c, KMC_ERR_ARG, "kmc_query: too many keys in one call");
+    if (c->KW == 1) hipLaunchKernelGGL(kmc_query_kernel<1>, dim3((u32)grid), dim3(KMC_Q_THREADS), 0, c->stream, v, d_hi, d_lo, n_keys, al16, d_cnt);
+    else hipLaunchKernelGGL(kmc_query_kernel<2>, dim3((u32)grid), dim3(KMC_Q_THREADS), 0, c->stream, v, d_hi, d_lo, n_keys, al16, d_cnt);
+    HIPCHK(c, hipGetLastError());
+    return KMC_OK;
+}
+
+static int kmc_query_device_impl(kmc_ctx* c, const void* d_key_hi, const void* d_key_lo, uint64_t n_keys, void* d_count) {
+    if (!c) return KMC_ERR_ARG;
+    int rc = view_begin(c, "kmc_query_device");
+    if (rc) return rc;
+    if (!n_keys) return KMC_OK;
+    if (!d_key_lo || !d_count) return fail(c, KMC_ERR_ARG, "kmc_query_device: null device pointer");
+    if ((((uintptr_t)d_key_hi | (uintptr_t)d_key_lo | (uintptr_t)d_count) & 7) != 0) return fail(c, KMC_ERR_ARG, "kmc_query_device: arrays must be 8-byte aligned");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    return query_launch(c, (const u64*)d_key_hi, (const u64*)d_key_lo, n_keys, (u64*)d_count);
+}
+
+static int kmc_query_impl(kmc_ctx* c, const uint64_t* key_hi, const uint64_t* key_lo, uint64_t n_keys, uint64_t* count) {
+    if (!c) return KMC_ERR_ARG;
+    int rc = view_begin(c, "kmc_query");
+    if (rc) return rc;
+    if (!n_keys) return KMC_OK;
+    if (!key_lo || !count) return fail(c, KMC_ERR_ARG, "kmc_query: null buffer");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    const size_t nb = (size_t)n_keys * sizeof(u64);
+    if ((rc = ensure(c, c->q_klo, nb)) || (rc = ensure(c, c->q_cnt, nb))) return rc;
+    if (key_hi && (rc = ensure(c, c->q_khi, nb))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->q_klo.p, key_lo, nb, hipMemcpyHostToDevice, c->stream));
+    if (key_hi) HIPCHK(c, hipMemcpyAsync(c->q_khi.p, key_hi, nb, hipMemcpyHostToDevice, c->stream));
+    rc = query_launch(c, key_hi ? (const u64*)c->q_khi.p : nullptr, (const u64*)c->q_klo.p, n_keys, (u64*)c->q_cnt.p);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(count, c->q_cnt.p, nb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return KMC_OK;
+}
+
+// the profile launches (device arrays; either output may be null)
+static int profile_launch(kmc_ctx* c, const uint8_t* d_bases, const u64* d_offsets, u64 n_reads, u64 n_bases, u64 min_count,
+                          u32* d_win, u64* d_stats) {
+    QView v;
+    int rc = query_view(c, "kmc_profile", &v);
+    if (rc) return rc;
+    const int k = c->cfg.k;
+    const u64 n_words = n_reads * KMC_PROFILE_WORDS;
+    const u32 sgrid = (u32)((n_words + KMC_PROF_INIT_THREADS - 1) / KMC_PROF_INIT_THREADS);
+    if (d_stats) hipLaunchKernelGGL(kmc_profile_init_kernel, dim3(sgrid), dim3(KMC_PROF_INIT_THREADS), 0, c->stream, (kmc_qull*)d_stats, n_reads);
+    // windows END up to k - 1 positions past the batch: those (invalid) windows zero the last k - 1 slots
+    const u64 n_chunks = (n_bases + (u64)k - 1 + KMC_CHUNK - 1) / KMC_CHUNK;
+    if (n_chunks && (d_win || d_stats)) {
+        const u64 want_waves = (u64)c->n_cu * 16;   // four waves on each SIMD
+        const u64 cpw = std::min<u64>(64, std::max<u64>(1, (n_chunks + want_waves - 1) / want_waves));
+        const u64 waves = (n_chunks + cpw - 1) / cpw;
+        const u64 grid = (waves + KMC_Q_WAVES - 1) / KMC_Q_WAVES;
+        if (grid > 0x7FFFFFFFull) return fail(c, KMC_ERR_ARG, "kmc_profile: batch too large for one call");
+        const u64 thr = std::max<u64>(min_count, 1);
+#define KMC_PROF_LAUNCH(KW_, CANON_)                                                                                              \
+        hipLaunchKernelGGL((kmc_profile_kernel<KW_, CANON_>), dim3((u32)grid), dim3(KMC_Q_THREADS), 0, c->stream, d_bases, n_bases, \
+                           d_offsets, n_reads, k, n_chunks, cpw, v, thr, d_win, (kmc_qull*)d_stats)
+        if (c->KW == 1) { if (c->cfg.canonical) KMC_PROF_LAUNCH(1, true); else KMC_PROF_LAUNCH(1, false); }
+        else { if (c->cfg.canonical) KMC_PROF_LAUNCH(2, true); else KMC_PROF_LAUNCH(2, false); }
+#undef KMC_PROF_LAUNCH
+    }
+    if (d_stats) hipLaunchKernelGGL(kmc_profile_fix_kernel, dim3((u32)((n_reads + KMC_PROF_INIT_THREADS - 1) / KMC_PROF_INIT_THREADS)),
+                                    dim3(KMC_PROF_INIT_THREADS), 0, c->stream, (kmc_qull*)d_stats, n_reads);
+    HIPCHK(c, hipGetLastError());
+    return KMC_OK;
+}
+
+static int kmc_profile_device_impl(kmc_ctx* c, const void* d_bases, const void* d_offsets, uint64_t n_reads, uint64_t n_bases,
+                                   uint64_t min_count, void* d_window_count, void* d_read_stats) {
+    if (!c) return KMC_ERR_ARG;
+    if (c->cfg.mode != KMC_MODE_CONTIG) return fail(c, KMC_ERR_ARG, "kmc_profile_device: contiguous k-mers only (not KMC_MODE_LR)");
+    int rc = view_begin(c, "kmc_profile_device");
+    if (rc) return rc;
+    if (!n_reads) return KMC_OK;
+    if (!d_bases || !d_offsets) return fail(c, KMC_ERR_ARG, "kmc_profile_device: null device pointer");
+    if (((uintptr_t)d_bases & 15) != 0) return fail(c, KMC_ERR_ARG, "kmc_profile_device: d_bases must be 16-byte aligned");
+    if (((uintptr_t)d_offsets & 7) != 0 || ((uintptr_t)d_read_stats & 7) != 0 || ((uintptr_t)d_window_count & 3) != 0)
+        return fail(c, KMC_ERR_ARG, "kmc_profile_device: d_offsets / d_read_stats must be 8-byte, d_window_count 4-byte aligned");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    return profile_launch(c, (const uint8_t*)d_bases, (const u64*)d_offsets, n_reads, n_bases, min_count, (u32*)d_window_count, (u64*)d_read_stats);
+}
+
+static int kmc_profile_impl(kmc_ctx* c, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads, uint64_t min_count,
+                            uint32_t* window_count, uint64_t* read_stats) {
+    if (!c) return KMC_ERR_ARG;
+    if (c->cfg.mode != KMC_MODE_CONTIG) return fail(c, KMC_ERR_ARG, "kmc_profile: contiguous k-mers only (not KMC_MODE_LR)");
+    int rc = view_begin(c, "kmc_profile");
+    if (rc) return rc;
+    if (!n_reads) return KMC_OK;
+    if (!bases || !offsets) return fail(c, KMC_ERR_ARG, "kmc_profile: null buffer");
+    if (offsets[0] != 0) return fail(c, KMC_ERR_ARG, "kmc_profile: offsets[0] must be 0");
+    for (u64 i = 0; i < n_reads; ++i)
+        if (offsets[i + 1] < offsets[i]) return fail(c, KMC_ERR_ARG, "kmc_profile: offsets must be non-decreasing (read %llu)", (unsigned long long)i);
+    const u64 n_bases = offsets[n_reads];
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    const size_t sb = (size_t)n_reads * KMC_PROFILE_WORDS * sizeof(u64), wb = (size_t)n_bases * sizeof(u32);
+    if ((rc = ensure(c, c->q_bases, n_bases + 64)) || (rc = ensure(c, c->q_offs, (n_reads + 1) * sizeof(u64)))) return rc;
+    if (window_count && n_bases && (rc = ensure(c, c->q_win, wb))) return rc;
+    if (read_stats && (rc = ensure(c, c->q_stats, sb))) return rc;
+    if (n_bases) HIPCHK(c, hipMemcpyAsync(c->q_bases.p, bases, n_bases, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->q_offs.p, offsets, (n_reads + 1) * sizeof(u64), hipMemcpyHostToDevice, c->stream));
+    rc = profile_launch(c, (const uint8_t*)c->q_bases.p, (const u64*)c->q_offs.p, n_reads, n_bases, min_count,
+                        window_count && n_bases ? (u32*)c->q_win.p : nullptr, read_stats ? (u64*)c->q_stats.p : nullptr);
+    if (rc) return rc;
+    if (window_count && n_bases) HIPCHK(c, hipMemcpyAsync(window_count, c->q_win.p, wb, hipMemcpyDeviceToHost, c->stream));
+    if (read_stats) HIPCHK(c, hipMemcpyAsync(read_stats, c->q_stats.p, sb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return KMC_OK;
 }
 
 extern "C" uint64_t kmc_slab_words(const kmc_ctx* c, uint64_t slab_entries) {
@@ -2806,6 +2966,20 @@ extern "C" int kmc_filter_device(kmc_ctx* c, uint64_t min_count, uint64_t max_co
 extern "C" int kmc_export_filtered(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t* key_hi, uint64_t* key_lo,
                                    uint64_t* count, uint64_t cap, uint64_t* n_kept) {
     return guarded(c, [&]() -> int { return kmc_export_filtered_impl(c, min_count, max_count, key_hi, key_lo, count, cap, n_kept); });
+}
+extern "C" int kmc_query(kmc_ctx* c, const uint64_t* key_hi, const uint64_t* key_lo, uint64_t n_keys, uint64_t* count) {
+    return guarded(c, [&]() -> int { return kmc_query_impl(c, key_hi, key_lo, n_keys, count); });
+}
+extern "C" int kmc_query_device(kmc_ctx* c, const void* d_key_hi, const void* d_key_lo, uint64_t n_keys, void* d_count) {
+    return guarded(c, [&]() -> int { return kmc_query_device_impl(c, d_key_hi, d_key_lo, n_keys, d_count); });
+}
+extern "C" int kmc_profile(kmc_ctx* c, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads, uint64_t min_count,
+                           uint32_t* window_count, uint64_t* read_stats) {
+    return guarded(c, [&]() -> int { return kmc_profile_impl(c, bases, offsets, n_reads, min_count, window_count, read_stats); });
+}
+extern "C" int kmc_profile_device(kmc_ctx* c, const void* d_bases, const void* d_offsets, uint64_t n_reads, uint64_t n_bases,
+                                  uint64_t min_count, void* d_window_count, void* d_read_stats) {
+    return guarded(c, [&]() -> int { return kmc_profile_device_impl(c, d_bases, d_offsets, n_reads, n_bases, min_count, d_window_count, d_read_stats); });
 }
 extern "C" int kmc_partition_device(kmc_ctx* c, uint32_t n_parts, uint64_t* part_begin, const void** d_key_hi,
                                     const void** d_key_lo, const void** d_count) {

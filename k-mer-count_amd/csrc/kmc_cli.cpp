@@ -5,7 +5,7 @@
 // test.py:15-18 takes the FASTA path as its only positional argument.  This tool keeps both:
 //
 //   k-mer-count [FASTA] [-k K] [--forward] [--expand] [--device N | --gpus N] [--algo auto|stream|walk|sort] [--stats]
-//               [--min-count N] [--max-count N] [--histo H]
+//               [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE]
 //
 //   --gpus N  the file's chunks go round-robin to GPUs 0..N-1 of this process, tables reduced on GPU 0
 //             (there is no CPU backend: SURVEY.md's "--backend cpu" is deliberately absent)
@@ -18,6 +18,12 @@
 //                                   reference mode: the keys expanded).  Additions: the reference has no such option.
 //   --histo H   instead of the table, the abundance histogram: "COUNT<TAB>KEYS" lines, ascending, non-zero only; the line
 //               for H counts the keys seen H times or more.  The count filters apply to it too.
+//
+//   --query-kmers FILE   (with -k K) instead of the table: for every line of FILE, a K-mer, "KMER<TAB>COUNT" in input order --
+//               the k-mer as given, looked up canonically unless --forward; 0 for a k-mer the input does not hold
+//   --profile FILE       (with -k K) instead of the table: for every read of FILE (FASTA / FASTQ), in file order,
+//               "INDEX<TAB>WINDOWS<TAB>PRESENT<TAB>MIN<TAB>MAX<TAB>SUM": its valid K-mer windows, how many of them the
+//               counted input holds --min-count times or more, and the smallest / largest / summed count over them
 //
 // Errors: message on stderr, exit code 101 (what a Rust panic exits with), never partial stdout.
 #include <errno.h>
@@ -67,6 +73,7 @@ int main(int argc, char** argv) {
     const char* path = "sample.fasta";  // main.rs:44
     int k = 0, canonical = 1, expand = 0, device = 0, algo = KMC_ALGO_AUTO, stats = 0, gpus = 1, histo = 0;
     long long min_count = 1, max_count = 0;   // (max_count 0: no upper bound)
+    const char *query_path = nullptr, *profile_path = nullptr;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         if (a == "-k" && i + 1 < argc) { if (!parse_int("-k", argv[++i], 1, 63, &k)) return 2; }
@@ -78,14 +85,17 @@ int main(int argc, char** argv) {
         else if (a == "--min-count" && i + 1 < argc) { if (!parse_count("--min-count", argv[++i], 1, LLONG_MAX, &min_count)) return 2; }
         else if (a == "--max-count" && i + 1 < argc) { if (!parse_count("--max-count", argv[++i], 1, LLONG_MAX, &max_count)) return 2; }
         else if (a == "--histo" && i + 1 < argc) { if (!parse_int("--histo", argv[++i], 1, (1 << 24) - 1, &histo)) return 2; }
+        else if (a == "--query-kmers" && i + 1 < argc) query_path = argv[++i];
+        else if (a == "--profile" && i + 1 < argc) profile_path = argv[++i];
         else if (a == "--algo" && i + 1 < argc) {
             std::string v = argv[++i];
             algo = v == "stream" ? KMC_ALGO_STREAM : v == "walk" ? KMC_ALGO_WALK : v == "sort" ? KMC_ALGO_SORT : KMC_ALGO_AUTO;
         } else if (a == "-h" || a == "--help") {
             fprintf(stderr, "usage: k-mer-count [FASTA] [-k K] [--forward] [--expand] [--device N | --gpus N] [--algo auto|stream|walk|sort] [--stats]\n"
-                            "                   [--min-count N] [--max-count N] [--histo H]\n");
+                            "                   [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE]\n");
             return 0;
-        } else if (a == "-k" || a == "--device" || a == "--gpus" || a == "--algo" || a == "--min-count" || a == "--max-count" || a == "--histo") {
+        } else if (a == "-k" || a == "--device" || a == "--gpus" || a == "--algo" || a == "--min-count" || a == "--max-count" || a == "--histo" ||
+                   a == "--query-kmers" || a == "--profile") {
             fprintf(stderr, "k-mer-count: %s needs a value\n", a.c_str());
             return 2;
         } else if (!a.empty() && a[0] != '-') path = argv[i];
@@ -94,6 +104,46 @@ int main(int argc, char** argv) {
     if (max_count && min_count > max_count) {
         fprintf(stderr, "k-mer-count: --min-count %lld is above --max-count %lld\n", min_count, max_count);
         return 2;
+    }
+    // --query-kmers / --profile: everything that can be wrong with them is found before a GPU is touched
+    std::vector<std::string> q_text;
+    std::vector<uint64_t> q_hi, q_lo;
+    kmc_reads prof;
+    memset(&prof, 0, sizeof(prof));
+    if (query_path || profile_path) {
+        const char* opt = query_path ? "--query-kmers" : "--profile";
+        if (query_path && profile_path) { fprintf(stderr, "k-mer-count: --query-kmers and --profile exclude each other\n"); return 2; }
+        if (!k) { fprintf(stderr, "k-mer-count: %s needs -k K\n", opt); return 2; }
+        if (histo) { fprintf(stderr, "k-mer-count: %s and --histo exclude each other\n", opt); return 2; }
+    }
+    if (query_path) {
+        FILE* f = fopen(query_path, "r");
+        if (!f) return die(query_path, strerror(errno));
+        char buf[256];
+        unsigned long long line_no = 0;
+        while (fgets(buf, sizeof(buf), f)) {
+            ++line_no;
+            size_t len = strlen(buf);
+            const bool whole = len && buf[len - 1] == '\n';
+            while (len && (buf[len - 1] == '\n' || buf[len - 1] == '\r')) buf[--len] = '\0';
+            uint64_t h = 0, l = 0;
+            const int erc = (len == (size_t)k && (whole || feof(f))) ? kmc_encode_key(buf, k, canonical, &h, &l) : KMC_ERR_ARG;
+            if (erc) {
+                fprintf(stderr, "k-mer-count: --query-kmers %s line %llu: %s\n", query_path, line_no,
+                        erc == KMC_ERR_ALPHABET ? "a character outside ACGT" : "not a k-mer of length K");
+                fclose(f);
+                return 2;
+            }
+            q_text.emplace_back(buf, len);
+            q_hi.push_back(h);
+            q_lo.push_back(l);
+        }
+        fclose(f);
+    }
+    if (profile_path) {
+        char eb[256] = {0};
+        const int prc = kmc_parse_fasta(profile_path, &prof, eb, sizeof(eb));
+        if (prc) return die(profile_path, eb[0] ? eb : kmc_status_string(prc));
     }
     const bool filtered = min_count > 1 || max_count != 0;
     kmc_config cfg;
@@ -123,6 +173,32 @@ int main(int argc, char** argv) {
     rc = gpus == 1 ? kmc_count_file(ctx, path, &nd, &nt) : kmc_count_file_multi(ctxs.data(), (uint32_t)ctxs.size(), path, &nd, &nt);
     if (rc) { int r = die(path, kmc_last_error(ctx)); destroy_all(); return r; }
     std::vector<char> obuf(1 << 22);
+    if (query_path) {
+        std::vector<uint64_t> qc(q_lo.size() ? q_lo.size() : 1);
+        rc = kmc_query(ctx, q_hi.data(), q_lo.data(), q_lo.size(), qc.data());
+        if (rc) { int r = die("kmc_query", kmc_last_error(ctx)); destroy_all(); return r; }
+        setvbuf(stdout, obuf.data(), _IOFBF, obuf.size());
+        for (size_t i = 0; i < q_lo.size(); ++i) printf("%s\t%llu\n", q_text[i].c_str(), (unsigned long long)qc[i]);
+        fflush(stdout);
+        destroy_all();
+        return 0;
+    }
+    if (profile_path) {
+        std::vector<uint64_t> rs((size_t)prof.n_reads * KMC_PROFILE_WORDS + 1);
+        const uint64_t n_prof = prof.n_reads;
+        rc = kmc_profile(ctx, prof.bases, prof.offsets, n_prof, (uint64_t)min_count, nullptr, rs.data());
+        kmc_free_reads(&prof);
+        if (rc) { int r = die("kmc_profile", kmc_last_error(ctx)); destroy_all(); return r; }
+        setvbuf(stdout, obuf.data(), _IOFBF, obuf.size());
+        for (uint64_t r = 0; r < n_prof; ++r) {
+            const uint64_t* w = &rs[(size_t)r * KMC_PROFILE_WORDS];
+            printf("%llu\t%llu\t%llu\t%llu\t%llu\t%llu\n", (unsigned long long)r, (unsigned long long)w[0], (unsigned long long)w[1],
+                   (unsigned long long)w[2], (unsigned long long)w[3], (unsigned long long)w[4]);
+        }
+        fflush(stdout);
+        destroy_all();
+        return 0;
+    }
     if (histo) {
         std::vector<uint64_t> h((size_t)histo + 1);
         rc = kmc_histogram(ctx, (uint64_t)min_count, (uint64_t)max_count, (uint32_t)histo + 1, h.data(), nullptr);

@@ -534,6 +534,28 @@ extern "C" void kmc_decode_key(uint64_t hi, uint64_t lo, int klen, char* out) {
     }
 }
 
+// inverse of kmc_decode_key; canonical: the smaller of the k-mer and its reverse complement
+extern "C" int kmc_encode_key(const char* kmer, int klen, int canonical, uint64_t* key_hi, uint64_t* key_lo) {
+    if (!kmer || !key_hi || !key_lo || klen < 1 || klen > 63) return KMC_ERR_ARG;
+    unsigned __int128 f = 0, r = 0;
+    for (int i = 0; i < klen; ++i) {
+        unsigned code;
+        switch (kmer[i]) {
+            case 'A': code = 0; break;
+            case 'C': code = 1; break;
+            case 'G': code = 2; break;
+            case 'T': code = 3; break;
+            default: return KMC_ERR_ALPHABET;
+        }
+        f = (f << 2) | code;
+        r |= (unsigned __int128)(3u - code) << (2 * i);
+    }
+    const unsigned __int128 key = canonical && r < f ? r : f;
+    *key_hi = (uint64_t)(key >> 64);
+    *key_lo = (uint64_t)key;
+    return KMC_OK;
+}
+
 // ---- synthetic input (host half) -------------------------------------------------------------
 
 static inline int ndigits(uint64_t v) { int d = 1; while (v >= 10) { v /= 10; d++; } return d; }

@@ -281,3 +281,21 @@ def global_histogram(owner, n_bins: int, min_count: int = 1, max_count: int = 0,
     dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
     dist.all_reduce(m, op=dist.ReduceOp.MAX, group=group)
     return t.cpu().numpy().view(np.uint64).copy(), int(m.item())
+
+
+def global_query(owner, key_hi, key_lo, group=None) -> np.ndarray:
+    """Global counts of the given packed keys after reduce_tables.  Every key then lives on exactly one owner rank and is
+    absent (0) on all others, so the global answer is the elementwise sum of the owners' answers: every rank asks its own
+    table for ALL the keys and one all_reduce(SUM) of n int64 follows.  Every rank passes the same keys.  `owner`: anything
+    with a query(key_lo, key_hi) method (a finalized KmerCounter); key_hi None: high words zero.
+    Returns uint64[n] on every rank."""
+    lo = np.ascontiguousarray(key_lo, dtype=np.uint64).ravel()
+    hi = None if key_hi is None else np.ascontiguousarray(key_hi, dtype=np.uint64).ravel()
+    c = owner.query(lo, hi)
+    if dist.get_backend(group) == "nccl":
+        dev = torch.device("cuda", getattr(owner, "device", torch.cuda.current_device()))
+    else:
+        dev = torch.device("cpu")
+    t = torch.from_numpy(np.asarray(c, dtype=np.uint64).view(np.int64).copy()).to(dev)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    return t.cpu().numpy().view(np.uint64).copy()

@@ -12,6 +12,8 @@ pub const KMC_ALGO_WALK: i32 = 2;
 pub const KMC_ALGO_SORT: i32 = 3;
 pub const KMC_FORGET_MEMO: c_int = 1;
 pub const KMC_FORGET_HISTORY: c_int = 2;
+/// words per read of `kmc_profile`'s read_stats
+pub const KMC_PROFILE_WORDS: usize = 5;
 
 // The structs and the extern block below are checked against include/kmc.h by
 // tests/test_abi_host.py::test_rust_binding_matches_the_header (names, arity, argument types, field
@@ -99,6 +101,14 @@ extern "C" {
                              d_count: *mut *const c_void, n_kept: *mut u64, kept_total: *mut u64) -> c_int;
     pub fn kmc_export_filtered(ctx: *mut KmcCtx, min_count: u64, max_count: u64, key_hi: *mut u64, key_lo: *mut u64, count: *mut u64,
                                cap: u64, n_kept: *mut u64) -> c_int;
+    // asking the table: key lookups and per-read profiles of the sorted view
+    pub fn kmc_encode_key(kmer: *const c_char, klen: c_int, canonical: c_int, key_hi: *mut u64, key_lo: *mut u64) -> c_int;
+    pub fn kmc_query(ctx: *mut KmcCtx, key_hi: *const u64, key_lo: *const u64, n_keys: u64, count: *mut u64) -> c_int;
+    pub fn kmc_query_device(ctx: *mut KmcCtx, d_key_hi: *const c_void, d_key_lo: *const c_void, n_keys: u64, d_count: *mut c_void) -> c_int;
+    pub fn kmc_profile(ctx: *mut KmcCtx, bases: *const u8, offsets: *const u64, n_reads: u64, min_count: u64, window_count: *mut u32,
+                       read_stats: *mut u64) -> c_int;
+    pub fn kmc_profile_device(ctx: *mut KmcCtx, d_bases: *const c_void, d_offsets: *const c_void, n_reads: u64, n_bases: u64,
+                              min_count: u64, d_window_count: *mut c_void, d_read_stats: *mut c_void) -> c_int;
     // multi-GPU reduce (one process per GPU; the collective itself is the host program's, e.g. RCCL)
     pub fn kmc_slab_words(ctx: *const KmcCtx, slab_entries: u64) -> u64;
     pub fn kmc_pack_slab_device(ctx: *mut KmcCtx, d_slab: *mut c_void, slab_entries: u64) -> c_int;
@@ -233,6 +243,38 @@ impl Counter {
             out.push((String::from_utf8_lossy(&buf).into_owned(), cnt[i]));
         }
         Ok(out)
+    }
+
+    /// Counts of the given packed keys in the table (0 = absent), looked up as given (`kmc_query`); `key_hi` may be
+    /// empty when the keys fit one word.
+    pub fn query(&mut self, key_hi: &[u64], key_lo: &[u64]) -> Result<Vec<u64>, KmcError> {
+        if !key_hi.is_empty() && key_hi.len() != key_lo.len() {
+            return Err(KmcError(-1, "key_hi and key_lo differ in length".into()));
+        }
+        let (mut nd, mut nt) = (0u64, 0u64);
+        self.check(unsafe { kmc_finalize(self.ctx, &mut nd, &mut nt) })?;
+        let mut count = vec![0u64; key_lo.len()];
+        let hi = if key_hi.is_empty() { std::ptr::null() } else { key_hi.as_ptr() };
+        self.check(unsafe { kmc_query(self.ctx, hi, key_lo.as_ptr(), key_lo.len() as u64, count.as_mut_ptr()) })?;
+        Ok(count)
+    }
+
+    /// Per-read k-mer profile of a batch against the table (`kmc_profile`; the batch is not counted): the count of the
+    /// window starting at every base (saturated u32) and, per read, [valid windows, windows with count >=
+    /// max(min_count, 1), min, max, sum].
+    pub fn profile(&mut self, bases: &[u8], offsets: &[u64], min_count: u64) -> Result<(Vec<u32>, Vec<[u64; KMC_PROFILE_WORDS]>), KmcError> {
+        let (mut nd, mut nt) = (0u64, 0u64);
+        self.check(unsafe { kmc_finalize(self.ctx, &mut nd, &mut nt) })?;
+        let n_reads = offsets.len().saturating_sub(1);
+        if n_reads > 0 && offsets[n_reads] as usize != bases.len() {
+            return Err(KmcError(-1, "offsets do not end at the number of bases".into()));
+        }
+        let mut win = vec![0u32; bases.len()];
+        let mut stats = vec![[0u64; KMC_PROFILE_WORDS]; n_reads];
+        self.check(unsafe {
+            kmc_profile(self.ctx, bases.as_ptr(), offsets.as_ptr(), n_reads as u64, min_count, win.as_mut_ptr(), stats.as_mut_ptr() as *mut u64)
+        })?;
+        Ok((win, stats))
     }
 }
 
