@@ -21,6 +21,7 @@
  *   (addition: no equivalent in the reference)             kmc_encode_key (ASCII k-mer -> packed key)
  *   (addition: no equivalent in the reference)             kmc_query / kmc_query_device (count of given keys)
  *   (addition: no equivalent in the reference)             kmc_profile / kmc_profile_device (per-read k-mer profile)
+ *   (addition: no equivalent in the reference)             kmc_compare / kmc_setop_device / kmc_export_setop (two tables)
  *
  * Conventions
  *   - Every function returns 0 (KMC_OK) or a negative kmc_status; no exception or abort crosses
@@ -252,6 +253,45 @@ int kmc_profile(kmc_ctx* ctx, const uint8_t* bases, const uint64_t* offsets, uin
 /* Device form: alignment / padding rules of kmc_add_batch_device for d_bases; asynchronous on the ctx stream. */
 int kmc_profile_device(kmc_ctx* ctx, const void* d_bases, const void* d_offsets, uint64_t n_reads, uint64_t n_bases,
                        uint64_t min_count, void* d_window_count, void* d_read_stats);
+
+/* ---- two tables: summary and set operations (additions, as above).  A and B are the sorted views of the last
+ * kmc_finalize of two contexts (a view queued by kmc_finalize_async counts as one).  For a key x, ca = its count in A if
+ * it is present there and min_a <= count <= max_a (max_a 0 = no upper bound), else 0; cb likewise with min_b / max_b.
+ * Only keys with ca != 0 or cb != 0 exist for the operation.
+ *   op          KMC_SETOP_INTERSECT: ca != 0 && cb != 0;  KMC_SETOP_UNION: ca != 0 || cb != 0;  KMC_SETOP_SUBTRACT: ca != 0 && cb == 0
+ *   count_mode  result count r = ca (LEFT), cb (RIGHT), min(ca, cb), max(ca, cb), ca + cb (SUM: plain 64-bit addition),
+ *               ca > cb ? ca - cb : 0 (DIFF)
+ * A selected key is emitted iff r != 0, in ascending key order: the result has the shape of a view (UNION + DIFF is
+ * "counter subtract"; UNION + LEFT with ranges is A filtered).
+ * Rules: a NULL context, an unknown op / count_mode, a non-zero max below its min: KMC_ERR_ARG.  a and b must agree in
+ * device, mode, k and canonical (KMC_ERR_ARG; the message names the field); a == b is allowed.  No view: KMC_ERR_STATE
+ * (message on the ctx that lacks it).  The two views together must hold fewer than 2^32 keys (KMC_ERR_CAPACITY).  Work
+ * runs on a's stream and the result lives in device arrays owned by a, valid until the next set operation / finalize /
+ * reset / destroy of a (same ordering contract as kmc_export_device; d_key_hi is NULL when keys fit one word).  b's view
+ * is only read.  Neither view, nor a partition, filter result or query index of either context is changed. ---- */
+#define KMC_SETOP_INTERSECT 0
+#define KMC_SETOP_UNION 1
+#define KMC_SETOP_SUBTRACT 2
+#define KMC_COUNT_LEFT 0
+#define KMC_COUNT_RIGHT 1
+#define KMC_COUNT_MIN 2
+#define KMC_COUNT_MAX 3
+#define KMC_COUNT_SUM 4
+#define KMC_COUNT_DIFF 5
+#define KMC_COMPARE_WORDS 8
+/* summary[KMC_COMPARE_WORDS]: [0] n_a = keys with ca != 0, [1] n_b, [2] n_both, [3] sum of ca, [4] sum of cb, [5] sum of ca
+ * over shared keys, [6] sum of cb over shared keys, [7] sum of min(ca, cb).  It does not depend on op / count_mode.
+ * Union size n_a + n_b - n_both, Jaccard n_both / union, containment n_both / n_a, weighted Jaccard
+ * [7] / ([3] + [4] - [7]) and the Bray-Curtis similarity 2 [7] / ([3] + [4]) are host arithmetic on it. */
+int kmc_compare(kmc_ctx* a, kmc_ctx* b, uint64_t min_a, uint64_t max_a, uint64_t min_b, uint64_t max_b, uint64_t* summary);
+/* *n_out / *total_out (may be NULL) = entries of the result and the sum of their counts; summary may be NULL. */
+int kmc_setop_device(kmc_ctx* a, kmc_ctx* b, int op, int count_mode, uint64_t min_a, uint64_t max_a, uint64_t min_b,
+                     uint64_t max_b, const void** d_key_hi, const void** d_key_lo, const void** d_count, uint64_t* n_out,
+                     uint64_t* total_out, uint64_t* summary);
+/* The same, copied to caller arrays of `cap` entries (key_hi may be NULL if the caller knows k <= 32).  *n_out is always
+ * set; cap < *n_out -> KMC_ERR_ARG and nothing is copied (call with cap 0 and NULL arrays to size the buffers). */
+int kmc_export_setop(kmc_ctx* a, kmc_ctx* b, int op, int count_mode, uint64_t min_a, uint64_t max_a, uint64_t min_b,
+                     uint64_t max_b, uint64_t* key_hi, uint64_t* key_lo, uint64_t* count, uint64_t cap, uint64_t* n_out);
 
 /* Multi-GPU reduce for small tables: ONE fixed-size all-gather instead of size exchange +
  * all-to-all (the reduce of main.rs:87's grouping across GPUs; for the generator's input a table is

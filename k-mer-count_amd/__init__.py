@@ -86,9 +86,15 @@ ABI_SYMBOLS = [
     "kmc_count_file_multi", "kmc_read_pieces", "kmc_sync", "kmc_read_peak_device", "kmc_finalize_async",
     "kmc_histogram", "kmc_filter_device", "kmc_export_filtered",
     "kmc_encode_key", "kmc_query", "kmc_query_device", "kmc_profile", "kmc_profile_device",
+    "kmc_compare", "kmc_setop_device", "kmc_export_setop",
 ]
 
 PROFILE_WORDS = 5  # KMC_PROFILE_WORDS: valid windows, present windows, min, max, sum
+COMPARE_WORDS = 8  # KMC_COMPARE_WORDS: n_a, n_b, n_both, sum_a, sum_b, shared_sum_a, shared_sum_b, sum_min
+SETOP_INTERSECT, SETOP_UNION, SETOP_SUBTRACT = 0, 1, 2
+COUNT_LEFT, COUNT_RIGHT, COUNT_MIN, COUNT_MAX, COUNT_SUM, COUNT_DIFF = 0, 1, 2, 3, 4, 5
+SETOP_NAMES = {"intersect": SETOP_INTERSECT, "union": SETOP_UNION, "subtract": SETOP_SUBTRACT}
+COUNT_NAMES = {"left": COUNT_LEFT, "right": COUNT_RIGHT, "min": COUNT_MIN, "max": COUNT_MAX, "sum": COUNT_SUM, "diff": COUNT_DIFF}
 
 _lib = None
 
@@ -147,6 +153,9 @@ def lib() -> C.CDLL:
     L.kmc_query_device.argtypes = [vp, vp, vp, u64, vp]
     L.kmc_profile.argtypes = [vp, vp, vp, u64, u64, vp, vp]
     L.kmc_profile_device.argtypes = [vp, vp, vp, u64, u64, u64, vp, vp]
+    L.kmc_compare.argtypes = [vp, vp, u64, u64, u64, u64, vp]
+    L.kmc_setop_device.argtypes = [vp, vp, i32, i32, u64, u64, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), pu64, pu64, vp]
+    L.kmc_export_setop.argtypes = [vp, vp, i32, i32, u64, u64, u64, u64, vp, vp, vp, u64, pu64]
     L.kmc_owner_of.argtypes = [u64, u64, u32]
     L.kmc_owner_of.restype = u32
     L.kmc_get_stats.argtypes = [vp, C.POINTER(Stats)]
@@ -245,6 +254,67 @@ class Table:
         return (self.klen == other.klen and self.n_distinct == other.n_distinct
                 and np.array_equal(self.key_hi, other.key_hi) and np.array_equal(self.key_lo, other.key_lo)
                 and np.array_equal(self.count, other.count))
+
+
+_COMPARE_FIELDS = ("n_a", "n_b", "n_both", "sum_a", "sum_b", "shared_sum_a", "shared_sum_b", "sum_min")
+
+
+@dataclass
+class Comparison:
+    """The eight words of kmc_compare and the similarities that are host arithmetic on them (0.0 where a
+    denominator is 0: two empty sides are not similar, and not NaN)."""
+    n_a: int
+    n_b: int
+    n_both: int
+    sum_a: int
+    sum_b: int
+    shared_sum_a: int
+    shared_sum_b: int
+    sum_min: int
+
+    @classmethod
+    def from_words(cls, words) -> "Comparison":
+        return cls(*[int(w) for w in words])
+
+    def words(self) -> list:
+        return [getattr(self, f) for f in _COMPARE_FIELDS]
+
+    @staticmethod
+    def _ratio(num: int, den: int) -> float:
+        return num / den if den else 0.0
+
+    @property
+    def union(self) -> int:
+        return self.n_a + self.n_b - self.n_both
+
+    @property
+    def jaccard(self) -> float:
+        return self._ratio(self.n_both, self.union)
+
+    @property
+    def containment_a(self) -> float:
+        return self._ratio(self.n_both, self.n_a)
+
+    @property
+    def containment_b(self) -> float:
+        return self._ratio(self.n_both, self.n_b)
+
+    @property
+    def weighted_jaccard(self) -> float:
+        return self._ratio(self.sum_min, self.sum_a + self.sum_b - self.sum_min)
+
+    @property
+    def bray_curtis(self) -> float:
+        """Bray-Curtis similarity 2 sum(min) / (sum_a + sum_b)."""
+        return self._ratio(2 * self.sum_min, self.sum_a + self.sum_b)
+
+    def to_text(self) -> str:
+        """``NAME\tVALUE`` lines as the CLI's --compare prints them."""
+        lines = ["%s\t%d" % (f, getattr(self, f)) for f in _COMPARE_FIELDS]
+        lines.append("union\t%d" % self.union)
+        for f in ("jaccard", "containment_a", "containment_b", "weighted_jaccard", "bray_curtis"):
+            lines.append("%s\t%.6f" % (f, getattr(self, f)))
+        return "\n".join(lines) + "\n"
 
 
 def parse_fasta(path: str) -> Tuple[np.ndarray, np.ndarray]:
@@ -430,6 +500,47 @@ class KmerCounter:
         if nk:
             self._chk(self._L.kmc_export_filtered(self._h, int(min_count), int(max_count), hi.ctypes.data, lo.ctypes.data,
                                                   cnt.ctypes.data, nk, C.byref(n)))
+        return Table(hi, lo, cnt, self.k)
+
+    # -- two tables: summary and set operations over the sorted views of self (A) and other (B) --
+    @staticmethod
+    def _setop_codes(op, counts) -> Tuple[int, int]:
+        o = SETOP_NAMES[op] if isinstance(op, str) else int(op)
+        m = COUNT_NAMES[counts] if isinstance(counts, str) else int(counts)
+        return o, m
+
+    def compare(self, other: "KmerCounter", min_a: int = 1, max_a: int = 0, min_b: int = 1, max_b: int = 0) -> Comparison:
+        """kmc_compare: how many keys (with counts in [min_a, max_a] / [min_b, max_b]; max 0: no upper bound) each side
+        has, how many both have, and the count sums Jaccard, containment, weighted Jaccard and Bray-Curtis derive from."""
+        w = (C.c_uint64 * COMPARE_WORDS)()
+        self._chk(self._L.kmc_compare(self._h, other._h, int(min_a), int(max_a), int(min_b), int(max_b), w))
+        return Comparison.from_words(list(w))
+
+    def setop_device(self, other: "KmerCounter", op, counts=COUNT_LEFT, min_a: int = 1, max_a: int = 0, min_b: int = 1,
+                     max_b: int = 0, return_summary: bool = False):
+        """(d_key_hi or 0, d_key_lo, d_count, n_out, total_out) of ``self op other`` in device arrays owned by self
+        (kmc_setop_device); op / counts are the SETOP_* / COUNT_* codes or their names.  return_summary=True appends
+        the Comparison."""
+        o, m = self._setop_codes(op, counts)
+        a, b, c, n, t = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        w = (C.c_uint64 * COMPARE_WORDS)()
+        self._chk(self._L.kmc_setop_device(self._h, other._h, o, m, int(min_a), int(max_a), int(min_b), int(max_b), C.byref(a), C.byref(b),
+                                           C.byref(c), C.byref(n), C.byref(t), w if return_summary else None))
+        r = (a.value or 0, b.value or 0, c.value or 0, n.value, t.value)
+        return r + (Comparison.from_words(list(w)),) if return_summary else r
+
+    def setop(self, other: "KmerCounter", op, counts=COUNT_LEFT, min_a: int = 1, max_a: int = 0, min_b: int = 1, max_b: int = 0) -> Table:
+        """``self op other`` on the host: intersect / union / subtract with the result count given by ``counts``."""
+        o, m = self._setop_codes(op, counts)
+        args = (self._h, other._h, o, m, int(min_a), int(max_a), int(min_b), int(max_b))
+        n = C.c_uint64()
+        rc = self._L.kmc_export_setop(*args, None, None, None, 0, C.byref(n))
+        if rc not in (OK, ERR_ARG) or (rc == ERR_ARG and n.value == 0):
+            self._chk(rc)
+        nk = n.value
+        hi, lo, cnt = np.zeros(nk, np.uint64), np.zeros(nk, np.uint64), np.zeros(nk, np.uint64)
+        if nk:
+            self._chk(self._L.kmc_export_setop(*args, hi.ctypes.data, lo.ctypes.data, cnt.ctypes.data, nk, C.byref(n)))
         return Table(hi, lo, cnt, self.k)
 
     # -- asking the table: key lookups and per-read profiles (of the sorted view; finalize() first) --

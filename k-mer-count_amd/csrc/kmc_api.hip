@@ -36,6 +36,7 @@
 #include "kmc_peak.hip.h"
 #include "kmc_spectrum.hip.h"
 #include "kmc_query.hip.h"
+#include "kmc_setops.hip.h"
 #include "kmc_ingest.h"
 
 namespace {
@@ -184,6 +185,9 @@ struct kmc_ctx {
     // host forms: query keys and counts, a batch's bases and offsets, its window counts and read statistics
     u64 view_gen = 0, q_gen = ~0ull;
     DevBuf q_idx, q_khi, q_klo, q_cnt, q_bases, q_offs, q_win, q_stats;
+    // kmc_compare / kmc_setop_device (kmc_setops.hip.h), on the ctx given as `a`: the result, the merge-path partition of the
+    // two views (first A / B entry of every tile), emitted keys per tile and their scan, [n_out | summary words | total_out]
+    DevBuf so_hi, so_lo, so_cnt, so_pa, so_pb, so_tile, so_tpos, so_bsum, so_ctl;
 };
 
 namespace {
@@ -1710,7 +1714,8 @@ extern "C" void kmc_destroy(kmc_ctx* c) {
                       &c->m_bitmap, &c->m_rank, &c->m_nd, &c->m_base, &c->m_ctl, &c->m_clist, &c->m_w[0], &c->m_w[1],
                       &c->snap_hi, &c->snap_lo, &c->snap_cnt, &c->snap_n, &c->snap_occ, &c->rx_hi, &c->rx_lo, &c->rx_cnt,
                       &c->f_hi, &c->f_lo, &c->f_cnt, &c->f_tile, &c->f_tpos, &c->f_bsum, &c->f_ctl, &c->h_hist,
-                      &c->q_idx, &c->q_khi, &c->q_klo, &c->q_cnt, &c->q_bases, &c->q_offs, &c->q_win, &c->q_stats};
+                      &c->q_idx, &c->q_khi, &c->q_klo, &c->q_cnt, &c->q_bases, &c->q_offs, &c->q_win, &c->q_stats,
+                      &c->so_hi, &c->so_lo, &c->so_cnt, &c->so_pa, &c->so_pb, &c->so_tile, &c->so_tpos, &c->so_bsum, &c->so_ctl};
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
     sk_free(c);
     try { free_runs(c, true); } catch (...) { /* (only the pool bookkeeping can throw; the buffers it could not list leak with the process) */ }
@@ -2459,6 +2464,170 @@ static int kmc_profile_impl(kmc_ctx* c, const uint8_t* bases, const uint64_t* of
     return KMC_OK;
 }
 
+// ---- two tables compared: summary and set operations over the sorted views of two contexts (kmc_setops.hip.h) ----
+// What every set-operation call checks first: arguments, that a and b count the same kind of key on one device, both views.
+// b's view is only read, on a's stream: b is synchronised first where kmc_export_device would do so.
+static int setop_begin(kmc_ctx* a, kmc_ctx* b, const char* what, int op, int count_mode, uint64_t min_a, uint64_t max_a,
+                       uint64_t min_b, uint64_t max_b) {
+    if (op < KMC_SETOP_INTERSECT || op > KMC_SETOP_SUBTRACT) return fail(a, KMC_ERR_ARG, "%s: unknown op %d", what, op);
+    if (count_mode < KMC_COUNT_LEFT || count_mode > KMC_COUNT_DIFF) return fail(a, KMC_ERR_ARG, "%s: unknown count_mode %d", what, count_mode);
+    if (max_a && min_a > max_a) return fail(a, KMC_ERR_ARG, "%s: min_a %llu > max_a %llu", what, (unsigned long long)min_a, (unsigned long long)max_a);
+    if (max_b && min_b > max_b) return fail(a, KMC_ERR_ARG, "%s: min_b %llu > max_b %llu", what, (unsigned long long)min_b, (unsigned long long)max_b);
+    if (a->cfg.device != b->cfg.device) return fail(a, KMC_ERR_ARG, "%s: the contexts differ in device (%d / %d)", what, a->cfg.device, b->cfg.device);
+    if (a->cfg.mode != b->cfg.mode) return fail(a, KMC_ERR_ARG, "%s: the contexts differ in mode (%d / %d)", what, a->cfg.mode, b->cfg.mode);
+    if (a->klen != b->klen || a->KW != b->KW) return fail(a, KMC_ERR_ARG, "%s: the contexts differ in k (%d / %d)", what, a->klen, b->klen);
+    if ((a->cfg.canonical != 0) != (b->cfg.canonical != 0))
+        return fail(a, KMC_ERR_ARG, "%s: the contexts differ in canonical (%d / %d)", what, a->cfg.canonical, b->cfg.canonical);
+    int rc = view_begin(a, what);
+    if (rc) return rc;
+    if (b != a) {
+        rc = view_begin(b, what);
+        if (rc) return rc;
+        if (b->view_unsynced) {
+            HIPCHK(b, hipSetDevice(b->cfg.device));
+            HIPCHK(b, hipStreamSynchronize(b->stream));
+            b->view_unsynced = false;
+        }
+    }
+    if (a->n_sorted + b->n_sorted >= (1ull << 32))
+        return fail(a, KMC_ERR_CAPACITY, "%s: the two views hold 2^32 keys or more together", what);
+    HIPCHK(a, hipSetDevice(a->cfg.device));
+    return KMC_OK;
+}
+
+static SoView so_view(const kmc_ctx* c, uint64_t min_c, uint64_t max_c) {
+    SoView v;
+    v.hi = c->KW == 2 ? c->v_hi : nullptr;
+    v.lo = c->v_lo;
+    v.cnt = c->v_cnt;
+    v.n = c->n_sorted;
+    v.min_c = min_c;
+    v.max_c = max_c ? (u64)max_c : ~0ull;
+    return v;
+}
+
+// Partition + one pass over both views.  pass 0: the summary; pass 1: the summary, the emitted keys per tile and their
+// scan (so_tpos).  h[0] = n_out (pass 1), h[1..8] = summary, h[9] = total_out.  Waits for the result.
+static int setop_reduce(kmc_ctx* a, kmc_ctx* b, int pass, int op, int count_mode, const SoView& A, const SoView& B, u64* h) {
+    memset(h, 0, (KMC_SO_WORDS + 1) * sizeof(u64));
+    const u64 nm = A.n + B.n;
+    if (!nm) return KMC_OK;
+    auto mis = [](const SoView& v) { return v.n && (((uintptr_t)v.hi | (uintptr_t)v.lo | (uintptr_t)v.cnt) & 15) != 0; };
+    if (mis(A) || mis(B)) return fail(a, KMC_ERR_HIP, "internal error: sorted view not 16-byte aligned");
+    const u32 n_tiles = (u32)((nm + KMC_SO_TILE - 1) / KMC_SO_TILE);
+    const u32 nb = (n_tiles + KMC_SCAN_PER_BLOCK - 1) / KMC_SCAN_PER_BLOCK;
+    int rc;
+    if ((rc = ensure(a, a->so_pa, ((size_t)n_tiles + 1) * sizeof(u32))) || (rc = ensure(a, a->so_pb, ((size_t)n_tiles + 1) * sizeof(u32))) ||
+        (rc = ensure(a, a->so_tile, (size_t)n_tiles * sizeof(u32))) || (rc = ensure(a, a->so_tpos, (size_t)n_tiles * sizeof(u32))) ||
+        (rc = ensure(a, a->so_bsum, ((size_t)nb + 2) * sizeof(u32))) || (rc = ensure(a, a->so_ctl, (KMC_SO_WORDS + 1) * sizeof(u64))))
+        return rc;
+    u64* ctl = (u64*)a->so_ctl.p;   // [n_out (u32 written by the scan, high half stays 0) | summary | total_out]
+    HIPCHK(a, hipMemsetAsync(ctl, 0, (KMC_SO_WORDS + 1) * sizeof(u64), a->stream));
+    u32 *pa = (u32*)a->so_pa.p, *pb = (u32*)a->so_pb.p, *tile = (u32*)a->so_tile.p;
+    const u32 pgrid = (n_tiles + 1 + 255) / 256;
+    const u32 grid = (u32)std::min<u64>(n_tiles, (u64)a->n_cu * 8);
+    (void)b;
+#define KMC_SO_REDUCE(KW_)                                                                                                              \
+    do {                                                                                                                                \
+        hipLaunchKernelGGL(kmc_setop_partition_kernel<KW_>, dim3(pgrid), dim3(256), 0, a->stream, A, B, n_tiles, pa, pb);               \
+        if (pass == 0)                                                                                                                  \
+            hipLaunchKernelGGL((kmc_setop_join_kernel<KW_, 0>), dim3(grid), dim3(KMC_SO_THREADS), 0, a->stream, A, B, op, count_mode, n_tiles, \
+                               (const u32*)pa, (const u32*)pb, (u32*)nullptr, (const u32*)nullptr, (kmc_soull*)(ctl + 1), (u64*)nullptr,   \
+                               (u64*)nullptr, (u64*)nullptr);                                                                           \
+        else                                                                                                                            \
+            hipLaunchKernelGGL((kmc_setop_join_kernel<KW_, 1>), dim3(grid), dim3(KMC_SO_THREADS), 0, a->stream, A, B, op, count_mode, n_tiles, \
+                               (const u32*)pa, (const u32*)pb, tile, (const u32*)nullptr, (kmc_soull*)(ctl + 1), (u64*)nullptr,            \
+                               (u64*)nullptr, (u64*)nullptr);                                                                           \
+    } while (0)
+    if (a->KW == 1) KMC_SO_REDUCE(1); else KMC_SO_REDUCE(2);
+#undef KMC_SO_REDUCE
+    if (pass == 1) {
+        hipLaunchKernelGGL(kmc_scan_sums_kernel<0>, dim3(nb), dim3(256), 0, a->stream, (const void*)tile, n_tiles, (u32*)a->so_bsum.p);
+        hipLaunchKernelGGL(kmc_scan_top_kernel, dim3(1), dim3(1024), 0, a->stream, (u32*)a->so_bsum.p, nb, (u32*)ctl);
+        hipLaunchKernelGGL(kmc_scan_final_kernel<0>, dim3(nb), dim3(256), 0, a->stream, (const void*)tile, n_tiles, (const u32*)a->so_bsum.p,
+                           (u32*)a->so_tpos.p);
+    }
+    HIPCHK(a, hipGetLastError());
+    HIPCHK(a, hipMemcpyAsync(h, ctl, (KMC_SO_WORDS + 1) * sizeof(u64), hipMemcpyDeviceToHost, a->stream));
+    HIPCHK(a, hipStreamSynchronize(a->stream));
+    return KMC_OK;
+}
+
+// scatter half (setop_reduce pass 1 ran first): the emitted entries into so_hi / so_lo / so_cnt; finished when it returns
+static int setop_scatter(kmc_ctx* a, int op, int count_mode, const SoView& A, const SoView& B, u64 n_out) {
+    const size_t bytes = (size_t)std::max<u64>(n_out, 1) * sizeof(u64);
+    int rc;
+    if ((rc = ensure(a, a->so_lo, bytes)) || (rc = ensure(a, a->so_cnt, bytes))) return rc;
+    if (a->KW == 2 && (rc = ensure(a, a->so_hi, bytes))) return rc;
+    if (!n_out) return KMC_OK;
+    const u32 n_tiles = (u32)((A.n + B.n + KMC_SO_TILE - 1) / KMC_SO_TILE);
+    const u32 grid = (u32)std::min<u64>(n_tiles, (u64)a->n_cu * 8);
+    if (a->KW == 1)
+        hipLaunchKernelGGL((kmc_setop_join_kernel<1, 2>), dim3(grid), dim3(KMC_SO_THREADS), 0, a->stream, A, B, op, count_mode, n_tiles,
+                           (const u32*)a->so_pa.p, (const u32*)a->so_pb.p, (u32*)nullptr, (const u32*)a->so_tpos.p, (kmc_soull*)nullptr,
+                           (u64*)nullptr, (u64*)a->so_lo.p, (u64*)a->so_cnt.p);
+    else
+        hipLaunchKernelGGL((kmc_setop_join_kernel<2, 2>), dim3(grid), dim3(KMC_SO_THREADS), 0, a->stream, A, B, op, count_mode, n_tiles,
+                           (const u32*)a->so_pa.p, (const u32*)a->so_pb.p, (u32*)nullptr, (const u32*)a->so_tpos.p, (kmc_soull*)nullptr,
+                           (u64*)a->so_hi.p, (u64*)a->so_lo.p, (u64*)a->so_cnt.p);
+    HIPCHK(a, hipGetLastError());
+    HIPCHK(a, hipStreamSynchronize(a->stream));
+    return KMC_OK;
+}
+
+static int kmc_compare_impl(kmc_ctx* a, kmc_ctx* b, uint64_t min_a, uint64_t max_a, uint64_t min_b, uint64_t max_b, uint64_t* summary) {
+    if (!a || !b) return a ? fail(a, KMC_ERR_ARG, "kmc_compare: null context") : KMC_ERR_ARG;
+    if (!summary) return fail(a, KMC_ERR_ARG, "kmc_compare: null summary");
+    int rc = setop_begin(a, b, "kmc_compare", KMC_SETOP_INTERSECT, KMC_COUNT_LEFT, min_a, max_a, min_b, max_b);
+    if (rc) return rc;
+    u64 h[KMC_SO_WORDS + 1];
+    rc = setop_reduce(a, b, 0, KMC_SETOP_INTERSECT, KMC_COUNT_LEFT, so_view(a, min_a, max_a), so_view(b, min_b, max_b), h);
+    if (rc) return rc;
+    memcpy(summary, h + 1, KMC_COMPARE_WORDS * sizeof(u64));
+    return KMC_OK;
+}
+
+static int kmc_setop_device_impl(kmc_ctx* a, kmc_ctx* b, int op, int count_mode, uint64_t min_a, uint64_t max_a, uint64_t min_b,
+                                 uint64_t max_b, const void** d_key_hi, const void** d_key_lo, const void** d_count, uint64_t* n_out,
+                                 uint64_t* total_out, uint64_t* summary) {
+    if (!a || !b) return a ? fail(a, KMC_ERR_ARG, "kmc_setop_device: null context") : KMC_ERR_ARG;
+    int rc = setop_begin(a, b, "kmc_setop_device", op, count_mode, min_a, max_a, min_b, max_b);
+    if (rc) return rc;
+    const SoView A = so_view(a, min_a, max_a), B = so_view(b, min_b, max_b);
+    u64 h[KMC_SO_WORDS + 1];
+    rc = setop_reduce(a, b, 1, op, count_mode, A, B, h);
+    if (rc) return rc;
+    rc = setop_scatter(a, op, count_mode, A, B, h[0]);
+    if (rc) return rc;
+    if (d_key_hi) *d_key_hi = a->KW == 2 ? a->so_hi.p : nullptr;
+    if (d_key_lo) *d_key_lo = a->so_lo.p;
+    if (d_count) *d_count = a->so_cnt.p;
+    if (n_out) *n_out = h[0];
+    if (total_out) *total_out = h[KMC_SO_WORDS];
+    if (summary) memcpy(summary, h + 1, KMC_COMPARE_WORDS * sizeof(u64));
+    return KMC_OK;
+}
+
+static int kmc_export_setop_impl(kmc_ctx* a, kmc_ctx* b, int op, int count_mode, uint64_t min_a, uint64_t max_a, uint64_t min_b,
+                                 uint64_t max_b, uint64_t* key_hi, uint64_t* key_lo, uint64_t* count, uint64_t cap, uint64_t* n_out) {
+    if (n_out) *n_out = 0;
+    if (!a || !b) return a ? fail(a, KMC_ERR_ARG, "kmc_export_setop: null context") : KMC_ERR_ARG;
+    int rc = setop_begin(a, b, "kmc_export_setop", op, count_mode, min_a, max_a, min_b, max_b);
+    if (rc) return rc;
+    const SoView A = so_view(a, min_a, max_a), B = so_view(b, min_b, max_b);
+    u64 h[KMC_SO_WORDS + 1];
+    rc = setop_reduce(a, b, 1, op, count_mode, A, B, h);
+    if (rc) return rc;
+    const u64 n = h[0];
+    if (n_out) *n_out = n;
+    if (cap < n) return fail(a, KMC_ERR_ARG, "kmc_export_setop: capacity %llu < %llu result keys", (unsigned long long)cap, (unsigned long long)n);
+    if (!n) return KMC_OK;
+    if (!key_lo || !count) return fail(a, KMC_ERR_ARG, "null buffer");
+    rc = setop_scatter(a, op, count_mode, A, B, n);
+    if (rc) return rc;
+    return copy_to_host(a, a->so_hi.p, a->so_lo.p, a->so_cnt.p, n, key_hi, key_lo, count);
+}
+
 extern "C" uint64_t kmc_slab_words(const kmc_ctx* c, uint64_t slab_entries) {
     return c ? KMC_SLAB_HEADER + slab_entries * (u64)(c->KW + 1) : 0;
 }
@@ -2980,6 +3149,22 @@ extern "C" int kmc_profile(kmc_ctx* c, const uint8_t* bases, const uint64_t* off
 extern "C" int kmc_profile_device(kmc_ctx* c, const void* d_bases, const void* d_offsets, uint64_t n_reads, uint64_t n_bases,
                                   uint64_t min_count, void* d_window_count, void* d_read_stats) {
     return guarded(c, [&]() -> int { return kmc_profile_device_impl(c, d_bases, d_offsets, n_reads, n_bases, min_count, d_window_count, d_read_stats); });
+}
+extern "C" int kmc_compare(kmc_ctx* a, kmc_ctx* b, uint64_t min_a, uint64_t max_a, uint64_t min_b, uint64_t max_b, uint64_t* summary) {
+    return guarded(a, [&]() -> int { return kmc_compare_impl(a, b, min_a, max_a, min_b, max_b, summary); });
+}
+extern "C" int kmc_setop_device(kmc_ctx* a, kmc_ctx* b, int op, int count_mode, uint64_t min_a, uint64_t max_a, uint64_t min_b,
+                                uint64_t max_b, const void** d_key_hi, const void** d_key_lo, const void** d_count, uint64_t* n_out,
+                                uint64_t* total_out, uint64_t* summary) {
+    return guarded(a, [&]() -> int {
+        return kmc_setop_device_impl(a, b, op, count_mode, min_a, max_a, min_b, max_b, d_key_hi, d_key_lo, d_count, n_out, total_out, summary);
+    });
+}
+extern "C" int kmc_export_setop(kmc_ctx* a, kmc_ctx* b, int op, int count_mode, uint64_t min_a, uint64_t max_a, uint64_t min_b,
+                                uint64_t max_b, uint64_t* key_hi, uint64_t* key_lo, uint64_t* count, uint64_t cap, uint64_t* n_out) {
+    return guarded(a, [&]() -> int {
+        return kmc_export_setop_impl(a, b, op, count_mode, min_a, max_a, min_b, max_b, key_hi, key_lo, count, cap, n_out);
+    });
 }
 extern "C" int kmc_partition_device(kmc_ctx* c, uint32_t n_parts, uint64_t* part_begin, const void** d_key_hi,
                                     const void** d_key_lo, const void** d_count) {

@@ -6,6 +6,7 @@
 //
 //   k-mer-count [FASTA] [-k K] [--forward] [--expand] [--device N | --gpus N] [--algo auto|stream|walk|sort] [--stats]
 //               [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE]
+//               [--with FASTA2 (--compare | --setop intersect|union|subtract [--counts left|right|min|max|sum|diff])]
 //
 //   --gpus N  the file's chunks go round-robin to GPUs 0..N-1 of this process, tables reduced on GPU 0
 //             (there is no CPU backend: SURVEY.md's "--backend cpu" is deliberately absent)
@@ -24,6 +25,13 @@
 //   --profile FILE       (with -k K) instead of the table: for every read of FILE (FASTA / FASTQ), in file order,
 //               "INDEX<TAB>WINDOWS<TAB>PRESENT<TAB>MIN<TAB>MAX<TAB>SUM": its valid K-mer windows, how many of them the
 //               counted input holds --min-count times or more, and the smallest / largest / summed count over them
+//
+//   --with FASTA2        (with -k K) a second file, counted into a second table on the same device; one of:
+//     --compare          instead of the table: "NAME<TAB>VALUE" lines -- the eight words of kmc_compare (n_a, n_b, n_both, sum_a,
+//               sum_b, shared_sum_a, shared_sum_b, sum_min), then union, jaccard, containment_a, containment_b,
+//               weighted_jaccard, bray_curtis (six decimals)
+//     --setop OP         instead of the table: "KMER<TAB>COUNT" of FASTA OP FASTA2, the count chosen by --counts (default left)
+//               --min-count / --max-count are then the range applied to the counts of BOTH inputs
 //
 // Errors: message on stderr, exit code 101 (what a Rust panic exits with), never partial stdout.
 #include <errno.h>
@@ -73,7 +81,8 @@ int main(int argc, char** argv) {
     const char* path = "sample.fasta";  // main.rs:44
     int k = 0, canonical = 1, expand = 0, device = 0, algo = KMC_ALGO_AUTO, stats = 0, gpus = 1, histo = 0;
     long long min_count = 1, max_count = 0;   // (max_count 0: no upper bound)
-    const char *query_path = nullptr, *profile_path = nullptr;
+    const char *query_path = nullptr, *profile_path = nullptr, *with_path = nullptr;
+    int compare = 0, setop = -1, count_mode = -1;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         if (a == "-k" && i + 1 < argc) { if (!parse_int("-k", argv[++i], 1, 63, &k)) return 2; }
@@ -87,15 +96,27 @@ int main(int argc, char** argv) {
         else if (a == "--histo" && i + 1 < argc) { if (!parse_int("--histo", argv[++i], 1, (1 << 24) - 1, &histo)) return 2; }
         else if (a == "--query-kmers" && i + 1 < argc) query_path = argv[++i];
         else if (a == "--profile" && i + 1 < argc) profile_path = argv[++i];
-        else if (a == "--algo" && i + 1 < argc) {
+        else if (a == "--with" && i + 1 < argc) with_path = argv[++i];
+        else if (a == "--compare") compare = 1;
+        else if (a == "--setop" && i + 1 < argc) {
+            std::string v = argv[++i];
+            setop = v == "intersect" ? KMC_SETOP_INTERSECT : v == "union" ? KMC_SETOP_UNION : v == "subtract" ? KMC_SETOP_SUBTRACT : -1;
+            if (setop < 0) { fprintf(stderr, "k-mer-count: --setop needs intersect, union or subtract (got '%s')\n", v.c_str()); return 2; }
+        } else if (a == "--counts" && i + 1 < argc) {
+            std::string v = argv[++i];
+            count_mode = v == "left" ? KMC_COUNT_LEFT : v == "right" ? KMC_COUNT_RIGHT : v == "min" ? KMC_COUNT_MIN : v == "max" ? KMC_COUNT_MAX
+                         : v == "sum" ? KMC_COUNT_SUM : v == "diff" ? KMC_COUNT_DIFF : -1;
+            if (count_mode < 0) { fprintf(stderr, "k-mer-count: --counts needs left, right, min, max, sum or diff (got '%s')\n", v.c_str()); return 2; }
+        } else if (a == "--algo" && i + 1 < argc) {
             std::string v = argv[++i];
             algo = v == "stream" ? KMC_ALGO_STREAM : v == "walk" ? KMC_ALGO_WALK : v == "sort" ? KMC_ALGO_SORT : KMC_ALGO_AUTO;
         } else if (a == "-h" || a == "--help") {
             fprintf(stderr, "usage: k-mer-count [FASTA] [-k K] [--forward] [--expand] [--device N | --gpus N] [--algo auto|stream|walk|sort] [--stats]\n"
-                            "                   [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE]\n");
+                            "                   [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE]\n"
+                            "                   [--with FASTA2 (--compare | --setop intersect|union|subtract [--counts left|right|min|max|sum|diff])]\n");
             return 0;
         } else if (a == "-k" || a == "--device" || a == "--gpus" || a == "--algo" || a == "--min-count" || a == "--max-count" || a == "--histo" ||
-                   a == "--query-kmers" || a == "--profile") {
+                   a == "--query-kmers" || a == "--profile" || a == "--with" || a == "--setop" || a == "--counts") {
             fprintf(stderr, "k-mer-count: %s needs a value\n", a.c_str());
             return 2;
         } else if (!a.empty() && a[0] != '-') path = argv[i];
@@ -145,6 +166,19 @@ int main(int argc, char** argv) {
         const int prc = kmc_parse_fasta(profile_path, &prof, eb, sizeof(eb));
         if (prc) return die(profile_path, eb[0] ? eb : kmc_status_string(prc));
     }
+    // --with / --compare / --setop: bad combinations end here, before a GPU is touched
+    {
+        const bool action = compare || setop >= 0;
+        const char* bad = nullptr;
+        if (with_path && !action) bad = "--with needs --compare or --setop";
+        else if (action && !with_path) bad = "--compare / --setop need --with FASTA2";
+        else if (compare && setop >= 0) bad = "--compare and --setop exclude each other";
+        else if (count_mode >= 0 && setop < 0) bad = "--counts needs --setop";
+        else if (with_path && !k) bad = "--with needs -k K";
+        else if (with_path && (histo || query_path || profile_path)) bad = "--with and --histo / --query-kmers / --profile exclude each other";
+        else if (with_path && gpus != 1) bad = "--with and --gpus exclude each other";
+        if (bad) { fprintf(stderr, "k-mer-count: %s\n", bad); return 2; }
+    }
     const bool filtered = min_count > 1 || max_count != 0;
     kmc_config cfg;
     memset(&cfg, 0, sizeof(cfg));
@@ -173,6 +207,52 @@ int main(int argc, char** argv) {
     rc = gpus == 1 ? kmc_count_file(ctx, path, &nd, &nt) : kmc_count_file_multi(ctxs.data(), (uint32_t)ctxs.size(), path, &nd, &nt);
     if (rc) { int r = die(path, kmc_last_error(ctx)); destroy_all(); return r; }
     std::vector<char> obuf(1 << 22);
+    if (with_path) {
+        cfg.device = device;
+        kmc_ctx* other = nullptr;
+        rc = kmc_create(&other, &cfg);
+        if (rc) { int r = die("kmc_create", kmc_last_error(nullptr)); destroy_all(); return r; }
+        ctxs.push_back(other);
+        uint64_t nd2 = 0, nt2 = 0;
+        rc = kmc_count_file(other, with_path, &nd2, &nt2);
+        if (rc) { int r = die(with_path, kmc_last_error(other)); destroy_all(); return r; }
+        const uint64_t lo_c = (uint64_t)min_count, hi_c = (uint64_t)max_count;
+        if (compare) {
+            uint64_t w[KMC_COMPARE_WORDS];
+            rc = kmc_compare(ctx, other, lo_c, hi_c, lo_c, hi_c, w);
+            if (rc) { int r = die("kmc_compare", kmc_last_error(ctx)); destroy_all(); return r; }
+            static const char* names[KMC_COMPARE_WORDS] = {"n_a", "n_b", "n_both", "sum_a", "sum_b", "shared_sum_a", "shared_sum_b", "sum_min"};
+            for (int i = 0; i < KMC_COMPARE_WORDS; ++i) printf("%s\t%llu\n", names[i], (unsigned long long)w[i]);
+            auto ratio = [](double x, double y) { return y != 0.0 ? x / y : 0.0; };
+            const uint64_t uni = w[0] + w[1] - w[2];
+            printf("union\t%llu\n", (unsigned long long)uni);
+            printf("jaccard\t%.6f\n", ratio((double)w[2], (double)uni));
+            printf("containment_a\t%.6f\n", ratio((double)w[2], (double)w[0]));
+            printf("containment_b\t%.6f\n", ratio((double)w[2], (double)w[1]));
+            printf("weighted_jaccard\t%.6f\n", ratio((double)w[7], (double)w[3] + (double)w[4] - (double)w[7]));
+            printf("bray_curtis\t%.6f\n", ratio(2.0 * (double)w[7], (double)w[3] + (double)w[4]));
+            fflush(stdout);
+            destroy_all();
+            return 0;
+        }
+        const int cm = count_mode >= 0 ? count_mode : KMC_COUNT_LEFT;
+        uint64_t n = 0;
+        rc = kmc_export_setop(ctx, other, setop, cm, lo_c, hi_c, lo_c, hi_c, nullptr, nullptr, nullptr, 0, &n);
+        if (rc && !(rc == KMC_ERR_ARG && n)) { int r = die("kmc_export_setop", kmc_last_error(ctx)); destroy_all(); return r; }
+        std::vector<uint64_t> shi(n ? n : 1), slo(n ? n : 1), scnt(n ? n : 1);
+        rc = kmc_export_setop(ctx, other, setop, cm, lo_c, hi_c, lo_c, hi_c, shi.data(), slo.data(), scnt.data(), n, &n);
+        if (rc) { int r = die("kmc_export_setop", kmc_last_error(ctx)); destroy_all(); return r; }
+        setvbuf(stdout, obuf.data(), _IOFBF, obuf.size());
+        char sl[96];
+        for (uint64_t i = 0; i < n; ++i) {
+            kmc_decode_key(shi[i], slo[i], k, sl);
+            const int m = snprintf(sl + k, sizeof(sl) - k, "\t%llu\n", (unsigned long long)scnt[i]);
+            fwrite(sl, 1, (size_t)(k + m), stdout);
+        }
+        fflush(stdout);
+        destroy_all();
+        return 0;
+    }
     if (query_path) {
         std::vector<uint64_t> qc(q_lo.size() ? q_lo.size() : 1);
         rc = kmc_query(ctx, q_hi.data(), q_lo.data(), q_lo.size(), qc.data());

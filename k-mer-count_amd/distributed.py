@@ -299,3 +299,20 @@ def global_query(owner, key_hi, key_lo, group=None) -> np.ndarray:
     t = torch.from_numpy(np.asarray(c, dtype=np.uint64).view(np.int64).copy()).to(dev)
     dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
     return t.cpu().numpy().view(np.uint64).copy()
+
+
+def global_compare(owner_a, owner_b, min_a: int = 1, max_a: int = 0, min_b: int = 1, max_b: int = 0, group=None):
+    """Global kmc_compare of two samples after reduce_tables.  Both samples are then partitioned by the same kmc_owner_of,
+    so a key lives on the same rank in both: every rank compares its own two partitions (`owner_a.compare(owner_b, ...)`,
+    two finalized KmerCounters) and the eight words, all of them sums over keys, are added with one all_reduce(SUM).
+    Returns the package's Comparison (words and derived similarities) on every rank."""
+    from . import Comparison
+    c = owner_a.compare(owner_b, min_a, max_a, min_b, max_b)
+    words = np.array([int(w) for w in (c.words() if hasattr(c, "words") else c)], dtype=np.uint64)
+    if dist.get_backend(group) == "nccl":
+        dev = torch.device("cuda", getattr(owner_a, "device", torch.cuda.current_device()))
+    else:
+        dev = torch.device("cpu")
+    t = torch.from_numpy(words.view(np.int64).copy()).to(dev)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    return Comparison.from_words(t.cpu().numpy().view(np.uint64).tolist())

@@ -14,6 +14,16 @@ pub const KMC_FORGET_MEMO: c_int = 1;
 pub const KMC_FORGET_HISTORY: c_int = 2;
 /// words per read of `kmc_profile`'s read_stats
 pub const KMC_PROFILE_WORDS: usize = 5;
+pub const KMC_COMPARE_WORDS: usize = 8;
+pub const KMC_SETOP_INTERSECT: i32 = 0;
+pub const KMC_SETOP_UNION: i32 = 1;
+pub const KMC_SETOP_SUBTRACT: i32 = 2;
+pub const KMC_COUNT_LEFT: i32 = 0;
+pub const KMC_COUNT_RIGHT: i32 = 1;
+pub const KMC_COUNT_MIN: i32 = 2;
+pub const KMC_COUNT_MAX: i32 = 3;
+pub const KMC_COUNT_SUM: i32 = 4;
+pub const KMC_COUNT_DIFF: i32 = 5;
 
 // The structs and the extern block below are checked against include/kmc.h by
 // tests/test_abi_host.py::test_rust_binding_matches_the_header (names, arity, argument types, field
@@ -109,6 +119,13 @@ extern "C" {
                        read_stats: *mut u64) -> c_int;
     pub fn kmc_profile_device(ctx: *mut KmcCtx, d_bases: *const c_void, d_offsets: *const c_void, n_reads: u64, n_bases: u64,
                               min_count: u64, d_window_count: *mut c_void, d_read_stats: *mut c_void) -> c_int;
+    // two tables: summary and set operations over the sorted views of two contexts
+    pub fn kmc_compare(a: *mut KmcCtx, b: *mut KmcCtx, min_a: u64, max_a: u64, min_b: u64, max_b: u64, summary: *mut u64) -> c_int;
+    pub fn kmc_setop_device(a: *mut KmcCtx, b: *mut KmcCtx, op: c_int, count_mode: c_int, min_a: u64, max_a: u64, min_b: u64, max_b: u64,
+                            d_key_hi: *mut *const c_void, d_key_lo: *mut *const c_void, d_count: *mut *const c_void, n_out: *mut u64,
+                            total_out: *mut u64, summary: *mut u64) -> c_int;
+    pub fn kmc_export_setop(a: *mut KmcCtx, b: *mut KmcCtx, op: c_int, count_mode: c_int, min_a: u64, max_a: u64, min_b: u64, max_b: u64,
+                            key_hi: *mut u64, key_lo: *mut u64, count: *mut u64, cap: u64, n_out: *mut u64) -> c_int;
     // multi-GPU reduce (one process per GPU; the collective itself is the host program's, e.g. RCCL)
     pub fn kmc_slab_words(ctx: *const KmcCtx, slab_entries: u64) -> u64;
     pub fn kmc_pack_slab_device(ctx: *mut KmcCtx, d_slab: *mut c_void, slab_entries: u64) -> c_int;
@@ -275,6 +292,46 @@ impl Counter {
             kmc_profile(self.ctx, bases.as_ptr(), offsets.as_ptr(), n_reads as u64, min_count, win.as_mut_ptr(), stats.as_mut_ptr() as *mut u64)
         })?;
         Ok((win, stats))
+    }
+
+    /// The eight words of `kmc_compare` for this table (A) and `other` (B), counts restricted to `range_a` / `range_b`
+    /// = (min, max), max 0: no upper bound.  [n_a, n_b, n_both, sum_a, sum_b, shared_sum_a, shared_sum_b, sum_min];
+    /// Jaccard is `w[2] / (w[0] + w[1] - w[2])`, weighted Jaccard `w[7] / (w[3] + w[4] - w[7])`.
+    pub fn compare(&mut self, other: &mut Counter, range_a: (u64, u64), range_b: (u64, u64)) -> Result<[u64; KMC_COMPARE_WORDS], KmcError> {
+        let (mut nd, mut nt) = (0u64, 0u64);
+        self.check(unsafe { kmc_finalize(self.ctx, &mut nd, &mut nt) })?;
+        other.check(unsafe { kmc_finalize(other.ctx, &mut nd, &mut nt) })?;
+        let mut w = [0u64; KMC_COMPARE_WORDS];
+        self.check(unsafe { kmc_compare(self.ctx, other.ctx, range_a.0, range_a.1, range_b.0, range_b.1, w.as_mut_ptr()) })?;
+        Ok(w)
+    }
+
+    /// `self op other` (KMC_SETOP_*) with the result count given by `count_mode` (KMC_COUNT_*), sorted like `table()`.
+    pub fn setop(&mut self, other: &mut Counter, op: i32, count_mode: i32, range_a: (u64, u64), range_b: (u64, u64)) -> Result<Vec<(String, u64)>, KmcError> {
+        let (mut nd, mut nt) = (0u64, 0u64);
+        self.check(unsafe { kmc_finalize(self.ctx, &mut nd, &mut nt) })?;
+        other.check(unsafe { kmc_finalize(other.ctx, &mut nd, &mut nt) })?;
+        let mut n = 0u64;
+        let null = std::ptr::null_mut();
+        let rc = unsafe { kmc_export_setop(self.ctx, other.ctx, op, count_mode, range_a.0, range_a.1, range_b.0, range_b.1, null, null, null, 0, &mut n) };
+        if rc != 0 && n == 0 {
+            self.check(rc)?;
+        }
+        let k = n as usize;
+        let (mut hi, mut lo, mut cnt) = (vec![0u64; k], vec![0u64; k], vec![0u64; k]);
+        if k > 0 {
+            self.check(unsafe {
+                kmc_export_setop(self.ctx, other.ctx, op, count_mode, range_a.0, range_a.1, range_b.0, range_b.1, hi.as_mut_ptr(), lo.as_mut_ptr(),
+                                 cnt.as_mut_ptr(), n, &mut n)
+            })?;
+        }
+        let mut buf = vec![0u8; self.klen as usize];
+        let mut out = Vec::with_capacity(k);
+        for i in 0..k {
+            unsafe { kmc_decode_key(hi[i], lo[i], self.klen, buf.as_mut_ptr() as *mut c_char) };
+            out.push((String::from_utf8_lossy(&buf).into_owned(), cnt[i]));
+        }
+        Ok(out)
     }
 }
 
