@@ -22,6 +22,7 @@
  *   (addition: no equivalent in the reference)             kmc_query / kmc_query_device (count of given keys)
  *   (addition: no equivalent in the reference)             kmc_profile / kmc_profile_device (per-read k-mer profile)
  *   (addition: no equivalent in the reference)             kmc_compare / kmc_setop_device / kmc_export_setop (two tables)
+ *   (addition: no equivalent in the reference)             kmc_graph / kmc_graph_device (de Bruijn graph of the table)
  *
  * Conventions
  *   - Every function returns 0 (KMC_OK) or a negative kmc_status; no exception or abort crosses
@@ -292,6 +293,44 @@ int kmc_setop_device(kmc_ctx* a, kmc_ctx* b, int op, int count_mode, uint64_t mi
  * set; cap < *n_out -> KMC_ERR_ARG and nothing is copied (call with cap 0 and NULL arrays to size the buffers). */
 int kmc_export_setop(kmc_ctx* a, kmc_ctx* b, int op, int count_mode, uint64_t min_a, uint64_t max_a, uint64_t min_b,
                      uint64_t max_b, uint64_t* key_hi, uint64_t* key_lo, uint64_t* count, uint64_t cap, uint64_t* n_out);
+
+/* ---- the table as a de Bruijn graph: neighbour masks and unitig ends (additions, as above).  KMC_MODE_CONTIG only (LR:
+ * KMC_ERR_ARG), every k, canonical or forward ctx.  Write a key as its k-character string x.  canon(f) = min(f, revcomp(f))
+ * as strings in a canonical ctx, f itself in a forward ctx (the ctx's own key rule, kmc_encode_key).  A key is SOLID iff it
+ * is in the sorted view of the last kmc_finalize (a view queued by kmc_finalize_async counts as one) and
+ * min_count <= count <= max_count (max_count 0 = no upper bound), the range rule of kmc_filter_device.
+ * For a solid key x, side R (right) and side L (left), base c in ACGT (codes 0..3):
+ *   ext(x, R, c) = canon(x[1:] + c),  ext(x, L, c) = canon(c + x[:-1]).
+ *   bit c of adj (bits 0..3) is set iff ext(x, R, c) is solid; bit 4 + c (bits 4..7) iff ext(x, L, c) is solid.  Degrees are
+ *     the popcounts of the two nibbles: they count BASES, not distinct neighbour keys.  Self-loops (homopolymers) and
+ *     palindromes get no special case: the formula is the definition.
+ *   facing side: if f = x[1:] + c (or c + x[:-1]) was kept as it is by canon, the neighbour y is entered on the opposite
+ *     side (an R-extension enters y on its L side and vice versa); if canon flipped it, on the same side.
+ *   side S of x CONTINUES iff its degree is 1 and the facing side of that one neighbour has degree 1 too.  Otherwise side
+ *     S is a UNITIG END: bit 8 (R) / bit 9 (L).
+ *   bit 10 = the key is solid.  A key of the view that is not solid gets adj = 0.  Bits 11..15 are 0.
+ * adj is one uint16_t per key OF THE VIEW, IN VIEW ORDER (entry i belongs to row i of kmc_export).
+ * summary[KMC_GRAPH_WORDS], over solid keys: [0] nodes, [1] sum of R degrees, [2] sum of L degrees, [3] isolated nodes (both
+ * degrees 0), [4] dead ends (exactly one degree 0), [5] branching nodes (a degree >= 2), [6] unitig-end sides (bits 8 and 9
+ * summed), [7] nodes with both end bits set (single-node unitigs).  Non-circular unitigs = [6] / 2 is host arithmetic.
+ * Rules: a NULL ctx, KMC_MODE_LR, a non-zero max_count below min_count: KMC_ERR_ARG; no view: KMC_ERR_STATE (exactly where
+ * kmc_export says so); a view of 2^32 keys or more: KMC_ERR_CAPACITY (the prefix index's rule; the first graph or query call
+ * of a view builds the index, the other reuses it); an empty view gives zeros.  The table, the view, a partition, a filter
+ * result, a set-operation result and the query index are not changed. ---- */
+#define KMC_GRAPH_WORDS 8
+#define KMC_GRAPH_RIGHT(adj) ((adj) & 15u)
+#define KMC_GRAPH_LEFT(adj) (((adj) >> 4) & 15u)
+#define KMC_GRAPH_END_R(adj) (((adj) >> 8) & 1u)
+#define KMC_GRAPH_END_L(adj) (((adj) >> 9) & 1u)
+#define KMC_GRAPH_SOLID(adj) (((adj) >> 10) & 1u)
+/* adj in a ctx-owned device array of uint16_t, valid until the next kmc_graph* call / finalize / reset / destroy (same
+ * ordering contract as kmc_export_device).  d_adj, n_keys (keys of the view) and summary may each be NULL. */
+int kmc_graph_device(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, const void** d_adj, uint64_t* n_keys,
+                     uint64_t* summary);
+/* The same, copied to the caller's array adj of cap uint16_t entries.  *n_keys is always set; cap < *n_keys -> KMC_ERR_ARG and
+ * nothing is copied, except that adj == NULL with cap == 0 is the summary-only / sizing call.  summary may be NULL. */
+int kmc_graph(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, void* adj, uint64_t cap, uint64_t* n_keys,
+              uint64_t* summary);
 
 /* Multi-GPU reduce for small tables: ONE fixed-size all-gather instead of size exchange +
  * all-to-all (the reduce of main.rs:87's grouping across GPUs; for the generator's input a table is

@@ -87,10 +87,13 @@ ABI_SYMBOLS = [
     "kmc_histogram", "kmc_filter_device", "kmc_export_filtered",
     "kmc_encode_key", "kmc_query", "kmc_query_device", "kmc_profile", "kmc_profile_device",
     "kmc_compare", "kmc_setop_device", "kmc_export_setop",
+    "kmc_graph", "kmc_graph_device",
 ]
 
 PROFILE_WORDS = 5  # KMC_PROFILE_WORDS: valid windows, present windows, min, max, sum
 COMPARE_WORDS = 8  # KMC_COMPARE_WORDS: n_a, n_b, n_both, sum_a, sum_b, shared_sum_a, shared_sum_b, sum_min
+GRAPH_WORDS = 8    # KMC_GRAPH_WORDS: nodes, R degrees, L degrees, isolated, dead ends, branching, end sides, single-node unitigs
+GRAPH_END_R, GRAPH_END_L, GRAPH_SOLID = 1 << 8, 1 << 9, 1 << 10   # bits of an adj word above the two neighbour nibbles (R: 0..3, L: 4..7)
 SETOP_INTERSECT, SETOP_UNION, SETOP_SUBTRACT = 0, 1, 2
 COUNT_LEFT, COUNT_RIGHT, COUNT_MIN, COUNT_MAX, COUNT_SUM, COUNT_DIFF = 0, 1, 2, 3, 4, 5
 SETOP_NAMES = {"intersect": SETOP_INTERSECT, "union": SETOP_UNION, "subtract": SETOP_SUBTRACT}
@@ -156,6 +159,8 @@ def lib() -> C.CDLL:
     L.kmc_compare.argtypes = [vp, vp, u64, u64, u64, u64, vp]
     L.kmc_setop_device.argtypes = [vp, vp, i32, i32, u64, u64, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), pu64, pu64, vp]
     L.kmc_export_setop.argtypes = [vp, vp, i32, i32, u64, u64, u64, u64, vp, vp, vp, u64, pu64]
+    L.kmc_graph_device.argtypes = [vp, u64, u64, C.POINTER(vp), pu64, vp]
+    L.kmc_graph.argtypes = [vp, u64, u64, vp, u64, pu64, vp]
     L.kmc_owner_of.argtypes = [u64, u64, u32]
     L.kmc_owner_of.restype = u32
     L.kmc_get_stats.argtypes = [vp, C.POINTER(Stats)]
@@ -314,6 +319,42 @@ class Comparison:
         lines.append("union\t%d" % self.union)
         for f in ("jaccard", "containment_a", "containment_b", "weighted_jaccard", "bray_curtis"):
             lines.append("%s\t%.6f" % (f, getattr(self, f)))
+        return "\n".join(lines) + "\n"
+
+
+_GRAPH_FIELDS = ("nodes", "right_degrees", "left_degrees", "isolated", "dead_ends", "branching", "end_sides", "single_node_unitigs")
+
+
+@dataclass
+class GraphSummary:
+    """The eight words of kmc_graph over the solid keys: nodes, the sums of the right and left degrees, nodes without a
+    neighbour, nodes with neighbours on one side only, nodes with a degree of 2 or more, sides that end a unitig, nodes
+    that are a unitig of their own."""
+    nodes: int
+    right_degrees: int
+    left_degrees: int
+    isolated: int
+    dead_ends: int
+    branching: int
+    end_sides: int
+    single_node_unitigs: int
+
+    @classmethod
+    def from_words(cls, words) -> "GraphSummary":
+        return cls(*[int(w) for w in words])
+
+    def words(self) -> list:
+        return [getattr(self, f) for f in _GRAPH_FIELDS]
+
+    @property
+    def unitigs(self) -> int:
+        """Non-circular unitigs: every one has two end sides."""
+        return self.end_sides // 2
+
+    def to_text(self) -> str:
+        """``NAME\tVALUE`` lines as the CLI's --graph-stats prints them."""
+        lines = ["%s\t%d" % (f, getattr(self, f)) for f in _GRAPH_FIELDS]
+        lines.append("unitigs\t%d" % self.unitigs)
         return "\n".join(lines) + "\n"
 
 
@@ -542,6 +583,28 @@ class KmerCounter:
         if nk:
             self._chk(self._L.kmc_export_setop(*args, hi.ctypes.data, lo.ctypes.data, cnt.ctypes.data, nk, C.byref(n)))
         return Table(hi, lo, cnt, self.k)
+
+    # -- the table as a de Bruijn graph: neighbour masks, unitig ends, summary (of the sorted view; finalize() first) --
+    def graph(self, min_count: int = 1, max_count: int = 0, adj: bool = True):
+        """(adj, GraphSummary) of kmc_graph: adj is uint16[n keys of the view] in the order of export() -- bits 0..3 the
+        solid right extensions (ACGT), 4..7 the left ones, GRAPH_END_R / GRAPH_END_L "this side ends a unitig", GRAPH_SOLID
+        "min_count <= count <= max_count" (max_count 0: no upper bound; other keys get 0) -- or None with adj=False."""
+        n = C.c_uint64()
+        w = (C.c_uint64 * GRAPH_WORDS)()
+        if not adj:
+            self._chk(self._L.kmc_graph(self._h, int(min_count), int(max_count), None, 0, C.byref(n), w))
+            return None, GraphSummary.from_words(list(w))
+        nd = self.export_device()[3]
+        out = np.zeros(nd, np.uint16)
+        self._chk(self._L.kmc_graph(self._h, int(min_count), int(max_count), out.ctypes.data if nd else None, nd, C.byref(n), w))
+        return out, GraphSummary.from_words(list(w))
+
+    def graph_device(self, min_count: int = 1, max_count: int = 0):
+        """(d_adj, n, GraphSummary): adj in a ctx-owned device array of n uint16 (kmc_graph_device)."""
+        p, n = C.c_void_p(), C.c_uint64()
+        w = (C.c_uint64 * GRAPH_WORDS)()
+        self._chk(self._L.kmc_graph_device(self._h, int(min_count), int(max_count), C.byref(p), C.byref(n), w))
+        return p.value or 0, n.value, GraphSummary.from_words(list(w))
 
     # -- asking the table: key lookups and per-read profiles (of the sorted view; finalize() first) --
     def query(self, key_lo, key_hi=None) -> np.ndarray:

@@ -37,6 +37,7 @@
 #include "kmc_spectrum.hip.h"
 #include "kmc_query.hip.h"
 #include "kmc_setops.hip.h"
+#include "kmc_graph.hip.h"
 #include "kmc_ingest.h"
 
 namespace {
@@ -188,6 +189,8 @@ struct kmc_ctx {
     // kmc_compare / kmc_setop_device (kmc_setops.hip.h), on the ctx given as `a`: the result, the merge-path partition of the
     // two views (first A / B entry of every tile), emitted keys per tile and their scan, [n_out | summary words | total_out]
     DevBuf so_hi, so_lo, so_cnt, so_pa, so_pb, so_tile, so_tpos, so_bsum, so_ctl;
+    // kmc_graph / kmc_graph_device (kmc_graph.hip.h): one 16-bit word per key of the view, the eight summary words
+    DevBuf g_adj, g_ctl;
 };
 
 namespace {
@@ -1715,7 +1718,8 @@ extern "C" void kmc_destroy(kmc_ctx* c) {
                       &c->snap_hi, &c->snap_lo, &c->snap_cnt, &c->snap_n, &c->snap_occ, &c->rx_hi, &c->rx_lo, &c->rx_cnt,
                       &c->f_hi, &c->f_lo, &c->f_cnt, &c->f_tile, &c->f_tpos, &c->f_bsum, &c->f_ctl, &c->h_hist,
                       &c->q_idx, &c->q_khi, &c->q_klo, &c->q_cnt, &c->q_bases, &c->q_offs, &c->q_win, &c->q_stats,
-                      &c->so_hi, &c->so_lo, &c->so_cnt, &c->so_pa, &c->so_pb, &c->so_tile, &c->so_tpos, &c->so_bsum, &c->so_ctl};
+                      &c->so_hi, &c->so_lo, &c->so_cnt, &c->so_pa, &c->so_pb, &c->so_tile, &c->so_tpos, &c->so_bsum, &c->so_ctl,
+                      &c->g_adj, &c->g_ctl};
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
     sk_free(c);
     try { free_runs(c, true); } catch (...) { /* (only the pool bookkeeping can throw; the buffers it could not list leak with the process) */ }
@@ -2628,6 +2632,86 @@ static int kmc_export_setop_impl(kmc_ctx* a, kmc_ctx* b, int op, int count_mode,
     return copy_to_host(a, a->so_hi.p, a->so_lo.p, a->so_cnt.p, n, key_hi, key_lo, count);
 }
 
+// ---- the de Bruijn graph of the sorted view: neighbour masks, unitig ends, summary (kmc_graph.hip.h) ----
+// What both calls check first; on success the view is resolved and *n its size.
+static int graph_begin(kmc_ctx* c, const char* what, uint64_t min_count, uint64_t max_count) {
+    if (c->cfg.mode != KMC_MODE_CONTIG) return fail(c, KMC_ERR_ARG, "%s: contiguous k-mers only (not KMC_MODE_LR)", what);
+    int rc = view_begin(c, what, min_count, max_count);
+    if (rc) return rc;
+    if (c->n_sorted >= (1ull << 32)) return fail(c, KMC_ERR_CAPACITY, "%s: a view of 2^32 keys or more cannot be indexed", what);
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    return KMC_OK;
+}
+
+// adj of every view key into g_adj, the summary into h[KMC_GRAPH_WORDS]; finished when it returns (kmc_export_device's
+// ordering contract).  Shares the prefix index with the query calls (query_view).
+static int graph_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count, u64* h) {
+    memset(h, 0, KMC_GRAPH_WORDS * sizeof(u64));
+    const u64 n = c->n_sorted;
+    int rc;
+    if ((rc = ensure(c, c->g_adj, (size_t)std::max<u64>(n, 1) * sizeof(uint16_t))) || (rc = ensure(c, c->g_ctl, KMC_GRAPH_WORDS * sizeof(u64)))) return rc;
+    if (!n) return KMC_OK;
+    QView v;
+    rc = query_view(c, what, &v);
+    if (rc) return rc;
+    kmc_qull* ctl = (kmc_qull*)c->g_ctl.p;
+    HIPCHK(c, hipMemsetAsync(ctl, 0, KMC_GRAPH_WORDS * sizeof(u64), c->stream));
+    const u64 lo_c = std::max<u64>(min_count, 1), hi_c = max_count ? max_count : ~0ull;
+    const u64 want = (n + KMC_G_THREADS - 1) / KMC_G_THREADS;
+    const int k = c->klen;
+    // as many workgroups as are resident at once (they walk the view with a grid stride), fewer for a small view
+#define KMC_GRAPH_LAUNCH(KW_, CANON_)                                                                                           \
+    do {                                                                                                                        \
+        int per_cu = 0;                                                                                                         \
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kmc_graph_kernel<KW_, CANON_>, KMC_G_THREADS, 0) != hipSuccess || per_cu < 1) \
+            per_cu = 4;                                                                                                         \
+        const u32 grid = (u32)std::min<u64>(want, (u64)c->n_cu * (u64)per_cu);                                                  \
+        hipLaunchKernelGGL((kmc_graph_kernel<KW_, CANON_>), dim3(grid), dim3(KMC_G_THREADS), 0, c->stream, v, lo_c, hi_c, k,    \
+                           (uint16_t*)c->g_adj.p, ctl);                                                                         \
+    } while (0)
+    if (c->KW == 1) { if (c->cfg.canonical) KMC_GRAPH_LAUNCH(1, true); else KMC_GRAPH_LAUNCH(1, false); }
+    else { if (c->cfg.canonical) KMC_GRAPH_LAUNCH(2, true); else KMC_GRAPH_LAUNCH(2, false); }
+#undef KMC_GRAPH_LAUNCH
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h, ctl, KMC_GRAPH_WORDS * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return KMC_OK;
+}
+
+static int kmc_graph_device_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, const void** d_adj, uint64_t* n_keys, uint64_t* summary) {
+    if (!c) return KMC_ERR_ARG;
+    int rc = graph_begin(c, "kmc_graph_device", min_count, max_count);
+    if (rc) return rc;
+    u64 h[KMC_GRAPH_WORDS];
+    rc = graph_run(c, "kmc_graph_device", min_count, max_count, h);
+    if (rc) return rc;
+    if (d_adj) *d_adj = c->g_adj.p;
+    if (n_keys) *n_keys = c->n_sorted;
+    if (summary) memcpy(summary, h, sizeof(h));
+    return KMC_OK;
+}
+
+static int kmc_graph_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, void* adj, uint64_t cap, uint64_t* n_keys, uint64_t* summary) {
+    if (n_keys) *n_keys = 0;
+    if (!c) return KMC_ERR_ARG;
+    int rc = graph_begin(c, "kmc_graph", min_count, max_count);
+    if (rc) return rc;
+    const u64 n = c->n_sorted;
+    if (n_keys) *n_keys = n;
+    const bool sizing = !adj && !cap;   // the summary alone / how large adj must be
+    if (!sizing && cap < n) return fail(c, KMC_ERR_ARG, "kmc_graph: capacity %llu < %llu keys of the view", (unsigned long long)cap, (unsigned long long)n);
+    if (!sizing && n && !adj) return fail(c, KMC_ERR_ARG, "kmc_graph: null buffer");
+    u64 h[KMC_GRAPH_WORDS];
+    rc = graph_run(c, "kmc_graph", min_count, max_count, h);
+    if (rc) return rc;
+    if (adj && n) {
+        HIPCHK(c, hipMemcpyAsync(adj, c->g_adj.p, (size_t)n * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    if (summary) memcpy(summary, h, sizeof(h));
+    return KMC_OK;
+}
+
 extern "C" uint64_t kmc_slab_words(const kmc_ctx* c, uint64_t slab_entries) {
     return c ? KMC_SLAB_HEADER + slab_entries * (u64)(c->KW + 1) : 0;
 }
@@ -3165,6 +3249,12 @@ extern "C" int kmc_export_setop(kmc_ctx* a, kmc_ctx* b, int op, int count_mode, 
     return guarded(a, [&]() -> int {
         return kmc_export_setop_impl(a, b, op, count_mode, min_a, max_a, min_b, max_b, key_hi, key_lo, count, cap, n_out);
     });
+}
+extern "C" int kmc_graph_device(kmc_ctx* c, uint64_t min_count, uint64_t max_count, const void** d_adj, uint64_t* n_keys, uint64_t* summary) {
+    return guarded(c, [&]() -> int { return kmc_graph_device_impl(c, min_count, max_count, d_adj, n_keys, summary); });
+}
+extern "C" int kmc_graph(kmc_ctx* c, uint64_t min_count, uint64_t max_count, void* adj, uint64_t cap, uint64_t* n_keys, uint64_t* summary) {
+    return guarded(c, [&]() -> int { return kmc_graph_impl(c, min_count, max_count, adj, cap, n_keys, summary); });
 }
 extern "C" int kmc_partition_device(kmc_ctx* c, uint32_t n_parts, uint64_t* part_begin, const void** d_key_hi,
                                     const void** d_key_lo, const void** d_count) {

@@ -7,6 +7,7 @@
 //   k-mer-count [FASTA] [-k K] [--forward] [--expand] [--device N | --gpus N] [--algo auto|stream|walk|sort] [--stats]
 //               [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE]
 //               [--with FASTA2 (--compare | --setop intersect|union|subtract [--counts left|right|min|max|sum|diff])]
+//               [--graph | --graph-stats]
 //
 //   --gpus N  the file's chunks go round-robin to GPUs 0..N-1 of this process, tables reduced on GPU 0
 //             (there is no CPU backend: SURVEY.md's "--backend cpu" is deliberately absent)
@@ -32,6 +33,13 @@
 //               weighted_jaccard, bray_curtis (six decimals)
 //     --setop OP         instead of the table: "KMER<TAB>COUNT" of FASTA OP FASTA2, the count chosen by --counts (default left)
 //               --min-count / --max-count are then the range applied to the counts of BOTH inputs
+//
+//   --graph              (with -k K) instead of the table: the table as a de Bruijn graph.  For every solid key -- count within
+//               --min-count / --max-count -- in key order "KMER<TAB>COUNT<TAB>R<TAB>L<TAB>ENDS": R / L the bases (in ACGT order, "."
+//               for none) that extend the key to the right / left into another solid key, ENDS the sides at which a unitig
+//               ends: ".", "R", "L" or "LR"
+//   --graph-stats        (with -k K) instead of the table: "NAME<TAB>VALUE" lines -- the eight words of kmc_graph (nodes,
+//               right_degrees, left_degrees, isolated, dead_ends, branching, end_sides, single_node_unitigs), then unitigs
 //
 // Errors: message on stderr, exit code 101 (what a Rust panic exits with), never partial stdout.
 #include <errno.h>
@@ -82,7 +90,7 @@ int main(int argc, char** argv) {
     int k = 0, canonical = 1, expand = 0, device = 0, algo = KMC_ALGO_AUTO, stats = 0, gpus = 1, histo = 0;
     long long min_count = 1, max_count = 0;   // (max_count 0: no upper bound)
     const char *query_path = nullptr, *profile_path = nullptr, *with_path = nullptr;
-    int compare = 0, setop = -1, count_mode = -1;
+    int compare = 0, setop = -1, count_mode = -1, graph = 0, graph_stats = 0;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         if (a == "-k" && i + 1 < argc) { if (!parse_int("-k", argv[++i], 1, 63, &k)) return 2; }
@@ -98,6 +106,8 @@ int main(int argc, char** argv) {
         else if (a == "--profile" && i + 1 < argc) profile_path = argv[++i];
         else if (a == "--with" && i + 1 < argc) with_path = argv[++i];
         else if (a == "--compare") compare = 1;
+        else if (a == "--graph") graph = 1;
+        else if (a == "--graph-stats") graph_stats = 1;
         else if (a == "--setop" && i + 1 < argc) {
             std::string v = argv[++i];
             setop = v == "intersect" ? KMC_SETOP_INTERSECT : v == "union" ? KMC_SETOP_UNION : v == "subtract" ? KMC_SETOP_SUBTRACT : -1;
@@ -113,7 +123,8 @@ int main(int argc, char** argv) {
         } else if (a == "-h" || a == "--help") {
             fprintf(stderr, "usage: k-mer-count [FASTA] [-k K] [--forward] [--expand] [--device N | --gpus N] [--algo auto|stream|walk|sort] [--stats]\n"
                             "                   [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE]\n"
-                            "                   [--with FASTA2 (--compare | --setop intersect|union|subtract [--counts left|right|min|max|sum|diff])]\n");
+                            "                   [--with FASTA2 (--compare | --setop intersect|union|subtract [--counts left|right|min|max|sum|diff])]\n"
+                            "                   [--graph | --graph-stats]\n");
             return 0;
         } else if (a == "-k" || a == "--device" || a == "--gpus" || a == "--algo" || a == "--min-count" || a == "--max-count" || a == "--histo" ||
                    a == "--query-kmers" || a == "--profile" || a == "--with" || a == "--setop" || a == "--counts") {
@@ -178,6 +189,18 @@ int main(int argc, char** argv) {
         else if (with_path && (histo || query_path || profile_path)) bad = "--with and --histo / --query-kmers / --profile exclude each other";
         else if (with_path && gpus != 1) bad = "--with and --gpus exclude each other";
         if (bad) { fprintf(stderr, "k-mer-count: %s\n", bad); return 2; }
+    }
+    // --graph / --graph-stats: the same
+    if (graph || graph_stats) {
+        const char* opt = graph ? "--graph" : "--graph-stats";
+        const char* bad = nullptr;
+        if (graph && graph_stats) bad = "--graph-stats exclude each other";
+        else if (!k) bad = "needs -k K";
+        else if (histo) bad = "--histo exclude each other";
+        else if (query_path || profile_path) bad = "--query-kmers / --profile exclude each other";
+        else if (with_path || compare || setop >= 0) bad = "--with / --compare / --setop exclude each other";
+        else if (expand) bad = "--expand exclude each other";
+        if (bad) { fprintf(stderr, "k-mer-count: %s %s%s\n", opt, strncmp(bad, "needs", 5) ? "and " : "", bad); return 2; }
     }
     const bool filtered = min_count > 1 || max_count != 0;
     kmc_config cfg;
@@ -274,6 +297,49 @@ int main(int argc, char** argv) {
             const uint64_t* w = &rs[(size_t)r * KMC_PROFILE_WORDS];
             printf("%llu\t%llu\t%llu\t%llu\t%llu\t%llu\n", (unsigned long long)r, (unsigned long long)w[0], (unsigned long long)w[1],
                    (unsigned long long)w[2], (unsigned long long)w[3], (unsigned long long)w[4]);
+        }
+        fflush(stdout);
+        destroy_all();
+        return 0;
+    }
+    if (graph_stats) {
+        uint64_t w[KMC_GRAPH_WORDS], n = 0;
+        rc = kmc_graph(ctx, (uint64_t)min_count, (uint64_t)max_count, nullptr, 0, &n, w);
+        if (rc) { int r = die("kmc_graph", kmc_last_error(ctx)); destroy_all(); return r; }
+        static const char* names[KMC_GRAPH_WORDS] = {"nodes", "right_degrees", "left_degrees", "isolated", "dead_ends", "branching",
+                                                     "end_sides", "single_node_unitigs"};
+        for (int i = 0; i < KMC_GRAPH_WORDS; ++i) printf("%s\t%llu\n", names[i], (unsigned long long)w[i]);
+        printf("unitigs\t%llu\n", (unsigned long long)(w[6] / 2));
+        fflush(stdout);
+        destroy_all();
+        return 0;
+    }
+    if (graph) {
+        std::vector<uint64_t> ghi(nd ? nd : 1), glo(nd ? nd : 1), gcnt(nd ? nd : 1);
+        std::vector<uint16_t> adj(nd ? nd : 1);
+        uint64_t n = 0;
+        rc = kmc_export(ctx, ghi.data(), glo.data(), gcnt.data(), nd);
+        if (rc) { int r = die("kmc_export", kmc_last_error(ctx)); destroy_all(); return r; }
+        rc = kmc_graph(ctx, (uint64_t)min_count, (uint64_t)max_count, adj.data(), nd, &n, nullptr);
+        if (rc) { int r = die("kmc_graph", kmc_last_error(ctx)); destroy_all(); return r; }
+        setvbuf(stdout, obuf.data(), _IOFBF, obuf.size());
+        char gl[128];
+        for (uint64_t i = 0; i < n; ++i) {
+            const unsigned a = adj[i];
+            if (!KMC_GRAPH_SOLID(a)) continue;
+            kmc_decode_key(ghi[i], glo[i], k, gl);
+            int m = k + snprintf(gl + k, sizeof(gl) - k, "\t%llu\t", (unsigned long long)gcnt[i]);
+            for (int side = 0; side < 2; ++side) {
+                const unsigned nib = side ? KMC_GRAPH_LEFT(a) : KMC_GRAPH_RIGHT(a);
+                if (!nib) gl[m++] = '.';
+                for (int c = 0; c < 4; ++c) if ((nib >> c) & 1) gl[m++] = "ACGT"[c];
+                gl[m++] = '\t';
+            }
+            if (KMC_GRAPH_END_L(a)) gl[m++] = 'L';
+            if (KMC_GRAPH_END_R(a)) gl[m++] = 'R';
+            if (!KMC_GRAPH_END_L(a) && !KMC_GRAPH_END_R(a)) gl[m++] = '.';
+            gl[m++] = '\n';
+            fwrite(gl, 1, (size_t)m, stdout);
         }
         fflush(stdout);
         destroy_all();

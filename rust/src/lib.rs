@@ -24,6 +24,8 @@ pub const KMC_COUNT_MIN: i32 = 2;
 pub const KMC_COUNT_MAX: i32 = 3;
 pub const KMC_COUNT_SUM: i32 = 4;
 pub const KMC_COUNT_DIFF: i32 = 5;
+/// summary words of `kmc_graph`
+pub const KMC_GRAPH_WORDS: usize = 8;
 
 // The structs and the extern block below are checked against include/kmc.h by
 // tests/test_abi_host.py::test_rust_binding_matches_the_header (names, arity, argument types, field
@@ -126,6 +128,9 @@ extern "C" {
                             total_out: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_export_setop(a: *mut KmcCtx, b: *mut KmcCtx, op: c_int, count_mode: c_int, min_a: u64, max_a: u64, min_b: u64, max_b: u64,
                             key_hi: *mut u64, key_lo: *mut u64, count: *mut u64, cap: u64, n_out: *mut u64) -> c_int;
+    // the table as a de Bruijn graph: neighbour masks, unitig ends, summary (adj: uint16_t per key of the view)
+    pub fn kmc_graph_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, d_adj: *mut *const c_void, n_keys: *mut u64, summary: *mut u64) -> c_int;
+    pub fn kmc_graph(ctx: *mut KmcCtx, min_count: u64, max_count: u64, adj: *mut c_void, cap: u64, n_keys: *mut u64, summary: *mut u64) -> c_int;
     // multi-GPU reduce (one process per GPU; the collective itself is the host program's, e.g. RCCL)
     pub fn kmc_slab_words(ctx: *const KmcCtx, slab_entries: u64) -> u64;
     pub fn kmc_pack_slab_device(ctx: *mut KmcCtx, d_slab: *mut c_void, slab_entries: u64) -> c_int;
@@ -332,6 +337,20 @@ impl Counter {
             out.push((String::from_utf8_lossy(&buf).into_owned(), cnt[i]));
         }
         Ok(out)
+    }
+
+    /// The table as a de Bruijn graph (`kmc_graph`): one word per key of `table()`, in its order -- bits 0..3 the solid right
+    /// extensions (ACGT), 4..7 the left ones, 8 / 9 "side R / L is a unitig end", 10 "the key is solid" -- and the eight
+    /// summary words [nodes, R degrees, L degrees, isolated, dead ends, branching, end sides, single-node unitigs].  Solid:
+    /// `min_count <= count <= max_count` (`max_count` 0: no upper bound).
+    pub fn graph(&mut self, min_count: u64, max_count: u64) -> Result<(Vec<u16>, [u64; KMC_GRAPH_WORDS]), KmcError> {
+        let (mut nd, mut nt) = (0u64, 0u64);
+        self.check(unsafe { kmc_finalize(self.ctx, &mut nd, &mut nt) })?;
+        let mut adj = vec![0u16; nd as usize];
+        let mut w = [0u64; KMC_GRAPH_WORDS];
+        let mut n = 0u64;
+        self.check(unsafe { kmc_graph(self.ctx, min_count, max_count, adj.as_mut_ptr() as *mut c_void, nd, &mut n, w.as_mut_ptr()) })?;
+        Ok((adj, w))
     }
 }
 
