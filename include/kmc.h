@@ -57,7 +57,8 @@ typedef enum kmc_status {
     KMC_ERR_IO = -5,         /* cannot open/read file            (main.rs:44) */
     KMC_ERR_FORMAT = -6,     /* "Expected > at record start."    (main.rs:59) */
     KMC_ERR_ALPHABET = -7,   /* non-ACGT byte in LR mode         (main.rs:23) */
-    KMC_ERR_CAPACITY = -8,   /* count table and spill area exhausted */
+    KMC_ERR_CAPACITY = -8,   /* count table and spill area exhausted; a view of 2^32 keys or more
+                                (the sort's own lists are sized from a bound: no input overflows them) */
     KMC_ERR_STATE = -9       /* call out of order (e.g. export before finalize) */
 } kmc_status;
 

@@ -838,11 +838,39 @@ int msd_sort_to_run(kmc_ctx* c, u64* const hi[2], u64* const lo[2], u64* const w
     u32 leaf_cap = KW == 1 ? KMC_MSD_LEAF1 : (w[0] ? KMC_MSD_LEAF2W : KMC_MSD_LEAF2);
     if (KW == 2 && !w[0] && c->msd_dup_heavy) leaf_cap = 1024;
     const bool clustered = repeated_keys || c->msd_dup_heavy;   // (one-word leaves: the larger wave scratch)
+    // List sizes are bounds, not estimates: the overflow checks below cannot fire on any input (they stay as a guard
+    // against a change that breaks the reasoning; tests/test_key_shapes_gpu.py holds the inputs that come closest).
+    //   max_seg   the segments of one level are disjoint spans of MORE than leaf_cap keys each (smaller children are
+    //             terminals): at most n / (leaf_cap + 1) of them, the root included when n is small.  The kind-2
+    //             terminals listed in m_clist are such spans too.
+    //   levels    a child is queued at hib - 10, a segment that is not moved at top_diff + 1 <= hib - 10, and a segment
+    //             with hib <= 10 has terminals only: L = ceil(kb / 10) levels at most.
+    //   term_cap  what ONE level adds (kmc_msd_scan_kernel): a segment is one terminal as it stands (all keys equal, or
+    //             not moved with few bits left: kind 2), or is queued again without a terminal, or is walked.  A walked
+    //             segment with B big children (more than leaf_cap keys) has at most B + 1 runs of small children between
+    //             them, and a run of S keys gives at most 2 S / leaf_cap + 1 merged leaves (two neighbouring leaves of a
+    //             run hold more than leaf_cap keys together, or they would have been one).  A big child is queued again
+    //             -- or, at the last level or with at most cnt_bits bits left, is a terminal itself: B more.  In `wide`
+    //             mode (at most 8 segments) each of the 16 waves closes its own run: 15 more per segment.  Summed over a
+    //             level's segments:
+    //                 leaf runs      big children + segments             <= 2 n / leaf_cap below level 0 (both are
+    //                                disjoint spans of more than leaf_cap keys), B + 1 <= n / leaf_cap + 1 at level 0
+    //                 whole segments one each, instead of their runs     (counted in the line above)
+    //                 wide           15 * 8                              = 120
+    //                 leaves         2 / leaf_cap per key that ends in a leaf here: 2 n / leaf_cap over the WHOLE sort
+    //                 big children that are terminals: n / leaf_cap over the WHOLE sort (disjoint, and final)
+    //             Over L levels: n_term <= 2 (L - 1) n / leaf_cap + n / leaf_cap + 1 + 120 L + 3 n / leaf_cap
+    //                                    = (2 L + 2) * (n / leaf_cap) + 120 L + 1; the list holds
+    //                 term_cap = (2 L + 2) * (n / leaf_cap) + 128 L + 64.
+    //             The staircase input (every segment sheds one key below and one above a core of leaf_cap + 1 keys at
+    //             every level) fills 0.70 of it at k = 63.  k <= 31: L = 7, 16 n / leaf_cap as before; k = 63: L = 13,
+    //             28 n / leaf_cap (16 n / leaf_cap + 65536 overflowed on 33 M weighted two-word keys of that shape).
     const u64 max_seg = n / leaf_cap + 257;
     const u32 cnt_bits = weights ? 0u : (u32)KMC_MSD_CNT_BITS;   // long spans with few bits left: LDS histograms (plain counts only)
     const u32 rsz = pre0 ? (u32)KMC_MSD_RANGE : msd_range_for(n);   // keys per range (a workgroup of the histogram / scatter passes)
     const u64 max_ranges = n / rsz + max_seg + 1;
-    const u64 term_cap = 16 * (n / leaf_cap) + 65536;
+    const u64 n_levels = (kb + KMC_MSD_BITS - 1) / KMC_MSD_BITS;
+    const u64 term_cap = (2 * n_levels + 2) * (n / leaf_cap) + 128 * n_levels + 64;
     const u64 n_words = (n + 63) / 64;
     int rc;
     rc = msd_scratch(c, max_ranges, max_seg, term_cap, n_words);
