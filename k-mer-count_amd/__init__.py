@@ -500,18 +500,35 @@ class KmerCounter:
         self._chk(self._L.kmc_export(self._h, hi.ctypes.data, lo.ctypes.data, cnt.ctypes.data, nd))
         return Table(hi, lo, cnt, self.k)
 
+    def _device_triple(self, call) -> Tuple[int, int, int]:
+        """(d_key_hi or 0, d_key_lo, d_count) of call(key_hi, key_lo, count), which takes the three pointer out-arguments."""
+        d = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._chk(call(*map(C.byref, d)))
+        return tuple(p.value or 0 for p in d)
+
+    def _sized_table(self, call) -> Table:
+        """A host table from an export call of the shape call(key_hi, key_lo, count, cap, n_out): asked for the size
+        first (no buffers, cap 0: ERR_ARG with the size in n_out unless the result is empty), then for the entries."""
+        n = C.c_uint64()
+        rc = call(None, None, None, 0, C.byref(n))
+        if rc not in (OK, ERR_ARG) or (rc == ERR_ARG and n.value == 0):
+            self._chk(rc)
+        nk = n.value
+        hi, lo, cnt = np.zeros(nk, np.uint64), np.zeros(nk, np.uint64), np.zeros(nk, np.uint64)
+        if nk:
+            self._chk(call(hi.ctypes.data, lo.ctypes.data, cnt.ctypes.data, nk, C.byref(n)))
+        return Table(hi, lo, cnt, self.k)
+
     def export_device(self) -> Tuple[int, int, int, int]:
         """(d_key_hi or 0, d_key_lo, d_count, n) of the sorted table of the last finalize."""
-        a, b, c, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64()
-        self._chk(self._L.kmc_export_device(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(n)))
-        return a.value or 0, b.value or 0, c.value or 0, n.value
+        n = C.c_uint64()
+        return self._device_triple(lambda *d: self._L.kmc_export_device(self._h, *d, C.byref(n))) + (n.value,)
 
     def partition_device(self, n_parts: int):
         """Owner-partitioned view for the all-to-all: (part_begin[n_parts+1], d_hi, d_lo, d_cnt)."""
         pb = (C.c_uint64 * (n_parts + 1))()
-        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        self._chk(self._L.kmc_partition_device(self._h, n_parts, pb, C.byref(a), C.byref(b), C.byref(c)))
-        return list(pb), a.value or 0, b.value or 0, c.value or 0
+        d = self._device_triple(lambda *d: self._L.kmc_partition_device(self._h, n_parts, pb, *d))
+        return (list(pb),) + d
 
     # -- after counting: abundance histogram, count-range filter (of the sorted view) --
     def histogram(self, n_bins: int = 10001, min_count: int = 1, max_count: int = 0, return_max: bool = False):
@@ -526,22 +543,13 @@ class KmerCounter:
     def filter_device(self, min_count: int, max_count: int = 0) -> Tuple[int, int, int, int, int]:
         """(d_key_hi or 0, d_key_lo, d_count, n_kept, kept_total): the keys of the sorted view with count in
         [min_count, max_count], in view order, in ctx-owned device arrays (kmc_filter_device)."""
-        a, b, c, n, t = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
-        self._chk(self._L.kmc_filter_device(self._h, int(min_count), int(max_count), C.byref(a), C.byref(b), C.byref(c), C.byref(n), C.byref(t)))
-        return a.value or 0, b.value or 0, c.value or 0, n.value, t.value
+        n, t = C.c_uint64(), C.c_uint64()
+        d = self._device_triple(lambda *d: self._L.kmc_filter_device(self._h, int(min_count), int(max_count), *d, C.byref(n), C.byref(t)))
+        return d + (n.value, t.value)
 
     def export_filtered(self, min_count: int, max_count: int = 0) -> Table:
         """The sorted view restricted to counts in [min_count, max_count] (max_count 0: no upper bound), on the host."""
-        n = C.c_uint64()
-        rc = self._L.kmc_export_filtered(self._h, int(min_count), int(max_count), None, None, None, 0, C.byref(n))
-        if rc not in (OK, ERR_ARG) or (rc == ERR_ARG and n.value == 0):
-            self._chk(rc)
-        nk = n.value
-        hi, lo, cnt = np.zeros(nk, np.uint64), np.zeros(nk, np.uint64), np.zeros(nk, np.uint64)
-        if nk:
-            self._chk(self._L.kmc_export_filtered(self._h, int(min_count), int(max_count), hi.ctypes.data, lo.ctypes.data,
-                                                  cnt.ctypes.data, nk, C.byref(n)))
-        return Table(hi, lo, cnt, self.k)
+        return self._sized_table(lambda *out: self._L.kmc_export_filtered(self._h, int(min_count), int(max_count), *out))
 
     # -- two tables: summary and set operations over the sorted views of self (A) and other (B) --
     @staticmethod
@@ -563,26 +571,17 @@ class KmerCounter:
         (kmc_setop_device); op / counts are the SETOP_* / COUNT_* codes or their names.  return_summary=True appends
         the Comparison."""
         o, m = self._setop_codes(op, counts)
-        a, b, c, n, t = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        n, t = C.c_uint64(), C.c_uint64()
         w = (C.c_uint64 * COMPARE_WORDS)()
-        self._chk(self._L.kmc_setop_device(self._h, other._h, o, m, int(min_a), int(max_a), int(min_b), int(max_b), C.byref(a), C.byref(b),
-                                           C.byref(c), C.byref(n), C.byref(t), w if return_summary else None))
-        r = (a.value or 0, b.value or 0, c.value or 0, n.value, t.value)
+        r = self._device_triple(lambda *d: self._L.kmc_setop_device(self._h, other._h, o, m, int(min_a), int(max_a), int(min_b), int(max_b), *d,
+                                                                    C.byref(n), C.byref(t), w if return_summary else None)) + (n.value, t.value)
         return r + (Comparison.from_words(list(w)),) if return_summary else r
 
     def setop(self, other: "KmerCounter", op, counts=COUNT_LEFT, min_a: int = 1, max_a: int = 0, min_b: int = 1, max_b: int = 0) -> Table:
         """``self op other`` on the host: intersect / union / subtract with the result count given by ``counts``."""
         o, m = self._setop_codes(op, counts)
         args = (self._h, other._h, o, m, int(min_a), int(max_a), int(min_b), int(max_b))
-        n = C.c_uint64()
-        rc = self._L.kmc_export_setop(*args, None, None, None, 0, C.byref(n))
-        if rc not in (OK, ERR_ARG) or (rc == ERR_ARG and n.value == 0):
-            self._chk(rc)
-        nk = n.value
-        hi, lo, cnt = np.zeros(nk, np.uint64), np.zeros(nk, np.uint64), np.zeros(nk, np.uint64)
-        if nk:
-            self._chk(self._L.kmc_export_setop(*args, hi.ctypes.data, lo.ctypes.data, cnt.ctypes.data, nk, C.byref(n)))
-        return Table(hi, lo, cnt, self.k)
+        return self._sized_table(lambda *out: self._L.kmc_export_setop(*args, *out))
 
     # -- the table as a de Bruijn graph: neighbour masks, unitig ends, summary (of the sorted view; finalize() first) --
     def graph(self, min_count: int = 1, max_count: int = 0, adj: bool = True):

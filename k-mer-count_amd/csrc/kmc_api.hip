@@ -4,27 +4,18 @@
 // One ctx == one GPU.  All work is queued on the ctx stream; kernels are the hand-written
 // gfx950 kernels of kmc_stream.hip.h / kmc_walk.hip.h / kmc_table.hip.h.  There is no CPU path: if
 // the HIP runtime has no device, kmc_create fails.
-#include <stdarg.h>
-#include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
 
 #include <cstring>
 
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
 #include <atomic>
 #include <climits>
 #include <chrono>
-#include <deque>
 #include <thread>
-#include <new>
 #include <string>
-#include <vector>
 
-#include "../../include/kmc.h"
-#include "kmc_device.hip.h"
+#define KMC_SCAN_TOP_DEFINE   // kmc_scan.hip.h: this translation unit holds kmc_scan_top_kernel
+#include "kmc_ctx.hip.h"
 #include "kmc_stream.hip.h"
 #include "kmc_synth.hip.h"
 #include "kmc_table.hip.h"
@@ -34,192 +25,11 @@
 #include "kmc_msd.hip.h"
 #include "kmc_extract.hip.h"
 #include "kmc_peak.hip.h"
-#include "kmc_spectrum.hip.h"
-#include "kmc_query.hip.h"
-#include "kmc_setops.hip.h"
-#include "kmc_graph.hip.h"
 #include "kmc_ingest.h"
-
-namespace {
 
 thread_local char g_create_err[512] = {0};
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-};
-
-struct Table {
-    u64 *hi = nullptr, *lo = nullptr, *cnt = nullptr, *mid = nullptr;  // (mid: three-word keys of the (k+16)-mer table, k >= 48)
-    u64 cap = 0;
-};
-
-}  // namespace
-
-struct kmc_ctx {
-    kmc_config cfg{};
-    int KW = 1;     // key words
-    int klen = 0;   // characters per key (k, or 54 in LR mode)
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    char err[512] = {0};
-
-    Table tab;
-    u64* d_counters = nullptr;      // KMC_CTR_N u64
-    u64* h_counters = nullptr;      // pinned mirror
-    u64* occ_list = nullptr;        // first KMC_OCC_LIST_CAP claimed slots (fast finalize of small tables)
-    u64 *occ_key_lo = nullptr, *occ_key_hi = nullptr;   // ... and their keys, dense (GTable::occ_key_*)
-    u32* fin_rank = nullptr;        // ticket counter of kmc_small_finalize_kernel (zero between launches)
-    u64* h_pub = nullptr;           // pinned, 2 * KMC_CTR_N: where kmc_small_finalize_kernel publishes its outcome + the counters.  Its
-                                    // own block: a kernel queued by kmc_finalize_async may publish after the host has reset or
-                                    // polled h_counters; poll_fin copies what the awaited launch published into h_counters
-    u64* d_mirror = nullptr;        // h_pub as the device sees it
-    u64* h_restore = nullptr;       // pinned: the counters to put back when a drained table is filled again (undrain)
-    // planner invariant (kmc_stats.n_planner_stale): every kernel queued OUTSIDE the count launches' own accounting that
-    // changes the table -- the (k+16)-mer unfold, merges -- bumps table_epoch; a poll records the epoch it has seen; a
-    // risky launch must save a table whose counters were polled at the current epoch
-    u64 table_epoch = 0, polled_epoch = 0;
-    u64 fin_seq = 0;                // number of the last kmc_small_finalize_kernel launch (the kernel publishes it with its result)
-    bool async_fin = false;         // kmc_finalize_async: a finalize is queued whose outcome the host has not looked at yet
-    bool drained = false;           // the last kmc_finalize emptied the table into the sorted view (kmc_small_finalize_kernel):
-                                    // table and device counters are as after kmc_reset, h_counters hold the true totals
-    u64 *spill_hi = nullptr, *spill_lo = nullptr, *spill_cnt = nullptr;
-    u64 spill_cap = 0;
-
-    // staging for host batches
-    DevBuf st_bases, st_offsets;
-    // sorted view
-    DevBuf o_hi, o_lo, o_cnt, t_hi, t_lo, t_cnt, t_idx0, p_hi, p_lo, p_cnt;
-    u64 n_sorted = 0;
-    bool sorted_valid = false;
-    // walk-kernel workspace
-    DevBuf walk_ws;
-    DevBuf vr_reads, vr_cnt, vr_pos;  // pieces of long reads for the walk kernel: [starts | ends], per-read counts and their scan
-    DevBuf walk_memo;  // two shared memo snapshots + dense counters, kept across launches (kmc_walk.hip.h)
-    int memo_parity = 0;  // snapshot slot the next walk launch reads
-    bool walk_ws_clean = false;  // workspace header + dense counters are zero (left so by kmc_walk_tail_kernel)
-    // KMC_ALGO_SORT: scratch for one sub-batch and the sorted (key,count) runs produced so far
-    DevBuf s_lo[2], s_hi[2];
-    // the walk kernel's log of steps that fell off its LDS memo (kmc_walk.hip.h SkLog, kmc_sklog.hip.h): per-workgroup spans,
-    // their fill counts, the 1024 hash bins the records are partitioned into, the bins' cursors
-    DevBuf lg_rec, lg_count, lg_bins, lg_cursor;
-    bool sklog_on = false;   // this data source overflows the LDS memo (a poll saw (k+16)-mers in the second-level table): log from now on
-    DevBuf a_hist, a_rand, a_ror;   // level-0 histogram rows / AND / OR words of the accumulated key ranges (kmc_extract.hip.h)
-    // KMC_ALGO_SORT accumulates: a batch only EXTRACTS its keys behind those of the batches before it (s_lo[0] /
-    // s_hi[0]); they are sorted into ONE run when somebody needs the result (kmc_finalize, a reduce) or when 2^31
-    // positions have come together.  (Sorting batch by batch left one run per batch -- 16 for a 1 GB file read in
-    // 64 MB chunks -- and kmc_finalize then merged them by sorting everything once more: 0.9 s for 760 M 63-mers.)
-    u64 acc_n = 0;           // key positions accumulated and not yet sorted
-    u64 acc_hint = 0;        // positions the caller expects in all (kmc_count_file: the file size); sizes the first allocation
-    DevBuf lr_rank;  // LR mode: rank of every position's 27-mer among the batch's distinct 27-mers
-    // hand-written MSD radix sort (kmc_msd.hip.h): per-range histograms, segment lists, terminals
-    DevBuf m_hist, m_stot, m_bsum, m_rmin, m_rmax, m_seg[2], m_first, m_cbase, m_skip, m_term, m_ord, m_bitmap, m_rank, m_nd, m_base, m_ctl, m_clist, m_w[2];
-    MsdCtl* h_ctl = nullptr;  // pinned mirror of the sort's device counters
-    struct Run { u64 *hi = nullptr, *lo = nullptr, *cnt = nullptr; u64 n = 0, cap = 0; u64 total = 0; bool total_known = false; };
-    std::vector<Run> runs;       // live runs
-    std::vector<Run> run_pool;   // buffers of dropped runs, reused (multi-GB hipMalloc/hipFree per batch is slow)
-    Run view_run;                // the merged, sorted view built by the last kmc_finalize (table entries + runs)
-    const u64 *v_hi = nullptr, *v_lo = nullptr, *v_cnt = nullptr;  // the sorted view of the last finalize
-    bool msd_dup_heavy = false;  // the last large unweighted sort collapsed its keys more than fourfold (leaf size of two-word sorts)
-    bool prefer_sort = false;  // AUTO: the data source proved high-cardinality  // per-workgroup memo slots, kept across launches (kmc_walk.hip.h)
-
-    // hipEvent pairs bracketing every count-kernel launch, batch by batch: a batch's events are read once they have
-    // completed (harvest_timing), possibly several batches later -- a caller that never synchronises this ctx (the
-    // multi-GPU step: count, pack, reset) still gets every batch's kernel time into kernel_ms_lifetime
-    struct TimedBatch { std::vector<hipEvent_t> ev; int algo = 0; u64 n_bases = 0; u32 count_launches = 0; };
-    std::deque<TimedBatch> tb;                // batches whose events have not been read yet (front = oldest)
-    // KMC_ALGO_AUTO chooses by MEASURED cost: kernel milliseconds per base of this ctx's recent walk-path batches (walk
-    // kernel + (k+16)-mer unfold + the table merge at finalize) and sort-path batches (< 0: not measured yet)
-    double walk_ms_per_base = -1.0, sort_ms_per_base = -1.0;
-    bool sort_by_cost = false;   // AUTO: the last comparison of the two rates said "sort" (prefer_sort: structural -- the source overflowed everything)
-    std::vector<hipEvent_t> ev_free;          // events to reuse
-    kmc_stats st{};
-    int fin_parity = 0;    // which OUT/SUM counter pair the next kmc_finalize uses
-    u64 fin_hint = 0;      // table entries at the last kmc_finalize (sizes the next speculative small-table finalize)
-    // The rank sort of kmc_small_finalize_kernel is quadratic: 16 us for 1 k keys, 0.24 ms for 24 k, 0.8 ms for 68 k (measured).  The
-    // weighted radix sort that larger tables take costs 0.25-0.3 ms at that size (a dozen small launches, two polls): tables
-    // that were larger than this at the last finalize go there directly.  (KMC_FIN_SMALL_MAX overrides: the parity test of
-    // the kernel's size boundaries runs it up to its limit, KMC_FIN_KERNEL_MAX.)
-    u64 fin_small_max = 40000;
-    bool view_unsynced = false;   // the last small-table finalize was waited for through the mirror, not the stream (poll_fin)
-    bool batch_pending = false;  // a COUNT kernel (unknown number of new keys) is queued since the last poll
-    u64 unpolled_adds = 0;       // upper bound of keys added by merge kernels since the last poll
-    bool walk_overflowed = false;  // the last WALK/STREAM launches counted >5% of their k-mers with global atomics
-                                   // (memo / LDS table overflow = high-cardinality input)
-    u64 direct_seen = 0, kmers_seen = 0;
-    bool pending = false;  // a batch has been queued since the last counter poll
-    double rho_last = 0.0; // same, over the most recent sub-batch
-    double rho_hist = -1.0; // new keys per k-mer of the previous batch as a whole (< 0: no history); survives kmc_reset
-    bool b_open = false; double b_rho_max = 0.0; u64 b_occ0 = 0, b_kmers = 0;  // the batch whose last launch is still unobserved
-    double rho_max = 0.0;  // largest observed (new distinct) / (k-mers) over a sub-batch
-    int n_cu = 256;
-    // A launch sized by a prediction (more k-mers than the table and spill area absorb for certain) is
-    // "risky": the table is saved first, and if the spill area overflows the table is put back and the
-    // rest of the batch is counted by the sort path, which needs no table (recover_overflow).
-    struct Risky {
-        bool armed = false;
-        int mode = 0;                 // 1: entries listed in occ_list; 2: whole table copied
-        bool empty = false;           // mode 1 and the table held nothing: there is nothing to save (no kernel)
-        const uint8_t* d_bases = nullptr; const u64* d_offsets = nullptr; u64 n_reads = 0, n_bases = 0;
-        u64 base_from = 0;            // first base position the risky launch covers ...
-        const u64* d_from = nullptr;  // ... or where to read it on the device (end of the last piece walked before)
-        u64 ctr[KMC_CTR_N] = {0};     // the device counters before the launch
-    } risky;
-    DevBuf snap_hi, snap_lo, snap_cnt, snap_n, snap_occ;
-    // second-level memo of the walk kernel: (k+16)-mer table (kmc_walk.hip.h); three key words for k >= 48
-    Table sk;
-    u64* d_sk_counters = nullptr;
-    u64* h_sk_counters = nullptr;   // pinned mirror (valid after a poll)
-    u64 *sk_spill_hi = nullptr, *sk_spill_lo = nullptr, *sk_spill_cnt = nullptr, *sk_spill_mid = nullptr;
-    u64 sk_spill_cap = 0;
-    u64* sk_occ = nullptr;          // list of its claimed slots (what the unfold kernel walks)
-    bool recovered = false;  // the last poll found an overflow and recovered: the batch in flight is complete
-    bool sk_dirty = false;   // walk launches since the last unfold of the (k+16)-mer table
-    bool sk_fixed = false;   // its size was set by KMC_SK_SLOTS (tests): never re-allocated
-    bool sk_grow = false;    // a poll found it more than half full: re-allocate larger when it is next empty
-    DevBuf rx_hi, rx_lo, rx_cnt;  // receive buffers of the one-process multi-GPU reduce (a peer's sorted table)
-    // kmc_filter_device's result (its own buffers: a filter leaves the view and a partition the caller holds alone), the
-    // per-tile kept counts and their scan, [n_kept | kept_total]; kmc_histogram's device histogram + max
-    DevBuf f_hi, f_lo, f_cnt, f_tile, f_tpos, f_bsum, f_ctl, h_hist;
-    // kmc_query / kmc_profile (kmc_query.hip.h): the prefix index of the view numbered q_gen (view_gen counts the views this
-    // ctx has produced: every place that publishes one bumps it, so an index can never outlive its view), staging of the
-    // host forms: query keys and counts, a batch's bases and offsets, its window counts and read statistics
-    u64 view_gen = 0, q_gen = ~0ull;
-    DevBuf q_idx, q_khi, q_klo, q_cnt, q_bases, q_offs, q_win, q_stats;
-    // kmc_compare / kmc_setop_device (kmc_setops.hip.h), on the ctx given as `a`: the result, the merge-path partition of the
-    // two views (first A / B entry of every tile), emitted keys per tile and their scan, [n_out | summary words | total_out]
-    DevBuf so_hi, so_lo, so_cnt, so_pa, so_pb, so_tile, so_tpos, so_bsum, so_ctl;
-    // kmc_graph / kmc_graph_device (kmc_graph.hip.h): one 16-bit word per key of the view, the eight summary words
-    DevBuf g_adj, g_ctl;
-};
-
 namespace {
-
-int fail(kmc_ctx* c, int code, const char* fmt, ...) {
-    char buf[512] = {0};
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    memcpy(c ? c->err : g_create_err, buf, sizeof(buf));
-    return code;
-}
-
-#define HIPCHK(c, call)                                                                       \
-    do {                                                                                      \
-        hipError_t e__ = (call);                                                              \
-        if (e__ != hipSuccess)                                                                \
-            return fail((c), e__ == hipErrorOutOfMemory ? KMC_ERR_NOMEM : KMC_ERR_HIP, "%s: %s", #call, hipGetErrorString(e__)); \
-    } while (0)
-
-int ensure(kmc_ctx* c, DevBuf& b, size_t bytes) {
-    if (b.bytes >= bytes && b.p) return KMC_OK;
-    if (b.p) { HIPCHK(c, hipFree(b.p)); b.p = nullptr; b.bytes = 0; }
-    size_t want = bytes + bytes / 8 + 256;
-    HIPCHK(c, hipMalloc(&b.p, want));
-    b.bytes = want;
-    return KMC_OK;
-}
 
 // like ensure, but the first `keep` bytes survive (grows geometrically: the copy is amortised)
 int ensure_keep(kmc_ctx* c, DevBuf& b, size_t bytes, size_t keep) {
@@ -236,12 +46,6 @@ int ensure_keep(kmc_ctx* c, DevBuf& b, size_t bytes, size_t keep) {
     b.p = np;
     b.bytes = want;
     return KMC_OK;
-}
-
-void free_buf(DevBuf& b) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.bytes = 0;
 }
 
 void free_runs(kmc_ctx* c, bool release);
@@ -422,14 +226,6 @@ u64 next_pow2(u64 v) {
     u64 p = 1;
     while (p < v) p <<= 1;
     return p;
-}
-
-int grid_for(const kmc_ctx* c, u64 n, int threads) {
-    u64 blocks = (n + threads - 1) / threads;
-    u64 cap = (u64)c->n_cu * 8;
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    return (int)blocks;
 }
 
 // workgroups of kmc_reset_kernel: every one of them draws a ticket from ONE word at the end (the counters are cleared behind
@@ -618,8 +414,8 @@ int launch_small_finalize(kmc_ctx* c, int grid) {
     // when it carries this launch's number (earlier launches may still be in flight: kmc_finalize_async)
     const u64 seq = ++c->fin_seq;
     const u64* skc = c->d_counters + KMC_CTR_N;
-    if (c->KW == 1) hipLaunchKernelGGL(kmc_small_finalize_kernel<1>, dim3(grid), dim3(1024), 0, c->stream, g, skc, c->fin_rank, c->d_mirror, seq, (u64*)nullptr, (u64*)c->o_lo.p, (u64*)c->o_cnt.p);
-    else hipLaunchKernelGGL(kmc_small_finalize_kernel<2>, dim3(grid), dim3(1024), 0, c->stream, g, skc, c->fin_rank, c->d_mirror, seq, (u64*)c->o_hi.p, (u64*)c->o_lo.p, (u64*)c->o_cnt.p);
+    if (c->KW == 1) hipLaunchKernelGGL(kmc_small_finalize_kernel<1>, dim3(grid), dim3(1024), 0, c->stream, g, skc, c->fin_rank, c->d_mirror, seq, (u64*)nullptr, (u64*)c->o.lo.p, (u64*)c->o.cnt.p);
+    else hipLaunchKernelGGL(kmc_small_finalize_kernel<2>, dim3(grid), dim3(1024), 0, c->stream, g, skc, c->fin_rank, c->d_mirror, seq, (u64*)c->o.hi.p, (u64*)c->o.lo.p, (u64*)c->o.cnt.p);
     HIPCHK(c, hipGetLastError());
     return KMC_OK;
 }
@@ -636,7 +432,7 @@ int undrain(kmc_ctx* c) {
     HIPCHK(c, hipMemcpyAsync(c->d_counters, c->h_restore, KMC_CTR_N * sizeof(u64), hipMemcpyHostToDevice, c->stream));
     c->fin_parity = 0;
     if (c->n_sorted) {
-        launch_merge_pairs(c, (const u64*)c->o_hi.p, (const u64*)c->o_lo.p, (const u64*)c->o_cnt.p, c->n_sorted);
+        launch_merge_pairs(c, (const u64*)c->o.hi.p, (const u64*)c->o.lo.p, (const u64*)c->o.cnt.p, c->n_sorted);
         HIPCHK(c, hipGetLastError());
     }
     return KMC_OK;
@@ -651,9 +447,9 @@ int resolve_async(kmc_ctx* c) {
     if (rc) return rc;
     if (c->drained) {
         const u64 n = c->h_counters[KMC_CTR_OCCUPIED];
-        c->v_hi = c->KW == 2 ? (const u64*)c->o_hi.p : nullptr;
-        c->v_lo = (const u64*)c->o_lo.p;
-        c->v_cnt = (const u64*)c->o_cnt.p;
+        c->v_hi = c->KW == 2 ? (const u64*)c->o.hi.p : nullptr;
+        c->v_lo = (const u64*)c->o.lo.p;
+        c->v_cnt = (const u64*)c->o.cnt.p;
         c->n_sorted = n;
         c->sorted_valid = true;
         c->view_gen += 1;
@@ -665,6 +461,7 @@ int resolve_async(kmc_ctx* c) {
     return settle(c);
 }
 
+}  // namespace
 // What the calls that read the view do first: a finalize queued by kmc_finalize_async counts as one -- also when its
 // kernel gave up (a table it does not take): then the ordinary finalize makes the view here.
 int resolve_view(kmc_ctx* c) {
@@ -673,6 +470,7 @@ int resolve_view(kmc_ctx* c) {
     if (rc || !queued || c->sorted_valid) return rc;
     return kmc_finalize(c, nullptr, nullptr);
 }
+namespace {
 
 // Give the counts of the (k+16)-mer table to their k-mers (kmc_sk_unfold_kernel).  What the last poll
 // saw of that table is certain to come (16 k-mers per entry): room is made for it first.  Entries
@@ -928,10 +726,7 @@ int msd_sort_to_run(kmc_ctx* c, u64* const hi[2], u64* const lo[2], u64* const w
     if (!n_term) return KMC_OK;  // nothing but filler
     // terminals in position order, their pairs, the dense run
     {   // rank of every bitmap word = exclusive prefix of the popcounts
-        const u32 nb = (u32)((n_words + KMC_SCAN_PER_BLOCK - 1) / KMC_SCAN_PER_BLOCK);
-        hipLaunchKernelGGL(kmc_scan_sums_kernel<1>, dim3(nb), dim3(256), 0, c->stream, (const void*)c->m_bitmap.p, (u32)n_words, (u32*)c->m_bsum.p);
-        hipLaunchKernelGGL(kmc_scan_top_kernel, dim3(1), dim3(1024), 0, c->stream, (u32*)c->m_bsum.p, nb, &ctl->scan_total);
-        hipLaunchKernelGGL(kmc_scan_final_kernel<1>, dim3(nb), dim3(256), 0, c->stream, (const void*)c->m_bitmap.p, (u32)n_words, (const u32*)c->m_bsum.p, (u32*)c->m_rank.p);
+        launch_exclusive_scan<1>(c->stream, c->m_bitmap.p, (u32)n_words, (u32*)c->m_bsum.p, (u32*)c->m_rank.p, &ctl->scan_total);
     }
     hipLaunchKernelGGL(kmc_msd_order_kernel, dim3(grid_for(c, n_term, 256)), dim3(256), 0, c->stream, (const MsdTerm*)c->m_term.p, n_term,
                        (const unsigned long long*)c->m_bitmap.p, (const u32*)c->m_rank.p, (MsdTerm*)c->m_ord.p, (u32*)c->m_clist.p, ctl);
@@ -981,10 +776,7 @@ int msd_sort_to_run(kmc_ctx* c, u64* const hi[2], u64* const lo[2], u64* const w
         kmc_ctx::Run dense;
         rc = take_run(c, std::max<u64>(n_pairs, 1), &dense);
         if (rc) { c->run_pool.push_back(run); return rc; }
-        const u32 nb = (n_term + KMC_SCAN_PER_BLOCK - 1) / KMC_SCAN_PER_BLOCK;
-        hipLaunchKernelGGL(kmc_scan_sums_kernel<0>, dim3(nb), dim3(256), 0, c->stream, (const void*)c->m_nd.p, n_term, (u32*)c->m_bsum.p);
-        hipLaunchKernelGGL(kmc_scan_top_kernel, dim3(1), dim3(1024), 0, c->stream, (u32*)c->m_bsum.p, nb, &ctl->n_pairs);
-        hipLaunchKernelGGL(kmc_scan_final_kernel<0>, dim3(nb), dim3(256), 0, c->stream, (const void*)c->m_nd.p, n_term, (const u32*)c->m_bsum.p, (u32*)c->m_base.p);
+        launch_exclusive_scan<0>(c->stream, c->m_nd.p, n_term, (u32*)c->m_bsum.p, (u32*)c->m_base.p, &ctl->n_pairs);
         if (KW == 1) hipLaunchKernelGGL(kmc_msd_gather_kernel<1>, dim3(grid_for(c, (u64)n_term * 64, 256)), dim3(256), 0, c->stream, (const MsdTerm*)c->m_ord.p, n_term,
                                         (const u32*)c->m_nd.p, (const u32*)c->m_base.p, (const u64*)run.hi, (const u64*)run.lo, (const u64*)run.cnt, dense.hi, dense.lo, dense.cnt);
         else hipLaunchKernelGGL(kmc_msd_gather_kernel<2>, dim3(grid_for(c, (u64)n_term * 64, 256)), dim3(256), 0, c->stream, (const MsdTerm*)c->m_ord.p, n_term,
@@ -1185,7 +977,7 @@ int drop_batch_from_table(kmc_ctx* c, const u64* ctr0) {
 
 // pieces of at most KMC_WALK_MAX_READ bases for a batch with longer reads (kmc_walk.hip.h): vr_reads = [starts | ends]
 int build_vreads(kmc_ctx* c, const u64* d_offsets, u64 n_reads, u64* n_v_out) {
-    // pieces per read (u32), their exclusive prefix (the three-kernel scan of kmc_msd.hip.h), then the pieces
+    // pieces per read (u32), their exclusive prefix (the three-kernel scan of kmc_scan.hip.h), then the pieces
     if (n_reads >= (1ull << 32)) return fail(c, KMC_ERR_ARG, "batch too large for one walk pass");
     const u32 nb = (u32)((n_reads + KMC_SCAN_PER_BLOCK - 1) / KMC_SCAN_PER_BLOCK);
     int rc = ensure(c, c->vr_cnt, (size_t)n_reads * sizeof(u32));
@@ -1200,9 +992,7 @@ int build_vreads(kmc_ctx* c, const u64* d_offsets, u64 n_reads, u64* n_v_out) {
     MsdCtl* ctl = (MsdCtl*)c->m_ctl.p;
     u32 *cnt = (u32*)c->vr_cnt.p, *pos = (u32*)c->vr_pos.p;
     hipLaunchKernelGGL(kmc_vreads_count_kernel, dim3(grid_for(c, n_reads, 256)), dim3(256), 0, c->stream, d_offsets, n_reads, c->cfg.k, cnt);
-    hipLaunchKernelGGL(kmc_scan_sums_kernel<0>, dim3(nb), dim3(256), 0, c->stream, (const void*)cnt, (u32)n_reads, (u32*)c->m_bsum.p);
-    hipLaunchKernelGGL(kmc_scan_top_kernel, dim3(1), dim3(1024), 0, c->stream, (u32*)c->m_bsum.p, nb, &ctl->scan_total);
-    hipLaunchKernelGGL(kmc_scan_final_kernel<0>, dim3(nb), dim3(256), 0, c->stream, (const void*)cnt, (u32)n_reads, (const u32*)c->m_bsum.p, pos);
+    launch_exclusive_scan<0>(c->stream, cnt, (u32)n_reads, (u32*)c->m_bsum.p, pos, &ctl->scan_total);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(c->h_ctl, ctl, sizeof(MsdCtl), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1737,21 +1527,20 @@ extern "C" void kmc_destroy(kmc_ctx* c) {
     if (c->spill_hi) (void)hipFree(c->spill_hi);
     if (c->spill_lo) (void)hipFree(c->spill_lo);
     if (c->spill_cnt) (void)hipFree(c->spill_cnt);
-    DevBuf* bufs[] = {&c->st_bases, &c->st_offsets, &c->o_hi, &c->o_lo, &c->o_cnt, &c->t_hi, &c->t_lo, &c->t_cnt,
-                      &c->t_idx0, &c->p_hi, &c->p_lo, &c->p_cnt, &c->walk_ws, &c->walk_memo, &c->vr_reads, &c->vr_cnt, &c->vr_pos,
+    DevBuf* bufs[] = {&c->st_bases, &c->st_offsets, &c->t_idx0, &c->walk_ws, &c->walk_memo, &c->vr_reads, &c->vr_cnt, &c->vr_pos,
                       &c->s_lo[0], &c->s_lo[1], &c->s_hi[0], &c->s_hi[1], &c->lr_rank, &c->a_hist, &c->a_rand, &c->a_ror,
                       &c->lg_rec, &c->lg_count, &c->lg_bins, &c->lg_cursor,
                       &c->m_hist, &c->m_stot, &c->m_bsum, &c->m_rmin, &c->m_rmax, &c->m_seg[0], &c->m_seg[1], &c->m_first, &c->m_cbase, &c->m_skip, &c->m_term, &c->m_ord,
                       &c->m_bitmap, &c->m_rank, &c->m_nd, &c->m_base, &c->m_ctl, &c->m_clist, &c->m_w[0], &c->m_w[1],
-                      &c->snap_hi, &c->snap_lo, &c->snap_cnt, &c->snap_n, &c->snap_occ, &c->rx_hi, &c->rx_lo, &c->rx_cnt,
-                      &c->f_hi, &c->f_lo, &c->f_cnt, &c->f_tile, &c->f_tpos, &c->f_bsum, &c->f_ctl, &c->h_hist,
+                      &c->snap_hi, &c->snap_lo, &c->snap_cnt, &c->snap_n, &c->snap_occ, &c->h_hist, &c->c_tile, &c->c_tpos, &c->c_bsum, &c->c_ctl,
                       &c->q_idx, &c->q_khi, &c->q_klo, &c->q_cnt, &c->q_bases, &c->q_offs, &c->q_win, &c->q_stats,
-                      &c->so_hi, &c->so_lo, &c->so_cnt, &c->so_pa, &c->so_pb, &c->so_tile, &c->so_tpos, &c->so_bsum, &c->so_ctl,
-                      &c->g_adj, &c->g_ctl};
+                      &c->so_pa, &c->so_pb, &c->g_adj, &c->g_ctl};
+    KeyBufs* keys[] = {&c->o, &c->t, &c->p, &c->rx, &c->f, &c->so};
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
     sk_free(c);
     try { free_runs(c, true); } catch (...) { /* (only the pool bookkeeping can throw; the buffers it could not list leak with the process) */ }
     for (DevBuf* b : bufs) free_buf(*b);
+    for (KeyBufs* k : keys) free_keys(*k);
     for (auto& b : c->tb) for (hipEvent_t e : b.ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ev_free) (void)hipEventDestroy(e);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
@@ -1931,11 +1720,7 @@ static int kmc_merge_pairs_device_impl(kmc_ctx* c, const void* d_key_hi, const v
 
 // The view buffers a small-table finalize writes: room for its largest table
 static int ensure_small_view(kmc_ctx* c) {
-    const size_t fb = (size_t)KMC_FIN_KERNEL_MAX * sizeof(u64);
-    int rc = ensure(c, c->o_lo, fb);
-    if (!rc) rc = ensure(c, c->o_cnt, fb);
-    if (!rc && c->KW == 2) rc = ensure(c, c->o_hi, fb);
-    return rc;
+    return ensure_keys(c, c->o, KMC_FIN_KERNEL_MAX);
 }
 // A poll of kmc_finalize, behind its own small-table finalize (fin) or plain, and settle; then the keys a recovery
 // extracted (the poll may have recovered an overflow by extracting the rest of a batch), sorted into a run
@@ -2006,9 +1791,9 @@ static int kmc_finalize_impl(kmc_ctx* c, uint64_t* n_distinct, uint64_t* n_total
     u64 n_kmers = 0;
     const bool single_run = n_tab == 0 && c->runs.size() == 1;
     if (c->view_run.lo) { c->view_run.n = 0; c->run_pool.push_back(c->view_run); c->view_run = kmc_ctx::Run{}; }  // the previous finalize's view
-    c->v_hi = c->KW == 2 ? (const u64*)c->o_hi.p : nullptr;
-    c->v_lo = (const u64*)c->o_lo.p;
-    c->v_cnt = (const u64*)c->o_cnt.p;
+    c->v_hi = c->KW == 2 ? (const u64*)c->o.hi.p : nullptr;
+    c->v_lo = (const u64*)c->o.lo.p;
+    c->v_cnt = (const u64*)c->o.cnt.p;
     if (fast_done) {
         // small table: the rank-sort kernel already gathered, sorted and wrote the view
         n_kmers = c->h_counters[KMC_CTR_SUM2];
@@ -2027,36 +1812,33 @@ static int kmc_finalize_impl(kmc_ctx* c, uint64_t* n_distinct, uint64_t* n_total
             for (auto& r : c->run_pool) { if (r.hi) (void)hipFree(r.hi); (void)hipFree(r.lo); (void)hipFree(r.cnt); }
             c->run_pool.clear();
         }
-        const size_t nb = (size_t)n * sizeof(u64);
-        DevBuf* need[] = {&c->o_lo, &c->o_cnt, &c->t_lo, &c->t_cnt};
-        for (DevBuf* b : need) { rc = ensure(c, *b, nb); if (rc) return rc; }
-        if (c->KW == 2) { rc = ensure(c, c->o_hi, nb); if (rc) return rc; rc = ensure(c, c->t_hi, nb); if (rc) return rc; }
+        if ((rc = ensure_keys(c, c->o, n)) || (rc = ensure_keys(c, c->t, n))) return rc;
         if (n_tab && n_tab <= KMC_OCC_LIST_CAP && c->occ_list && c->h_counters[KMC_CTR_SPILL] == 0 && c->h_counters[KMC_CTR_ERR] == 0) {
             // every claimed slot is listed (and its key kept in the dense key list): no scan of the table
             GTable g = gtable_of(c, c->tab);
             const int grid = grid_for(c, n_tab, 256);
-            if (c->KW == 1) hipLaunchKernelGGL(kmc_compact_list_kernel<1>, dim3(grid), dim3(256), 0, c->stream, g, n_tab, (u64*)nullptr, (u64*)c->t_lo.p, (u64*)c->t_cnt.p);
-            else hipLaunchKernelGGL(kmc_compact_list_kernel<2>, dim3(grid), dim3(256), 0, c->stream, g, n_tab, (u64*)c->t_hi.p, (u64*)c->t_lo.p, (u64*)c->t_cnt.p);
+            if (c->KW == 1) hipLaunchKernelGGL(kmc_compact_list_kernel<1>, dim3(grid), dim3(256), 0, c->stream, g, n_tab, (u64*)nullptr, (u64*)c->t.lo.p, (u64*)c->t.cnt.p);
+            else hipLaunchKernelGGL(kmc_compact_list_kernel<2>, dim3(grid), dim3(256), 0, c->stream, g, n_tab, (u64*)c->t.hi.p, (u64*)c->t.lo.p, (u64*)c->t.cnt.p);
             HIPCHK(c, hipGetLastError());
         } else if (n_tab) {
             const int parity = c->fin_parity;
             c->fin_parity ^= 1;
             GTable g = gtable_of(c, c->tab);
             int grid = grid_for(c, c->tab.cap, 256);
-            if (c->KW == 1) hipLaunchKernelGGL(kmc_compact_kernel<1>, dim3(grid), dim3(256), 0, c->stream, g, (u64*)nullptr, (u64*)c->t_lo.p, (u64*)c->t_cnt.p, (u64*)nullptr, parity);
-            else hipLaunchKernelGGL(kmc_compact_kernel<2>, dim3(grid), dim3(256), 0, c->stream, g, (u64*)c->t_hi.p, (u64*)c->t_lo.p, (u64*)c->t_cnt.p, (u64*)nullptr, parity);
+            if (c->KW == 1) hipLaunchKernelGGL(kmc_compact_kernel<1>, dim3(grid), dim3(256), 0, c->stream, g, (u64*)nullptr, (u64*)c->t.lo.p, (u64*)c->t.cnt.p, (u64*)nullptr, parity);
+            else hipLaunchKernelGGL(kmc_compact_kernel<2>, dim3(grid), dim3(256), 0, c->stream, g, (u64*)c->t.hi.p, (u64*)c->t.lo.p, (u64*)c->t.cnt.p, (u64*)nullptr, parity);
             HIPCHK(c, hipGetLastError());
         }
         u64 off = n_tab;
         for (auto& r : c->runs) {
-            HIPCHK(c, hipMemcpyAsync((u64*)c->t_lo.p + off, r.lo, r.n * sizeof(u64), hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync((u64*)c->t_cnt.p + off, r.cnt, r.n * sizeof(u64), hipMemcpyDeviceToDevice, c->stream));
-            if (c->KW == 2) HIPCHK(c, hipMemcpyAsync((u64*)c->t_hi.p + off, r.hi, r.n * sizeof(u64), hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync((u64*)c->t.lo.p + off, r.lo, r.n * sizeof(u64), hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync((u64*)c->t.cnt.p + off, r.cnt, r.n * sizeof(u64), hipMemcpyDeviceToDevice, c->stream));
+            if (c->KW == 2) HIPCHK(c, hipMemcpyAsync((u64*)c->t.hi.p + off, r.hi, r.n * sizeof(u64), hipMemcpyDeviceToDevice, c->stream));
             off += r.n;
         }
-        u64* const khi[2] = {(u64*)c->t_hi.p, (u64*)c->o_hi.p};
-        u64* const klo[2] = {(u64*)c->t_lo.p, (u64*)c->o_lo.p};
-        u64* const kwt[2] = {(u64*)c->t_cnt.p, (u64*)c->o_cnt.p};
+        u64* const khi[2] = {(u64*)c->t.hi.p, (u64*)c->o.hi.p};
+        u64* const klo[2] = {(u64*)c->t.lo.p, (u64*)c->o.lo.p};
+        u64* const kwt[2] = {(u64*)c->t.cnt.p, (u64*)c->o.cnt.p};
         const size_t before = c->runs.size();
         rc = launch_begin(c);   // (the merge is part of what the path that left a large table costs)
         if (rc) return rc;
@@ -2110,633 +1892,6 @@ static int kmc_finalize_async_impl(kmc_ctx* c) {
     if (rc) return rc;
     c->async_fin = true;
     c->sorted_valid = false;   // (until somebody has looked)
-    return KMC_OK;
-}
-
-// What the calls that read the view check first: resolve_view, the count range (max_count != 0), that there is a view
-static int view_begin(kmc_ctx* c, const char* what, uint64_t min_count = 0, uint64_t max_count = 0) {
-    int rc = resolve_view(c);
-    if (rc) return rc;
-    if (max_count && min_count > max_count)
-        return fail(c, KMC_ERR_ARG, "%s: min_count %llu > max_count %llu", what, (unsigned long long)min_count, (unsigned long long)max_count);
-    if (!c->sorted_valid) return fail(c, KMC_ERR_STATE, "%s before kmc_finalize", what);
-    return KMC_OK;
-}
-
-// n entries of a table on the device into the caller's arrays (key_hi: optional, zeros for one-word keys)
-static int copy_to_host(kmc_ctx* c, const void* hi, const void* lo, const void* cnt, u64 n, uint64_t* key_hi, uint64_t* key_lo, uint64_t* count) {
-    HIPCHK(c, hipMemcpyAsync(key_lo, lo, n * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(count, cnt, n * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    if (key_hi) {
-        if (c->KW == 2) HIPCHK(c, hipMemcpyAsync(key_hi, hi, n * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-        else memset(key_hi, 0, n * sizeof(u64));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return KMC_OK;
-}
-
-static int kmc_export_impl(kmc_ctx* c, uint64_t* key_hi, uint64_t* key_lo, uint64_t* count, uint64_t cap) {
-    if (!c) return KMC_ERR_ARG;
-    { int rc = view_begin(c, "kmc_export"); if (rc) return rc; }
-    const u64 n = c->n_sorted;
-    if (cap < n) return fail(c, KMC_ERR_ARG, "export capacity %llu < %llu distinct keys", (unsigned long long)cap, (unsigned long long)n);
-    if (!n) return KMC_OK;
-    if (!key_lo || !count) return fail(c, KMC_ERR_ARG, "null buffer");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    return copy_to_host(c, c->v_hi, c->v_lo, c->v_cnt, n, key_hi, key_lo, count);
-}
-
-static int kmc_export_device_impl(kmc_ctx* c, const void** d_key_hi, const void** d_key_lo, const void** d_count, uint64_t* n_distinct) {
-    if (!c) return KMC_ERR_ARG;
-    { int rc = view_begin(c, "kmc_export_device"); if (rc) return rc; }
-    if (c->view_unsynced) {   // (see poll_fin: the finalize kernel told the host it was done before it ended)
-        HIPCHK(c, hipSetDevice(c->cfg.device));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->view_unsynced = false;
-    }
-    if (d_key_hi) *d_key_hi = c->KW == 2 ? c->v_hi : nullptr;
-    if (d_key_lo) *d_key_lo = c->v_lo;
-    if (d_count) *d_count = c->v_cnt;
-    if (n_distinct) *n_distinct = c->n_sorted;
-    return KMC_OK;
-}
-
-extern "C" uint32_t kmc_owner_of(uint64_t key_hi, uint64_t key_lo, uint32_t n_parts) { return kmc_owner(key_hi, key_lo, n_parts); }
-
-static int kmc_partition_device_impl(kmc_ctx* c, uint32_t n_parts, uint64_t* part_begin, const void** d_key_hi,
-                                    const void** d_key_lo, const void** d_count) {
-    if (!c || !n_parts || !part_begin) return KMC_ERR_ARG;
-    { int rc = view_begin(c, "kmc_partition_device"); if (rc) return rc; }
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    const u64 n = c->n_sorted;
-    const size_t nb = (size_t)std::max<u64>(n, 1) * sizeof(u64);
-    int rc;
-    DevBuf* need[] = {&c->p_lo, &c->p_cnt};
-    for (DevBuf* b : need) { rc = ensure(c, *b, nb); if (rc) return rc; }
-    rc = ensure(c, c->t_idx0, (size_t)std::max<u64>(n_parts, 1) * sizeof(u64)); if (rc) return rc;
-    if (c->KW == 2) { rc = ensure(c, c->p_hi, nb); if (rc) return rc; }
-    if (n_parts > 4096) return fail(c, KMC_ERR_ARG, "kmc_partition_device: more than 4096 parts");
-    std::vector<unsigned long long> cnt((size_t)n_parts, 0ull);
-    unsigned long long* d_cnt = (unsigned long long*)c->t_idx0.p;  // (scratch: n_parts counters, then cursors)
-    if (n) {
-        const int g2 = grid_for(c, n, 256);
-        const u64* vhi = c->KW == 2 ? c->v_hi : (const u64*)nullptr;
-        HIPCHK(c, hipMemsetAsync(d_cnt, 0, (size_t)n_parts * sizeof(unsigned long long), c->stream));
-        hipLaunchKernelGGL(kmc_owner_count_kernel, dim3(g2), dim3(256), (size_t)n_parts * sizeof(unsigned int), c->stream, vhi, c->v_lo, n, n_parts, d_cnt);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(cnt.data(), d_cnt, (size_t)n_parts * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    u64 pos = 0;
-    std::vector<unsigned long long> cursor((size_t)n_parts);
-    for (u32 p = 0; p < n_parts; ++p) { part_begin[p] = pos; cursor[p] = pos; pos += cnt[p]; }
-    part_begin[n_parts] = pos;
-    if (n) {
-        const u64* vhi = c->KW == 2 ? c->v_hi : (const u64*)nullptr;
-        HIPCHK(c, hipMemcpyAsync(d_cnt, cursor.data(), (size_t)n_parts * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(kmc_owner_scatter_kernel, dim3(grid_for(c, n, 256)), dim3(256), 0, c->stream, vhi, c->v_lo, c->v_cnt, n, n_parts, d_cnt,
-                           (u64*)c->p_hi.p, (u64*)c->p_lo.p, (u64*)c->p_cnt.p);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipStreamSynchronize(c->stream));  // (cursor[] is host memory of this call)
-    }
-    if (d_key_hi) *d_key_hi = c->KW == 2 ? c->p_hi.p : nullptr;
-    if (d_key_lo) *d_key_lo = c->p_lo.p;
-    if (d_count) *d_count = c->p_cnt.p;
-    return KMC_OK;
-}
-
-// ---- abundance histogram and count-range filter of the sorted view (kmc_spectrum.hip.h) ----
-static bool filter_is_identity(uint64_t min_count, uint64_t max_count) { return min_count <= 1 && max_count == 0; }
-
-static int kmc_histogram_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint32_t n_bins, uint64_t* hist, uint64_t* max_seen) {
-    if (!c) return KMC_ERR_ARG;
-    int rc = view_begin(c, "kmc_histogram", min_count, max_count);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    if (n_bins < 2 || n_bins > (1u << 24)) return fail(c, KMC_ERR_ARG, "kmc_histogram: n_bins %u outside 2..2^24", n_bins);
-    if (!hist) return fail(c, KMC_ERR_ARG, "kmc_histogram: null histogram");
-    const u64 n = c->n_sorted;
-    if (!n) {
-        memset(hist, 0, (size_t)n_bins * sizeof(u64));
-        if (max_seen) *max_seen = 0;
-        return KMC_OK;
-    }
-    rc = ensure(c, c->h_hist, ((size_t)n_bins + 1) * sizeof(u64));   // [hist | max]
-    if (rc) return rc;
-    kmc_ull* d = (kmc_ull*)c->h_hist.p;
-    HIPCHK(c, hipMemsetAsync(d, 0, ((size_t)n_bins + 1) * sizeof(u64), c->stream));
-    const u32 lds_bins = std::min<u32>(n_bins, KMC_SPEC_LDS_BINS);
-    const u32 head = ((uintptr_t)c->v_cnt & 15) ? 1u : 0u;
-    const u64 n_pairs = (n - head) / 2;
-    // 64 KiB of LDS: two workgroups per CU (160 KiB); smaller histograms four.  No more workgroups than there are
-    // pairs for: each one clears and flushes its whole LDS part.
-    const u64 per_cu = (u64)lds_bins * sizeof(u32) > 40960 ? 2 : 4;
-    const u64 grid = std::max<u64>(1, std::min<u64>((u64)c->n_cu * per_cu, (n_pairs + 2 * KMC_SPEC_THREADS - 1) / (2 * KMC_SPEC_THREADS)));
-    hipLaunchKernelGGL(kmc_histogram_kernel, dim3((u32)grid), dim3(KMC_SPEC_THREADS), (size_t)lds_bins * sizeof(u32), c->stream,
-                       c->v_cnt, n, head, (u64)min_count, max_count ? (u64)max_count : ~0ull, n_bins, lds_bins, d, d + n_bins);
-    HIPCHK(c, hipGetLastError());
-    u64 mx = 0;
-    HIPCHK(c, hipMemcpyAsync(hist, d, (size_t)n_bins * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(&mx, d + n_bins, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (max_seen) *max_seen = mx;
-    return KMC_OK;
-}
-
-// reduce half of the filter: kept entries per tile, their exclusive scan (f_tpos), n_kept and the sum of kept counts
-static int filter_count(kmc_ctx* c, u64 lo_c, u64 hi_c, u64* n_kept, u64* kept_total) {
-    const u64 n = c->n_sorted;
-    *n_kept = 0;
-    *kept_total = 0;
-    if (!n) return KMC_OK;
-    if (((uintptr_t)c->v_cnt | (uintptr_t)c->v_lo | (uintptr_t)(c->KW == 2 ? c->v_hi : nullptr)) & 15)
-        return fail(c, KMC_ERR_HIP, "internal error: sorted view not 16-byte aligned");
-    const u64 n_tiles = (n + KMC_FILT_TILE - 1) / KMC_FILT_TILE;   // (n < 2^32: at most 2^21 tiles)
-    const u32 nb = (u32)((n_tiles + KMC_SCAN_PER_BLOCK - 1) / KMC_SCAN_PER_BLOCK);
-    int rc = ensure(c, c->f_tile, (size_t)n_tiles * sizeof(u32)); if (rc) return rc;
-    rc = ensure(c, c->f_tpos, (size_t)n_tiles * sizeof(u32)); if (rc) return rc;
-    rc = ensure(c, c->f_bsum, ((size_t)nb + 2) * sizeof(u32)); if (rc) return rc;
-    rc = ensure(c, c->f_ctl, 2 * sizeof(u64)); if (rc) return rc;
-    u64* ctl = (u64*)c->f_ctl.p;   // [n_kept (u32 written by the scan, high half stays 0) | kept_total]
-    HIPCHK(c, hipMemsetAsync(ctl, 0, 2 * sizeof(u64), c->stream));
-    const u32 cgrid = (u32)std::min<u64>(n_tiles, (u64)c->n_cu * 8);
-    hipLaunchKernelGGL(kmc_filter_count_kernel, dim3(cgrid), dim3(KMC_FILT_THREADS), 0, c->stream, c->v_cnt, n, n_tiles, lo_c, hi_c,
-                       (u32*)c->f_tile.p, (kmc_ull*)(ctl + 1));
-    hipLaunchKernelGGL(kmc_scan_sums_kernel<0>, dim3(nb), dim3(256), 0, c->stream, (const void*)c->f_tile.p, (u32)n_tiles, (u32*)c->f_bsum.p);
-    hipLaunchKernelGGL(kmc_scan_top_kernel, dim3(1), dim3(1024), 0, c->stream, (u32*)c->f_bsum.p, nb, (u32*)ctl);
-    hipLaunchKernelGGL(kmc_scan_final_kernel<0>, dim3(nb), dim3(256), 0, c->stream, (const void*)c->f_tile.p, (u32)n_tiles,
-                       (const u32*)c->f_bsum.p, (u32*)c->f_tpos.p);
-    HIPCHK(c, hipGetLastError());
-    u64 h[2] = {0, 0};
-    HIPCHK(c, hipMemcpyAsync(h, ctl, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *n_kept = h[0];
-    *kept_total = h[1];
-    return KMC_OK;
-}
-
-// scatter half: the kept entries into f_hi / f_lo / f_cnt at tile base + wave offset + lane prefix (filter_count ran first);
-// finished when it returns (kmc_export_device's ordering contract)
-static int filter_scatter(kmc_ctx* c, u64 lo_c, u64 hi_c, u64 n_kept) {
-    const size_t nb = (size_t)std::max<u64>(n_kept, 1) * sizeof(u64);
-    int rc = ensure(c, c->f_lo, nb); if (rc) return rc;
-    rc = ensure(c, c->f_cnt, nb); if (rc) return rc;
-    if (c->KW == 2) { rc = ensure(c, c->f_hi, nb); if (rc) return rc; }
-    if (!n_kept) return KMC_OK;
-    const u64 n = c->n_sorted;
-    const u64 n_tiles = (n + KMC_FILT_TILE - 1) / KMC_FILT_TILE;
-    if (c->KW == 1)
-        hipLaunchKernelGGL(kmc_filter_scatter_kernel<1>, dim3((u32)n_tiles), dim3(KMC_FILT_THREADS), 0, c->stream, (const u64*)nullptr, c->v_lo, c->v_cnt,
-                           n, lo_c, hi_c, (const u32*)c->f_tpos.p, (u64*)nullptr, (u64*)c->f_lo.p, (u64*)c->f_cnt.p);
-    else
-        hipLaunchKernelGGL(kmc_filter_scatter_kernel<2>, dim3((u32)n_tiles), dim3(KMC_FILT_THREADS), 0, c->stream, c->v_hi, c->v_lo, c->v_cnt,
-                           n, lo_c, hi_c, (const u32*)c->f_tpos.p, (u64*)c->f_hi.p, (u64*)c->f_lo.p, (u64*)c->f_cnt.p);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return KMC_OK;
-}
-
-static int kmc_filter_device_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, const void** d_key_hi, const void** d_key_lo,
-                                  const void** d_count, uint64_t* n_kept, uint64_t* kept_total) {
-    if (!c) return KMC_ERR_ARG;
-    int rc = view_begin(c, "kmc_filter_device", min_count, max_count);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    if (filter_is_identity(min_count, max_count)) {   // keeps everything: the view itself, nothing launched
-        uint64_t nd = 0;
-        rc = kmc_export_device_impl(c, d_key_hi, d_key_lo, d_count, &nd);
-        if (rc) return rc;
-        if (n_kept) *n_kept = nd;
-        if (kept_total) *kept_total = nd ? c->st.n_kmers : 0;
-        return KMC_OK;
-    }
-    const u64 hi_c = max_count ? (u64)max_count : ~0ull;
-    u64 nk = 0, kt = 0;
-    rc = filter_count(c, min_count, hi_c, &nk, &kt);
-    if (rc) return rc;
-    rc = filter_scatter(c, min_count, hi_c, nk);
-    if (rc) return rc;
-    if (d_key_hi) *d_key_hi = c->KW == 2 ? c->f_hi.p : nullptr;
-    if (d_key_lo) *d_key_lo = c->f_lo.p;
-    if (d_count) *d_count = c->f_cnt.p;
-    if (n_kept) *n_kept = nk;
-    if (kept_total) *kept_total = kt;
-    return KMC_OK;
-}
-
-static int kmc_export_filtered_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t* key_hi, uint64_t* key_lo,
-                                    uint64_t* count, uint64_t cap, uint64_t* n_kept) {
-    if (!c) return KMC_ERR_ARG;
-    if (n_kept) *n_kept = 0;
-    int rc = view_begin(c, "kmc_export_filtered", min_count, max_count);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    const bool ident = filter_is_identity(min_count, max_count);
-    const u64 hi_c = max_count ? (u64)max_count : ~0ull;
-    u64 nk = c->n_sorted, kt = 0;
-    if (!ident) { rc = filter_count(c, min_count, hi_c, &nk, &kt); if (rc) return rc; }
-    if (n_kept) *n_kept = nk;
-    if (cap < nk) return fail(c, KMC_ERR_ARG, "kmc_export_filtered: capacity %llu < %llu kept keys", (unsigned long long)cap, (unsigned long long)nk);
-    if (!nk) return KMC_OK;
-    if (!key_lo || !count) return fail(c, KMC_ERR_ARG, "null buffer");
-    if (ident) return kmc_export_impl(c, key_hi, key_lo, count, cap);
-    rc = filter_scatter(c, min_count, hi_c, nk);
-    if (rc) return rc;
-    return copy_to_host(c, c->f_hi.p, c->f_lo.p, c->f_cnt.p, nk, key_hi, key_lo, count);
-}
-
-// ---- key lookups and per-read profiles against the sorted view (kmc_query.hip.h) ----
-// The view as the query kernels see it, its prefix index built first if this view has none yet (one launch; kept until the
-// ctx publishes another view).  An empty view gets an index of one empty bucket, so the kernels need no special case.
-static int query_view(kmc_ctx* c, const char* what, QView* out) {
-    const u64 n = c->n_sorted;
-    if (n >= (1ull << 32)) return fail(c, KMC_ERR_CAPACITY, "%s: a view of 2^32 keys or more cannot be indexed", what);
-    const int kb = 2 * c->klen;
-    const int P = kmc_query_index_bits(n, kb);
-    QView v;
-    v.hi = c->KW == 2 ? c->v_hi : nullptr;
-    v.lo = c->v_lo;
-    v.cnt = c->v_cnt;
-    v.n = n;
-    v.sh = kb - P;
-    v.max_lo = kb >= 64 ? ~0ull : (1ull << kb) - 1;
-    v.max_hi = kb <= 64 ? 0ull : (1ull << (kb - 64)) - 1;
-    if (c->q_gen != c->view_gen || !c->q_idx.p) {
-        int rc = ensure(c, c->q_idx, (((size_t)1 << P) + 2) * sizeof(u32));
-        if (rc) return rc;
-        v.idx = (u32*)c->q_idx.p;
-        const u32 grid = (u32)((n + 1 + 255) / 256);
-        if (c->KW == 1) hipLaunchKernelGGL(kmc_query_index_kernel<1>, dim3(grid), dim3(256), 0, c->stream, v, 1u << P);
-        else hipLaunchKernelGGL(kmc_query_index_kernel<2>, dim3(grid), dim3(256), 0, c->stream, v, 1u << P);
-        HIPCHK(c, hipGetLastError());
-        c->q_gen = c->view_gen;
-    }
-    v.idx = (u32*)c->q_idx.p;
-    *out = v;
-    return KMC_OK;
-}
-
-// the lookup launch (device arrays; d_hi may be null: high words zero)
-static int query_launch(kmc_ctx* c, const u64* d_hi, const u64* d_lo, u64 n_keys, u64* d_cnt) {
-    QView v;
-    int rc = query_view(c, "kmc_query", &v);
-    if (rc) return rc;
-    const int al16 = (((uintptr_t)d_hi | (uintptr_t)d_lo | (uintptr_t)d_cnt) & 15) == 0;
-    const u64 per_wg = (u64)KMC_Q_THREADS * KMC_Q_U;
-    const u64 grid = (n_keys + per_wg - 1) / per_wg;
-    if (grid > 0x7FFFFFFFull) return fail(c, KMC_ERR_ARG, "kmc_query: too many keys in one call");
-    if (c->KW == 1) hipLaunchKernelGGL(kmc_query_kernel<1>, dim3((u32)grid), dim3(KMC_Q_THREADS), 0, c->stream, v, d_hi, d_lo, n_keys, al16, d_cnt);
-    else hipLaunchKernelGGL(kmc_query_kernel<2>, dim3((u32)grid), dim3(KMC_Q_THREADS), 0, c->stream, v, d_hi, d_lo, n_keys, al16, d_cnt);
-    HIPCHK(c, hipGetLastError());
-    return KMC_OK;
-}
-
-static int kmc_query_device_impl(kmc_ctx* c, const void* d_key_hi, const void* d_key_lo, uint64_t n_keys, void* d_count) {
-    if (!c) return KMC_ERR_ARG;
-    int rc = view_begin(c, "kmc_query_device");
-    if (rc) return rc;
-    if (!n_keys) return KMC_OK;
-    if (!d_key_lo || !d_count) return fail(c, KMC_ERR_ARG, "kmc_query_device: null device pointer");
-    if ((((uintptr_t)d_key_hi | (uintptr_t)d_key_lo | (uintptr_t)d_count) & 7) != 0) return fail(c, KMC_ERR_ARG, "kmc_query_device: arrays must be 8-byte aligned");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    return query_launch(c, (const u64*)d_key_hi, (const u64*)d_key_lo, n_keys, (u64*)d_count);
-}
-
-static int kmc_query_impl(kmc_ctx* c, const uint64_t* key_hi, const uint64_t* key_lo, uint64_t n_keys, uint64_t* count) {
-    if (!c) return KMC_ERR_ARG;
-    int rc = view_begin(c, "kmc_query");
-    if (rc) return rc;
-    if (!n_keys) return KMC_OK;
-    if (!key_lo || !count) return fail(c, KMC_ERR_ARG, "kmc_query: null buffer");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    const size_t nb = (size_t)n_keys * sizeof(u64);
-    if ((rc = ensure(c, c->q_klo, nb)) || (rc = ensure(c, c->q_cnt, nb))) return rc;
-    if (key_hi && (rc = ensure(c, c->q_khi, nb))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->q_klo.p, key_lo, nb, hipMemcpyHostToDevice, c->stream));
-    if (key_hi) HIPCHK(c, hipMemcpyAsync(c->q_khi.p, key_hi, nb, hipMemcpyHostToDevice, c->stream));
-    rc = query_launch(c, key_hi ? (const u64*)c->q_khi.p : nullptr, (const u64*)c->q_klo.p, n_keys, (u64*)c->q_cnt.p);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(count, c->q_cnt.p, nb, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return KMC_OK;
-}
-
-// the profile launches (device arrays; either output may be null)
-static int profile_launch(kmc_ctx* c, const uint8_t* d_bases, const u64* d_offsets, u64 n_reads, u64 n_bases, u64 min_count,
-                          u32* d_win, u64* d_stats) {
-    QView v;
-    int rc = query_view(c, "kmc_profile", &v);
-    if (rc) return rc;
-    const int k = c->cfg.k;
-    const u64 n_words = n_reads * KMC_PROFILE_WORDS;
-    const u32 sgrid = (u32)((n_words + KMC_PROF_INIT_THREADS - 1) / KMC_PROF_INIT_THREADS);
-    if (d_stats) hipLaunchKernelGGL(kmc_profile_init_kernel, dim3(sgrid), dim3(KMC_PROF_INIT_THREADS), 0, c->stream, (kmc_qull*)d_stats, n_reads);
-    // windows END up to k - 1 positions past the batch: those (invalid) windows zero the last k - 1 slots
-    const u64 n_chunks = (n_bases + (u64)k - 1 + KMC_CHUNK - 1) / KMC_CHUNK;
-    if (n_chunks && (d_win || d_stats)) {
-        const u64 want_waves = (u64)c->n_cu * 16;   // four waves on each SIMD
-        const u64 cpw = std::min<u64>(64, std::max<u64>(1, (n_chunks + want_waves - 1) / want_waves));
-        const u64 waves = (n_chunks + cpw - 1) / cpw;
-        const u64 grid = (waves + KMC_Q_WAVES - 1) / KMC_Q_WAVES;
-        if (grid > 0x7FFFFFFFull) return fail(c, KMC_ERR_ARG, "kmc_profile: batch too large for one call");
-        const u64 thr = std::max<u64>(min_count, 1);
-#define KMC_PROF_LAUNCH(KW_, CANON_)                                                                                              \
-        hipLaunchKernelGGL((kmc_profile_kernel<KW_, CANON_>), dim3((u32)grid), dim3(KMC_Q_THREADS), 0, c->stream, d_bases, n_bases, \
-                           d_offsets, n_reads, k, n_chunks, cpw, v, thr, d_win, (kmc_qull*)d_stats)
-        if (c->KW == 1) { if (c->cfg.canonical) KMC_PROF_LAUNCH(1, true); else KMC_PROF_LAUNCH(1, false); }
-        else { if (c->cfg.canonical) KMC_PROF_LAUNCH(2, true); else KMC_PROF_LAUNCH(2, false); }
-#undef KMC_PROF_LAUNCH
-    }
-    if (d_stats) hipLaunchKernelGGL(kmc_profile_fix_kernel, dim3((u32)((n_reads + KMC_PROF_INIT_THREADS - 1) / KMC_PROF_INIT_THREADS)),
-                                    dim3(KMC_PROF_INIT_THREADS), 0, c->stream, (kmc_qull*)d_stats, n_reads);
-    HIPCHK(c, hipGetLastError());
-    return KMC_OK;
-}
-
-static int kmc_profile_device_impl(kmc_ctx* c, const void* d_bases, const void* d_offsets, uint64_t n_reads, uint64_t n_bases,
-                                   uint64_t min_count, void* d_window_count, void* d_read_stats) {
-    if (!c) return KMC_ERR_ARG;
-    if (c->cfg.mode != KMC_MODE_CONTIG) return fail(c, KMC_ERR_ARG, "kmc_profile_device: contiguous k-mers only (not KMC_MODE_LR)");
-    int rc = view_begin(c, "kmc_profile_device");
-    if (rc) return rc;
-    if (!n_reads) return KMC_OK;
-    if (!d_bases || !d_offsets) return fail(c, KMC_ERR_ARG, "kmc_profile_device: null device pointer");
-    if (((uintptr_t)d_bases & 15) != 0) return fail(c, KMC_ERR_ARG, "kmc_profile_device: d_bases must be 16-byte aligned");
-    if (((uintptr_t)d_offsets & 7) != 0 || ((uintptr_t)d_read_stats & 7) != 0 || ((uintptr_t)d_window_count & 3) != 0)
-        return fail(c, KMC_ERR_ARG, "kmc_profile_device: d_offsets / d_read_stats must be 8-byte, d_window_count 4-byte aligned");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    return profile_launch(c, (const uint8_t*)d_bases, (const u64*)d_offsets, n_reads, n_bases, min_count, (u32*)d_window_count, (u64*)d_read_stats);
-}
-
-static int kmc_profile_impl(kmc_ctx* c, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads, uint64_t min_count,
-                            uint32_t* window_count, uint64_t* read_stats) {
-    if (!c) return KMC_ERR_ARG;
-    if (c->cfg.mode != KMC_MODE_CONTIG) return fail(c, KMC_ERR_ARG, "kmc_profile: contiguous k-mers only (not KMC_MODE_LR)");
-    int rc = view_begin(c, "kmc_profile");
-    if (rc) return rc;
-    if (!n_reads) return KMC_OK;
-    if (!bases || !offsets) return fail(c, KMC_ERR_ARG, "kmc_profile: null buffer");
-    if (offsets[0] != 0) return fail(c, KMC_ERR_ARG, "kmc_profile: offsets[0] must be 0");
-    for (u64 i = 0; i < n_reads; ++i)
-        if (offsets[i + 1] < offsets[i]) return fail(c, KMC_ERR_ARG, "kmc_profile: offsets must be non-decreasing (read %llu)", (unsigned long long)i);
-    const u64 n_bases = offsets[n_reads];
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    const size_t sb = (size_t)n_reads * KMC_PROFILE_WORDS * sizeof(u64), wb = (size_t)n_bases * sizeof(u32);
-    if ((rc = ensure(c, c->q_bases, n_bases + 64)) || (rc = ensure(c, c->q_offs, (n_reads + 1) * sizeof(u64)))) return rc;
-    if (window_count && n_bases && (rc = ensure(c, c->q_win, wb))) return rc;
-    if (read_stats && (rc = ensure(c, c->q_stats, sb))) return rc;
-    if (n_bases) HIPCHK(c, hipMemcpyAsync(c->q_bases.p, bases, n_bases, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->q_offs.p, offsets, (n_reads + 1) * sizeof(u64), hipMemcpyHostToDevice, c->stream));
-    rc = profile_launch(c, (const uint8_t*)c->q_bases.p, (const u64*)c->q_offs.p, n_reads, n_bases, min_count,
-                        window_count && n_bases ? (u32*)c->q_win.p : nullptr, read_stats ? (u64*)c->q_stats.p : nullptr);
-    if (rc) return rc;
-    if (window_count && n_bases) HIPCHK(c, hipMemcpyAsync(window_count, c->q_win.p, wb, hipMemcpyDeviceToHost, c->stream));
-    if (read_stats) HIPCHK(c, hipMemcpyAsync(read_stats, c->q_stats.p, sb, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return KMC_OK;
-}
-
-// ---- two tables compared: summary and set operations over the sorted views of two contexts (kmc_setops.hip.h) ----
-// What every set-operation call checks first: arguments, that a and b count the same kind of key on one device, both views.
-// b's view is only read, on a's stream: b is synchronised first where kmc_export_device would do so.
-static int setop_begin(kmc_ctx* a, kmc_ctx* b, const char* what, int op, int count_mode, uint64_t min_a, uint64_t max_a,
-                       uint64_t min_b, uint64_t max_b) {
-    if (op < KMC_SETOP_INTERSECT || op > KMC_SETOP_SUBTRACT) return fail(a, KMC_ERR_ARG, "%s: unknown op %d", what, op);
-    if (count_mode < KMC_COUNT_LEFT || count_mode > KMC_COUNT_DIFF) return fail(a, KMC_ERR_ARG, "%s: unknown count_mode %d", what, count_mode);
-    if (max_a && min_a > max_a) return fail(a, KMC_ERR_ARG, "%s: min_a %llu > max_a %llu", what, (unsigned long long)min_a, (unsigned long long)max_a);
-    if (max_b && min_b > max_b) return fail(a, KMC_ERR_ARG, "%s: min_b %llu > max_b %llu", what, (unsigned long long)min_b, (unsigned long long)max_b);
-    if (a->cfg.device != b->cfg.device) return fail(a, KMC_ERR_ARG, "%s: the contexts differ in device (%d / %d)", what, a->cfg.device, b->cfg.device);
-    if (a->cfg.mode != b->cfg.mode) return fail(a, KMC_ERR_ARG, "%s: the contexts differ in mode (%d / %d)", what, a->cfg.mode, b->cfg.mode);
-    if (a->klen != b->klen || a->KW != b->KW) return fail(a, KMC_ERR_ARG, "%s: the contexts differ in k (%d / %d)", what, a->klen, b->klen);
-    if ((a->cfg.canonical != 0) != (b->cfg.canonical != 0))
-        return fail(a, KMC_ERR_ARG, "%s: the contexts differ in canonical (%d / %d)", what, a->cfg.canonical, b->cfg.canonical);
-    int rc = view_begin(a, what);
-    if (rc) return rc;
-    if (b != a) {
-        rc = view_begin(b, what);
-        if (rc) return rc;
-        if (b->view_unsynced) {
-            HIPCHK(b, hipSetDevice(b->cfg.device));
-            HIPCHK(b, hipStreamSynchronize(b->stream));
-            b->view_unsynced = false;
-        }
-    }
-    if (a->n_sorted + b->n_sorted >= (1ull << 32))
-        return fail(a, KMC_ERR_CAPACITY, "%s: the two views hold 2^32 keys or more together", what);
-    HIPCHK(a, hipSetDevice(a->cfg.device));
-    return KMC_OK;
-}
-
-static SoView so_view(const kmc_ctx* c, uint64_t min_c, uint64_t max_c) {
-    SoView v;
-    v.hi = c->KW == 2 ? c->v_hi : nullptr;
-    v.lo = c->v_lo;
-    v.cnt = c->v_cnt;
-    v.n = c->n_sorted;
-    v.min_c = min_c;
-    v.max_c = max_c ? (u64)max_c : ~0ull;
-    return v;
-}
-
-// Partition + one pass over both views.  pass 0: the summary; pass 1: the summary, the emitted keys per tile and their
-// scan (so_tpos).  h[0] = n_out (pass 1), h[1..8] = summary, h[9] = total_out.  Waits for the result.
-static int setop_reduce(kmc_ctx* a, kmc_ctx* b, int pass, int op, int count_mode, const SoView& A, const SoView& B, u64* h) {
-    memset(h, 0, (KMC_SO_WORDS + 1) * sizeof(u64));
-    const u64 nm = A.n + B.n;
-    if (!nm) return KMC_OK;
-    auto mis = [](const SoView& v) { return v.n && (((uintptr_t)v.hi | (uintptr_t)v.lo | (uintptr_t)v.cnt) & 15) != 0; };
-    if (mis(A) || mis(B)) return fail(a, KMC_ERR_HIP, "internal error: sorted view not 16-byte aligned");
-    const u32 n_tiles = (u32)((nm + KMC_SO_TILE - 1) / KMC_SO_TILE);
-    const u32 nb = (n_tiles + KMC_SCAN_PER_BLOCK - 1) / KMC_SCAN_PER_BLOCK;
-    int rc;
-    if ((rc = ensure(a, a->so_pa, ((size_t)n_tiles + 1) * sizeof(u32))) || (rc = ensure(a, a->so_pb, ((size_t)n_tiles + 1) * sizeof(u32))) ||
-        (rc = ensure(a, a->so_tile, (size_t)n_tiles * sizeof(u32))) || (rc = ensure(a, a->so_tpos, (size_t)n_tiles * sizeof(u32))) ||
-        (rc = ensure(a, a->so_bsum, ((size_t)nb + 2) * sizeof(u32))) || (rc = ensure(a, a->so_ctl, (KMC_SO_WORDS + 1) * sizeof(u64))))
-        return rc;
-    u64* ctl = (u64*)a->so_ctl.p;   // [n_out (u32 written by the scan, high half stays 0) | summary | total_out]
-    HIPCHK(a, hipMemsetAsync(ctl, 0, (KMC_SO_WORDS + 1) * sizeof(u64), a->stream));
-    u32 *pa = (u32*)a->so_pa.p, *pb = (u32*)a->so_pb.p, *tile = (u32*)a->so_tile.p;
-    const u32 pgrid = (n_tiles + 1 + 255) / 256;
-    const u32 grid = (u32)std::min<u64>(n_tiles, (u64)a->n_cu * 8);
-    (void)b;
-#define KMC_SO_REDUCE(KW_)                                                                                                              \
-    do {                                                                                                                                \
-        hipLaunchKernelGGL(kmc_setop_partition_kernel<KW_>, dim3(pgrid), dim3(256), 0, a->stream, A, B, n_tiles, pa, pb);               \
-        if (pass == 0)                                                                                                                  \
-            hipLaunchKernelGGL((kmc_setop_join_kernel<KW_, 0>), dim3(grid), dim3(KMC_SO_THREADS), 0, a->stream, A, B, op, count_mode, n_tiles, \
-                               (const u32*)pa, (const u32*)pb, (u32*)nullptr, (const u32*)nullptr, (kmc_soull*)(ctl + 1), (u64*)nullptr,   \
-                               (u64*)nullptr, (u64*)nullptr);                                                                           \
-        else                                                                                                                            \
-            hipLaunchKernelGGL((kmc_setop_join_kernel<KW_, 1>), dim3(grid), dim3(KMC_SO_THREADS), 0, a->stream, A, B, op, count_mode, n_tiles, \
-                               (const u32*)pa, (const u32*)pb, tile, (const u32*)nullptr, (kmc_soull*)(ctl + 1), (u64*)nullptr,            \
-                               (u64*)nullptr, (u64*)nullptr);                                                                           \
-    } while (0)
-    if (a->KW == 1) KMC_SO_REDUCE(1); else KMC_SO_REDUCE(2);
-#undef KMC_SO_REDUCE
-    if (pass == 1) {
-        hipLaunchKernelGGL(kmc_scan_sums_kernel<0>, dim3(nb), dim3(256), 0, a->stream, (const void*)tile, n_tiles, (u32*)a->so_bsum.p);
-        hipLaunchKernelGGL(kmc_scan_top_kernel, dim3(1), dim3(1024), 0, a->stream, (u32*)a->so_bsum.p, nb, (u32*)ctl);
-        hipLaunchKernelGGL(kmc_scan_final_kernel<0>, dim3(nb), dim3(256), 0, a->stream, (const void*)tile, n_tiles, (const u32*)a->so_bsum.p,
-                           (u32*)a->so_tpos.p);
-    }
-    HIPCHK(a, hipGetLastError());
-    HIPCHK(a, hipMemcpyAsync(h, ctl, (KMC_SO_WORDS + 1) * sizeof(u64), hipMemcpyDeviceToHost, a->stream));
-    HIPCHK(a, hipStreamSynchronize(a->stream));
-    return KMC_OK;
-}
-
-// scatter half (setop_reduce pass 1 ran first): the emitted entries into so_hi / so_lo / so_cnt; finished when it returns
-static int setop_scatter(kmc_ctx* a, int op, int count_mode, const SoView& A, const SoView& B, u64 n_out) {
-    const size_t bytes = (size_t)std::max<u64>(n_out, 1) * sizeof(u64);
-    int rc;
-    if ((rc = ensure(a, a->so_lo, bytes)) || (rc = ensure(a, a->so_cnt, bytes))) return rc;
-    if (a->KW == 2 && (rc = ensure(a, a->so_hi, bytes))) return rc;
-    if (!n_out) return KMC_OK;
-    const u32 n_tiles = (u32)((A.n + B.n + KMC_SO_TILE - 1) / KMC_SO_TILE);
-    const u32 grid = (u32)std::min<u64>(n_tiles, (u64)a->n_cu * 8);
-    if (a->KW == 1)
-        hipLaunchKernelGGL((kmc_setop_join_kernel<1, 2>), dim3(grid), dim3(KMC_SO_THREADS), 0, a->stream, A, B, op, count_mode, n_tiles,
-                           (const u32*)a->so_pa.p, (const u32*)a->so_pb.p, (u32*)nullptr, (const u32*)a->so_tpos.p, (kmc_soull*)nullptr,
-                           (u64*)nullptr, (u64*)a->so_lo.p, (u64*)a->so_cnt.p);
-    else
-        hipLaunchKernelGGL((kmc_setop_join_kernel<2, 2>), dim3(grid), dim3(KMC_SO_THREADS), 0, a->stream, A, B, op, count_mode, n_tiles,
-                           (const u32*)a->so_pa.p, (const u32*)a->so_pb.p, (u32*)nullptr, (const u32*)a->so_tpos.p, (kmc_soull*)nullptr,
-                           (u64*)a->so_hi.p, (u64*)a->so_lo.p, (u64*)a->so_cnt.p);
-    HIPCHK(a, hipGetLastError());
-    HIPCHK(a, hipStreamSynchronize(a->stream));
-    return KMC_OK;
-}
-
-static int kmc_compare_impl(kmc_ctx* a, kmc_ctx* b, uint64_t min_a, uint64_t max_a, uint64_t min_b, uint64_t max_b, uint64_t* summary) {
-    if (!a || !b) return a ? fail(a, KMC_ERR_ARG, "kmc_compare: null context") : KMC_ERR_ARG;
-    if (!summary) return fail(a, KMC_ERR_ARG, "kmc_compare: null summary");
-    int rc = setop_begin(a, b, "kmc_compare", KMC_SETOP_INTERSECT, KMC_COUNT_LEFT, min_a, max_a, min_b, max_b);
-    if (rc) return rc;
-    u64 h[KMC_SO_WORDS + 1];
-    rc = setop_reduce(a, b, 0, KMC_SETOP_INTERSECT, KMC_COUNT_LEFT, so_view(a, min_a, max_a), so_view(b, min_b, max_b), h);
-    if (rc) return rc;
-    memcpy(summary, h + 1, KMC_COMPARE_WORDS * sizeof(u64));
-    return KMC_OK;
-}
-
-static int kmc_setop_device_impl(kmc_ctx* a, kmc_ctx* b, int op, int count_mode, uint64_t min_a, uint64_t max_a, uint64_t min_b,
-                                 uint64_t max_b, const void** d_key_hi, const void** d_key_lo, const void** d_count, uint64_t* n_out,
-                                 uint64_t* total_out, uint64_t* summary) {
-    if (!a || !b) return a ? fail(a, KMC_ERR_ARG, "kmc_setop_device: null context") : KMC_ERR_ARG;
-    int rc = setop_begin(a, b, "kmc_setop_device", op, count_mode, min_a, max_a, min_b, max_b);
-    if (rc) return rc;
-    const SoView A = so_view(a, min_a, max_a), B = so_view(b, min_b, max_b);
-    u64 h[KMC_SO_WORDS + 1];
-    rc = setop_reduce(a, b, 1, op, count_mode, A, B, h);
-    if (rc) return rc;
-    rc = setop_scatter(a, op, count_mode, A, B, h[0]);
-    if (rc) return rc;
-    if (d_key_hi) *d_key_hi = a->KW == 2 ? a->so_hi.p : nullptr;
-    if (d_key_lo) *d_key_lo = a->so_lo.p;
-    if (d_count) *d_count = a->so_cnt.p;
-    if (n_out) *n_out = h[0];
-    if (total_out) *total_out = h[KMC_SO_WORDS];
-    if (summary) memcpy(summary, h + 1, KMC_COMPARE_WORDS * sizeof(u64));
-    return KMC_OK;
-}
-
-static int kmc_export_setop_impl(kmc_ctx* a, kmc_ctx* b, int op, int count_mode, uint64_t min_a, uint64_t max_a, uint64_t min_b,
-                                 uint64_t max_b, uint64_t* key_hi, uint64_t* key_lo, uint64_t* count, uint64_t cap, uint64_t* n_out) {
-    if (n_out) *n_out = 0;
-    if (!a || !b) return a ? fail(a, KMC_ERR_ARG, "kmc_export_setop: null context") : KMC_ERR_ARG;
-    int rc = setop_begin(a, b, "kmc_export_setop", op, count_mode, min_a, max_a, min_b, max_b);
-    if (rc) return rc;
-    const SoView A = so_view(a, min_a, max_a), B = so_view(b, min_b, max_b);
-    u64 h[KMC_SO_WORDS + 1];
-    rc = setop_reduce(a, b, 1, op, count_mode, A, B, h);
-    if (rc) return rc;
-    const u64 n = h[0];
-    if (n_out) *n_out = n;
-    if (cap < n) return fail(a, KMC_ERR_ARG, "kmc_export_setop: capacity %llu < %llu result keys", (unsigned long long)cap, (unsigned long long)n);
-    if (!n) return KMC_OK;
-    if (!key_lo || !count) return fail(a, KMC_ERR_ARG, "null buffer");
-    rc = setop_scatter(a, op, count_mode, A, B, n);
-    if (rc) return rc;
-    return copy_to_host(a, a->so_hi.p, a->so_lo.p, a->so_cnt.p, n, key_hi, key_lo, count);
-}
-
-// ---- the de Bruijn graph of the sorted view: neighbour masks, unitig ends, summary (kmc_graph.hip.h) ----
-// What both calls check first; on success the view is resolved and *n its size.
-static int graph_begin(kmc_ctx* c, const char* what, uint64_t min_count, uint64_t max_count) {
-    if (c->cfg.mode != KMC_MODE_CONTIG) return fail(c, KMC_ERR_ARG, "%s: contiguous k-mers only (not KMC_MODE_LR)", what);
-    int rc = view_begin(c, what, min_count, max_count);
-    if (rc) return rc;
-    if (c->n_sorted >= (1ull << 32)) return fail(c, KMC_ERR_CAPACITY, "%s: a view of 2^32 keys or more cannot be indexed", what);
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    return KMC_OK;
-}
-
-// adj of every view key into g_adj, the summary into h[KMC_GRAPH_WORDS]; finished when it returns (kmc_export_device's
-// ordering contract).  Shares the prefix index with the query calls (query_view).
-static int graph_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count, u64* h) {
-    memset(h, 0, KMC_GRAPH_WORDS * sizeof(u64));
-    const u64 n = c->n_sorted;
-    int rc;
-    if ((rc = ensure(c, c->g_adj, (size_t)std::max<u64>(n, 1) * sizeof(uint16_t))) || (rc = ensure(c, c->g_ctl, KMC_GRAPH_WORDS * sizeof(u64)))) return rc;
-    if (!n) return KMC_OK;
-    QView v;
-    rc = query_view(c, what, &v);
-    if (rc) return rc;
-    kmc_qull* ctl = (kmc_qull*)c->g_ctl.p;
-    HIPCHK(c, hipMemsetAsync(ctl, 0, KMC_GRAPH_WORDS * sizeof(u64), c->stream));
-    const u64 lo_c = std::max<u64>(min_count, 1), hi_c = max_count ? max_count : ~0ull;
-    const u64 want = (n + KMC_G_THREADS - 1) / KMC_G_THREADS;
-    const int k = c->klen;
-    // as many workgroups as are resident at once (they walk the view with a grid stride), fewer for a small view
-#define KMC_GRAPH_LAUNCH(KW_, CANON_)                                                                                           \
-    do {                                                                                                                        \
-        int per_cu = 0;                                                                                                         \
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kmc_graph_kernel<KW_, CANON_>, KMC_G_THREADS, 0) != hipSuccess || per_cu < 1) \
-            per_cu = 4;                                                                                                         \
-        const u32 grid = (u32)std::min<u64>(want, (u64)c->n_cu * (u64)per_cu);                                                  \
-        hipLaunchKernelGGL((kmc_graph_kernel<KW_, CANON_>), dim3(grid), dim3(KMC_G_THREADS), 0, c->stream, v, lo_c, hi_c, k,    \
-                           (uint16_t*)c->g_adj.p, ctl);                                                                         \
-    } while (0)
-    if (c->KW == 1) { if (c->cfg.canonical) KMC_GRAPH_LAUNCH(1, true); else KMC_GRAPH_LAUNCH(1, false); }
-    else { if (c->cfg.canonical) KMC_GRAPH_LAUNCH(2, true); else KMC_GRAPH_LAUNCH(2, false); }
-#undef KMC_GRAPH_LAUNCH
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(h, ctl, KMC_GRAPH_WORDS * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return KMC_OK;
-}
-
-static int kmc_graph_device_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, const void** d_adj, uint64_t* n_keys, uint64_t* summary) {
-    if (!c) return KMC_ERR_ARG;
-    int rc = graph_begin(c, "kmc_graph_device", min_count, max_count);
-    if (rc) return rc;
-    u64 h[KMC_GRAPH_WORDS];
-    rc = graph_run(c, "kmc_graph_device", min_count, max_count, h);
-    if (rc) return rc;
-    if (d_adj) *d_adj = c->g_adj.p;
-    if (n_keys) *n_keys = c->n_sorted;
-    if (summary) memcpy(summary, h, sizeof(h));
-    return KMC_OK;
-}
-
-static int kmc_graph_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, void* adj, uint64_t cap, uint64_t* n_keys, uint64_t* summary) {
-    if (n_keys) *n_keys = 0;
-    if (!c) return KMC_ERR_ARG;
-    int rc = graph_begin(c, "kmc_graph", min_count, max_count);
-    if (rc) return rc;
-    const u64 n = c->n_sorted;
-    if (n_keys) *n_keys = n;
-    const bool sizing = !adj && !cap;   // the summary alone / how large adj must be
-    if (!sizing && cap < n) return fail(c, KMC_ERR_ARG, "kmc_graph: capacity %llu < %llu keys of the view", (unsigned long long)cap, (unsigned long long)n);
-    if (!sizing && n && !adj) return fail(c, KMC_ERR_ARG, "kmc_graph: null buffer");
-    u64 h[KMC_GRAPH_WORDS];
-    rc = graph_run(c, "kmc_graph", min_count, max_count, h);
-    if (rc) return rc;
-    if (adj && n) {
-        HIPCHK(c, hipMemcpyAsync(adj, c->g_adj.p, (size_t)n * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    if (summary) memcpy(summary, h, sizeof(h));
     return KMC_OK;
 }
 
@@ -2937,13 +2092,13 @@ static int reduce_tables(kmc_ctx** ctxs, uint32_t n_ctx) {
             }
             HIPCHK(c0, hipSetDevice(dst->cfg.device));
             const size_t nb = (size_t)nd * sizeof(u64);
-            rc = ensure(dst, dst->rx_lo, nb); if (!rc) rc = ensure(dst, dst->rx_cnt, nb); if (!rc && dst->KW == 2) rc = ensure(dst, dst->rx_hi, nb);
+            rc = ensure_keys(dst, dst->rx, nd);
             if (rc) { if (dst != c0) memcpy(c0->err, dst->err, sizeof(c0->err)); return rc; }
-            hipError_t e = hipMemcpyPeerAsync(dst->rx_lo.p, dst->cfg.device, src->v_lo, src->cfg.device, nb, dst->stream);
-            if (e == hipSuccess) e = hipMemcpyPeerAsync(dst->rx_cnt.p, dst->cfg.device, src->v_cnt, src->cfg.device, nb, dst->stream);
-            if (e == hipSuccess && dst->KW == 2) e = hipMemcpyPeerAsync(dst->rx_hi.p, dst->cfg.device, src->v_hi, src->cfg.device, nb, dst->stream);
+            hipError_t e = hipMemcpyPeerAsync(dst->rx.lo.p, dst->cfg.device, src->v_lo, src->cfg.device, nb, dst->stream);
+            if (e == hipSuccess) e = hipMemcpyPeerAsync(dst->rx.cnt.p, dst->cfg.device, src->v_cnt, src->cfg.device, nb, dst->stream);
+            if (e == hipSuccess && dst->KW == 2) e = hipMemcpyPeerAsync(dst->rx.hi.p, dst->cfg.device, src->v_hi, src->cfg.device, nb, dst->stream);
             if (e != hipSuccess) return fail(c0, KMC_ERR_HIP, "peer copy from device %d failed: %s", src->cfg.device, hipGetErrorString(e));
-            rc = kmc_merge_pairs_device(dst, dst->KW == 2 ? dst->rx_hi.p : nullptr, dst->rx_lo.p, dst->rx_cnt.p, nd);
+            rc = kmc_merge_pairs_device(dst, dst->KW == 2 ? dst->rx.hi.p : nullptr, dst->rx.lo.p, dst->rx.cnt.p, nd);
             if (rc) { if (dst != c0) memcpy(c0->err, dst->err, sizeof(c0->err)); return rc; }
         }
         for (uint32_t i = 0; i + stride < n_ctx; i += 2 * stride) {  // the round's copies and merges have finished
@@ -3195,20 +2350,6 @@ extern "C" int kmc_debug_walk_stamps(uint64_t* out, uint32_t n_words) {
 }
 #endif
 // ---- the ABI proper: no C++ exception leaves the library (kmc.h: "no exception or abort crosses the ABI") ----
-namespace {
-template <typename F>
-int guarded(kmc_ctx* c, F&& f) noexcept {
-    try {
-        return f();
-    } catch (const std::bad_alloc&) {
-        return fail(c, KMC_ERR_NOMEM, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(c, KMC_ERR_HIP, "internal error: %s", e.what());
-    } catch (...) {
-        return fail(c, KMC_ERR_HIP, "internal error (unknown C++ exception)");
-    }
-}
-}  // namespace
 extern "C" int kmc_create(kmc_ctx** out, const kmc_config* cfg) {
     return guarded(nullptr, [&]() -> int { return kmc_create_impl(out, cfg); });
 }
@@ -3230,63 +2371,6 @@ extern "C" int kmc_finalize(kmc_ctx* c, uint64_t* n_distinct, uint64_t* n_total)
 }
 extern "C" int kmc_finalize_async(kmc_ctx* c) {
     return guarded(c, [&]() -> int { return kmc_finalize_async_impl(c); });
-}
-extern "C" int kmc_export(kmc_ctx* c, uint64_t* key_hi, uint64_t* key_lo, uint64_t* count, uint64_t cap) {
-    return guarded(c, [&]() -> int { return kmc_export_impl(c, key_hi, key_lo, count, cap); });
-}
-extern "C" int kmc_export_device(kmc_ctx* c, const void** d_key_hi, const void** d_key_lo, const void** d_count, uint64_t* n_distinct) {
-    return guarded(c, [&]() -> int { return kmc_export_device_impl(c, d_key_hi, d_key_lo, d_count, n_distinct); });
-}
-extern "C" int kmc_histogram(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint32_t n_bins, uint64_t* hist, uint64_t* max_seen) {
-    return guarded(c, [&]() -> int { return kmc_histogram_impl(c, min_count, max_count, n_bins, hist, max_seen); });
-}
-extern "C" int kmc_filter_device(kmc_ctx* c, uint64_t min_count, uint64_t max_count, const void** d_key_hi, const void** d_key_lo,
-                                 const void** d_count, uint64_t* n_kept, uint64_t* kept_total) {
-    return guarded(c, [&]() -> int { return kmc_filter_device_impl(c, min_count, max_count, d_key_hi, d_key_lo, d_count, n_kept, kept_total); });
-}
-extern "C" int kmc_export_filtered(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t* key_hi, uint64_t* key_lo,
-                                   uint64_t* count, uint64_t cap, uint64_t* n_kept) {
-    return guarded(c, [&]() -> int { return kmc_export_filtered_impl(c, min_count, max_count, key_hi, key_lo, count, cap, n_kept); });
-}
-extern "C" int kmc_query(kmc_ctx* c, const uint64_t* key_hi, const uint64_t* key_lo, uint64_t n_keys, uint64_t* count) {
-    return guarded(c, [&]() -> int { return kmc_query_impl(c, key_hi, key_lo, n_keys, count); });
-}
-extern "C" int kmc_query_device(kmc_ctx* c, const void* d_key_hi, const void* d_key_lo, uint64_t n_keys, void* d_count) {
-    return guarded(c, [&]() -> int { return kmc_query_device_impl(c, d_key_hi, d_key_lo, n_keys, d_count); });
-}
-extern "C" int kmc_profile(kmc_ctx* c, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads, uint64_t min_count,
-                           uint32_t* window_count, uint64_t* read_stats) {
-    return guarded(c, [&]() -> int { return kmc_profile_impl(c, bases, offsets, n_reads, min_count, window_count, read_stats); });
-}
-extern "C" int kmc_profile_device(kmc_ctx* c, const void* d_bases, const void* d_offsets, uint64_t n_reads, uint64_t n_bases,
-                                  uint64_t min_count, void* d_window_count, void* d_read_stats) {
-    return guarded(c, [&]() -> int { return kmc_profile_device_impl(c, d_bases, d_offsets, n_reads, n_bases, min_count, d_window_count, d_read_stats); });
-}
-extern "C" int kmc_compare(kmc_ctx* a, kmc_ctx* b, uint64_t min_a, uint64_t max_a, uint64_t min_b, uint64_t max_b, uint64_t* summary) {
-    return guarded(a, [&]() -> int { return kmc_compare_impl(a, b, min_a, max_a, min_b, max_b, summary); });
-}
-extern "C" int kmc_setop_device(kmc_ctx* a, kmc_ctx* b, int op, int count_mode, uint64_t min_a, uint64_t max_a, uint64_t min_b,
-                                uint64_t max_b, const void** d_key_hi, const void** d_key_lo, const void** d_count, uint64_t* n_out,
-                                uint64_t* total_out, uint64_t* summary) {
-    return guarded(a, [&]() -> int {
-        return kmc_setop_device_impl(a, b, op, count_mode, min_a, max_a, min_b, max_b, d_key_hi, d_key_lo, d_count, n_out, total_out, summary);
-    });
-}
-extern "C" int kmc_export_setop(kmc_ctx* a, kmc_ctx* b, int op, int count_mode, uint64_t min_a, uint64_t max_a, uint64_t min_b,
-                                uint64_t max_b, uint64_t* key_hi, uint64_t* key_lo, uint64_t* count, uint64_t cap, uint64_t* n_out) {
-    return guarded(a, [&]() -> int {
-        return kmc_export_setop_impl(a, b, op, count_mode, min_a, max_a, min_b, max_b, key_hi, key_lo, count, cap, n_out);
-    });
-}
-extern "C" int kmc_graph_device(kmc_ctx* c, uint64_t min_count, uint64_t max_count, const void** d_adj, uint64_t* n_keys, uint64_t* summary) {
-    return guarded(c, [&]() -> int { return kmc_graph_device_impl(c, min_count, max_count, d_adj, n_keys, summary); });
-}
-extern "C" int kmc_graph(kmc_ctx* c, uint64_t min_count, uint64_t max_count, void* adj, uint64_t cap, uint64_t* n_keys, uint64_t* summary) {
-    return guarded(c, [&]() -> int { return kmc_graph_impl(c, min_count, max_count, adj, cap, n_keys, summary); });
-}
-extern "C" int kmc_partition_device(kmc_ctx* c, uint32_t n_parts, uint64_t* part_begin, const void** d_key_hi,
-                                    const void** d_key_lo, const void** d_count) {
-    return guarded(c, [&]() -> int { return kmc_partition_device_impl(c, n_parts, part_begin, d_key_hi, d_key_lo, d_count); });
 }
 extern "C" int kmc_pack_slab_device(kmc_ctx* c, void* d_slab, uint64_t slab_entries) {
     return guarded(c, [&]() -> int { return kmc_pack_slab_device_impl(c, d_slab, slab_entries); });

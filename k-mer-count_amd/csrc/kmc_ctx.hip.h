@@ -1,0 +1,246 @@
+// kmc_ctx.hip.h -- what kmc_api.hip and kmc_views.hip share (internal, not installed): the context behind include/kmc.h,
+// its device buffers, error reporting, and what the view layer calls of the counting side.
+#pragma once
+#include <stdarg.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <algorithm>
+#include <deque>
+#include <exception>
+#include <new>
+#include <vector>
+
+#include "../../include/kmc.h"
+#include "kmc_device.hip.h"
+
+struct MsdCtl;   // kmc_msd.hip.h
+
+struct DevBuf { void* p = nullptr; size_t bytes = 0; };
+
+// a (key, count) table the library hands out or keeps for itself; hi is allocated for two-word keys only
+struct KeyBufs { DevBuf hi, lo, cnt; };
+
+struct Table {
+    u64 *hi = nullptr, *lo = nullptr, *cnt = nullptr, *mid = nullptr;  // (mid: three-word keys of the (k+16)-mer table, k >= 48)
+    u64 cap = 0;
+};
+
+struct kmc_ctx {
+    kmc_config cfg{};
+    int KW = 1;     // key words
+    int klen = 0;   // characters per key (k, or 54 in LR mode)
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    char err[512] = {0};
+
+    Table tab;
+    u64* d_counters = nullptr;      // KMC_CTR_N u64
+    u64* h_counters = nullptr;      // pinned mirror
+    u64* occ_list = nullptr;        // first KMC_OCC_LIST_CAP claimed slots (fast finalize of small tables)
+    u64 *occ_key_lo = nullptr, *occ_key_hi = nullptr;   // ... and their keys, dense (GTable::occ_key_*)
+    u32* fin_rank = nullptr;        // ticket counter of kmc_small_finalize_kernel (zero between launches)
+    u64* h_pub = nullptr;           // pinned, 2 * KMC_CTR_N: where kmc_small_finalize_kernel publishes its outcome + the counters.  Its
+                                    // own block: a kernel queued by kmc_finalize_async may publish after the host has reset or
+                                    // polled h_counters; poll_fin copies what the awaited launch published into h_counters
+    u64* d_mirror = nullptr;        // h_pub as the device sees it
+    u64* h_restore = nullptr;       // pinned: the counters to put back when a drained table is filled again (undrain)
+    // planner invariant (kmc_stats.n_planner_stale): every kernel queued OUTSIDE the count launches' own accounting that
+    // changes the table -- the (k+16)-mer unfold, merges -- bumps table_epoch; a poll records the epoch it has seen; a
+    // risky launch must save a table whose counters were polled at the current epoch
+    u64 table_epoch = 0, polled_epoch = 0;
+    u64 fin_seq = 0;                // number of the last kmc_small_finalize_kernel launch (the kernel publishes it with its result)
+    bool async_fin = false;         // kmc_finalize_async: a finalize is queued whose outcome the host has not looked at yet
+    bool drained = false;           // the last kmc_finalize emptied the table into the sorted view (kmc_small_finalize_kernel):
+                                    // table and device counters are as after kmc_reset, h_counters hold the true totals
+    u64 *spill_hi = nullptr, *spill_lo = nullptr, *spill_cnt = nullptr;
+    u64 spill_cap = 0;
+
+    // staging for host batches
+    DevBuf st_bases, st_offsets;
+    // sorted view
+    KeyBufs o, t, p;   // the small-table finalize's view / the merge sort's input / kmc_partition_device's result
+    DevBuf t_idx0;     // the partition's per-owner counters, then cursors
+    u64 n_sorted = 0;
+    bool sorted_valid = false;
+    // walk-kernel workspace
+    DevBuf walk_ws;
+    DevBuf vr_reads, vr_cnt, vr_pos;  // pieces of long reads for the walk kernel: [starts | ends], per-read counts and their scan
+    DevBuf walk_memo;  // two shared memo snapshots + dense counters, kept across launches (kmc_walk.hip.h)
+    int memo_parity = 0;  // snapshot slot the next walk launch reads
+    bool walk_ws_clean = false;  // workspace header + dense counters are zero (left so by kmc_walk_tail_kernel)
+    // KMC_ALGO_SORT: scratch for one sub-batch and the sorted (key,count) runs produced so far
+    DevBuf s_lo[2], s_hi[2];
+    // the walk kernel's log of steps that fell off its LDS memo (kmc_walk.hip.h SkLog, kmc_sklog.hip.h): per-workgroup spans,
+    // their fill counts, the 1024 hash bins the records are partitioned into, the bins' cursors
+    DevBuf lg_rec, lg_count, lg_bins, lg_cursor;
+    bool sklog_on = false;   // this data source overflows the LDS memo (a poll saw (k+16)-mers in the second-level table): log from now on
+    DevBuf a_hist, a_rand, a_ror;   // level-0 histogram rows / AND / OR words of the accumulated key ranges (kmc_extract.hip.h)
+    // KMC_ALGO_SORT accumulates: a batch only EXTRACTS its keys behind those of the batches before it (s_lo[0] /
+    // s_hi[0]); they are sorted into ONE run when somebody needs the result (kmc_finalize, a reduce) or when 2^31
+    // positions have come together.  (Sorting batch by batch left one run per batch -- 16 for a 1 GB file read in
+    // 64 MB chunks -- and kmc_finalize then merged them by sorting everything once more: 0.9 s for 760 M 63-mers.)
+    u64 acc_n = 0;           // key positions accumulated and not yet sorted
+    u64 acc_hint = 0;        // positions the caller expects in all (kmc_count_file: the file size); sizes the first allocation
+    DevBuf lr_rank;  // LR mode: rank of every position's 27-mer among the batch's distinct 27-mers
+    // hand-written MSD radix sort (kmc_msd.hip.h): per-range histograms, segment lists, terminals
+    DevBuf m_hist, m_stot, m_bsum, m_rmin, m_rmax, m_seg[2], m_first, m_cbase, m_skip, m_term, m_ord, m_bitmap, m_rank, m_nd, m_base, m_ctl, m_clist, m_w[2];
+    MsdCtl* h_ctl = nullptr;  // pinned mirror of the sort's device counters
+    struct Run { u64 *hi = nullptr, *lo = nullptr, *cnt = nullptr; u64 n = 0, cap = 0; u64 total = 0; bool total_known = false; };
+    std::vector<Run> runs;       // live runs
+    std::vector<Run> run_pool;   // buffers of dropped runs, reused (multi-GB hipMalloc/hipFree per batch is slow)
+    Run view_run;                // the merged, sorted view built by the last kmc_finalize (table entries + runs)
+    const u64 *v_hi = nullptr, *v_lo = nullptr, *v_cnt = nullptr;  // the sorted view of the last finalize
+    bool msd_dup_heavy = false;  // the last large unweighted sort collapsed its keys more than fourfold (leaf size of two-word sorts)
+    bool prefer_sort = false;  // AUTO: the data source proved high-cardinality  // per-workgroup memo slots, kept across launches (kmc_walk.hip.h)
+
+    // hipEvent pairs bracketing every count-kernel launch, batch by batch: a batch's events are read once they have
+    // completed (harvest_timing), possibly several batches later -- a caller that never synchronises this ctx (the
+    // multi-GPU step: count, pack, reset) still gets every batch's kernel time into kernel_ms_lifetime
+    struct TimedBatch { std::vector<hipEvent_t> ev; int algo = 0; u64 n_bases = 0; u32 count_launches = 0; };
+    std::deque<TimedBatch> tb;                // batches whose events have not been read yet (front = oldest)
+    // KMC_ALGO_AUTO chooses by MEASURED cost: kernel milliseconds per base of this ctx's recent walk-path batches (walk
+    // kernel + (k+16)-mer unfold + the table merge at finalize) and sort-path batches (< 0: not measured yet)
+    double walk_ms_per_base = -1.0, sort_ms_per_base = -1.0;
+    bool sort_by_cost = false;   // AUTO: the last comparison of the two rates said "sort" (prefer_sort: structural -- the source overflowed everything)
+    std::vector<hipEvent_t> ev_free;          // events to reuse
+    kmc_stats st{};
+    int fin_parity = 0;    // which OUT/SUM counter pair the next kmc_finalize uses
+    u64 fin_hint = 0;      // table entries at the last kmc_finalize (sizes the next speculative small-table finalize)
+    // The rank sort of kmc_small_finalize_kernel is quadratic: 16 us for 1 k keys, 0.24 ms for 24 k, 0.8 ms for 68 k (measured).  The
+    // weighted radix sort that larger tables take costs 0.25-0.3 ms at that size (a dozen small launches, two polls): tables
+    // that were larger than this at the last finalize go there directly.  (KMC_FIN_SMALL_MAX overrides: the parity test of
+    // the kernel's size boundaries runs it up to its limit, KMC_FIN_KERNEL_MAX.)
+    u64 fin_small_max = 40000;
+    bool view_unsynced = false;   // the last small-table finalize was waited for through the mirror, not the stream (poll_fin)
+    bool batch_pending = false;  // a COUNT kernel (unknown number of new keys) is queued since the last poll
+    u64 unpolled_adds = 0;       // upper bound of keys added by merge kernels since the last poll
+    bool walk_overflowed = false;  // the last WALK/STREAM launches counted >5% of their k-mers with global atomics
+                                   // (memo / LDS table overflow = high-cardinality input)
+    u64 direct_seen = 0, kmers_seen = 0;
+    bool pending = false;  // a batch has been queued since the last counter poll
+    double rho_last = 0.0; // same, over the most recent sub-batch
+    double rho_hist = -1.0; // new keys per k-mer of the previous batch as a whole (< 0: no history); survives kmc_reset
+    bool b_open = false; double b_rho_max = 0.0; u64 b_occ0 = 0, b_kmers = 0;  // the batch whose last launch is still unobserved
+    double rho_max = 0.0;  // largest observed (new distinct) / (k-mers) over a sub-batch
+    int n_cu = 256;
+    // A launch sized by a prediction (more k-mers than the table and spill area absorb for certain) is
+    // "risky": the table is saved first, and if the spill area overflows the table is put back and the
+    // rest of the batch is counted by the sort path, which needs no table (recover_overflow).
+    struct Risky {
+        bool armed = false;
+        int mode = 0;                 // 1: entries listed in occ_list; 2: whole table copied
+        bool empty = false;           // mode 1 and the table held nothing: there is nothing to save (no kernel)
+        const uint8_t* d_bases = nullptr; const u64* d_offsets = nullptr; u64 n_reads = 0, n_bases = 0;
+        u64 base_from = 0;            // first base position the risky launch covers ...
+        const u64* d_from = nullptr;  // ... or where to read it on the device (end of the last piece walked before)
+        u64 ctr[KMC_CTR_N] = {0};     // the device counters before the launch
+    } risky;
+    DevBuf snap_hi, snap_lo, snap_cnt, snap_n, snap_occ;
+    // second-level memo of the walk kernel: (k+16)-mer table (kmc_walk.hip.h); three key words for k >= 48
+    Table sk;
+    u64* d_sk_counters = nullptr;
+    u64* h_sk_counters = nullptr;   // pinned mirror (valid after a poll)
+    u64 *sk_spill_hi = nullptr, *sk_spill_lo = nullptr, *sk_spill_cnt = nullptr, *sk_spill_mid = nullptr;
+    u64 sk_spill_cap = 0;
+    u64* sk_occ = nullptr;          // list of its claimed slots (what the unfold kernel walks)
+    bool recovered = false;  // the last poll found an overflow and recovered: the batch in flight is complete
+    bool sk_dirty = false;   // walk launches since the last unfold of the (k+16)-mer table
+    bool sk_fixed = false;   // its size was set by KMC_SK_SLOTS (tests): never re-allocated
+    bool sk_grow = false;    // a poll found it more than half full: re-allocate larger when it is next empty
+    KeyBufs rx;  // receive buffers of the one-process multi-GPU reduce (a peer's sorted table)
+    // kmc_filter_device's result (its own buffers: a filter leaves the view and a partition the caller holds alone);
+    // kmc_histogram's device histogram + max
+    KeyBufs f;
+    DevBuf h_hist;
+    // scratch of a compaction (compact_plan): kept entries per tile, their scan, its block sums, the control words.  The
+    // filter and the set operations share it: both are done with it when their call returns.
+    DevBuf c_tile, c_tpos, c_bsum, c_ctl;
+    // kmc_query / kmc_profile (kmc_query.hip.h): the prefix index of the view numbered q_gen (view_gen counts the views this
+    // ctx has produced: every place that publishes one bumps it, so an index can never outlive its view), staging of the
+    // host forms: query keys and counts, a batch's bases and offsets, its window counts and read statistics
+    u64 view_gen = 0, q_gen = ~0ull;
+    DevBuf q_idx, q_khi, q_klo, q_cnt, q_bases, q_offs, q_win, q_stats;
+    // kmc_compare / kmc_setop_device (kmc_setops.hip.h), on the ctx given as `a`: the result, the merge-path partition of the
+    // two views (first A / B entry of every tile)
+    KeyBufs so;
+    DevBuf so_pa, so_pb;
+    // kmc_graph / kmc_graph_device (kmc_graph.hip.h): one 16-bit word per key of the view, the eight summary words
+    DevBuf g_adj, g_ctl;
+};
+
+#pragma GCC visibility push(hidden)   // what follows is shared between the translation units, never exported
+
+extern thread_local char g_create_err[512];   // kmc_last_error(nullptr): why kmc_create failed (kmc_api.hip)
+
+inline int fail(kmc_ctx* c, int code, const char* fmt, ...) {
+    char buf[512] = {0};
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    memcpy(c ? c->err : g_create_err, buf, sizeof(buf));
+    return code;
+}
+
+#define HIPCHK(c, call)                                                                       \
+    do {                                                                                      \
+        hipError_t e__ = (call);                                                              \
+        if (e__ != hipSuccess)                                                                \
+            return fail((c), e__ == hipErrorOutOfMemory ? KMC_ERR_NOMEM : KMC_ERR_HIP, "%s: %s", #call, hipGetErrorString(e__)); \
+    } while (0)
+
+inline int ensure(kmc_ctx* c, DevBuf& b, size_t bytes) {
+    if (b.bytes >= bytes && b.p) return KMC_OK;
+    if (b.p) { HIPCHK(c, hipFree(b.p)); b.p = nullptr; b.bytes = 0; }
+    size_t want = bytes + bytes / 8 + 256;
+    HIPCHK(c, hipMalloc(&b.p, want));
+    b.bytes = want;
+    return KMC_OK;
+}
+
+inline void free_buf(DevBuf& b) {
+    if (b.p) (void)hipFree(b.p);
+    b = DevBuf{};
+}
+
+// room for n entries (one at least), the high words for two-word keys only
+inline int ensure_keys(kmc_ctx* c, KeyBufs& k, u64 n) {
+    const size_t nb = (size_t)std::max<u64>(n, 1) * sizeof(u64);
+    int rc = ensure(c, k.lo, nb);
+    if (!rc) rc = ensure(c, k.cnt, nb);
+    if (!rc && c->KW == 2) rc = ensure(c, k.hi, nb);
+    return rc;
+}
+
+// the device pointers as the ABI returns them (each optional; no high words for one-word keys)
+inline void publish_keys(const kmc_ctx* c, const KeyBufs& k, const void** d_key_hi, const void** d_key_lo, const void** d_count) {
+    if (d_key_hi) *d_key_hi = c->KW == 2 ? k.hi.p : nullptr;
+    if (d_key_lo) *d_key_lo = k.lo.p;
+    if (d_count) *d_count = k.cnt.p;
+}
+
+inline void free_keys(KeyBufs& k) { free_buf(k.hi); free_buf(k.lo); free_buf(k.cnt); }
+
+inline int grid_for(const kmc_ctx* c, u64 n, int threads) {
+    return (int)std::max<u64>(1, std::min<u64>((n + threads - 1) / threads, (u64)c->n_cu * 8));
+}
+
+// What the calls that read the view do first: a finalize queued by kmc_finalize_async counts as one (kmc_api.hip)
+int resolve_view(kmc_ctx* c);
+
+// no C++ exception leaves the library (kmc.h: "no exception or abort crosses the ABI")
+template <typename F>
+int guarded(kmc_ctx* c, F&& f) noexcept {
+    try {
+        return f();
+    } catch (const std::bad_alloc&) {
+        return fail(c, KMC_ERR_NOMEM, "out of host memory");
+    } catch (const std::exception& e) {
+        return fail(c, KMC_ERR_HIP, "internal error: %s", e.what());
+    } catch (...) {
+        return fail(c, KMC_ERR_HIP, "internal error (unknown C++ exception)");
+    }
+}
+
+#pragma GCC visibility pop

@@ -10,6 +10,11 @@
 
 typedef uint32_t u32;
 typedef uint64_t u64;
+typedef unsigned long long kmc_ull;   // what the 64-bit atomics take (u64 is unsigned long)
+typedef kmc_ull kmc_ull2 __attribute__((ext_vector_type(2)));
+
+// a sorted (key, count) table in HBM as kernels and host code pass it around; hi is null for one-word keys
+struct KView { const u64 *hi, *lo, *cnt; u64 n; };
 
 #define KMC_EMPTY64 (~0ull)
 #define KMC_LOCKED64 (~0ull - 1ull)
@@ -245,6 +250,16 @@ __device__ __forceinline__ void revcomp_key(u64 hi, u64 lo, int k, u64& rhi, u64
 
 __device__ __forceinline__ bool key_less(u64 ahi, u64 alo, u64 bhi, u64 blo) {
     return ahi < bhi || (ahi == bhi && alo < blo);
+}
+__device__ __forceinline__ bool key_equal(u64 ahi, u64 alo, u64 bhi, u64 blo) { return ahi == bhi && alo == blo; }
+
+// owner of a key for the multi-GPU all-to-all (kmc_owner_of is this function on the host)
+__host__ __device__ inline u32 kmc_owner(u64 hi, u64 lo, u32 n_parts) {
+    u64 z = lo ^ (hi * 0x9E3779B97F4A7C15ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return (u32)((z >> 32) * (u64)n_parts >> 32);
 }
 
 __device__ __forceinline__ u64 wave_sum_u64(u64 v) {

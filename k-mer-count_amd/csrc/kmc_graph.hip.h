@@ -50,7 +50,7 @@ __device__ __forceinline__ void g_top_or(u64& hi, u64& lo, int tb, u64 c) {
 // One lane, one key of the view per trip.  adj[i] belongs to view row i.  summary: KMC_G_WORDS words, zero before the launch.
 template <int KW, bool CANON>
 __global__ __launch_bounds__(KMC_G_THREADS)
-void kmc_graph_kernel(QView v, u64 lo_c, u64 hi_c, int k, uint16_t* __restrict__ adj, kmc_qull* __restrict__ summary) {
+void kmc_graph_kernel(QView v, u64 lo_c, u64 hi_c, int k, uint16_t* __restrict__ adj, kmc_ull* __restrict__ summary) {
     const int lane = threadIdx.x & 63;
     const u64 wave = (u64)blockIdx.x * KMC_G_WAVES + (threadIdx.x >> 6);
     const u64 stride = (u64)gridDim.x * KMC_G_WAVES * 64;
@@ -145,6 +145,6 @@ void kmc_graph_kernel(QView v, u64 lo_c, u64 hi_c, int k, uint16_t* __restrict__
 #pragma unroll
     for (int w = 0; w < KMC_G_WORDS; ++w) {
         const u64 s = wave_sum_u64((u64)acc[w]);
-        if (lane == 0 && s) atomicAdd(&summary[w], (kmc_qull)s);
+        if (lane == 0 && s) atomicAdd(&summary[w], (kmc_ull)s);
     }
 }

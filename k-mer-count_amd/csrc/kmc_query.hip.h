@@ -21,18 +21,12 @@
 #define KMC_Q_MAX_P 27            // index of at most 2^27 + 1 u32 entries (512 MiB), reached at 2^28 keys
 #define KMC_PROF_INIT_THREADS 256
 
-typedef unsigned long long kmc_qull;
-typedef kmc_qull kmc_qull2 __attribute__((ext_vector_type(2)));
 typedef u32 kmc_u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
 
 // The sorted view and its index as the kernels see them.  sh = key bits - P; a key above (max_hi, max_lo) -- more than
 // the ctx's key bits -- is absent without a look (its prefix would lie outside the index).
-struct QView {
-    const u64* hi;
-    const u64* lo;
-    const u64* cnt;
+struct QView : KView {
     u32* idx;
-    u64 n;
     int sh;
     u64 max_hi, max_lo;
 };
@@ -140,10 +134,10 @@ void kmc_query_kernel(QView v, const u64* __restrict__ key_hi, const u64* __rest
 #pragma unroll
     for (int r = 0; r < KMC_Q_U / 2; ++r) {
         const u64 e = base + 2 * ((u64)r * 64 + lane);
-        kmc_qull2 l = {0ull, 0ull}, h = {0ull, 0ull};
+        kmc_ull2 l = {0ull, 0ull}, h = {0ull, 0ull};
         if (al16 && e + 1 < n_keys) {
-            l = *reinterpret_cast<const kmc_qull2*>(key_lo + e);
-            if (key_hi) h = *reinterpret_cast<const kmc_qull2*>(key_hi + e);
+            l = *reinterpret_cast<const kmc_ull2*>(key_lo + e);
+            if (key_hi) h = *reinterpret_cast<const kmc_ull2*>(key_hi + e);
         } else {
             if (e < n_keys) { l.x = key_lo[e]; if (key_hi) h.x = key_hi[e]; }
             if (e + 1 < n_keys) { l.y = key_lo[e + 1]; if (key_hi) h.y = key_hi[e + 1]; }
@@ -157,8 +151,8 @@ void kmc_query_kernel(QView v, const u64* __restrict__ key_hi, const u64* __rest
     for (int r = 0; r < KMC_Q_U / 2; ++r) {
         const u64 e = base + 2 * ((u64)r * 64 + lane);
         if (al16 && e + 1 < n_keys) {
-            const kmc_qull2 o = {out[2 * r], out[2 * r + 1]};
-            *reinterpret_cast<kmc_qull2*>(count + e) = o;
+            const kmc_ull2 o = {out[2 * r], out[2 * r + 1]};
+            *reinterpret_cast<kmc_ull2*>(count + e) = o;
         } else {
             if (e < n_keys) count[e] = out[2 * r];
             if (e + 1 < n_keys) count[e + 1] = out[2 * r + 1];
@@ -171,12 +165,12 @@ void kmc_query_kernel(QView v, const u64* __restrict__ key_hi, const u64* __rest
 // that atomicMin works, and kmc_profile_fix_kernel puts 0 there for reads without a valid window.
 #define KMC_PROFILE_STAT_WORDS 5
 __global__ __launch_bounds__(KMC_PROF_INIT_THREADS)
-void kmc_profile_init_kernel(kmc_qull* __restrict__ rs, u64 n_reads) {
+void kmc_profile_init_kernel(kmc_ull* __restrict__ rs, u64 n_reads) {
     const u64 i = (u64)blockIdx.x * KMC_PROF_INIT_THREADS + threadIdx.x;
     if (i < n_reads * KMC_PROFILE_STAT_WORDS) rs[i] = (i % KMC_PROFILE_STAT_WORDS) == 2 ? ~0ull : 0ull;
 }
 __global__ __launch_bounds__(KMC_PROF_INIT_THREADS)
-void kmc_profile_fix_kernel(kmc_qull* __restrict__ rs, u64 n_reads) {
+void kmc_profile_fix_kernel(kmc_ull* __restrict__ rs, u64 n_reads) {
     const u64 r = (u64)blockIdx.x * KMC_PROF_INIT_THREADS + threadIdx.x;
     if (r < n_reads && rs[r * KMC_PROFILE_STAT_WORDS] == 0) rs[r * KMC_PROFILE_STAT_WORDS + 2] = 0;
 }
@@ -193,14 +187,14 @@ struct ProfAcc {
         nv += o.nv; np += o.np;
         mn = o.mn < mn ? o.mn : mn; mx = o.mx > mx ? o.mx : mx; sm += o.sm;
     }
-    __device__ __forceinline__ void flush(kmc_qull* __restrict__ rs, u64 rid) const {
+    __device__ __forceinline__ void flush(kmc_ull* __restrict__ rs, u64 rid) const {
         if (!nv) return;
-        kmc_qull* row = rs + rid * KMC_PROFILE_STAT_WORDS;
-        atomicAdd(&row[0], (kmc_qull)nv);
-        if (np) atomicAdd(&row[1], (kmc_qull)np);
-        atomicMin(&row[2], (kmc_qull)mn);
-        if (mx) atomicMax(&row[3], (kmc_qull)mx);
-        if (sm) atomicAdd(&row[4], (kmc_qull)sm);
+        kmc_ull* row = rs + rid * KMC_PROFILE_STAT_WORDS;
+        atomicAdd(&row[0], (kmc_ull)nv);
+        if (np) atomicAdd(&row[1], (kmc_ull)np);
+        atomicMin(&row[2], (kmc_ull)mn);
+        if (mx) atomicMax(&row[3], (kmc_ull)mx);
+        if (sm) atomicAdd(&row[4], (kmc_ull)sm);
     }
 };
 
@@ -223,7 +217,7 @@ template <int KW, bool CANON>
 __global__ __launch_bounds__(KMC_Q_THREADS)
 void kmc_profile_kernel(const uint8_t* __restrict__ bases, u64 n_bases, const u64* __restrict__ offsets, u64 n_reads, int k,
                         u64 n_chunks, u64 chunks_per_wave, QView v, u64 thr, u32* __restrict__ window_count,
-                        kmc_qull* __restrict__ read_stats) {
+                        kmc_ull* __restrict__ read_stats) {
     constexpr int NW = 2 * KW + 1;  // window words: own + 2*KW preceding lanes
     __shared__ ProfLds L;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;

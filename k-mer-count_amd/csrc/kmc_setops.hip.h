@@ -14,7 +14,7 @@
 // KMC_SO_ITEMS elements in LDS (same tie rule, same fix) and merges them serially.
 //
 //   kmc_setop_join_kernel<KW, 0>  compare: the summary only; wave reduction, one set of atomics per workgroup
-//   kmc_setop_join_kernel<KW, 1>  count:   the same plus emitted keys per tile (scanned by kmc_msd.hip.h's kmc_scan_*) and sum of r
+//   kmc_setop_join_kernel<KW, 1>  count:   the same plus emitted keys per tile (scanned by kmc_scan.hip.h) and sum of r
 //   kmc_setop_join_kernel<KW, 2>  scatter: emitted entries compacted in LDS, copied out coalesced at the tile's base
 #pragma once
 #include "kmc_device.hip.h"
@@ -25,24 +25,15 @@
 #define KMC_SO_CAP (KMC_SO_TILE + 2)                  // LDS entries: TILE + 1 at most, kept even
 #define KMC_SO_WORDS 9                                // device accumulators: the 8 summary words, then sum of r (total_out)
 
-typedef unsigned long long kmc_soull;
-typedef kmc_soull kmc_soull2 __attribute__((ext_vector_type(2)));
-
-struct SoView {
-    const u64 *hi, *lo, *cnt;   // hi: two-word keys only
-    u64 n;
-    u64 min_c, max_c;           // count range (max_c: ~0 for "no upper bound")
-};
+struct SoView : KView { u64 min_c, max_c; };   // count range (max_c: ~0 for "no upper bound")
 
 template <int KW>
 __device__ __forceinline__ bool so_less(u64 h1, u64 l1, u64 h2, u64 l2) {
-    if (KW == 2) return h1 < h2 || (h1 == h2 && l1 < l2);
-    return l1 < l2;
+    return KW == 2 ? key_less(h1, l1, h2, l2) : l1 < l2;   // (one-word keys: the high words are not looked at)
 }
 template <int KW>
 __device__ __forceinline__ bool so_equal(u64 h1, u64 l1, u64 h2, u64 l2) {
-    if (KW == 2) return h1 == h2 && l1 == l2;
-    return l1 == l2;
+    return KW == 2 ? key_equal(h1, l1, h2, l2) : l1 == l2;
 }
 
 // Where diagonal d of the merged sequence crosses A (na keys) and B (nb keys): ia + ib == d, A first on equal keys.
@@ -81,8 +72,8 @@ __device__ __forceinline__ void so_stage(const u64* __restrict__ src, u64 n, u32
     const u32 e0 = s & ~1u, n_pairs = (s + len - e0 + 1) >> 1;
     for (u32 p = tid; p < n_pairs; p += KMC_SO_THREADS) {
         const u32 e = e0 + 2 * p;
-        kmc_soull2 v = {0ull, 0ull};
-        if ((u64)e + 1 < n) v = *reinterpret_cast<const kmc_soull2*>(src + e);
+        kmc_ull2 v = {0ull, 0ull};
+        if ((u64)e + 1 < n) v = *reinterpret_cast<const kmc_ull2*>(src + e);
         else v.x = src[e];
         if (e >= s) dst[e - s] = v.x;
         if (e + 1 < s + len) dst[e + 1 - s] = v.y;
@@ -151,7 +142,7 @@ __device__ __forceinline__ u32 so_merge(const u64* khi, const u64* klo, const u6
 template <int KW, int PASS>
 __global__ __launch_bounds__(KMC_SO_THREADS)
 void kmc_setop_join_kernel(SoView A, SoView B, int op, int mode, u32 n_tiles, const u32* __restrict__ pa, const u32* __restrict__ pb,
-                           u32* __restrict__ tile_cnt, const u32* __restrict__ tile_base, kmc_soull* __restrict__ acc_out,
+                           u32* __restrict__ tile_cnt, const u32* __restrict__ tile_base, kmc_ull* __restrict__ acc_out,
                            u64* __restrict__ out_hi, u64* __restrict__ out_lo, u64* __restrict__ out_cnt) {
     __shared__ __align__(16) u64 s_lo[KMC_SO_CAP];
     __shared__ __align__(16) u64 s_hi[KW == 2 ? KMC_SO_CAP : 2];
@@ -161,7 +152,7 @@ void kmc_setop_join_kernel(SoView A, SoView B, int op, int mode, u32 n_tiles, co
     __shared__ __align__(16) u64 o_c[PASS == 2 ? KMC_SO_CAP : 2];
     __shared__ u32 s_a[KMC_SO_THREADS + 1], s_b[KMC_SO_THREADS + 1];
     __shared__ u32 s_wv[KMC_SO_THREADS / 64];
-    __shared__ kmc_soull s_acc[KMC_SO_THREADS / 64][KMC_SO_WORDS];
+    __shared__ kmc_ull s_acc[KMC_SO_THREADS / 64][KMC_SO_WORDS];
     const u32 tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     SoAcc acc;
 #pragma unroll
@@ -223,7 +214,7 @@ void kmc_setop_join_kernel(SoView A, SoView B, int op, int mode, u32 n_tiles, co
         }
         __syncthreads();
         if (tid < KMC_SO_WORDS) {
-            kmc_soull s = 0;
+            kmc_ull s = 0;
             for (int q = 0; q < KMC_SO_THREADS / 64; ++q) s += s_acc[q][tid];
             if (s) atomicAdd(&acc_out[tid], s);
         }

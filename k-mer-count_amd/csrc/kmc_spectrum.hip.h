@@ -24,8 +24,6 @@
 #define KMC_FILT_ROUNDS 4         // a filter tile = ROUNDS x 256 lanes x 2 entries (one 16-byte load of counts per lane and round)
 #define KMC_FILT_TILE (KMC_FILT_ROUNDS * KMC_FILT_THREADS * 2)
 
-typedef unsigned long long kmc_ull;
-typedef kmc_ull kmc_ull2 __attribute__((ext_vector_type(2)));
 
 struct SpecAcc {
     u32 low[KMC_SPEC_LOW];
@@ -110,7 +108,7 @@ void kmc_histogram_kernel(const u64* __restrict__ cnt, u64 n, u32 head, u64 lo_c
     }
 }
 
-// ---- order-preserving filter: per-tile kept counts, exclusive scan of them (kmc_msd.hip.h's kmc_scan_* kernels), scatter ----
+// ---- order-preserving filter: per-tile kept counts, exclusive scan of them (kmc_scan.hip.h), scatter ----
 // Tile t covers entries [t * TILE, (t + 1) * TILE); in round r lane l of wave w holds the pair 2 * (r * 256 + w * 64 + l) + {0, 1}
 // of the tile: entries in view order are round-major, then wave, then lane, then the pair's element -- which is the order of the
 // scatter's positions (tile base + earlier rounds and waves + the lane's prefix in the wave's two ballots).

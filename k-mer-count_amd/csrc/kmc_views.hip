@@ -1,0 +1,661 @@
+// kmc_views.hip -- the calls of include/kmc.h that only READ the sorted view a finalize left in HBM.  From the counting
+// side (kmc_api.hip) they need resolve_view and the ctx (kmc_ctx.hip.h).
+#include <type_traits>
+
+#include "kmc_ctx.hip.h"
+#include "kmc_scan.hip.h"
+#include "kmc_partition.hip.h"
+#include "kmc_spectrum.hip.h"
+#include "kmc_query.hip.h"
+#include "kmc_setops.hip.h"
+#include "kmc_graph.hip.h"
+
+namespace {
+
+// the ctx's key words, and whether it counts canonical k-mers, as compile-time constants of a generic lambda
+template <typename F>
+void with_kw(const kmc_ctx* c, F&& f) {
+    if (c->KW == 1) f(std::integral_constant<int, 1>{}); else f(std::integral_constant<int, 2>{});
+}
+template <typename F>
+void with_kw_canon(const kmc_ctx* c, F&& f) {
+    with_kw(c, [&](auto KW) { if (c->cfg.canonical) f(KW, std::true_type{}); else f(KW, std::false_type{}); });
+}
+
+// the sorted view of the last finalize (no high words for one-word keys)
+KView view_of(const kmc_ctx* c) {
+    return KView{c->KW == 2 ? c->v_hi : nullptr, c->v_lo, c->v_cnt, c->n_sorted};
+}
+
+// the kernels that read two entries per 16-byte load ask for this (an empty view has no arrays to speak of)
+bool view_aligned16(const KView& v) { return !v.n || (((uintptr_t)v.hi | (uintptr_t)v.lo | (uintptr_t)v.cnt) & 15) == 0; }
+
+// upper end of a count range: 0 stands for "no upper bound"
+u64 count_hi(uint64_t max_count) { return max_count ? (u64)max_count : ~0ull; }
+
+// the view is about to be read outside the ctx's stream order: a finalize that poll_fin saw done before it ended is waited for
+int sync_view(kmc_ctx* c) {
+    if (!c->view_unsynced) return KMC_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->view_unsynced = false;
+    return KMC_OK;
+}
+
+// What the calls that read the view check first: resolve_view, the count range (max_count != 0), that there is a view
+int view_begin(kmc_ctx* c, const char* what, uint64_t min_count = 0, uint64_t max_count = 0) {
+    if (int rc = resolve_view(c)) return rc;
+    if (max_count && min_count > max_count)
+        return fail(c, KMC_ERR_ARG, "%s: min_count %llu > max_count %llu", what, (unsigned long long)min_count, (unsigned long long)max_count);
+    if (!c->sorted_valid) return fail(c, KMC_ERR_STATE, "%s before kmc_finalize", what);
+    return KMC_OK;
+}
+
+// n entries of a table on the device into the caller's arrays (key_hi: optional, zeros for one-word keys)
+int copy_to_host(kmc_ctx* c, const void* hi, const void* lo, const void* cnt, u64 n, uint64_t* key_hi, uint64_t* key_lo, uint64_t* count) {
+    HIPCHK(c, hipMemcpyAsync(key_lo, lo, n * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(count, cnt, n * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    if (key_hi) {
+        if (c->KW == 2) HIPCHK(c, hipMemcpyAsync(key_hi, hi, n * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+        else memset(key_hi, 0, n * sizeof(u64));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return KMC_OK;
+}
+
+// Scratch of an order-preserving compaction of n_tiles tiles -- counts (c_tile), their scan (c_tpos), block sums -- and
+// ctl_words zeroed control words (c_ctl): word 0 takes the scan's total (a u32), the rest are the caller's.
+int compact_plan(kmc_ctx* c, u64 n_tiles, u32 ctl_words) {
+    const size_t nb = (size_t)((n_tiles + KMC_SCAN_PER_BLOCK - 1) / KMC_SCAN_PER_BLOCK);
+    int rc;
+    if ((rc = ensure(c, c->c_tile, (size_t)n_tiles * sizeof(u32))) || (rc = ensure(c, c->c_tpos, (size_t)n_tiles * sizeof(u32))) ||
+        (rc = ensure(c, c->c_bsum, (nb + 2) * sizeof(u32))) || (rc = ensure(c, c->c_ctl, ctl_words * sizeof(u64))))
+        return rc;
+    HIPCHK(c, hipMemsetAsync(c->c_ctl.p, 0, ctl_words * sizeof(u64), c->stream));
+    return KMC_OK;
+}
+// behind the caller's count kernel: the scan of c_tile into c_tpos, its total into control word 0, then the control words
+// into h[ctl_words]; waits for them
+int compact_scan_and_read(kmc_ctx* c, u64 n_tiles, u64* h, u32 ctl_words) {
+    launch_exclusive_scan<0>(c->stream, c->c_tile.p, (u32)n_tiles, (u32*)c->c_bsum.p, (u32*)c->c_tpos.p, (u32*)c->c_ctl.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h, c->c_ctl.p, ctl_words * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return KMC_OK;
+}
+
+}  // namespace
+
+// ---- export and owner partition ----
+static int kmc_export_impl(kmc_ctx* c, uint64_t* key_hi, uint64_t* key_lo, uint64_t* count, uint64_t cap) {
+    if (!c) return KMC_ERR_ARG;
+    { int rc = view_begin(c, "kmc_export"); if (rc) return rc; }
+    const u64 n = c->n_sorted;
+    if (cap < n) return fail(c, KMC_ERR_ARG, "export capacity %llu < %llu distinct keys", (unsigned long long)cap, (unsigned long long)n);
+    if (!n) return KMC_OK;
+    if (!key_lo || !count) return fail(c, KMC_ERR_ARG, "null buffer");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    return copy_to_host(c, c->v_hi, c->v_lo, c->v_cnt, n, key_hi, key_lo, count);
+}
+
+static int kmc_export_device_impl(kmc_ctx* c, const void** d_key_hi, const void** d_key_lo, const void** d_count, uint64_t* n_distinct) {
+    if (!c) return KMC_ERR_ARG;
+    int rc;
+    if ((rc = view_begin(c, "kmc_export_device")) || (rc = sync_view(c))) return rc;
+    const KView v = view_of(c);
+    if (d_key_hi) *d_key_hi = v.hi;
+    if (d_key_lo) *d_key_lo = v.lo;
+    if (d_count) *d_count = v.cnt;
+    if (n_distinct) *n_distinct = v.n;
+    return KMC_OK;
+}
+
+extern "C" uint32_t kmc_owner_of(uint64_t key_hi, uint64_t key_lo, uint32_t n_parts) { return kmc_owner(key_hi, key_lo, n_parts); }
+
+static int kmc_partition_device_impl(kmc_ctx* c, uint32_t n_parts, uint64_t* part_begin, const void** d_key_hi,
+                                    const void** d_key_lo, const void** d_count) {
+    if (!c || !n_parts || !part_begin) return KMC_ERR_ARG;
+    { int rc = view_begin(c, "kmc_partition_device"); if (rc) return rc; }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    const KView v = view_of(c);
+    const u64 n = v.n;
+    int rc;
+    if ((rc = ensure_keys(c, c->p, n)) || (rc = ensure(c, c->t_idx0, (size_t)std::max<u64>(n_parts, 1) * sizeof(u64)))) return rc;
+    if (n_parts > 4096) return fail(c, KMC_ERR_ARG, "kmc_partition_device: more than 4096 parts");
+    std::vector<unsigned long long> cnt((size_t)n_parts, 0ull);
+    unsigned long long* d_cnt = (unsigned long long*)c->t_idx0.p;  // (scratch: n_parts counters, then cursors)
+    if (n) {
+        const int g2 = grid_for(c, n, 256);
+        HIPCHK(c, hipMemsetAsync(d_cnt, 0, (size_t)n_parts * sizeof(unsigned long long), c->stream));
+        hipLaunchKernelGGL(kmc_owner_count_kernel, dim3(g2), dim3(256), (size_t)n_parts * sizeof(unsigned int), c->stream, v.hi, v.lo, n, n_parts, d_cnt);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(cnt.data(), d_cnt, (size_t)n_parts * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    u64 pos = 0;
+    std::vector<unsigned long long> cursor((size_t)n_parts);
+    for (u32 p = 0; p < n_parts; ++p) { part_begin[p] = pos; cursor[p] = pos; pos += cnt[p]; }
+    part_begin[n_parts] = pos;
+    if (n) {
+        HIPCHK(c, hipMemcpyAsync(d_cnt, cursor.data(), (size_t)n_parts * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(kmc_owner_scatter_kernel, dim3(grid_for(c, n, 256)), dim3(256), 0, c->stream, v.hi, v.lo, v.cnt, n, n_parts, d_cnt,
+                           (u64*)c->p.hi.p, (u64*)c->p.lo.p, (u64*)c->p.cnt.p);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));  // (cursor[] is host memory of this call)
+    }
+    publish_keys(c, c->p, d_key_hi, d_key_lo, d_count);
+    return KMC_OK;
+}
+
+// ---- abundance histogram and count-range filter of the sorted view (kmc_spectrum.hip.h) ----
+static bool filter_is_identity(uint64_t min_count, uint64_t max_count) { return min_count <= 1 && max_count == 0; }
+
+static int kmc_histogram_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint32_t n_bins, uint64_t* hist, uint64_t* max_seen) {
+    if (!c) return KMC_ERR_ARG;
+    int rc = view_begin(c, "kmc_histogram", min_count, max_count);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (n_bins < 2 || n_bins > (1u << 24)) return fail(c, KMC_ERR_ARG, "kmc_histogram: n_bins %u outside 2..2^24", n_bins);
+    if (!hist) return fail(c, KMC_ERR_ARG, "kmc_histogram: null histogram");
+    const u64 n = c->n_sorted;
+    if (!n) {
+        memset(hist, 0, (size_t)n_bins * sizeof(u64));
+        if (max_seen) *max_seen = 0;
+        return KMC_OK;
+    }
+    rc = ensure(c, c->h_hist, ((size_t)n_bins + 1) * sizeof(u64));   // [hist | max]
+    if (rc) return rc;
+    kmc_ull* d = (kmc_ull*)c->h_hist.p;
+    HIPCHK(c, hipMemsetAsync(d, 0, ((size_t)n_bins + 1) * sizeof(u64), c->stream));
+    const u32 lds_bins = std::min<u32>(n_bins, KMC_SPEC_LDS_BINS);
+    const u32 head = ((uintptr_t)c->v_cnt & 15) ? 1u : 0u;
+    const u64 n_pairs = (n - head) / 2;
+    // 64 KiB of LDS: two workgroups per CU (160 KiB); smaller histograms four.  No more workgroups than there are
+    // pairs for: each one clears and flushes its whole LDS part.
+    const u64 per_cu = (u64)lds_bins * sizeof(u32) > 40960 ? 2 : 4;
+    const u64 grid = std::max<u64>(1, std::min<u64>((u64)c->n_cu * per_cu, (n_pairs + 2 * KMC_SPEC_THREADS - 1) / (2 * KMC_SPEC_THREADS)));
+    hipLaunchKernelGGL(kmc_histogram_kernel, dim3((u32)grid), dim3(KMC_SPEC_THREADS), (size_t)lds_bins * sizeof(u32), c->stream,
+                       c->v_cnt, n, head, (u64)min_count, count_hi(max_count), n_bins, lds_bins, d, d + n_bins);
+    HIPCHK(c, hipGetLastError());
+    u64 mx = 0;
+    HIPCHK(c, hipMemcpyAsync(hist, d, (size_t)n_bins * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&mx, d + n_bins, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (max_seen) *max_seen = mx;
+    return KMC_OK;
+}
+
+// reduce half of the filter: kept entries per tile, their exclusive scan (c_tpos), n_kept and the sum of kept counts
+static int filter_count(kmc_ctx* c, u64 lo_c, u64 hi_c, u64* n_kept, u64* kept_total) {
+    const KView v = view_of(c);
+    *n_kept = *kept_total = 0;
+    if (!v.n) return KMC_OK;
+    if (!view_aligned16(v)) return fail(c, KMC_ERR_HIP, "internal error: sorted view not 16-byte aligned");
+    const u64 n_tiles = (v.n + KMC_FILT_TILE - 1) / KMC_FILT_TILE;   // (n < 2^32: at most 2^21 tiles)
+    int rc = compact_plan(c, n_tiles, 2);   // [n_kept | kept_total]
+    if (rc) return rc;
+    const u32 cgrid = (u32)std::min<u64>(n_tiles, (u64)c->n_cu * 8);
+    hipLaunchKernelGGL(kmc_filter_count_kernel, dim3(cgrid), dim3(KMC_FILT_THREADS), 0, c->stream, v.cnt, v.n, n_tiles, lo_c, hi_c,
+                       (u32*)c->c_tile.p, (kmc_ull*)c->c_ctl.p + 1);
+    u64 h[2] = {0, 0};
+    if ((rc = compact_scan_and_read(c, n_tiles, h, 2))) return rc;
+    *n_kept = h[0];
+    *kept_total = h[1];
+    return KMC_OK;
+}
+
+// scatter half: the kept entries into the filter's result at tile base + wave offset + lane prefix (filter_count ran first);
+// finished when it returns (kmc_export_device's ordering contract)
+static int filter_scatter(kmc_ctx* c, u64 lo_c, u64 hi_c, u64 n_kept) {
+    if (int rc = ensure_keys(c, c->f, n_kept)) return rc;
+    if (!n_kept) return KMC_OK;
+    const KView v = view_of(c);
+    const u64 n_tiles = (v.n + KMC_FILT_TILE - 1) / KMC_FILT_TILE;
+    with_kw(c, [&](auto KW) {
+        hipLaunchKernelGGL(kmc_filter_scatter_kernel<KW()>, dim3((u32)n_tiles), dim3(KMC_FILT_THREADS), 0, c->stream, v.hi, v.lo, v.cnt,
+                           v.n, lo_c, hi_c, (const u32*)c->c_tpos.p, (u64*)c->f.hi.p, (u64*)c->f.lo.p, (u64*)c->f.cnt.p);
+    });
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return KMC_OK;
+}
+
+static int kmc_filter_device_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, const void** d_key_hi, const void** d_key_lo,
+                                  const void** d_count, uint64_t* n_kept, uint64_t* kept_total) {
+    if (!c) return KMC_ERR_ARG;
+    int rc = view_begin(c, "kmc_filter_device", min_count, max_count);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (filter_is_identity(min_count, max_count)) {   // keeps everything: the view itself, nothing launched
+        uint64_t nd = 0;
+        rc = kmc_export_device_impl(c, d_key_hi, d_key_lo, d_count, &nd);
+        if (rc) return rc;
+        if (n_kept) *n_kept = nd;
+        if (kept_total) *kept_total = nd ? c->st.n_kmers : 0;
+        return KMC_OK;
+    }
+    u64 nk = 0, kt = 0;
+    if ((rc = filter_count(c, min_count, count_hi(max_count), &nk, &kt)) || (rc = filter_scatter(c, min_count, count_hi(max_count), nk))) return rc;
+    publish_keys(c, c->f, d_key_hi, d_key_lo, d_count);
+    if (n_kept) *n_kept = nk;
+    if (kept_total) *kept_total = kt;
+    return KMC_OK;
+}
+
+static int kmc_export_filtered_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t* key_hi, uint64_t* key_lo,
+                                    uint64_t* count, uint64_t cap, uint64_t* n_kept) {
+    if (!c) return KMC_ERR_ARG;
+    if (n_kept) *n_kept = 0;
+    int rc = view_begin(c, "kmc_export_filtered", min_count, max_count);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    const bool ident = filter_is_identity(min_count, max_count);
+    u64 nk = c->n_sorted, kt = 0;
+    if (!ident) { rc = filter_count(c, min_count, count_hi(max_count), &nk, &kt); if (rc) return rc; }
+    if (n_kept) *n_kept = nk;
+    if (cap < nk) return fail(c, KMC_ERR_ARG, "kmc_export_filtered: capacity %llu < %llu kept keys", (unsigned long long)cap, (unsigned long long)nk);
+    if (!nk) return KMC_OK;
+    if (!key_lo || !count) return fail(c, KMC_ERR_ARG, "null buffer");
+    if (ident) return kmc_export_impl(c, key_hi, key_lo, count, cap);
+    rc = filter_scatter(c, min_count, count_hi(max_count), nk);
+    if (rc) return rc;
+    return copy_to_host(c, c->f.hi.p, c->f.lo.p, c->f.cnt.p, nk, key_hi, key_lo, count);
+}
+
+// ---- key lookups and per-read profiles against the sorted view (kmc_query.hip.h) ----
+// The view as the query kernels see it, its prefix index built first if this view has none yet (one launch; kept until the
+// ctx publishes another view).  An empty view gets an index of one empty bucket, so the kernels need no special case.
+static int query_view(kmc_ctx* c, const char* what, QView* out) {
+    const u64 n = c->n_sorted;
+    if (n >= (1ull << 32)) return fail(c, KMC_ERR_CAPACITY, "%s: a view of 2^32 keys or more cannot be indexed", what);
+    const int kb = 2 * c->klen;
+    const int P = kmc_query_index_bits(n, kb);
+    QView v;
+    static_cast<KView&>(v) = view_of(c);
+    v.sh = kb - P;
+    v.max_lo = kb >= 64 ? ~0ull : (1ull << kb) - 1;
+    v.max_hi = kb <= 64 ? 0ull : (1ull << (kb - 64)) - 1;
+    if (c->q_gen != c->view_gen || !c->q_idx.p) {
+        int rc = ensure(c, c->q_idx, (((size_t)1 << P) + 2) * sizeof(u32));
+        if (rc) return rc;
+        v.idx = (u32*)c->q_idx.p;
+        const u32 grid = (u32)((n + 1 + 255) / 256);
+        with_kw(c, [&](auto KW) { hipLaunchKernelGGL(kmc_query_index_kernel<KW()>, dim3(grid), dim3(256), 0, c->stream, v, 1u << P); });
+        HIPCHK(c, hipGetLastError());
+        c->q_gen = c->view_gen;
+    }
+    v.idx = (u32*)c->q_idx.p;
+    *out = v;
+    return KMC_OK;
+}
+
+// the lookup launch (device arrays; d_hi may be null: high words zero)
+static int query_launch(kmc_ctx* c, const u64* d_hi, const u64* d_lo, u64 n_keys, u64* d_cnt) {
+    QView v;
+    if (int rc = query_view(c, "kmc_query", &v)) return rc;
+    const int al16 = (((uintptr_t)d_hi | (uintptr_t)d_lo | (uintptr_t)d_cnt) & 15) == 0;
+    const u64 per_wg = (u64)KMC_Q_THREADS * KMC_Q_U;
+    const u64 grid = (n_keys + per_wg - 1) / per_wg;
+    if (grid > 0x7FFFFFFFull) return fail(c, KMC_ERR_ARG, "kmc_query: too many keys in one call");
+    with_kw(c, [&](auto KW) {
+        hipLaunchKernelGGL(kmc_query_kernel<KW()>, dim3((u32)grid), dim3(KMC_Q_THREADS), 0, c->stream, v, d_hi, d_lo, n_keys, al16, d_cnt);
+    });
+    HIPCHK(c, hipGetLastError());
+    return KMC_OK;
+}
+
+static int kmc_query_device_impl(kmc_ctx* c, const void* d_key_hi, const void* d_key_lo, uint64_t n_keys, void* d_count) {
+    if (!c) return KMC_ERR_ARG;
+    if (int rc = view_begin(c, "kmc_query_device")) return rc;
+    if (!n_keys) return KMC_OK;
+    if (!d_key_lo || !d_count) return fail(c, KMC_ERR_ARG, "kmc_query_device: null device pointer");
+    if ((((uintptr_t)d_key_hi | (uintptr_t)d_key_lo | (uintptr_t)d_count) & 7) != 0) return fail(c, KMC_ERR_ARG, "kmc_query_device: arrays must be 8-byte aligned");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    return query_launch(c, (const u64*)d_key_hi, (const u64*)d_key_lo, n_keys, (u64*)d_count);
+}
+
+static int kmc_query_impl(kmc_ctx* c, const uint64_t* key_hi, const uint64_t* key_lo, uint64_t n_keys, uint64_t* count) {
+    if (!c) return KMC_ERR_ARG;
+    int rc = view_begin(c, "kmc_query");
+    if (rc) return rc;
+    if (!n_keys) return KMC_OK;
+    if (!key_lo || !count) return fail(c, KMC_ERR_ARG, "kmc_query: null buffer");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    const size_t nb = (size_t)n_keys * sizeof(u64);
+    if ((rc = ensure(c, c->q_klo, nb)) || (rc = ensure(c, c->q_cnt, nb))) return rc;
+    if (key_hi && (rc = ensure(c, c->q_khi, nb))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->q_klo.p, key_lo, nb, hipMemcpyHostToDevice, c->stream));
+    if (key_hi) HIPCHK(c, hipMemcpyAsync(c->q_khi.p, key_hi, nb, hipMemcpyHostToDevice, c->stream));
+    rc = query_launch(c, key_hi ? (const u64*)c->q_khi.p : nullptr, (const u64*)c->q_klo.p, n_keys, (u64*)c->q_cnt.p);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(count, c->q_cnt.p, nb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return KMC_OK;
+}
+
+// the profile launches (device arrays; either output may be null)
+static int profile_launch(kmc_ctx* c, const uint8_t* d_bases, const u64* d_offsets, u64 n_reads, u64 n_bases, u64 min_count,
+                          u32* d_win, u64* d_stats) {
+    QView v;
+    if (int rc = query_view(c, "kmc_profile", &v)) return rc;
+    const int k = c->cfg.k;
+    const u64 n_words = n_reads * KMC_PROFILE_WORDS;
+    const u32 sgrid = (u32)((n_words + KMC_PROF_INIT_THREADS - 1) / KMC_PROF_INIT_THREADS);
+    if (d_stats) hipLaunchKernelGGL(kmc_profile_init_kernel, dim3(sgrid), dim3(KMC_PROF_INIT_THREADS), 0, c->stream, (kmc_ull*)d_stats, n_reads);
+    // windows END up to k - 1 positions past the batch: those (invalid) windows zero the last k - 1 slots
+    const u64 n_chunks = (n_bases + (u64)k - 1 + KMC_CHUNK - 1) / KMC_CHUNK;
+    if (n_chunks && (d_win || d_stats)) {
+        const u64 want_waves = (u64)c->n_cu * 16;   // four waves on each SIMD
+        const u64 cpw = std::min<u64>(64, std::max<u64>(1, (n_chunks + want_waves - 1) / want_waves));
+        const u64 waves = (n_chunks + cpw - 1) / cpw;
+        const u64 grid = (waves + KMC_Q_WAVES - 1) / KMC_Q_WAVES;
+        if (grid > 0x7FFFFFFFull) return fail(c, KMC_ERR_ARG, "kmc_profile: batch too large for one call");
+        const u64 thr = std::max<u64>(min_count, 1);
+        with_kw_canon(c, [&](auto KW, auto CANON) {
+            hipLaunchKernelGGL((kmc_profile_kernel<KW(), CANON()>), dim3((u32)grid), dim3(KMC_Q_THREADS), 0, c->stream, d_bases, n_bases,
+                               d_offsets, n_reads, k, n_chunks, cpw, v, thr, d_win, (kmc_ull*)d_stats);
+        });
+    }
+    if (d_stats) hipLaunchKernelGGL(kmc_profile_fix_kernel, dim3((u32)((n_reads + KMC_PROF_INIT_THREADS - 1) / KMC_PROF_INIT_THREADS)),
+                                    dim3(KMC_PROF_INIT_THREADS), 0, c->stream, (kmc_ull*)d_stats, n_reads);
+    HIPCHK(c, hipGetLastError());
+    return KMC_OK;
+}
+
+static int kmc_profile_device_impl(kmc_ctx* c, const void* d_bases, const void* d_offsets, uint64_t n_reads, uint64_t n_bases,
+                                   uint64_t min_count, void* d_window_count, void* d_read_stats) {
+    if (!c) return KMC_ERR_ARG;
+    if (c->cfg.mode != KMC_MODE_CONTIG) return fail(c, KMC_ERR_ARG, "kmc_profile_device: contiguous k-mers only (not KMC_MODE_LR)");
+    if (int rc = view_begin(c, "kmc_profile_device")) return rc;
+    if (!n_reads) return KMC_OK;
+    if (!d_bases || !d_offsets) return fail(c, KMC_ERR_ARG, "kmc_profile_device: null device pointer");
+    if (((uintptr_t)d_bases & 15) != 0) return fail(c, KMC_ERR_ARG, "kmc_profile_device: d_bases must be 16-byte aligned");
+    if (((uintptr_t)d_offsets & 7) != 0 || ((uintptr_t)d_read_stats & 7) != 0 || ((uintptr_t)d_window_count & 3) != 0)
+        return fail(c, KMC_ERR_ARG, "kmc_profile_device: d_offsets / d_read_stats must be 8-byte, d_window_count 4-byte aligned");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    return profile_launch(c, (const uint8_t*)d_bases, (const u64*)d_offsets, n_reads, n_bases, min_count, (u32*)d_window_count, (u64*)d_read_stats);
+}
+
+static int kmc_profile_impl(kmc_ctx* c, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads, uint64_t min_count,
+                            uint32_t* window_count, uint64_t* read_stats) {
+    if (!c) return KMC_ERR_ARG;
+    if (c->cfg.mode != KMC_MODE_CONTIG) return fail(c, KMC_ERR_ARG, "kmc_profile: contiguous k-mers only (not KMC_MODE_LR)");
+    int rc = view_begin(c, "kmc_profile");
+    if (rc) return rc;
+    if (!n_reads) return KMC_OK;
+    if (!bases || !offsets) return fail(c, KMC_ERR_ARG, "kmc_profile: null buffer");
+    if (offsets[0] != 0) return fail(c, KMC_ERR_ARG, "kmc_profile: offsets[0] must be 0");
+    for (u64 i = 0; i < n_reads; ++i)
+        if (offsets[i + 1] < offsets[i]) return fail(c, KMC_ERR_ARG, "kmc_profile: offsets must be non-decreasing (read %llu)", (unsigned long long)i);
+    const u64 n_bases = offsets[n_reads];
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    const size_t sb = (size_t)n_reads * KMC_PROFILE_WORDS * sizeof(u64), wb = (size_t)n_bases * sizeof(u32);
+    if ((rc = ensure(c, c->q_bases, n_bases + 64)) || (rc = ensure(c, c->q_offs, (n_reads + 1) * sizeof(u64)))) return rc;
+    if (window_count && n_bases && (rc = ensure(c, c->q_win, wb))) return rc;
+    if (read_stats && (rc = ensure(c, c->q_stats, sb))) return rc;
+    if (n_bases) HIPCHK(c, hipMemcpyAsync(c->q_bases.p, bases, n_bases, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->q_offs.p, offsets, (n_reads + 1) * sizeof(u64), hipMemcpyHostToDevice, c->stream));
+    rc = profile_launch(c, (const uint8_t*)c->q_bases.p, (const u64*)c->q_offs.p, n_reads, n_bases, min_count,
+                        window_count && n_bases ? (u32*)c->q_win.p : nullptr, read_stats ? (u64*)c->q_stats.p : nullptr);
+    if (rc) return rc;
+    if (window_count && n_bases) HIPCHK(c, hipMemcpyAsync(window_count, c->q_win.p, wb, hipMemcpyDeviceToHost, c->stream));
+    if (read_stats) HIPCHK(c, hipMemcpyAsync(read_stats, c->q_stats.p, sb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return KMC_OK;
+}
+
+// ---- two tables compared: summary and set operations over the sorted views of two contexts (kmc_setops.hip.h) ----
+// What every set-operation call checks first: arguments, that a and b count the same kind of key on one device, both views.
+// b's view is only read, on a's stream: b is synchronised first where kmc_export_device would do so.
+static int setop_begin(kmc_ctx* a, kmc_ctx* b, const char* what, int op, int count_mode, uint64_t min_a, uint64_t max_a,
+                       uint64_t min_b, uint64_t max_b) {
+    if (op < KMC_SETOP_INTERSECT || op > KMC_SETOP_SUBTRACT) return fail(a, KMC_ERR_ARG, "%s: unknown op %d", what, op);
+    if (count_mode < KMC_COUNT_LEFT || count_mode > KMC_COUNT_DIFF) return fail(a, KMC_ERR_ARG, "%s: unknown count_mode %d", what, count_mode);
+    if (max_a && min_a > max_a) return fail(a, KMC_ERR_ARG, "%s: min_a %llu > max_a %llu", what, (unsigned long long)min_a, (unsigned long long)max_a);
+    if (max_b && min_b > max_b) return fail(a, KMC_ERR_ARG, "%s: min_b %llu > max_b %llu", what, (unsigned long long)min_b, (unsigned long long)max_b);
+    if (a->cfg.device != b->cfg.device) return fail(a, KMC_ERR_ARG, "%s: the contexts differ in device (%d / %d)", what, a->cfg.device, b->cfg.device);
+    if (a->cfg.mode != b->cfg.mode) return fail(a, KMC_ERR_ARG, "%s: the contexts differ in mode (%d / %d)", what, a->cfg.mode, b->cfg.mode);
+    if (a->klen != b->klen || a->KW != b->KW) return fail(a, KMC_ERR_ARG, "%s: the contexts differ in k (%d / %d)", what, a->klen, b->klen);
+    if ((a->cfg.canonical != 0) != (b->cfg.canonical != 0))
+        return fail(a, KMC_ERR_ARG, "%s: the contexts differ in canonical (%d / %d)", what, a->cfg.canonical, b->cfg.canonical);
+    int rc = view_begin(a, what);
+    if (rc) return rc;
+    if (b != a) {
+        if ((rc = view_begin(b, what)) || (rc = sync_view(b))) return rc;
+    }
+    if (a->n_sorted + b->n_sorted >= (1ull << 32))
+        return fail(a, KMC_ERR_CAPACITY, "%s: the two views hold 2^32 keys or more together", what);
+    HIPCHK(a, hipSetDevice(a->cfg.device));
+    return KMC_OK;
+}
+
+static SoView so_view(const kmc_ctx* c, uint64_t min_c, uint64_t max_c) {
+    return SoView{view_of(c), min_c, count_hi(max_c)};
+}
+
+// Partition + one pass over both views.  pass 0: the summary; pass 1: the summary, the emitted keys per tile and their
+// scan (c_tpos).  h[0] = n_out (pass 1), h[1..8] = summary, h[9] = total_out.  Waits for the result.
+static int setop_reduce(kmc_ctx* a, int pass, int op, int count_mode, const SoView& A, const SoView& B, u64* h) {
+    memset(h, 0, (KMC_SO_WORDS + 1) * sizeof(u64));
+    const u64 nm = A.n + B.n;
+    if (!nm) return KMC_OK;
+    if (!view_aligned16(A) || !view_aligned16(B)) return fail(a, KMC_ERR_HIP, "internal error: sorted view not 16-byte aligned");
+    const u32 n_tiles = (u32)((nm + KMC_SO_TILE - 1) / KMC_SO_TILE);
+    int rc;
+    if ((rc = ensure(a, a->so_pa, ((size_t)n_tiles + 1) * sizeof(u32))) || (rc = ensure(a, a->so_pb, ((size_t)n_tiles + 1) * sizeof(u32))) ||
+        (rc = compact_plan(a, n_tiles, KMC_SO_WORDS + 1)))   // [n_out | summary | total_out]
+        return rc;
+    kmc_ull* acc = (kmc_ull*)a->c_ctl.p + 1;
+    u32 *pa = (u32*)a->so_pa.p, *pb = (u32*)a->so_pb.p, *tile = (u32*)a->c_tile.p;
+    const u32 pgrid = (n_tiles + 1 + 255) / 256;
+    const u32 grid = (u32)std::min<u64>(n_tiles, (u64)a->n_cu * 8);
+    with_kw(a, [&](auto KW) {
+        hipLaunchKernelGGL(kmc_setop_partition_kernel<KW()>, dim3(pgrid), dim3(256), 0, a->stream, A, B, n_tiles, pa, pb);
+        if (pass == 0)
+            hipLaunchKernelGGL((kmc_setop_join_kernel<KW(), 0>), dim3(grid), dim3(KMC_SO_THREADS), 0, a->stream, A, B, op, count_mode, n_tiles,
+                               (const u32*)pa, (const u32*)pb, (u32*)nullptr, (const u32*)nullptr, acc, (u64*)nullptr, (u64*)nullptr, (u64*)nullptr);
+        else
+            hipLaunchKernelGGL((kmc_setop_join_kernel<KW(), 1>), dim3(grid), dim3(KMC_SO_THREADS), 0, a->stream, A, B, op, count_mode, n_tiles,
+                               (const u32*)pa, (const u32*)pb, tile, (const u32*)nullptr, acc, (u64*)nullptr, (u64*)nullptr, (u64*)nullptr);
+    });
+    if (pass == 1) return compact_scan_and_read(a, n_tiles, h, KMC_SO_WORDS + 1);
+    HIPCHK(a, hipGetLastError());   // the summary alone: nothing to scan
+    HIPCHK(a, hipMemcpyAsync(h, a->c_ctl.p, (KMC_SO_WORDS + 1) * sizeof(u64), hipMemcpyDeviceToHost, a->stream));
+    HIPCHK(a, hipStreamSynchronize(a->stream));
+    return KMC_OK;
+}
+
+// scatter half (setop_reduce pass 1 ran first): the emitted entries into the set operation's result; finished when it returns
+static int setop_scatter(kmc_ctx* a, int op, int count_mode, const SoView& A, const SoView& B, u64 n_out) {
+    if (int rc = ensure_keys(a, a->so, n_out)) return rc;
+    if (!n_out) return KMC_OK;
+    const u32 n_tiles = (u32)((A.n + B.n + KMC_SO_TILE - 1) / KMC_SO_TILE);
+    const u32 grid = (u32)std::min<u64>(n_tiles, (u64)a->n_cu * 8);
+    with_kw(a, [&](auto KW) {
+        hipLaunchKernelGGL((kmc_setop_join_kernel<KW(), 2>), dim3(grid), dim3(KMC_SO_THREADS), 0, a->stream, A, B, op, count_mode, n_tiles,
+                           (const u32*)a->so_pa.p, (const u32*)a->so_pb.p, (u32*)nullptr, (const u32*)a->c_tpos.p, (kmc_ull*)nullptr,
+                           (u64*)a->so.hi.p, (u64*)a->so.lo.p, (u64*)a->so.cnt.p);
+    });
+    HIPCHK(a, hipGetLastError());
+    HIPCHK(a, hipStreamSynchronize(a->stream));
+    return KMC_OK;
+}
+
+static int kmc_compare_impl(kmc_ctx* a, kmc_ctx* b, uint64_t min_a, uint64_t max_a, uint64_t min_b, uint64_t max_b, uint64_t* summary) {
+    if (!a || !b) return a ? fail(a, KMC_ERR_ARG, "kmc_compare: null context") : KMC_ERR_ARG;
+    if (!summary) return fail(a, KMC_ERR_ARG, "kmc_compare: null summary");
+    u64 h[KMC_SO_WORDS + 1];
+    int rc;
+    if ((rc = setop_begin(a, b, "kmc_compare", KMC_SETOP_INTERSECT, KMC_COUNT_LEFT, min_a, max_a, min_b, max_b)) ||
+        (rc = setop_reduce(a, 0, KMC_SETOP_INTERSECT, KMC_COUNT_LEFT, so_view(a, min_a, max_a), so_view(b, min_b, max_b), h))) return rc;
+    memcpy(summary, h + 1, KMC_COMPARE_WORDS * sizeof(u64));
+    return KMC_OK;
+}
+
+static int kmc_setop_device_impl(kmc_ctx* a, kmc_ctx* b, int op, int count_mode, uint64_t min_a, uint64_t max_a, uint64_t min_b,
+                                 uint64_t max_b, const void** d_key_hi, const void** d_key_lo, const void** d_count, uint64_t* n_out,
+                                 uint64_t* total_out, uint64_t* summary) {
+    if (!a || !b) return a ? fail(a, KMC_ERR_ARG, "kmc_setop_device: null context") : KMC_ERR_ARG;
+    int rc = setop_begin(a, b, "kmc_setop_device", op, count_mode, min_a, max_a, min_b, max_b);
+    if (rc) return rc;
+    const SoView A = so_view(a, min_a, max_a), B = so_view(b, min_b, max_b);
+    u64 h[KMC_SO_WORDS + 1];
+    if ((rc = setop_reduce(a, 1, op, count_mode, A, B, h)) || (rc = setop_scatter(a, op, count_mode, A, B, h[0]))) return rc;
+    publish_keys(a, a->so, d_key_hi, d_key_lo, d_count);
+    if (n_out) *n_out = h[0];
+    if (total_out) *total_out = h[KMC_SO_WORDS];
+    if (summary) memcpy(summary, h + 1, KMC_COMPARE_WORDS * sizeof(u64));
+    return KMC_OK;
+}
+
+static int kmc_export_setop_impl(kmc_ctx* a, kmc_ctx* b, int op, int count_mode, uint64_t min_a, uint64_t max_a, uint64_t min_b,
+                                 uint64_t max_b, uint64_t* key_hi, uint64_t* key_lo, uint64_t* count, uint64_t cap, uint64_t* n_out) {
+    if (n_out) *n_out = 0;
+    if (!a || !b) return a ? fail(a, KMC_ERR_ARG, "kmc_export_setop: null context") : KMC_ERR_ARG;
+    int rc = setop_begin(a, b, "kmc_export_setop", op, count_mode, min_a, max_a, min_b, max_b);
+    if (rc) return rc;
+    const SoView A = so_view(a, min_a, max_a), B = so_view(b, min_b, max_b);
+    u64 h[KMC_SO_WORDS + 1];
+    rc = setop_reduce(a, 1, op, count_mode, A, B, h);
+    if (rc) return rc;
+    const u64 n = h[0];
+    if (n_out) *n_out = n;
+    if (cap < n) return fail(a, KMC_ERR_ARG, "kmc_export_setop: capacity %llu < %llu result keys", (unsigned long long)cap, (unsigned long long)n);
+    if (!n) return KMC_OK;
+    if (!key_lo || !count) return fail(a, KMC_ERR_ARG, "null buffer");
+    rc = setop_scatter(a, op, count_mode, A, B, n);
+    if (rc) return rc;
+    return copy_to_host(a, a->so.hi.p, a->so.lo.p, a->so.cnt.p, n, key_hi, key_lo, count);
+}
+
+// ---- the de Bruijn graph of the sorted view: neighbour masks, unitig ends, summary (kmc_graph.hip.h) ----
+// What both calls check first; on success the view is resolved.
+static int graph_begin(kmc_ctx* c, const char* what, uint64_t min_count, uint64_t max_count) {
+    if (c->cfg.mode != KMC_MODE_CONTIG) return fail(c, KMC_ERR_ARG, "%s: contiguous k-mers only (not KMC_MODE_LR)", what);
+    if (int rc = view_begin(c, what, min_count, max_count)) return rc;
+    if (c->n_sorted >= (1ull << 32)) return fail(c, KMC_ERR_CAPACITY, "%s: a view of 2^32 keys or more cannot be indexed", what);
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    return KMC_OK;
+}
+
+// adj of every view key into g_adj, the summary into h[KMC_GRAPH_WORDS]; finished when it returns (kmc_export_device's
+// ordering contract).  Shares the prefix index with the query calls (query_view).
+static int graph_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count, u64* h) {
+    memset(h, 0, KMC_GRAPH_WORDS * sizeof(u64));
+    const u64 n = c->n_sorted;
+    int rc;
+    if ((rc = ensure(c, c->g_adj, (size_t)std::max<u64>(n, 1) * sizeof(uint16_t))) || (rc = ensure(c, c->g_ctl, KMC_GRAPH_WORDS * sizeof(u64)))) return rc;
+    if (!n) return KMC_OK;
+    QView v;
+    rc = query_view(c, what, &v);
+    if (rc) return rc;
+    kmc_ull* ctl = (kmc_ull*)c->g_ctl.p;
+    HIPCHK(c, hipMemsetAsync(ctl, 0, KMC_GRAPH_WORDS * sizeof(u64), c->stream));
+    const u64 lo_c = std::max<u64>(min_count, 1), hi_c = count_hi(max_count);
+    const u64 want = (n + KMC_G_THREADS - 1) / KMC_G_THREADS;
+    const int k = c->klen;
+    // as many workgroups as are resident at once (they walk the view with a grid stride), fewer for a small view
+    with_kw_canon(c, [&](auto KW, auto CANON) {
+        int per_cu = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kmc_graph_kernel<KW(), CANON()>, KMC_G_THREADS, 0) != hipSuccess || per_cu < 1)
+            per_cu = 4;
+        const u32 grid = (u32)std::min<u64>(want, (u64)c->n_cu * (u64)per_cu);
+        hipLaunchKernelGGL((kmc_graph_kernel<KW(), CANON()>), dim3(grid), dim3(KMC_G_THREADS), 0, c->stream, v, lo_c, hi_c, k,
+                           (uint16_t*)c->g_adj.p, ctl);
+    });
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h, ctl, KMC_GRAPH_WORDS * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return KMC_OK;
+}
+
+static int kmc_graph_device_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, const void** d_adj, uint64_t* n_keys, uint64_t* summary) {
+    if (!c) return KMC_ERR_ARG;
+    u64 h[KMC_GRAPH_WORDS];
+    int rc;
+    if ((rc = graph_begin(c, "kmc_graph_device", min_count, max_count)) || (rc = graph_run(c, "kmc_graph_device", min_count, max_count, h))) return rc;
+    if (d_adj) *d_adj = c->g_adj.p;
+    if (n_keys) *n_keys = c->n_sorted;
+    if (summary) memcpy(summary, h, sizeof(h));
+    return KMC_OK;
+}
+
+static int kmc_graph_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, void* adj, uint64_t cap, uint64_t* n_keys, uint64_t* summary) {
+    if (n_keys) *n_keys = 0;
+    if (!c) return KMC_ERR_ARG;
+    int rc = graph_begin(c, "kmc_graph", min_count, max_count);
+    if (rc) return rc;
+    const u64 n = c->n_sorted;
+    if (n_keys) *n_keys = n;
+    const bool sizing = !adj && !cap;   // the summary alone / how large adj must be
+    if (!sizing && cap < n) return fail(c, KMC_ERR_ARG, "kmc_graph: capacity %llu < %llu keys of the view", (unsigned long long)cap, (unsigned long long)n);
+    if (!sizing && n && !adj) return fail(c, KMC_ERR_ARG, "kmc_graph: null buffer");
+    u64 h[KMC_GRAPH_WORDS];
+    rc = graph_run(c, "kmc_graph", min_count, max_count, h);
+    if (rc) return rc;
+    if (adj && n) {
+        HIPCHK(c, hipMemcpyAsync(adj, c->g_adj.p, (size_t)n * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    if (summary) memcpy(summary, h, sizeof(h));
+    return KMC_OK;
+}
+
+// ---- the ABI proper (guarded: no C++ exception leaves the library) ----
+extern "C" int kmc_export(kmc_ctx* c, uint64_t* key_hi, uint64_t* key_lo, uint64_t* count, uint64_t cap) {
+    return guarded(c, [&]() -> int { return kmc_export_impl(c, key_hi, key_lo, count, cap); });
+}
+extern "C" int kmc_export_device(kmc_ctx* c, const void** d_key_hi, const void** d_key_lo, const void** d_count, uint64_t* n_distinct) {
+    return guarded(c, [&]() -> int { return kmc_export_device_impl(c, d_key_hi, d_key_lo, d_count, n_distinct); });
+}
+extern "C" int kmc_histogram(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint32_t n_bins, uint64_t* hist, uint64_t* max_seen) {
+    return guarded(c, [&]() -> int { return kmc_histogram_impl(c, min_count, max_count, n_bins, hist, max_seen); });
+}
+extern "C" int kmc_filter_device(kmc_ctx* c, uint64_t min_count, uint64_t max_count, const void** d_key_hi, const void** d_key_lo,
+                                 const void** d_count, uint64_t* n_kept, uint64_t* kept_total) {
+    return guarded(c, [&]() -> int { return kmc_filter_device_impl(c, min_count, max_count, d_key_hi, d_key_lo, d_count, n_kept, kept_total); });
+}
+extern "C" int kmc_export_filtered(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t* key_hi, uint64_t* key_lo,
+                                   uint64_t* count, uint64_t cap, uint64_t* n_kept) {
+    return guarded(c, [&]() -> int { return kmc_export_filtered_impl(c, min_count, max_count, key_hi, key_lo, count, cap, n_kept); });
+}
+extern "C" int kmc_query(kmc_ctx* c, const uint64_t* key_hi, const uint64_t* key_lo, uint64_t n_keys, uint64_t* count) {
+    return guarded(c, [&]() -> int { return kmc_query_impl(c, key_hi, key_lo, n_keys, count); });
+}
+extern "C" int kmc_query_device(kmc_ctx* c, const void* d_key_hi, const void* d_key_lo, uint64_t n_keys, void* d_count) {
+    return guarded(c, [&]() -> int { return kmc_query_device_impl(c, d_key_hi, d_key_lo, n_keys, d_count); });
+}
+extern "C" int kmc_profile(kmc_ctx* c, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads, uint64_t min_count,
+                           uint32_t* window_count, uint64_t* read_stats) {
+    return guarded(c, [&]() -> int { return kmc_profile_impl(c, bases, offsets, n_reads, min_count, window_count, read_stats); });
+}
+extern "C" int kmc_profile_device(kmc_ctx* c, const void* d_bases, const void* d_offsets, uint64_t n_reads, uint64_t n_bases,
+                                  uint64_t min_count, void* d_window_count, void* d_read_stats) {
+    return guarded(c, [&]() -> int { return kmc_profile_device_impl(c, d_bases, d_offsets, n_reads, n_bases, min_count, d_window_count, d_read_stats); });
+}
+extern "C" int kmc_compare(kmc_ctx* a, kmc_ctx* b, uint64_t min_a, uint64_t max_a, uint64_t min_b, uint64_t max_b, uint64_t* summary) {
+    return guarded(a, [&]() -> int { return kmc_compare_impl(a, b, min_a, max_a, min_b, max_b, summary); });
+}
+extern "C" int kmc_setop_device(kmc_ctx* a, kmc_ctx* b, int op, int count_mode, uint64_t min_a, uint64_t max_a, uint64_t min_b,
+                                uint64_t max_b, const void** d_key_hi, const void** d_key_lo, const void** d_count, uint64_t* n_out,
+                                uint64_t* total_out, uint64_t* summary) {
+    return guarded(a, [&]() -> int {
+        return kmc_setop_device_impl(a, b, op, count_mode, min_a, max_a, min_b, max_b, d_key_hi, d_key_lo, d_count, n_out, total_out, summary);
+    });
+}
+extern "C" int kmc_export_setop(kmc_ctx* a, kmc_ctx* b, int op, int count_mode, uint64_t min_a, uint64_t max_a, uint64_t min_b,
+                                uint64_t max_b, uint64_t* key_hi, uint64_t* key_lo, uint64_t* count, uint64_t cap, uint64_t* n_out) {
+    return guarded(a, [&]() -> int {
+        return kmc_export_setop_impl(a, b, op, count_mode, min_a, max_a, min_b, max_b, key_hi, key_lo, count, cap, n_out);
+    });
+}
+extern "C" int kmc_graph_device(kmc_ctx* c, uint64_t min_count, uint64_t max_count, const void** d_adj, uint64_t* n_keys, uint64_t* summary) {
+    return guarded(c, [&]() -> int { return kmc_graph_device_impl(c, min_count, max_count, d_adj, n_keys, summary); });
+}
+extern "C" int kmc_graph(kmc_ctx* c, uint64_t min_count, uint64_t max_count, void* adj, uint64_t cap, uint64_t* n_keys, uint64_t* summary) {
+    return guarded(c, [&]() -> int { return kmc_graph_impl(c, min_count, max_count, adj, cap, n_keys, summary); });
+}
+extern "C" int kmc_partition_device(kmc_ctx* c, uint32_t n_parts, uint64_t* part_begin, const void** d_key_hi,
+                                    const void** d_key_lo, const void** d_count) {
+    return guarded(c, [&]() -> int { return kmc_partition_device_impl(c, n_parts, part_begin, d_key_hi, d_key_lo, d_count); });
+}

@@ -10,6 +10,8 @@ rm -rf $w && mkdir -p $w/pkg/csrc $w/include
 cp $root/k-mer-count_amd/csrc/* $w/pkg/csrc/ && cp $root/include/kmc.h $w/include/
 [ -n "$hdr" ] && cp $hdr $w/pkg/csrc/kmc_walk.hip.h
 cd $w/pkg
-/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -I../include $flags -c csrc/kmc_api.hip -o kmc_api.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -pthread -o $root/k-mer-count_amd/libkmc_$name.so kmc_api.o $root/k-mer-count_amd/kmc_host.o
+for tu in kmc_api kmc_views; do
+  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -I../include $flags -c csrc/$tu.hip -o $tu.o
+done
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -pthread -o $root/k-mer-count_amd/libkmc_$name.so kmc_api.o kmc_views.o $root/k-mer-count_amd/kmc_host.o
 ls -la $root/k-mer-count_amd/libkmc_$name.so
