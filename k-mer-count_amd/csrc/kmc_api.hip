@@ -821,7 +821,7 @@ int flush_acc(kmc_ctx* c) {
 
 int run_sort_path(kmc_ctx* c, const uint8_t* d_bases, const u64* d_offsets, u64 n_reads, u64 n_bases, u64 range_begin) {
     const u64 n_chunks = (n_bases + KMC_CHUNK - 1) / KMC_CHUNK;
-    const u64 SB = 1ull << 21;  // chunks per sort (2^31 positions: the run kernels index with u32)
+    const u64 SB = c->sort_sub_chunks;  // chunks per sort (2^21 = 2^31 positions: the run kernels index with u32; KMC_SORT_SUB_CHUNKS lowers it)
     const u64 CPR = KMC_MSD_RANGE / KMC_CHUNK;   // chunks per range of the sort
     for (u64 cb = range_begin / KMC_CHUNK; cb < n_chunks; cb += SB) {
         const u64 ce = std::min(n_chunks, cb + SB);
@@ -1173,7 +1173,7 @@ int choose_algo(kmc_ctx* c, const u64* d_offsets, u64 n_reads, u64* max_read_len
 // Sub-batches of 2^25 window starts (61 x 8 B x 2 buffers = 32 GiB of keys in flight at most).
 int count_lr(kmc_ctx* c, const uint8_t* d_bases, const u64* d_offsets, u64 n_reads, u64 n_bases) {
     const u64 per = KMC_LRX_NS;
-    const u64 SB = 1ull << 25;
+    const u64 SB = c->lr_sub_starts;   // (2^25; KMC_LR_SUB_STARTS lowers it)
     int rc;
     for (u64 p0 = 0; p0 < n_bases; p0 += SB) {
         const u64 p1 = std::min(n_bases, p0 + SB);
@@ -1198,16 +1198,19 @@ int count_lr(kmc_ctx* c, const uint8_t* d_bases, const u64* d_offsets, u64 n_rea
         rc = msd_sort_to_run(c, khi, klo, kwt, nq, 2u * KMC_LR_L, 1, &mers, true);
         if (rc) return rc;
         const u64 n_distinct = mers.n;
-        if (n_distinct) {  // 2. every position's rank in it
-            hipLaunchKernelGGL(kmc_lr_mer_kernel<1>, dim3(mer_grid), dim3(KMC_LRX_THREADS), 0, c->stream,
-                               d_bases, n_bases, q0, q1, (u64*)nullptr, (const u64*)mers.lo, (u32)n_distinct, (u32*)c->lr_rank.p);
-            HIPCHK(c, hipGetLastError());
-            // 3. every key as a pair of ranks, sorted and run-length counted; 4. back to 108-bit keys
-            int B = 1;
-            while ((1ull << B) < n_distinct) ++B;
-            hipLaunchKernelGGL(kmc_lr_pair_kernel, dim3((unsigned)((p1 - p0 + KMC_LRX_POS - 1) / KMC_LRX_POS)), dim3(KMC_LRX_THREADS), 0, c->stream,
-                               d_offsets, n_reads, p0, p1, q0, nq, (const u32*)c->lr_rank.p, B, klo[0], c->d_counters);
-            HIPCHK(c, hipGetLastError());
+        // 2. every position's rank in it.  (A pass without a single valid 27-mer has an empty dictionary and no rank: the
+        //    pair kernel still runs, because every window of such a pass reads a byte outside ACGT and must raise error
+        //    bit 4 -- skipping the pass let a batch of N bases through as an empty table.  The dictionary is not read then.)
+        hipLaunchKernelGGL(kmc_lr_mer_kernel<1>, dim3(mer_grid), dim3(KMC_LRX_THREADS), 0, c->stream,
+                           d_bases, n_bases, q0, q1, (u64*)nullptr, (const u64*)mers.lo, (u32)n_distinct, (u32*)c->lr_rank.p);
+        HIPCHK(c, hipGetLastError());
+        // 3. every key as a pair of ranks, sorted and run-length counted; 4. back to 108-bit keys
+        int B = 1;
+        while ((1ull << B) < n_distinct) ++B;
+        hipLaunchKernelGGL(kmc_lr_pair_kernel, dim3((unsigned)((p1 - p0 + KMC_LRX_POS - 1) / KMC_LRX_POS)), dim3(KMC_LRX_THREADS), 0, c->stream,
+                           d_offsets, n_reads, p0, p1, q0, nq, (const u32*)c->lr_rank.p, B, klo[0], c->d_counters);
+        HIPCHK(c, hipGetLastError());
+        if (n_distinct) {   // (no dictionary: the pair kernel wrote nothing but filler)
             kmc_ctx::Run run;
             rc = msd_sort_to_run(c, khi, klo, kwt, n, 2u * (unsigned)B, 1, &run, true);
             if (rc) { c->run_pool.push_back(mers); return rc; }
@@ -1564,6 +1567,15 @@ static int kmc_create_impl(kmc_ctx** out, const kmc_config* cfg) {
     if (cfg->mode == KMC_MODE_LR) { c->KW = 2; c->klen = 54; c->cfg.k = 54; c->cfg.canonical = 0; }
     else { c->KW = cfg->k <= 31 ? 1 : 2; c->klen = cfg->k; }
     if (const char* e = getenv("KMC_FIN_SMALL_MAX")) c->fin_small_max = std::min<u64>(strtoull(e, nullptr, 10), KMC_FIN_KERNEL_MAX);
+    // (sub-batch seams: rounded up to the unit the kernels work in, never below one unit, never above the default)
+    auto seam = [](const char* name, u64 unit, u64 dflt) -> u64 {
+        const char* e = getenv(name);
+        if (!e) return dflt;
+        const u64 v = std::min<u64>(strtoull(e, nullptr, 10), dflt);
+        return std::min<u64>(std::max<u64>((v + unit - 1) / unit, 1) * unit, dflt);
+    };
+    c->sort_sub_chunks = seam("KMC_SORT_SUB_CHUNKS", KMC_MSD_RANGE / KMC_CHUNK, c->sort_sub_chunks);
+    c->lr_sub_starts = seam("KMC_LR_SUB_STARTS", KMC_LRX_POS, c->lr_sub_starts);
     int rc = KMC_OK;
     auto body = [&]() -> int {
         HIPCHK(c, hipSetDevice(cfg->device));

@@ -112,6 +112,11 @@ struct kmc_ctx {
     // that were larger than this at the last finalize go there directly.  (KMC_FIN_SMALL_MAX overrides: the parity test of
     // the kernel's size boundaries runs it up to its limit, KMC_FIN_KERNEL_MAX.)
     u64 fin_small_max = 40000;
+    // Sub-batch sizes of the sort path and of LR mode (run_sort_path, count_lr): the defaults are what the u32 indices of
+    // the run kernels and 32 GiB of keys in flight allow.  KMC_SORT_SUB_CHUNKS / KMC_LR_SUB_STARTS turn them down (never
+    // up) so that tests/test_sub_batches_gpu.py crosses sub-batch edges on inputs the CPU oracle can count.
+    u64 sort_sub_chunks = 1ull << 21;   // chunks per sort: a multiple of KMC_MSD_RANGE / KMC_CHUNK in [64, 2^21]
+    u64 lr_sub_starts = 1ull << 25;     // window starts per LR pass: a multiple of KMC_LRX_POS in [256, 2^25]
     bool view_unsynced = false;   // the last small-table finalize was waited for through the mirror, not the stream (poll_fin)
     bool batch_pending = false;  // a COUNT kernel (unknown number of new keys) is queued since the last poll
     u64 unpolled_adds = 0;       // upper bound of keys added by merge kernels since the last poll
