@@ -23,6 +23,7 @@
  *   (addition: no equivalent in the reference)             kmc_profile / kmc_profile_device (per-read k-mer profile)
  *   (addition: no equivalent in the reference)             kmc_compare / kmc_setop_device / kmc_export_setop (two tables)
  *   (addition: no equivalent in the reference)             kmc_graph / kmc_graph_device (de Bruijn graph of the table)
+ *   (addition: no equivalent in the reference)             kmc_unitigs / kmc_unitigs_device (its unitig sequences)
  *
  * Conventions
  *   - Every function returns 0 (KMC_OK) or a negative kmc_status; no exception or abort crosses
@@ -324,7 +325,7 @@ int kmc_export_setop(kmc_ctx* a, kmc_ctx* b, int op, int count_mode, uint64_t mi
 #define KMC_GRAPH_END_R(adj) (((adj) >> 8) & 1u)
 #define KMC_GRAPH_END_L(adj) (((adj) >> 9) & 1u)
 #define KMC_GRAPH_SOLID(adj) (((adj) >> 10) & 1u)
-/* adj in a ctx-owned device array of uint16_t, valid until the next kmc_graph* call / finalize / reset / destroy (same
+/* adj in a ctx-owned device array of uint16_t, valid until the next kmc_graph* or kmc_unitigs* call / finalize / reset / destroy (same
  * ordering contract as kmc_export_device).  d_adj, n_keys (keys of the view) and summary may each be NULL. */
 int kmc_graph_device(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, const void** d_adj, uint64_t* n_keys,
                      uint64_t* summary);
@@ -332,6 +333,62 @@ int kmc_graph_device(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, const
  * nothing is copied, except that adj == NULL with cap == 0 is the summary-only / sizing call.  summary may be NULL. */
 int kmc_graph(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, void* adj, uint64_t cap, uint64_t* n_keys,
               uint64_t* summary);
+
+/* ---- the unitigs of that graph: the maximal non-branching paths spelled out (additions, as above).  KMC_MODE_CONTIG only,
+ * every k, canonical or forward ctx; the solidity range and the adj words are those of kmc_graph.
+ * SIDE STATES.  a = 2 * row + s, row the view row of a solid key, s = 0 for side R, 1 for side L; a ^ 1 is the other side of
+ *   the same key.
+ * PARTNER AND JOIN.  partner(a) is defined iff side a continues (its end bit in adj is clear): it is (y, T), the one solid
+ *   neighbour y on that side and the side T of y that faces back (the facing-side rule above).  Side a is JOINED to
+ *   b = partner(a) iff partner(b) is defined, partner(b) == a and b != a; otherwise a is a TERMINAL.  The mutual check
+ *   matters: in a canonical ctx a k-mer whose extension is its own reverse complement is its own partner on the same side
+ *   (a hairpin), and for even k a palindromic k-mer makes two of its sides claim the same partner.
+ * SHAPE.  Joins are a symmetric matching on sides; with each key's own pair of sides the solid keys fall into disjoint
+ *   simple paths and simple cycles.
+ * CIRCULAR UNITIGS.  A cycle is cut on the L side of its smallest-row key m: side (m, L) and the side it was joined to
+ *   become terminals, the unitig is marked circular, and from there on it is a path.
+ * ORIENTATION AND SPELLING.  A path with end keys of rows r1, r2 (equal for a one-key unitig) starts at the end key of the
+ *   smaller row and moves away from that key's terminal side; in a forward ctx, or when r1 == r2, the direction that leaves
+ *   keys through side R is used (in a forward ctx the only one that spells a string).  The first key contributes its k
+ *   characters -- as stored if it is left through R, its reverse complement if left through L -- and every further key one
+ *   character, the last of its reading in that same sense.  A unitig of m keys has m + k - 1 bases; a circular one is
+ *   spelled linearly from the cut.
+ * ORDER.  Unitigs are numbered by the view row of their first key, ascending.  Every solid key occurs in exactly one
+ *   unitig, exactly once.
+ * Outputs: bases (ASCII ACGT, concatenated) with offsets[n_unitigs + 1], offsets[0] == 0 -- the layout kmc_add_batch takes;
+ * abund[u] = the sum of the counts of unitig u's keys (exact; the mean is host arithmetic); flags[u] bit 0
+ * (KMC_UNITIG_CIRCULAR) = circular.  summary[KMC_UNITIG_WORDS]: [0] unitigs, [1] bases, [2] keys (= solid keys), [3] circular
+ * unitigs, [4] one-key unitigs, [5] keys of the longest unitig, [6] sides that continue in adj but are not joined (hairpins,
+ * palindromes), [7] sum of abund.  With g the kmc_graph summary of the same range: [1] == [2] + (k - 1) * [0] and
+ * 2 * [0] == g[6] + [6] + 2 * [3].
+ * Rules: those of kmc_graph (NULL ctx, KMC_MODE_LR, a non-zero max_count below min_count: KMC_ERR_ARG; no view:
+ * KMC_ERR_STATE exactly where kmc_export says so; an empty view gives zeros), except that a view of 2^31 keys or more is
+ * KMC_ERR_CAPACITY (a side state is a u32).  The table, the view, a partition, a filter result, a set-operation result and
+ * the query index are not changed.  The adj array of kmc_graph_device IS rewritten: kmc_unitigs* counts as a kmc_graph*
+ * call (it leaves the adj words of its own range there whenever it computes: see kmc_unitigs for the one time it does not).
+ * Diagnostic: with KMC_UNITIG_TRACE set in the environment, every call that computes also prints one line to stderr,
+ * "kmc_unitigs: keys N rounds R cycle_states S adj_ms .. links_ms .. ranking_ms .. cycles_ms .. layout_ms .. emit_ms ..":
+ * its own phase times from event pairs on the ctx's stream, read at the end of the call (tools/measure_unitigs.py reads
+ * them).  It changes no result, queue or graph; unset, it costs one getenv per call. ---- */
+#define KMC_UNITIG_WORDS 8
+#define KMC_UNITIG_CIRCULAR 1u      /* bit 0 of a flags byte */
+/* The four arrays in ctx-owned device memory -- uint8_t bases[n_bases], uint64_t offsets[n_unitigs + 1], uint64_t
+ * abund[n_unitigs], uint8_t flags[n_unitigs] -- valid until the next kmc_unitigs* call / finalize / reset / destroy (same
+ * ordering contract as kmc_export_device).  d_bases / d_offsets obey the alignment and padding rule of kmc_add_batch_device:
+ * they can be handed to kmc_add_batch_device / kmc_profile_device of another ctx on this device.  Every output pointer may
+ * be NULL. */
+int kmc_unitigs_device(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, const void** d_bases, const void** d_offsets,
+                       const void** d_abund, const void** d_flags, uint64_t* n_unitigs, uint64_t* n_bases, uint64_t* summary);
+/* The same, copied to the caller's arrays: bases of cap_bases bytes; offsets of cap_unitigs + 1, abund and flags of cap_unitigs
+ * entries.  Every output pointer may be NULL (an array that is NULL is not copied and its cap not looked at).  *n_unitigs and
+ * *n_bases are always set; a cap too small for an array that was given -> KMC_ERR_ARG and nothing is copied.  All arrays NULL
+ * (caps 0) is the sizing / summary-only call.
+ * Cost: a call computes everything on the device, whatever it copies -- except that a kmc_unitigs call whose ctx still holds
+ * the result of the last kmc_unitigs* call for this very view and range copies from that result instead.  So the sizing
+ * call followed by the call that copies computes once, not twice; any finalize, or a kmc_unitigs* call with another
+ * range, in between makes the second call compute again.  kmc_unitigs_device always computes. */
+int kmc_unitigs(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, uint8_t* bases, uint64_t cap_bases, uint64_t* offsets,
+                uint64_t* abund, uint8_t* flags, uint64_t cap_unitigs, uint64_t* n_unitigs, uint64_t* n_bases, uint64_t* summary);
 
 /* Multi-GPU reduce for small tables: ONE fixed-size all-gather instead of size exchange +
  * all-to-all (the reduce of main.rs:87's grouping across GPUs; for the generator's input a table is

@@ -88,12 +88,15 @@ ABI_SYMBOLS = [
     "kmc_encode_key", "kmc_query", "kmc_query_device", "kmc_profile", "kmc_profile_device",
     "kmc_compare", "kmc_setop_device", "kmc_export_setop",
     "kmc_graph", "kmc_graph_device",
+    "kmc_unitigs", "kmc_unitigs_device",
 ]
 
 PROFILE_WORDS = 5  # KMC_PROFILE_WORDS: valid windows, present windows, min, max, sum
 COMPARE_WORDS = 8  # KMC_COMPARE_WORDS: n_a, n_b, n_both, sum_a, sum_b, shared_sum_a, shared_sum_b, sum_min
 GRAPH_WORDS = 8    # KMC_GRAPH_WORDS: nodes, R degrees, L degrees, isolated, dead ends, branching, end sides, single-node unitigs
 GRAPH_END_R, GRAPH_END_L, GRAPH_SOLID = 1 << 8, 1 << 9, 1 << 10   # bits of an adj word above the two neighbour nibbles (R: 0..3, L: 4..7)
+UNITIG_WORDS = 8   # KMC_UNITIG_WORDS: unitigs, bases, keys, circular, one-key, keys of the longest, unjoined sides, abundance
+UNITIG_CIRCULAR = 1  # KMC_UNITIG_CIRCULAR: bit 0 of a unitig's flags byte
 SETOP_INTERSECT, SETOP_UNION, SETOP_SUBTRACT = 0, 1, 2
 COUNT_LEFT, COUNT_RIGHT, COUNT_MIN, COUNT_MAX, COUNT_SUM, COUNT_DIFF = 0, 1, 2, 3, 4, 5
 SETOP_NAMES = {"intersect": SETOP_INTERSECT, "union": SETOP_UNION, "subtract": SETOP_SUBTRACT}
@@ -161,6 +164,8 @@ def lib() -> C.CDLL:
     L.kmc_export_setop.argtypes = [vp, vp, i32, i32, u64, u64, u64, u64, vp, vp, vp, u64, pu64]
     L.kmc_graph_device.argtypes = [vp, u64, u64, C.POINTER(vp), pu64, vp]
     L.kmc_graph.argtypes = [vp, u64, u64, vp, u64, pu64, vp]
+    L.kmc_unitigs_device.argtypes = [vp, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), pu64, pu64, vp]
+    L.kmc_unitigs.argtypes = [vp, u64, u64, vp, u64, vp, vp, vp, u64, pu64, pu64, vp]
     L.kmc_owner_of.argtypes = [u64, u64, u32]
     L.kmc_owner_of.restype = u32
     L.kmc_get_stats.argtypes = [vp, C.POINTER(Stats)]
@@ -356,6 +361,64 @@ class GraphSummary:
         lines = ["%s\t%d" % (f, getattr(self, f)) for f in _GRAPH_FIELDS]
         lines.append("unitigs\t%d" % self.unitigs)
         return "\n".join(lines) + "\n"
+
+
+_UNITIG_FIELDS = ("unitigs", "bases", "keys", "circular", "one_key", "longest_keys", "unjoined_sides", "abundance")
+
+
+@dataclass
+class UnitigSummary:
+    """The eight words of kmc_unitigs over the solid keys: unitigs, their bases, their keys (= the solid keys), circular
+    unitigs, unitigs of one key, the keys of the longest unitig, sides that continue in the graph but are not joined
+    (hairpins, palindromes), the sum of all abundances."""
+    unitigs: int
+    bases: int
+    keys: int
+    circular: int
+    one_key: int
+    longest_keys: int
+    unjoined_sides: int
+    abundance: int
+
+    @classmethod
+    def from_words(cls, words) -> "UnitigSummary":
+        return cls(*[int(w) for w in words])
+
+    def words(self) -> list:
+        return [getattr(self, f) for f in _UNITIG_FIELDS]
+
+    @property
+    def mean_keys(self) -> float:
+        """Keys per unitig."""
+        return self.keys / self.unitigs if self.unitigs else 0.0
+
+    def to_text(self) -> str:
+        """``NAME\tVALUE`` lines."""
+        return "\n".join("%s\t%d" % (f, getattr(self, f)) for f in _UNITIG_FIELDS) + "\n"
+
+
+@dataclass
+class Unitigs:
+    """What KmerCounter.unitigs returns: ``bases`` uint8[n_bases] (ASCII, concatenated), ``offsets`` uint64[n + 1], ``abund``
+    uint64[n] (summed counts of a unitig's keys), ``flags`` uint8[n] (UNITIG_CIRCULAR), ``summary``."""
+    bases: np.ndarray
+    offsets: np.ndarray
+    abund: np.ndarray
+    flags: np.ndarray
+    summary: UnitigSummary
+
+    def __len__(self) -> int:
+        return len(self.abund)
+
+    def strings(self) -> list:
+        text = self.bases.tobytes().decode("ascii")
+        o = self.offsets
+        return [text[int(o[i]):int(o[i + 1])] for i in range(len(self))]
+
+    def to_fasta(self) -> str:
+        """FASTA as the CLI's --unitigs prints it: ``>INDEX LN:i:BASES KC:i:ABUND CL:i:0|1`` and the sequence on one line."""
+        return "".join(">%d LN:i:%d KC:i:%d CL:i:%d\n%s\n" % (i, len(s), int(self.abund[i]), int(self.flags[i]) & UNITIG_CIRCULAR, s)
+                       for i, s in enumerate(self.strings()))
 
 
 def parse_fasta(path: str) -> Tuple[np.ndarray, np.ndarray]:
@@ -604,6 +667,31 @@ class KmerCounter:
         w = (C.c_uint64 * GRAPH_WORDS)()
         self._chk(self._L.kmc_graph_device(self._h, int(min_count), int(max_count), C.byref(p), C.byref(n), w))
         return p.value or 0, n.value, GraphSummary.from_words(list(w))
+
+    # -- the unitigs of that graph: sequences, abundances, circular flags (of the sorted view; finalize() first) --
+    def unitigs(self, min_count: int = 1, max_count: int = 0) -> "Unitigs":
+        """kmc_unitigs: the maximal non-branching paths of the graph of the keys with min_count <= count <= max_count
+        (max_count 0: no upper bound), spelled out, in the order of their first keys.  Two calls of the library, one
+        computation: the second, which copies, finds the result of the first, which sizes, still in the ctx."""
+        nu, nb = C.c_uint64(), C.c_uint64()
+        w = (C.c_uint64 * UNITIG_WORDS)()
+        lo, hi = int(min_count), int(max_count)
+        self._chk(self._L.kmc_unitigs(self._h, lo, hi, None, 0, None, None, None, 0, C.byref(nu), C.byref(nb), w))
+        bases, flags = np.zeros(nb.value, np.uint8), np.zeros(nu.value, np.uint8)
+        offsets, abund = np.zeros(nu.value + 1, np.uint64), np.zeros(nu.value, np.uint64)
+        self._chk(self._L.kmc_unitigs(self._h, lo, hi, bases.ctypes.data if nb.value else None, nb.value, offsets.ctypes.data,
+                                      abund.ctypes.data if nu.value else None, flags.ctypes.data if nu.value else None, nu.value,
+                                      C.byref(nu), C.byref(nb), w))
+        return Unitigs(bases, offsets, abund, flags, UnitigSummary.from_words(list(w)))
+
+    def unitigs_device(self, min_count: int = 1, max_count: int = 0):
+        """(d_bases, d_offsets, d_abund, d_flags, n_unitigs, n_bases, UnitigSummary) of kmc_unitigs_device: ctx-owned device
+        arrays; d_bases / d_offsets can be handed to another counter's add_batch_device / profile_device."""
+        p = [C.c_void_p() for _ in range(4)]
+        nu, nb = C.c_uint64(), C.c_uint64()
+        w = (C.c_uint64 * UNITIG_WORDS)()
+        self._chk(self._L.kmc_unitigs_device(self._h, int(min_count), int(max_count), *[C.byref(x) for x in p], C.byref(nu), C.byref(nb), w))
+        return tuple(x.value or 0 for x in p) + (nu.value, nb.value, UnitigSummary.from_words(list(w)))
 
     # -- asking the table: key lookups and per-read profiles (of the sorted view; finalize() first) --
     def query(self, key_lo, key_hi=None) -> np.ndarray:

@@ -1537,7 +1537,9 @@ extern "C" void kmc_destroy(kmc_ctx* c) {
                       &c->m_bitmap, &c->m_rank, &c->m_nd, &c->m_base, &c->m_ctl, &c->m_clist, &c->m_w[0], &c->m_w[1],
                       &c->snap_hi, &c->snap_lo, &c->snap_cnt, &c->snap_n, &c->snap_occ, &c->h_hist, &c->c_tile, &c->c_tpos, &c->c_bsum, &c->c_ctl,
                       &c->q_idx, &c->q_khi, &c->q_klo, &c->q_cnt, &c->q_bases, &c->q_offs, &c->q_win, &c->q_stats,
-                      &c->so_pa, &c->so_pb, &c->g_adj, &c->g_ctl};
+                      &c->so_pa, &c->so_pb, &c->g_adj, &c->g_ctl,
+                      &c->u_bases, &c->u_offs, &c->u_abund, &c->u_flags, &c->u_link, &c->u_join, &c->u_ptr[0], &c->u_ptr[1],
+                      &c->u_dist[0], &c->u_dist[1], &c->u_circ, &c->u_ctl};
     KeyBufs* keys[] = {&c->o, &c->t, &c->p, &c->rx, &c->f, &c->so};
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
     sk_free(c);

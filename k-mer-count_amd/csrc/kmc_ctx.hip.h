@@ -172,6 +172,14 @@ struct kmc_ctx {
     DevBuf so_pa, so_pb;
     // kmc_graph / kmc_graph_device (kmc_graph.hip.h): one 16-bit word per key of the view, the eight summary words
     DevBuf g_adj, g_ctl;
+    // kmc_unitigs / kmc_unitigs_device (kmc_unitig.hip.h): the result (bases, offsets, abundances, flags), and the work
+    // arrays over the 2n side states -- links, joins, two (pointer, distance) pairs of the ranking -- the cycle marks per
+    // key, the summary words and round counts.  u_gen / u_min / u_max / u_words: the view and the range the result arrays
+    // were computed for and their summary (u_gen != view_gen: none), so that kmc_unitigs' sizing call and the copy call that
+    // follows it compute once
+    DevBuf u_bases, u_offs, u_abund, u_flags;
+    u64 u_gen = ~0ull, u_min = 0, u_max = 0, u_words[8] = {};
+    DevBuf u_link, u_join, u_ptr[2], u_dist[2], u_circ, u_ctl;
 };
 
 #pragma GCC visibility push(hidden)   // what follows is shared between the translation units, never exported

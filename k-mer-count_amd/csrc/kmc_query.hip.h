@@ -118,6 +118,51 @@ __device__ __forceinline__ void q_lookup(const QView& v, const u64 (&khi)[U], co
     for (int u = 0; u < U; ++u) out[u] = (found >> u) & 1 ? v.cnt[lo[u]] : 0ull;
 }
 
+// The same search for the POSITION: pos[u] = view row of key u, KMC_Q_NOPOS if absent or !(okmask >> u & 1)
+// (kmc_unitig.hip.h: the row of a key's one neighbour).
+#define KMC_Q_NOPOS 0xFFFFFFFFu
+template <int KW, int U>
+__device__ __forceinline__ void q_find(const QView& v, const u64 (&khi)[U], const u64 (&klo)[U], u32 okmask, u32 (&pos)[U]) {
+    u32 lo[U], hi[U];
+    u32 found = 0;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        kmc_u32x2_a4 b = {0u, 0u};
+        if ((okmask >> u) & 1) b = *reinterpret_cast<const kmc_u32x2_a4*>(v.idx + q_prefix<KW>(v.sh, khi[u], klo[u]));
+        lo[u] = b.x; hi[u] = b.y;
+    }
+    u32 live = 0;
+#pragma unroll
+    for (int u = 0; u < U; ++u) live |= lo[u] < hi[u] ? 1u << u : 0u;
+    while (__builtin_amdgcn_ballot_w64(live != 0) != 0) {
+        u64 mlo[U], mhi[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const u32 mid = lo[u] + ((hi[u] - lo[u]) >> 1);
+            mlo[u] = 0; mhi[u] = 0;
+            if ((live >> u) & 1) {
+                mlo[u] = v.lo[mid];
+                if (KW == 2) mhi[u] = v.hi[mid];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if ((live >> u) & 1) {
+                const u32 mid = lo[u] + ((hi[u] - lo[u]) >> 1);
+                const bool eq = mlo[u] == klo[u] && (KW == 1 || mhi[u] == khi[u]);
+                const bool less = KW == 1 ? mlo[u] < klo[u] : key_less(mhi[u], mlo[u], khi[u], klo[u]);
+                if (eq) { lo[u] = mid; found |= 1u << u; live &= ~(1u << u); }
+                else {
+                    if (less) lo[u] = mid + 1; else hi[u] = mid;
+                    if (lo[u] >= hi[u]) live &= ~(1u << u);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) pos[u] = (found >> u) & 1 ? lo[u] : KMC_Q_NOPOS;
+}
+
 // count[i] = count of key i.  A wave takes 64 x KMC_Q_U consecutive keys: lane l the pairs 2 (r * 64 + l) + {0, 1}, r = 0..U/2-1,
 // so every load and store instruction moves 1 KiB contiguous (16 bytes per lane) when the arrays are 16-byte aligned (al16);
 // otherwise the same elements go word by word.  key_hi == nullptr: all high words are zero.

@@ -1,5 +1,7 @@
 // kmc_views.hip -- the calls of include/kmc.h that only READ the sorted view a finalize left in HBM.  From the counting
 // side (kmc_api.hip) they need resolve_view and the ctx (kmc_ctx.hip.h).
+#include <stdlib.h>
+
 #include <type_traits>
 
 #include "kmc_ctx.hip.h"
@@ -9,6 +11,7 @@
 #include "kmc_query.hip.h"
 #include "kmc_setops.hip.h"
 #include "kmc_graph.hip.h"
+#include "kmc_unitig.hip.h"
 
 namespace {
 
@@ -601,6 +604,228 @@ static int kmc_graph_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, vo
     return KMC_OK;
 }
 
+// ---- the unitigs of that graph: sequences, offsets, abundances, flags, summary (kmc_unitig.hip.h) ----
+// u_ctl: [0..7] the summary words ([0] while the call runs: keys the emit kernel could not place, always 0), [8] / [9] the totals of the two layout scans (unitigs, solid keys), then
+// KMC_U_ROUND_SLOTS u32 counts of the ranking rounds
+#define KMC_U_CTL_BYTES (10 * sizeof(u64) + KMC_U_ROUND_SLOTS * sizeof(u32))
+
+// Phase times of one call on stderr when KMC_UNITIG_TRACE is set (tools/measure_unitigs.py reads them): event pairs on the
+// ctx stream, read once at the end of the call.
+struct UnitigTrace {
+    static const int N = 8;
+    bool on = getenv("KMC_UNITIG_TRACE") != nullptr;
+    hipEvent_t ev[N] = {};
+    int n_ev = 0;
+    void mark(hipStream_t s) {
+        if (on && n_ev < N && hipEventCreate(&ev[n_ev]) == hipSuccess) { (void)hipEventRecord(ev[n_ev], s); ++n_ev; }
+    }
+    void report(u64 n, u32 rounds, u32 cycle_states) {
+        if (!on) return;
+        static const char* const name[N - 1] = {"adj", "links", "ranking", "cycles", "layout", "emit", ""};
+        fprintf(stderr, "kmc_unitigs: keys %llu rounds %u cycle_states %u", (unsigned long long)n, rounds, cycle_states);
+        for (int i = 0; i + 1 < n_ev; ++i) {
+            float ms = 0;
+            if (hipEventSynchronize(ev[i + 1]) == hipSuccess && hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess)
+                fprintf(stderr, " %s_ms %.4f", name[i], ms);
+        }
+        fprintf(stderr, "\n");
+    }
+    ~UnitigTrace() { for (int i = 0; i < n_ev; ++i) (void)hipEventDestroy(ev[i]); }
+};
+
+// Ranks the n2 side states along joined (kmc_unitig.hip.h): on return u_ptr[*cur] / u_dist[*cur] hold every path state's end
+// and distance, *open the states on cycles, *rounds is raised by the rounds launched.  Waits for the result.
+static int unitig_rank(kmc_ctx* c, u64 n2, int* cur, u32* rounds, u32* open) {
+    const u32* joined = (const u32*)c->u_join.p;
+    u32* ptr[2] = {(u32*)c->u_ptr[0].p, (u32*)c->u_ptr[1].p};
+    u32* dist[2] = {(u32*)c->u_dist[0].p, (u32*)c->u_dist[1].p};
+    u32* cnt = (u32*)((u64*)c->u_ctl.p + 10);
+    const u32 grid = (u32)((n2 + KMC_U_THREADS - 1) / KMC_U_THREADS);
+    HIPCHK(c, hipMemsetAsync(cnt, 0, KMC_U_ROUND_SLOTS * sizeof(u32), c->stream));
+    hipLaunchKernelGGL(kmc_unitig_rank_init_kernel, dim3(grid), dim3(KMC_U_THREADS), 0, c->stream, joined, n2, ptr[0], dist[0], cnt);
+    int max_rounds = 1;   // ceil(log2(n2)) + 1
+    while ((1ull << (max_rounds - 1)) < n2) ++max_rounds;
+    u32 h[KMC_U_ROUND_SLOTS] = {0};
+    int t = 0, b = 0;
+    bool done = false;
+    while (!done && t < max_rounds) {
+        const int batch = std::min(4, max_rounds - t);
+        for (int i = 0; i < batch; ++i) {
+            ++t;
+            hipLaunchKernelGGL(kmc_unitig_rank_round_kernel, dim3(grid), dim3(KMC_U_THREADS), 0, c->stream, joined, n2, (const u32*)ptr[b],
+                               (const u32*)dist[b], ptr[b ^ 1], dist[b ^ 1], cnt + t);
+            b ^= 1;
+        }
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(h, cnt, (size_t)(t + 1) * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (int s = t - batch + 1; s <= t; ++s) done = done || h[s] == 0 || h[s] == h[s - 1];
+    }
+    *cur = b;
+    *rounds += (u32)t;
+    *open = h[t];
+    return KMC_OK;
+}
+
+// Everything on the device: the four arrays into the ctx's u_* buffers, the summary into h[KMC_UNITIG_WORDS]; finished
+// when it returns (kmc_export_device's ordering contract).
+static int unitig_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count, u64* h) {
+    memset(h, 0, KMC_UNITIG_WORDS * sizeof(u64));
+    const u64 n = c->n_sorted, n2 = 2 * n;
+    int rc;
+    c->u_gen = ~0ull;   // the result arrays are rewritten from here on
+    if ((rc = ensure(c, c->u_offs, sizeof(u64))) || (rc = ensure(c, c->u_bases, 64)) || (rc = ensure(c, c->u_abund, sizeof(u64))) ||
+        (rc = ensure(c, c->u_flags, 8)))
+        return rc;
+    if (!n) {
+        HIPCHK(c, hipMemsetAsync(c->u_offs.p, 0, sizeof(u64), c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return KMC_OK;
+    }
+    UnitigTrace tr;
+    tr.mark(c->stream);
+    u64 g[KMC_GRAPH_WORDS];
+    if ((rc = graph_run(c, what, min_count, max_count, g))) return rc;
+    tr.mark(c->stream);
+    const size_t sb = (size_t)n2 * sizeof(u32);
+    const size_t nsb = (size_t)((n + KMC_SCAN_PER_BLOCK - 1) / KMC_SCAN_PER_BLOCK + 2) * sizeof(u32);
+    if ((rc = ensure(c, c->u_link, sb)) || (rc = ensure(c, c->u_join, sb)) || (rc = ensure(c, c->u_ptr[0], sb)) ||
+        (rc = ensure(c, c->u_ptr[1], sb)) || (rc = ensure(c, c->u_dist[0], sb)) || (rc = ensure(c, c->u_dist[1], sb)) ||
+        (rc = ensure(c, c->u_circ, (size_t)n)) || (rc = ensure(c, c->u_ctl, KMC_U_CTL_BYTES)) || (rc = ensure(c, c->c_bsum, nsb)))
+        return rc;
+    QView v;
+    if ((rc = query_view(c, what, &v))) return rc;
+    const int k = c->klen, canon = c->cfg.canonical ? 1 : 0;
+    const uint16_t* adj = (const uint16_t*)c->g_adj.p;
+    u32 *link = (u32*)c->u_link.p, *joined = (u32*)c->u_join.p;
+    uint8_t* circ = (uint8_t*)c->u_circ.p;
+    kmc_ull* ctl = (kmc_ull*)c->u_ctl.p;
+    const u32 grid_n = (u32)((n + KMC_U_THREADS - 1) / KMC_U_THREADS), grid_2n = (u32)((n2 + KMC_U_THREADS - 1) / KMC_U_THREADS);
+    HIPCHK(c, hipMemsetAsync(ctl, 0, KMC_U_CTL_BYTES, c->stream));
+    HIPCHK(c, hipMemsetAsync(circ, 0, (size_t)n, c->stream));
+    // links and joins
+    with_kw_canon(c, [&](auto KW, auto CANON) {
+        hipLaunchKernelGGL((kmc_unitig_link_kernel<KW(), CANON()>), dim3(grid_n), dim3(KMC_U_THREADS), 0, c->stream, v, k, adj, link);
+    });
+    hipLaunchKernelGGL(kmc_unitig_join_kernel, dim3(grid_2n), dim3(KMC_U_THREADS), 0, c->stream, (const u32*)link, n2, joined, ctl + 6);
+    HIPCHK(c, hipGetLastError());
+    tr.mark(c->stream);
+    // ranking; cycles, if there are any, are cut and the ranking runs again
+    int cur = 0;
+    u32 rounds = 0, open = 0, cycle_states = 0;
+    if ((rc = unitig_rank(c, n2, &cur, &rounds, &open))) return rc;
+    tr.mark(c->stream);
+    if (open) {
+        cycle_states = open;
+        u32* ptr[2] = {(u32*)c->u_ptr[0].p, (u32*)c->u_ptr[1].p};
+        u32* mrow[2] = {(u32*)c->u_dist[0].p, (u32*)c->u_dist[1].p};
+        hipLaunchKernelGGL(kmc_unitig_cycle_mark_kernel, dim3(grid_n), dim3(KMC_U_THREADS), 0, c->stream, (const u32*)joined,
+                           (const u32*)ptr[cur], n, circ);
+        hipLaunchKernelGGL(kmc_unitig_minrow_init_kernel, dim3(grid_2n), dim3(KMC_U_THREADS), 0, c->stream, (const u32*)joined, n2, ptr[0], mrow[0]);
+        int cover = 0, b = 0;   // 2^cover states of a cycle seen from every state: the longest cycle has at most `open`
+        while ((1ull << cover) < open) ++cover;
+        for (int i = 0; i < cover; ++i) {
+            hipLaunchKernelGGL(kmc_unitig_minrow_round_kernel, dim3(grid_2n), dim3(KMC_U_THREADS), 0, c->stream, n2, (const u32*)ptr[b],
+                               (const u32*)mrow[b], ptr[b ^ 1], mrow[b ^ 1]);
+            b ^= 1;
+        }
+        hipLaunchKernelGGL(kmc_unitig_cycle_cut_kernel, dim3(grid_n), dim3(KMC_U_THREADS), 0, c->stream, (const u32*)mrow[b], n, joined, circ);
+        HIPCHK(c, hipGetLastError());
+        if ((rc = unitig_rank(c, n2, &cur, &rounds, &open))) return rc;
+        if (open) return fail(c, KMC_ERR_HIP, "internal error: %s left %u side states on cycles after the cut", what, open);
+    }
+    tr.mark(c->stream);
+    // layout: first keys and their key counts (link is free now), their scans (joined is free now)
+    const u32 *ptr = (const u32*)c->u_ptr[cur].p, *dist = (const u32*)c->u_dist[cur].p;
+    u32 *is_first = link, *first_len = link + n, *uid_of = joined, *koff_of = joined + n;
+    hipLaunchKernelGGL(kmc_unitig_place_kernel, dim3(grid_n), dim3(KMC_U_THREADS), 0, c->stream, n, adj, ptr, dist, canon, is_first, first_len);
+    launch_exclusive_scan<0>(c->stream, is_first, (u32)n, (u32*)c->c_bsum.p, uid_of, (u32*)(ctl + 8));
+    launch_exclusive_scan<0>(c->stream, first_len, (u32)n, (u32*)c->c_bsum.p, koff_of, (u32*)(ctl + 9));
+    HIPCHK(c, hipGetLastError());
+    u64 w[10];
+    HIPCHK(c, hipMemcpyAsync(w, ctl, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const u64 nu = w[8], nk = w[9], nb = nk + (u64)(k - 1) * nu;
+    tr.mark(c->stream);
+    // emit (d_bases is readable up to the next 16-byte boundary: the rule of kmc_add_batch_device)
+    if ((rc = ensure(c, c->u_bases, (size_t)nb + 64)) || (rc = ensure(c, c->u_offs, (size_t)(nu + 1) * sizeof(u64))) ||
+        (rc = ensure(c, c->u_abund, (size_t)std::max<u64>(nu, 1) * sizeof(u64))) || (rc = ensure(c, c->u_flags, (size_t)std::max<u64>(nu, 8))))
+        return rc;
+    HIPCHK(c, hipMemsetAsync(c->u_abund.p, 0, (size_t)std::max<u64>(nu, 1) * sizeof(u64), c->stream));
+    with_kw(c, [&](auto KW) {
+        hipLaunchKernelGGL(kmc_unitig_emit_kernel<KW()>, dim3((u32)grid_for(c, n, KMC_U_THREADS)), dim3(KMC_U_THREADS), 0, c->stream,
+                           static_cast<const KView&>(v), k, canon, adj, ptr, dist, (const u32*)uid_of, (const u32*)koff_of, (const uint8_t*)circ,
+                           nu, nb, (uint8_t*)c->u_bases.p, (u64*)c->u_offs.p, (kmc_ull*)c->u_abund.p, (uint8_t*)c->u_flags.p, ctl);
+    });
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(w, ctl, KMC_UNITIG_WORDS * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    tr.mark(c->stream);
+    if (w[0]) return fail(c, KMC_ERR_HIP, "internal error: %s could not place %llu solid keys in the layout", what, (unsigned long long)w[0]);
+    h[0] = nu; h[1] = nb; h[2] = nk; h[3] = w[3]; h[4] = w[4]; h[5] = w[5]; h[6] = w[6]; h[7] = w[7];
+    tr.report(n, rounds, cycle_states);
+    return KMC_OK;
+}
+
+static int unitig_begin(kmc_ctx* c, const char* what, uint64_t min_count, uint64_t max_count) {
+    if (int rc = graph_begin(c, what, min_count, max_count)) return rc;
+    if (c->n_sorted >= (1ull << 31)) return fail(c, KMC_ERR_CAPACITY, "%s: a view of 2^31 keys or more has more sides than a u32 numbers", what);
+    return KMC_OK;
+}
+
+// the result arrays now hold the unitigs of this view and range (nothing but unitig_run writes them)
+static void unitig_keep(kmc_ctx* c, uint64_t min_count, uint64_t max_count, const u64* h) {
+    c->u_gen = c->view_gen; c->u_min = min_count; c->u_max = max_count;
+    memcpy(c->u_words, h, sizeof(c->u_words));
+}
+
+static int kmc_unitigs_device_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, const void** d_bases, const void** d_offsets,
+                                   const void** d_abund, const void** d_flags, uint64_t* n_unitigs, uint64_t* n_bases, uint64_t* summary) {
+    if (!c) return KMC_ERR_ARG;
+    u64 h[KMC_UNITIG_WORDS];
+    int rc;
+    if ((rc = unitig_begin(c, "kmc_unitigs_device", min_count, max_count)) || (rc = unitig_run(c, "kmc_unitigs_device", min_count, max_count, h))) return rc;
+    unitig_keep(c, min_count, max_count, h);
+    if (d_bases) *d_bases = c->u_bases.p;
+    if (d_offsets) *d_offsets = c->u_offs.p;
+    if (d_abund) *d_abund = c->u_abund.p;
+    if (d_flags) *d_flags = c->u_flags.p;
+    if (n_unitigs) *n_unitigs = h[0];
+    if (n_bases) *n_bases = h[1];
+    if (summary) memcpy(summary, h, sizeof(h));
+    return KMC_OK;
+}
+
+static int kmc_unitigs_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint8_t* bases, uint64_t cap_bases, uint64_t* offsets,
+                            uint64_t* abund, uint8_t* flags, uint64_t cap_unitigs, uint64_t* n_unitigs, uint64_t* n_bases, uint64_t* summary) {
+    if (n_unitigs) *n_unitigs = 0;
+    if (n_bases) *n_bases = 0;
+    if (!c) return KMC_ERR_ARG;
+    u64 h[KMC_UNITIG_WORDS];
+    int rc;
+    if ((rc = unitig_begin(c, "kmc_unitigs", min_count, max_count))) return rc;
+    if (c->u_gen == c->view_gen && c->u_min == min_count && c->u_max == max_count) {
+        memcpy(h, c->u_words, sizeof(h));   // the arrays of this view and range are still there: the call after a sizing call
+    } else {
+        if ((rc = unitig_run(c, "kmc_unitigs", min_count, max_count, h))) return rc;
+        unitig_keep(c, min_count, max_count, h);
+    }
+    const u64 nu = h[0], nb = h[1];
+    if (n_unitigs) *n_unitigs = nu;
+    if (n_bases) *n_bases = nb;
+    if (bases && cap_bases < nb)
+        return fail(c, KMC_ERR_ARG, "kmc_unitigs: capacity %llu < %llu bases", (unsigned long long)cap_bases, (unsigned long long)nb);
+    if ((offsets || abund || flags) && cap_unitigs < nu)
+        return fail(c, KMC_ERR_ARG, "kmc_unitigs: capacity %llu < %llu unitigs", (unsigned long long)cap_unitigs, (unsigned long long)nu);
+    if (bases && nb) HIPCHK(c, hipMemcpyAsync(bases, c->u_bases.p, (size_t)nb, hipMemcpyDeviceToHost, c->stream));
+    if (offsets) HIPCHK(c, hipMemcpyAsync(offsets, c->u_offs.p, (size_t)(nu + 1) * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    if (abund && nu) HIPCHK(c, hipMemcpyAsync(abund, c->u_abund.p, (size_t)nu * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    if (flags && nu) HIPCHK(c, hipMemcpyAsync(flags, c->u_flags.p, (size_t)nu, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (summary) memcpy(summary, h, sizeof(h));
+    return KMC_OK;
+}
+
 // ---- the ABI proper (guarded: no C++ exception leaves the library) ----
 extern "C" int kmc_export(kmc_ctx* c, uint64_t* key_hi, uint64_t* key_lo, uint64_t* count, uint64_t cap) {
     return guarded(c, [&]() -> int { return kmc_export_impl(c, key_hi, key_lo, count, cap); });
@@ -654,6 +879,18 @@ extern "C" int kmc_graph_device(kmc_ctx* c, uint64_t min_count, uint64_t max_cou
 }
 extern "C" int kmc_graph(kmc_ctx* c, uint64_t min_count, uint64_t max_count, void* adj, uint64_t cap, uint64_t* n_keys, uint64_t* summary) {
     return guarded(c, [&]() -> int { return kmc_graph_impl(c, min_count, max_count, adj, cap, n_keys, summary); });
+}
+extern "C" int kmc_unitigs_device(kmc_ctx* c, uint64_t min_count, uint64_t max_count, const void** d_bases, const void** d_offsets,
+                                  const void** d_abund, const void** d_flags, uint64_t* n_unitigs, uint64_t* n_bases, uint64_t* summary) {
+    return guarded(c, [&]() -> int {
+        return kmc_unitigs_device_impl(c, min_count, max_count, d_bases, d_offsets, d_abund, d_flags, n_unitigs, n_bases, summary);
+    });
+}
+extern "C" int kmc_unitigs(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint8_t* bases, uint64_t cap_bases, uint64_t* offsets,
+                           uint64_t* abund, uint8_t* flags, uint64_t cap_unitigs, uint64_t* n_unitigs, uint64_t* n_bases, uint64_t* summary) {
+    return guarded(c, [&]() -> int {
+        return kmc_unitigs_impl(c, min_count, max_count, bases, cap_bases, offsets, abund, flags, cap_unitigs, n_unitigs, n_bases, summary);
+    });
 }
 extern "C" int kmc_partition_device(kmc_ctx* c, uint32_t n_parts, uint64_t* part_begin, const void** d_key_hi,
                                     const void** d_key_lo, const void** d_count) {

@@ -26,6 +26,10 @@ pub const KMC_COUNT_SUM: i32 = 4;
 pub const KMC_COUNT_DIFF: i32 = 5;
 /// summary words of `kmc_graph`
 pub const KMC_GRAPH_WORDS: usize = 8;
+/// summary words of `kmc_unitigs`
+pub const KMC_UNITIG_WORDS: usize = 8;
+/// bit 0 of a unitig's flags byte
+pub const KMC_UNITIG_CIRCULAR: u8 = 1;
 
 // The structs and the extern block below are checked against include/kmc.h by
 // tests/test_abi_host.py::test_rust_binding_matches_the_header (names, arity, argument types, field
@@ -131,6 +135,9 @@ extern "C" {
     // the table as a de Bruijn graph: neighbour masks, unitig ends, summary (adj: uint16_t per key of the view)
     pub fn kmc_graph_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, d_adj: *mut *const c_void, n_keys: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_graph(ctx: *mut KmcCtx, min_count: u64, max_count: u64, adj: *mut c_void, cap: u64, n_keys: *mut u64, summary: *mut u64) -> c_int;
+    // the unitigs of that graph: bases + offsets, abundances, flags, summary
+    pub fn kmc_unitigs_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, d_bases: *mut *const c_void, d_offsets: *mut *const c_void, d_abund: *mut *const c_void, d_flags: *mut *const c_void, n_unitigs: *mut u64, n_bases: *mut u64, summary: *mut u64) -> c_int;
+    pub fn kmc_unitigs(ctx: *mut KmcCtx, min_count: u64, max_count: u64, bases: *mut u8, cap_bases: u64, offsets: *mut u64, abund: *mut u64, flags: *mut u8, cap_unitigs: u64, n_unitigs: *mut u64, n_bases: *mut u64, summary: *mut u64) -> c_int;
     // multi-GPU reduce (one process per GPU; the collective itself is the host program's, e.g. RCCL)
     pub fn kmc_slab_words(ctx: *const KmcCtx, slab_entries: u64) -> u64;
     pub fn kmc_pack_slab_device(ctx: *mut KmcCtx, d_slab: *mut c_void, slab_entries: u64) -> c_int;
@@ -351,6 +358,32 @@ impl Counter {
         let mut n = 0u64;
         self.check(unsafe { kmc_graph(self.ctx, min_count, max_count, adj.as_mut_ptr() as *mut c_void, nd, &mut n, w.as_mut_ptr()) })?;
         Ok((adj, w))
+    }
+
+    /// The unitigs of that graph (`kmc_unitigs`), in order: (sequence, summed count of its keys, circular) per unitig, and
+    /// the eight summary words [unitigs, bases, keys, circular, one-key, keys of the longest, unjoined sides, abundance].
+    pub fn unitigs(&mut self, min_count: u64, max_count: u64) -> Result<(Vec<(String, u64, bool)>, [u64; KMC_UNITIG_WORDS]), KmcError> {
+        let (mut nd, mut nt) = (0u64, 0u64);
+        self.check(unsafe { kmc_finalize(self.ctx, &mut nd, &mut nt) })?;
+        let (mut nu, mut nb) = (0u64, 0u64);
+        let mut w = [0u64; KMC_UNITIG_WORDS];
+        let null8 = std::ptr::null_mut::<u8>();
+        let null64 = std::ptr::null_mut::<u64>();
+        self.check(unsafe { kmc_unitigs(self.ctx, min_count, max_count, null8, 0, null64, null64, null8, 0, &mut nu, &mut nb, w.as_mut_ptr()) })?;
+        let mut bases = vec![0u8; nb as usize];
+        let mut offsets = vec![0u64; nu as usize + 1];
+        let mut abund = vec![0u64; nu as usize];
+        let mut flags = vec![0u8; nu as usize];
+        self.check(unsafe {
+            kmc_unitigs(self.ctx, min_count, max_count, bases.as_mut_ptr(), nb, offsets.as_mut_ptr(), abund.as_mut_ptr(), flags.as_mut_ptr(), nu,
+                        &mut nu, &mut nb, w.as_mut_ptr())
+        })?;
+        let mut out = Vec::with_capacity(nu as usize);
+        for u in 0..nu as usize {
+            let s = String::from_utf8_lossy(&bases[offsets[u] as usize..offsets[u + 1] as usize]).into_owned();
+            out.push((s, abund[u], flags[u] & KMC_UNITIG_CIRCULAR != 0));
+        }
+        Ok((out, w))
     }
 }
 
