@@ -24,6 +24,7 @@
  *   (addition: no equivalent in the reference)             kmc_compare / kmc_setop_device / kmc_export_setop (two tables)
  *   (addition: no equivalent in the reference)             kmc_graph / kmc_graph_device (de Bruijn graph of the table)
  *   (addition: no equivalent in the reference)             kmc_unitigs / kmc_unitigs_device (its unitig sequences)
+ *   (addition: no equivalent in the reference)             kmc_unitig_links / kmc_unitig_links_device (the edges between them)
  *
  * Conventions
  *   - Every function returns 0 (KMC_OK) or a negative kmc_status; no exception or abort crosses
@@ -389,6 +390,58 @@ int kmc_unitigs_device(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, con
  * range, in between makes the second call compute again.  kmc_unitigs_device always computes. */
 int kmc_unitigs(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, uint8_t* bases, uint64_t cap_bases, uint64_t* offsets,
                 uint64_t* abund, uint8_t* flags, uint64_t cap_unitigs, uint64_t* n_unitigs, uint64_t* n_bases, uint64_t* summary);
+
+/* ---- the links between those unitigs: the edges of the compacted graph (additions, as above).  Everything refers to the
+ * unitigs of kmc_unitigs for the same view and range: their numbering, their spelling, the joins after the cycle cuts.
+ * UNITIG ENDS.  Unitig u, spelled as the string S_u, has two ends: end 2u + 1, the END end, is the side through which the
+ *   reading leaves the last key; end 2u + 0, the START end, is the side of the first key opposite the one it is left
+ *   through.  A one-key unitig owns both sides of its key.  Every unitig end is one terminal side state, and every terminal
+ *   side state of a solid key is exactly one unitig end.  With rc the reading sense of a key (read on its other strand or
+ *   not), its exit side is L if rc, else R; side T of a key is its unitig's END end iff T is the exit side, else the START
+ *   end (one-key unitigs included).
+ * LINK RECORDS.  For a unitig end with side state a = (x, S): every base c whose bit is set in the S nibble of adj[x], in
+ *   ascending c; (y, T) = ext(x, S, c) and its facing side by the rules of kmc_graph.  If (y, T) is a terminal side state
+ *   this is one record end(a) -> end(y, T), stored as the uint32_t 2v + e of the target end.  If it is not, no record is
+ *   written and summary[5] counts it: that happens only around a palindromic key, so only for even k in a canonical ctx.
+ *   Records are directed and every one is kept: a link normally appears twice, once from each end, and nothing is
+ *   deduplicated.  A hairpin gives a single record from an end to itself; a cut cycle gives END -> START of the same unitig;
+ *   around palindromic keys the record set need not be symmetric.
+ * IN GFA TERMS.  Leaving u through its END end reads u+, through its START end u-; arriving at the START end of v reads
+ *   v+, at its END end v-.  A record is "L u o1 v o2 (k-1)M": the last k - 1 bases of the oriented u equal the first k - 1 of
+ *   the oriented v.  In a forward ctx every END-end record is + + and every START-end record its mirror.
+ * Outputs: link_offsets[2 * n_unitigs + 1], uint64_t, indexed by end, link_offsets[0] == 0; link_to[n_links], uint32_t; the
+ * records of end i are link_to[link_offsets[i] .. link_offsets[i + 1]).  summary[KMC_LINK_WORDS]: [0] unitigs, [1] records,
+ * [2] ends with no record, [3] ends with two or more, [4] records whose target is the source's own unitig, [5] extensions
+ * dropped because the target side is not terminal, [6] unitigs with no record at either end, [7] the largest number of
+ * records at one end (at most 4).  With g the kmc_graph and t the kmc_unitigs summary of the same range:
+ * g[1] + g[2] == [1] + [5] + 2 * (t[2] - t[0]) (every side that is not a unitig end has degree 1).
+ * Rules: those of kmc_unitigs (NULL ctx, KMC_MODE_LR, a non-zero max_count below min_count: KMC_ERR_ARG; no view:
+ * KMC_ERR_STATE; a view of 2^31 keys or more: KMC_ERR_CAPACITY; an empty view gives zeros and link_offsets[0] == 0); 2^32
+ * records or more: KMC_ERR_CAPACITY.  The table, the view, a partition, a filter result, a set-operation result and the
+ * query index are not changed.
+ * RELATION TO kmc_unitigs.  A links call counts as a kmc_unitigs* call.  If the ctx still holds the unitigs of this very
+ * view and range, and no kmc_graph* call has rewritten the adj words since, it runs the links pass alone; otherwise it
+ * computes the unitigs first and keeps that result.  So kmc_unitigs followed by kmc_unitig_links with the same range
+ * computes the unitigs once, and the ids in the records are those of the arrays kmc_unitigs handed out (they are in any
+ * case: the numbering depends on the view and the range alone).
+ * Diagnostic: with KMC_UNITIG_TRACE set, a links call that computes prints "kmc_unitig_links: keys N unitigs U records R
+ * unitigs_reused 0|1 links_ms .." to stderr -- a line of its own, behind the kmc_unitigs line if it computed the unitigs
+ * too, because that line already calls its partner phase links_ms (tools/measure_links.py reads both). ---- */
+#define KMC_LINK_WORDS 8
+/* The two arrays in ctx-owned device memory -- uint64_t link_offsets[2 * n_unitigs + 1], uint32_t link_to[n_links] -- valid
+ * until the next kmc_unitig_links*, kmc_unitigs* or kmc_graph* call / finalize / reset / destroy (same ordering contract as
+ * kmc_export_device).  Every output pointer may be NULL.  Always computes the links pass. */
+int kmc_unitig_links_device(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, const void** d_link_offsets,
+                            const void** d_link_to, uint64_t* n_unitigs, uint64_t* n_links, uint64_t* summary);
+/* The same, copied to the caller's arrays.  cap_ends counts ENDS: link_offsets has room for cap_ends + 1 entries and needs
+ * cap_ends >= 2 * *n_unitigs (not 2 * n_unitigs + 1); link_to has cap_links entries.  Every output pointer may be NULL (an
+ * array that is NULL is not copied and its cap not looked at).  *n_unitigs and *n_links are always set; a cap too small for
+ * an array that was given -> KMC_ERR_ARG and nothing is copied.  Both arrays NULL is the sizing / summary-only call.  A call
+ * whose ctx still holds the links of the last kmc_unitig_links* call for this very view and range copies from that result
+ * (the sizing call followed by the call that copies computes once); a finalize, or a kmc_unitigs* or kmc_unitig_links*
+ * call that computes, in between makes it compute again. */
+int kmc_unitig_links(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, uint64_t* link_offsets, uint64_t cap_ends,
+                     uint32_t* link_to, uint64_t cap_links, uint64_t* n_unitigs, uint64_t* n_links, uint64_t* summary);
 
 /* Multi-GPU reduce for small tables: ONE fixed-size all-gather instead of size exchange +
  * all-to-all (the reduce of main.rs:87's grouping across GPUs; for the generator's input a table is

@@ -89,6 +89,7 @@ ABI_SYMBOLS = [
     "kmc_compare", "kmc_setop_device", "kmc_export_setop",
     "kmc_graph", "kmc_graph_device",
     "kmc_unitigs", "kmc_unitigs_device",
+    "kmc_unitig_links", "kmc_unitig_links_device",
 ]
 
 PROFILE_WORDS = 5  # KMC_PROFILE_WORDS: valid windows, present windows, min, max, sum
@@ -97,6 +98,7 @@ GRAPH_WORDS = 8    # KMC_GRAPH_WORDS: nodes, R degrees, L degrees, isolated, dea
 GRAPH_END_R, GRAPH_END_L, GRAPH_SOLID = 1 << 8, 1 << 9, 1 << 10   # bits of an adj word above the two neighbour nibbles (R: 0..3, L: 4..7)
 UNITIG_WORDS = 8   # KMC_UNITIG_WORDS: unitigs, bases, keys, circular, one-key, keys of the longest, unjoined sides, abundance
 UNITIG_CIRCULAR = 1  # KMC_UNITIG_CIRCULAR: bit 0 of a unitig's flags byte
+LINK_WORDS = 8     # KMC_LINK_WORDS: unitigs, records, ends without / with several records, self records, dropped, isolated unitigs, most at one end
 SETOP_INTERSECT, SETOP_UNION, SETOP_SUBTRACT = 0, 1, 2
 COUNT_LEFT, COUNT_RIGHT, COUNT_MIN, COUNT_MAX, COUNT_SUM, COUNT_DIFF = 0, 1, 2, 3, 4, 5
 SETOP_NAMES = {"intersect": SETOP_INTERSECT, "union": SETOP_UNION, "subtract": SETOP_SUBTRACT}
@@ -166,6 +168,8 @@ def lib() -> C.CDLL:
     L.kmc_graph.argtypes = [vp, u64, u64, vp, u64, pu64, vp]
     L.kmc_unitigs_device.argtypes = [vp, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), pu64, pu64, vp]
     L.kmc_unitigs.argtypes = [vp, u64, u64, vp, u64, vp, vp, vp, u64, pu64, pu64, vp]
+    L.kmc_unitig_links_device.argtypes = [vp, u64, u64, C.POINTER(vp), C.POINTER(vp), pu64, pu64, vp]
+    L.kmc_unitig_links.argtypes = [vp, u64, u64, vp, u64, vp, u64, pu64, pu64, vp]
     L.kmc_owner_of.argtypes = [u64, u64, u32]
     L.kmc_owner_of.restype = u32
     L.kmc_get_stats.argtypes = [vp, C.POINTER(Stats)]
@@ -419,6 +423,67 @@ class Unitigs:
         """FASTA as the CLI's --unitigs prints it: ``>INDEX LN:i:BASES KC:i:ABUND CL:i:0|1`` and the sequence on one line."""
         return "".join(">%d LN:i:%d KC:i:%d CL:i:%d\n%s\n" % (i, len(s), int(self.abund[i]), int(self.flags[i]) & UNITIG_CIRCULAR, s)
                        for i, s in enumerate(self.strings()))
+
+    def to_gfa(self, links: "UnitigLinks", k: int) -> str:
+        """GFA 1.0 as the CLI's --gfa prints it: ``H VN:Z:1.0``, one ``S INDEX SEQ LN:i:BASES KC:i:ABUND CL:i:0|1`` per
+        unitig, one ``L U +|- V +|- (k-1)M`` per record of ``links`` (KmerCounter.unitig_links of the same range), tab-separated."""
+        if len(links.offsets) != 2 * len(self) + 1:
+            raise ValueError("the links are not those of these unitigs")
+        out = ["H\tVN:Z:1.0\n"]
+        out += ["S\t%d\t%s\tLN:i:%d\tKC:i:%d\tCL:i:%d\n" % (i, s, len(s), int(self.abund[i]), int(self.flags[i]) & UNITIG_CIRCULAR)
+                for i, s in enumerate(self.strings())]
+        out += ["L\t%d\t%s\t%d\t%s\t%dM\n" % (u, o1, v, o2, k - 1) for u, o1, v, o2 in links.records()]
+        return "".join(out)
+
+
+_LINK_FIELDS = ("unitigs", "records", "ends_without", "ends_branching", "self_records", "dropped", "isolated_unitigs", "max_records")
+
+
+@dataclass
+class LinkSummary:
+    """The eight words of kmc_unitig_links: unitigs, link records, unitig ends with no record, ends with two or more,
+    records whose target is the source's own unitig, extensions dropped because the side they reach is not a terminal
+    (around palindromic keys), unitigs with no record at either end, the most records at one end."""
+    unitigs: int
+    records: int
+    ends_without: int
+    ends_branching: int
+    self_records: int
+    dropped: int
+    isolated_unitigs: int
+    max_records: int
+
+    @classmethod
+    def from_words(cls, words) -> "LinkSummary":
+        return cls(*[int(w) for w in words])
+
+    def words(self) -> list:
+        return [getattr(self, f) for f in _LINK_FIELDS]
+
+    def to_text(self) -> str:
+        """``NAME\tVALUE`` lines."""
+        return "\n".join("%s\t%d" % (f, getattr(self, f)) for f in _LINK_FIELDS) + "\n"
+
+
+@dataclass
+class UnitigLinks:
+    """What KmerCounter.unitig_links returns: ``offsets`` uint64[2 n + 1] indexed by unitig end (2u: the START end of unitig
+    u, 2u + 1: its END end), ``to`` uint32[records] (the target ends), ``summary``.  The records of end i are
+    ``to[offsets[i]:offsets[i + 1]]``."""
+    offsets: np.ndarray
+    to: np.ndarray
+    summary: LinkSummary
+
+    def __len__(self) -> int:
+        return len(self.to)
+
+    def records(self):
+        """(u, o1, v, o2) per record in array order, in GFA terms: leaving u through its END end reads ``u +``, through
+        its START end ``u -``; arriving at the START end of v reads ``v +``, at its END end ``v -``."""
+        o = self.offsets
+        for i in range(len(o) - 1):
+            for t in self.to[int(o[i]):int(o[i + 1])]:
+                yield i >> 1, "+" if i & 1 else "-", int(t) >> 1, "-" if int(t) & 1 else "+"
 
 
 def parse_fasta(path: str) -> Tuple[np.ndarray, np.ndarray]:
@@ -692,6 +757,28 @@ class KmerCounter:
         w = (C.c_uint64 * UNITIG_WORDS)()
         self._chk(self._L.kmc_unitigs_device(self._h, int(min_count), int(max_count), *[C.byref(x) for x in p], C.byref(nu), C.byref(nb), w))
         return tuple(x.value or 0 for x in p) + (nu.value, nb.value, UnitigSummary.from_words(list(w)))
+
+    # -- the links between those unitigs: the edges of the compacted graph (of the sorted view; finalize() first) --
+    def unitig_links(self, min_count: int = 1, max_count: int = 0) -> "UnitigLinks":
+        """kmc_unitig_links: per unitig end the ends it reaches, for the unitigs of unitigs() with the same range (called
+        right after it, the unitigs are not computed again).  Two calls of the library, one computation, as in unitigs()."""
+        nu, nl = C.c_uint64(), C.c_uint64()
+        w = (C.c_uint64 * LINK_WORDS)()
+        lo, hi = int(min_count), int(max_count)
+        self._chk(self._L.kmc_unitig_links(self._h, lo, hi, None, 0, None, 0, C.byref(nu), C.byref(nl), w))
+        offsets, to = np.zeros(2 * nu.value + 1, np.uint64), np.zeros(nl.value, np.uint32)
+        self._chk(self._L.kmc_unitig_links(self._h, lo, hi, offsets.ctypes.data, 2 * nu.value, to.ctypes.data if nl.value else None,
+                                           nl.value, C.byref(nu), C.byref(nl), w))
+        return UnitigLinks(offsets, to, LinkSummary.from_words(list(w)))
+
+    def unitig_links_device(self, min_count: int = 1, max_count: int = 0):
+        """(d_link_offsets, d_link_to, n_unitigs, n_links, LinkSummary) of kmc_unitig_links_device: ctx-owned device arrays
+        of 2 * n_unitigs + 1 uint64 and n_links uint32."""
+        p = [C.c_void_p() for _ in range(2)]
+        nu, nl = C.c_uint64(), C.c_uint64()
+        w = (C.c_uint64 * LINK_WORDS)()
+        self._chk(self._L.kmc_unitig_links_device(self._h, int(min_count), int(max_count), *[C.byref(x) for x in p], C.byref(nu), C.byref(nl), w))
+        return tuple(x.value or 0 for x in p) + (nu.value, nl.value, LinkSummary.from_words(list(w)))
 
     # -- asking the table: key lookups and per-read profiles (of the sorted view; finalize() first) --
     def query(self, key_lo, key_hi=None) -> np.ndarray:

@@ -1539,7 +1539,8 @@ extern "C" void kmc_destroy(kmc_ctx* c) {
                       &c->q_idx, &c->q_khi, &c->q_klo, &c->q_cnt, &c->q_bases, &c->q_offs, &c->q_win, &c->q_stats,
                       &c->so_pa, &c->so_pb, &c->g_adj, &c->g_ctl,
                       &c->u_bases, &c->u_offs, &c->u_abund, &c->u_flags, &c->u_link, &c->u_join, &c->u_ptr[0], &c->u_ptr[1],
-                      &c->u_dist[0], &c->u_dist[1], &c->u_circ, &c->u_ctl};
+                      &c->u_dist[0], &c->u_dist[1], &c->u_circ, &c->u_ctl,
+                      &c->l_offs, &c->l_to, &c->l_cnt, &c->l_pos, &c->l_tgt, &c->l_ctl};
     KeyBufs* keys[] = {&c->o, &c->t, &c->p, &c->rx, &c->f, &c->so};
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
     sk_free(c);

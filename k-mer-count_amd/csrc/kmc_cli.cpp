@@ -7,7 +7,7 @@
 //   k-mer-count [FASTA] [-k K] [--forward] [--expand] [--device N | --gpus N] [--algo auto|stream|walk|sort] [--stats]
 //               [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE]
 //               [--with FASTA2 (--compare | --setop intersect|union|subtract [--counts left|right|min|max|sum|diff])]
-//               [--graph | --graph-stats | --unitigs]
+//               [--graph | --graph-stats | --unitigs | --gfa]
 //
 //   --gpus N  the file's chunks go round-robin to GPUs 0..N-1 of this process, tables reduced on GPU 0
 //             (there is no CPU backend: SURVEY.md's "--backend cpu" is deliberately absent)
@@ -43,6 +43,9 @@
 //   --unitigs            (with -k K) instead of the table: the unitigs of that graph (kmc_unitigs) as FASTA, one record per unitig
 //               in order: ">INDEX LN:i:BASES KC:i:ABUND CL:i:0|1" (ABUND the summed count of its keys, CL 1 for a circular
 //               one), then the sequence on one line.  --min-count / --max-count are the solidity range.
+//   --gfa                (with -k K) instead of the table: those unitigs and the links between them (kmc_unitig_links) as GFA 1.0,
+//               tab-separated: "H VN:Z:1.0", then per unitig in order "S INDEX SEQ LN:i:BASES KC:i:ABUND CL:i:0|1", then per link
+//               record in array order "L U +|- V +|- (K-1)M" (every link appears from both of its ends).  Same solidity range.
 //
 // Errors: message on stderr, exit code 101 (what a Rust panic exits with), never partial stdout.
 #include <errno.h>
@@ -93,7 +96,7 @@ int main(int argc, char** argv) {
     int k = 0, canonical = 1, expand = 0, device = 0, algo = KMC_ALGO_AUTO, stats = 0, gpus = 1, histo = 0;
     long long min_count = 1, max_count = 0;   // (max_count 0: no upper bound)
     const char *query_path = nullptr, *profile_path = nullptr, *with_path = nullptr;
-    int compare = 0, setop = -1, count_mode = -1, graph = 0, graph_stats = 0, unitigs = 0;
+    int compare = 0, setop = -1, count_mode = -1, graph = 0, graph_stats = 0, unitigs = 0, gfa = 0;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         if (a == "-k" && i + 1 < argc) { if (!parse_int("-k", argv[++i], 1, 63, &k)) return 2; }
@@ -112,6 +115,7 @@ int main(int argc, char** argv) {
         else if (a == "--graph") graph = 1;
         else if (a == "--graph-stats") graph_stats = 1;
         else if (a == "--unitigs") unitigs = 1;
+        else if (a == "--gfa") gfa = 1;
         else if (a == "--setop" && i + 1 < argc) {
             std::string v = argv[++i];
             setop = v == "intersect" ? KMC_SETOP_INTERSECT : v == "union" ? KMC_SETOP_UNION : v == "subtract" ? KMC_SETOP_SUBTRACT : -1;
@@ -128,7 +132,7 @@ int main(int argc, char** argv) {
             fprintf(stderr, "usage: k-mer-count [FASTA] [-k K] [--forward] [--expand] [--device N | --gpus N] [--algo auto|stream|walk|sort] [--stats]\n"
                             "                   [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE]\n"
                             "                   [--with FASTA2 (--compare | --setop intersect|union|subtract [--counts left|right|min|max|sum|diff])]\n"
-                            "                   [--graph | --graph-stats | --unitigs]\n");
+                            "                   [--graph | --graph-stats | --unitigs | --gfa]\n");
             return 0;
         } else if (a == "-k" || a == "--device" || a == "--gpus" || a == "--algo" || a == "--min-count" || a == "--max-count" || a == "--histo" ||
                    a == "--query-kmers" || a == "--profile" || a == "--with" || a == "--setop" || a == "--counts") {
@@ -194,12 +198,13 @@ int main(int argc, char** argv) {
         else if (with_path && gpus != 1) bad = "--with and --gpus exclude each other";
         if (bad) { fprintf(stderr, "k-mer-count: %s\n", bad); return 2; }
     }
-    // --graph / --graph-stats / --unitigs: the same
-    if (graph || graph_stats || unitigs) {
-        const char* opt = graph ? "--graph" : graph_stats ? "--graph-stats" : "--unitigs";
+    // --graph / --graph-stats / --unitigs / --gfa: the same
+    if (graph || graph_stats || unitigs || gfa) {
+        const char* opt = graph ? "--graph" : graph_stats ? "--graph-stats" : unitigs ? "--unitigs" : "--gfa";
         const char* bad = nullptr;
         if (graph && graph_stats) bad = "--graph-stats exclude each other";
         else if ((graph || graph_stats) && unitigs) bad = "--unitigs exclude each other";
+        else if ((graph || graph_stats || unitigs) && gfa) bad = "--gfa exclude each other";
         else if (!k) bad = "needs -k K";
         else if (histo) bad = "--histo exclude each other";
         else if (query_path || profile_path) bad = "--query-kmers / --profile exclude each other";
@@ -307,7 +312,7 @@ int main(int argc, char** argv) {
         destroy_all();
         return 0;
     }
-    if (unitigs) {
+    if (unitigs || gfa) {
         uint64_t nu = 0, nb = 0;
         rc = kmc_unitigs(ctx, (uint64_t)min_count, (uint64_t)max_count, nullptr, 0, nullptr, nullptr, nullptr, 0, &nu, &nb, nullptr);
         if (rc) { int r = die("kmc_unitigs", kmc_last_error(ctx)); destroy_all(); return r; }
@@ -315,7 +320,34 @@ int main(int argc, char** argv) {
         std::vector<uint64_t> uo(nu + 1), ua(nu ? nu : 1);
         rc = kmc_unitigs(ctx, (uint64_t)min_count, (uint64_t)max_count, ub.data(), nb, uo.data(), ua.data(), uf.data(), nu, &nu, &nb, nullptr);
         if (rc) { int r = die("kmc_unitigs", kmc_last_error(ctx)); destroy_all(); return r; }
+        std::vector<uint64_t> lo_(1);
+        std::vector<uint32_t> lt(1);
+        uint64_t nl = 0;
+        if (gfa) {   // (the unitigs are still in the ctx: the links pass alone runs)
+            rc = kmc_unitig_links(ctx, (uint64_t)min_count, (uint64_t)max_count, nullptr, 0, nullptr, 0, &nu, &nl, nullptr);
+            if (rc) { int r = die("kmc_unitig_links", kmc_last_error(ctx)); destroy_all(); return r; }
+            lo_.resize(2 * nu + 1);
+            lt.resize(nl ? nl : 1);
+            rc = kmc_unitig_links(ctx, (uint64_t)min_count, (uint64_t)max_count, lo_.data(), 2 * nu, lt.data(), nl, &nu, &nl, nullptr);
+            if (rc) { int r = die("kmc_unitig_links", kmc_last_error(ctx)); destroy_all(); return r; }
+        }
         setvbuf(stdout, obuf.data(), _IOFBF, obuf.size());
+        if (gfa) {
+            printf("H\tVN:Z:1.0\n");
+            for (uint64_t u = 0; u < nu; ++u) {
+                printf("S\t%llu\t", (unsigned long long)u);
+                fwrite(ub.data() + uo[u], 1, (size_t)(uo[u + 1] - uo[u]), stdout);
+                printf("\tLN:i:%llu\tKC:i:%llu\tCL:i:%u\n", (unsigned long long)(uo[u + 1] - uo[u]), (unsigned long long)ua[u],
+                       (unsigned)(uf[u] & KMC_UNITIG_CIRCULAR));
+            }
+            for (uint64_t e = 0; e < 2 * nu; ++e)
+                for (uint64_t j = lo_[e]; j < lo_[e + 1]; ++j)
+                    printf("L\t%llu\t%c\t%llu\t%c\t%dM\n", (unsigned long long)(e >> 1), (e & 1) ? '+' : '-', (unsigned long long)(lt[j] >> 1),
+                           (lt[j] & 1) ? '-' : '+', k - 1);
+            fflush(stdout);
+            destroy_all();
+            return 0;
+        }
         for (uint64_t u = 0; u < nu; ++u) {
             printf(">%llu LN:i:%llu KC:i:%llu CL:i:%u\n", (unsigned long long)u, (unsigned long long)(uo[u + 1] - uo[u]),
                    (unsigned long long)ua[u], (unsigned)(uf[u] & KMC_UNITIG_CIRCULAR));

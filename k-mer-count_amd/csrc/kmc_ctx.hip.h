@@ -180,6 +180,15 @@ struct kmc_ctx {
     DevBuf u_bases, u_offs, u_abund, u_flags;
     u64 u_gen = ~0ull, u_min = 0, u_max = 0, u_words[8] = {};
     DevBuf u_link, u_join, u_ptr[2], u_dist[2], u_circ, u_ctl;
+    // kmc_unitig_links / kmc_unitig_links_device (kmc_links.hip.h) read what unitig_run left besides its result: adj, the
+    // final ranking u_ptr[u_cur] / u_dist[u_cur], the unitig ids in u_join.  u_live says those are still the ones of the
+    // result u_gen names: unitig_run sets it when it is through, anything that rewrites adj (graph_run) clears it.
+    // The result (offsets per end, targets) with l_gen / l_min / l_max / l_words as above, the work arrays per end
+    // (counts, their scan), the resolved targets per view row, the control words.
+    int u_cur = 0;
+    bool u_live = false;
+    DevBuf l_offs, l_to, l_cnt, l_pos, l_tgt, l_ctl;
+    u64 l_gen = ~0ull, l_min = 0, l_max = 0, l_words[8] = {};
 };
 
 #pragma GCC visibility push(hidden)   // what follows is shared between the translation units, never exported

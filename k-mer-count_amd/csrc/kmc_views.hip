@@ -12,6 +12,7 @@
 #include "kmc_setops.hip.h"
 #include "kmc_graph.hip.h"
 #include "kmc_unitig.hip.h"
+#include "kmc_links.hip.h"
 
 namespace {
 
@@ -547,6 +548,7 @@ static int graph_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count,
     memset(h, 0, KMC_GRAPH_WORDS * sizeof(u64));
     const u64 n = c->n_sorted;
     int rc;
+    c->u_live = false;   // adj is rewritten from here on: a kept unitig result no longer has its work arrays
     if ((rc = ensure(c, c->g_adj, (size_t)std::max<u64>(n, 1) * sizeof(uint16_t))) || (rc = ensure(c, c->g_ctl, KMC_GRAPH_WORDS * sizeof(u64)))) return rc;
     if (!n) return KMC_OK;
     QView v;
@@ -673,7 +675,7 @@ static int unitig_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count
     memset(h, 0, KMC_UNITIG_WORDS * sizeof(u64));
     const u64 n = c->n_sorted, n2 = 2 * n;
     int rc;
-    c->u_gen = ~0ull;   // the result arrays are rewritten from here on
+    c->u_gen = c->l_gen = ~0ull;   // the result arrays are rewritten from here on (and the links of the old ones go with them)
     if ((rc = ensure(c, c->u_offs, sizeof(u64))) || (rc = ensure(c, c->u_bases, 64)) || (rc = ensure(c, c->u_abund, sizeof(u64))) ||
         (rc = ensure(c, c->u_flags, 8)))
         return rc;
@@ -763,6 +765,8 @@ static int unitig_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count
     tr.mark(c->stream);
     if (w[0]) return fail(c, KMC_ERR_HIP, "internal error: %s could not place %llu solid keys in the layout", what, (unsigned long long)w[0]);
     h[0] = nu; h[1] = nb; h[2] = nk; h[3] = w[3]; h[4] = w[4]; h[5] = w[5]; h[6] = w[6]; h[7] = w[7];
+    c->u_cur = cur;      // what kmc_unitig_links reads: adj, u_ptr / u_dist[cur], uid_of in u_join
+    c->u_live = true;
     tr.report(n, rounds, cycle_states);
     return KMC_OK;
 }
@@ -821,6 +825,144 @@ static int kmc_unitigs_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, 
     if (offsets) HIPCHK(c, hipMemcpyAsync(offsets, c->u_offs.p, (size_t)(nu + 1) * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     if (abund && nu) HIPCHK(c, hipMemcpyAsync(abund, c->u_abund.p, (size_t)nu * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     if (flags && nu) HIPCHK(c, hipMemcpyAsync(flags, c->u_flags.p, (size_t)nu, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (summary) memcpy(summary, h, sizeof(h));
+    return KMC_OK;
+}
+
+// ---- the links between those unitigs: offsets per unitig end, target ends, summary (kmc_links.hip.h) ----
+// The count pass keeps the targets it resolved in a scratch of 32 bytes per view row and the fill pass reads them
+// (DESIGN.md has the numbers); KMC_LINKS_LOOKUP_TWICE in the environment makes the fill pass look them up again instead --
+// a diagnostic for tools/measure_links.py, the result is the same.
+template <bool FILL>
+static void links_launch(kmc_ctx* c, const QView& v, bool scratch, u64 nu, u64 n_links) {
+    const u64 want = (v.n + KMC_L_THREADS - 1) / KMC_L_THREADS;
+    const int k = c->klen;
+    with_kw_canon(c, [&](auto KW, auto CANON) {
+        auto go = [&](auto SC) {
+            auto kern = kmc_links_kernel<KW(), CANON(), FILL, SC()>;
+            int per_cu = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, KMC_L_THREADS, 0) != hipSuccess || per_cu < 1) per_cu = 4;
+            const u32 grid = (u32)std::min<u64>(want, (u64)c->n_cu * (u64)per_cu);
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(KMC_L_THREADS), 0, c->stream, v, k, (const uint16_t*)c->g_adj.p,
+                               (const u32*)c->u_ptr[c->u_cur].p, (const u32*)c->u_dist[c->u_cur].p, (const u32*)c->u_join.p, nu, n_links,
+                               (u32*)c->l_tgt.p, (u32*)c->l_cnt.p, (const u32*)c->l_pos.p, (u32*)c->l_to.p, (kmc_ull*)c->l_ctl.p);
+        };
+        if (scratch) go(std::true_type{}); else go(std::false_type{});
+    });
+}
+
+// The links of the unitigs the ctx holds (u_words, u_live) into l_offs / l_to, the summary into h[KMC_LINK_WORDS]; finished
+// when it returns.
+static int links_run(kmc_ctx* c, const char* what, u64* h) {
+    memset(h, 0, KMC_LINK_WORDS * sizeof(u64));
+    const u64 n = c->n_sorted, nu = c->u_words[0], ne = 2 * nu;
+    int rc;
+    c->l_gen = ~0ull;
+    if ((rc = ensure(c, c->l_offs, (size_t)(ne + 1) * sizeof(u64))) || (rc = ensure(c, c->l_to, sizeof(u32)))) return rc;
+    if (!nu) {   // an empty view, or one without a solid key
+        HIPCHK(c, hipMemsetAsync(c->l_offs.p, 0, sizeof(u64), c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return KMC_OK;
+    }
+    if (nu > n) return fail(c, KMC_ERR_HIP, "internal error: %s found %llu unitigs of %llu keys", what, (unsigned long long)nu, (unsigned long long)n);
+    const bool scratch = getenv("KMC_LINKS_LOOKUP_TWICE") == nullptr;
+    const size_t eb = (size_t)ne * sizeof(u32);
+    if ((rc = ensure(c, c->l_cnt, eb)) || (rc = ensure(c, c->l_pos, eb)) || (rc = ensure(c, c->l_ctl, KMC_L_CTL_WORDS * sizeof(u64))) ||
+        (rc = ensure(c, c->c_bsum, (size_t)((ne + KMC_SCAN_PER_BLOCK - 1) / KMC_SCAN_PER_BLOCK + 2) * sizeof(u32))) ||
+        (scratch && (rc = ensure(c, c->l_tgt, (size_t)n * 8 * sizeof(u32)))))
+        return rc;
+    QView v;
+    if ((rc = query_view(c, what, &v))) return rc;
+    kmc_ull* ctl = (kmc_ull*)c->l_ctl.p;
+    HIPCHK(c, hipMemsetAsync(ctl, 0, KMC_L_CTL_WORDS * sizeof(u64), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->l_cnt.p, 0, eb, c->stream));
+    links_launch<false>(c, v, scratch, nu, 0);
+    HIPCHK(c, hipGetLastError());
+    u64 w[KMC_L_CTL_WORDS];
+    HIPCHK(c, hipMemcpyAsync(w, ctl, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (w[KMC_L_BAD]) return fail(c, KMC_ERR_HIP, "internal error: %s met %llu indices outside their arrays", what, (unsigned long long)w[KMC_L_BAD]);
+    const u64 nl = w[1];
+    if (nl >= (1ull << 32)) return fail(c, KMC_ERR_CAPACITY, "%s: 2^32 link records or more", what);
+    if ((rc = ensure(c, c->l_to, (size_t)std::max<u64>(nl, 1) * sizeof(u32)))) return rc;
+    launch_exclusive_scan<0>(c->stream, c->l_cnt.p, (u32)ne, (u32*)c->c_bsum.p, (u32*)c->l_pos.p, (u32*)ctl);
+    hipLaunchKernelGGL(kmc_links_offsets_kernel, dim3((u32)((nu + KMC_L_THREADS - 1) / KMC_L_THREADS)), dim3(KMC_L_THREADS), 0, c->stream,
+                       (const u32*)c->l_cnt.p, (const u32*)c->l_pos.p, nu, nl, (u64*)c->l_offs.p, ctl);
+    if (nl) links_launch<true>(c, v, scratch, nu, nl);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(w, ctl, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (w[KMC_L_BAD] || (w[0] & 0xFFFFFFFFull) != nl)
+        return fail(c, KMC_ERR_HIP, "internal error: %s could not place its records (%llu outside, %llu scanned of %llu)", what,
+                    (unsigned long long)w[KMC_L_BAD], (unsigned long long)(w[0] & 0xFFFFFFFFull), (unsigned long long)nl);
+    h[0] = nu; h[1] = nl;
+    for (int i = 2; i < KMC_LINK_WORDS; ++i) h[i] = w[i];
+    return KMC_OK;
+}
+
+// What both calls do once their arguments are in order: the kept links (host form only), or the links pass behind the
+// kept unitigs of this view and range if their work arrays are still theirs, or behind a unitig_run of its own.
+static int links_result(kmc_ctx* c, const char* what, u64 min_count, u64 max_count, bool may_reuse, u64* h) {
+    if (may_reuse && c->l_gen == c->view_gen && c->l_min == min_count && c->l_max == max_count) {
+        memcpy(h, c->l_words, sizeof(c->l_words));
+        return KMC_OK;
+    }
+    int rc;
+    const bool kept = c->u_live && c->u_gen == c->view_gen && c->u_min == min_count && c->u_max == max_count;
+    if (!kept) {
+        u64 t[KMC_UNITIG_WORDS];
+        if ((rc = unitig_run(c, what, min_count, max_count, t))) return rc;
+        unitig_keep(c, min_count, max_count, t);
+    }
+    UnitigTrace tr;
+    tr.mark(c->stream);
+    if ((rc = links_run(c, what, h))) return rc;
+    tr.mark(c->stream);
+    if (tr.on && tr.n_ev == 2) {
+        float ms = 0;
+        if (hipEventSynchronize(tr.ev[1]) == hipSuccess && hipEventElapsedTime(&ms, tr.ev[0], tr.ev[1]) == hipSuccess)
+            fprintf(stderr, "kmc_unitig_links: keys %llu unitigs %llu records %llu unitigs_reused %d links_ms %.4f\n",
+                    (unsigned long long)c->n_sorted, (unsigned long long)h[0], (unsigned long long)h[1], kept ? 1 : 0, ms);
+    }
+    c->l_gen = c->view_gen; c->l_min = min_count; c->l_max = max_count;
+    memcpy(c->l_words, h, sizeof(c->l_words));
+    return KMC_OK;
+}
+
+static int kmc_unitig_links_device_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, const void** d_link_offsets,
+                                        const void** d_link_to, uint64_t* n_unitigs, uint64_t* n_links, uint64_t* summary) {
+    if (!c) return KMC_ERR_ARG;
+    u64 h[KMC_LINK_WORDS];
+    int rc;
+    if ((rc = unitig_begin(c, "kmc_unitig_links_device", min_count, max_count)) ||
+        (rc = links_result(c, "kmc_unitig_links_device", min_count, max_count, false, h))) return rc;
+    if (d_link_offsets) *d_link_offsets = c->l_offs.p;
+    if (d_link_to) *d_link_to = c->l_to.p;
+    if (n_unitigs) *n_unitigs = h[0];
+    if (n_links) *n_links = h[1];
+    if (summary) memcpy(summary, h, sizeof(h));
+    return KMC_OK;
+}
+
+static int kmc_unitig_links_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t* link_offsets, uint64_t cap_ends,
+                                 uint32_t* link_to, uint64_t cap_links, uint64_t* n_unitigs, uint64_t* n_links, uint64_t* summary) {
+    if (n_unitigs) *n_unitigs = 0;
+    if (n_links) *n_links = 0;
+    if (!c) return KMC_ERR_ARG;
+    u64 h[KMC_LINK_WORDS];
+    int rc;
+    if ((rc = unitig_begin(c, "kmc_unitig_links", min_count, max_count)) ||
+        (rc = links_result(c, "kmc_unitig_links", min_count, max_count, true, h))) return rc;
+    const u64 ne = 2 * h[0], nl = h[1];
+    if (n_unitigs) *n_unitigs = h[0];
+    if (n_links) *n_links = nl;
+    if (link_offsets && cap_ends < ne)
+        return fail(c, KMC_ERR_ARG, "kmc_unitig_links: capacity %llu < %llu unitig ends", (unsigned long long)cap_ends, (unsigned long long)ne);
+    if (link_to && cap_links < nl)
+        return fail(c, KMC_ERR_ARG, "kmc_unitig_links: capacity %llu < %llu records", (unsigned long long)cap_links, (unsigned long long)nl);
+    if (link_offsets) HIPCHK(c, hipMemcpyAsync(link_offsets, c->l_offs.p, (size_t)(ne + 1) * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    if (link_to && nl) HIPCHK(c, hipMemcpyAsync(link_to, c->l_to.p, (size_t)nl * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (summary) memcpy(summary, h, sizeof(h));
     return KMC_OK;
@@ -890,6 +1032,18 @@ extern "C" int kmc_unitigs(kmc_ctx* c, uint64_t min_count, uint64_t max_count, u
                            uint64_t* abund, uint8_t* flags, uint64_t cap_unitigs, uint64_t* n_unitigs, uint64_t* n_bases, uint64_t* summary) {
     return guarded(c, [&]() -> int {
         return kmc_unitigs_impl(c, min_count, max_count, bases, cap_bases, offsets, abund, flags, cap_unitigs, n_unitigs, n_bases, summary);
+    });
+}
+extern "C" int kmc_unitig_links_device(kmc_ctx* c, uint64_t min_count, uint64_t max_count, const void** d_link_offsets, const void** d_link_to,
+                                       uint64_t* n_unitigs, uint64_t* n_links, uint64_t* summary) {
+    return guarded(c, [&]() -> int {
+        return kmc_unitig_links_device_impl(c, min_count, max_count, d_link_offsets, d_link_to, n_unitigs, n_links, summary);
+    });
+}
+extern "C" int kmc_unitig_links(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t* link_offsets, uint64_t cap_ends,
+                                uint32_t* link_to, uint64_t cap_links, uint64_t* n_unitigs, uint64_t* n_links, uint64_t* summary) {
+    return guarded(c, [&]() -> int {
+        return kmc_unitig_links_impl(c, min_count, max_count, link_offsets, cap_ends, link_to, cap_links, n_unitigs, n_links, summary);
     });
 }
 extern "C" int kmc_partition_device(kmc_ctx* c, uint32_t n_parts, uint64_t* part_begin, const void** d_key_hi,

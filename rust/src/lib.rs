@@ -30,6 +30,8 @@ pub const KMC_GRAPH_WORDS: usize = 8;
 pub const KMC_UNITIG_WORDS: usize = 8;
 /// bit 0 of a unitig's flags byte
 pub const KMC_UNITIG_CIRCULAR: u8 = 1;
+/// summary words of `kmc_unitig_links`
+pub const KMC_LINK_WORDS: usize = 8;
 
 // The structs and the extern block below are checked against include/kmc.h by
 // tests/test_abi_host.py::test_rust_binding_matches_the_header (names, arity, argument types, field
@@ -138,6 +140,9 @@ extern "C" {
     // the unitigs of that graph: bases + offsets, abundances, flags, summary
     pub fn kmc_unitigs_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, d_bases: *mut *const c_void, d_offsets: *mut *const c_void, d_abund: *mut *const c_void, d_flags: *mut *const c_void, n_unitigs: *mut u64, n_bases: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitigs(ctx: *mut KmcCtx, min_count: u64, max_count: u64, bases: *mut u8, cap_bases: u64, offsets: *mut u64, abund: *mut u64, flags: *mut u8, cap_unitigs: u64, n_unitigs: *mut u64, n_bases: *mut u64, summary: *mut u64) -> c_int;
+    // the links between those unitigs: offsets per unitig end, target ends, summary
+    pub fn kmc_unitig_links_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, d_link_offsets: *mut *const c_void, d_link_to: *mut *const c_void, n_unitigs: *mut u64, n_links: *mut u64, summary: *mut u64) -> c_int;
+    pub fn kmc_unitig_links(ctx: *mut KmcCtx, min_count: u64, max_count: u64, link_offsets: *mut u64, cap_ends: u64, link_to: *mut u32, cap_links: u64, n_unitigs: *mut u64, n_links: *mut u64, summary: *mut u64) -> c_int;
     // multi-GPU reduce (one process per GPU; the collective itself is the host program's, e.g. RCCL)
     pub fn kmc_slab_words(ctx: *const KmcCtx, slab_entries: u64) -> u64;
     pub fn kmc_pack_slab_device(ctx: *mut KmcCtx, d_slab: *mut c_void, slab_entries: u64) -> c_int;
@@ -384,6 +389,26 @@ impl Counter {
             out.push((s, abund[u], flags[u] & KMC_UNITIG_CIRCULAR != 0));
         }
         Ok((out, w))
+    }
+
+    /// The links between those unitigs (`kmc_unitig_links`): `offsets[2 n + 1]` indexed by unitig end (2u: the START end of
+    /// unitig u, 2u + 1: its END end), the target ends of the records, and the eight summary words [unitigs, records, ends
+    /// without a record, ends with two or more, self records, dropped, isolated unitigs, most records at one end].  Called
+    /// after `unitigs` with the same range it does not compute the unitigs again.
+    pub fn unitig_links(&mut self, min_count: u64, max_count: u64) -> Result<(Vec<u64>, Vec<u32>, [u64; KMC_LINK_WORDS]), KmcError> {
+        let (mut nd, mut nt) = (0u64, 0u64);
+        self.check(unsafe { kmc_finalize(self.ctx, &mut nd, &mut nt) })?;
+        let (mut nu, mut nl) = (0u64, 0u64);
+        let mut w = [0u64; KMC_LINK_WORDS];
+        self.check(unsafe {
+            kmc_unitig_links(self.ctx, min_count, max_count, std::ptr::null_mut::<u64>(), 0, std::ptr::null_mut::<u32>(), 0, &mut nu, &mut nl, w.as_mut_ptr())
+        })?;
+        let mut offsets = vec![0u64; 2 * nu as usize + 1];
+        let mut to = vec![0u32; nl as usize];
+        self.check(unsafe {
+            kmc_unitig_links(self.ctx, min_count, max_count, offsets.as_mut_ptr(), 2 * nu, to.as_mut_ptr(), nl, &mut nu, &mut nl, w.as_mut_ptr())
+        })?;
+        Ok((offsets, to, w))
     }
 }
 
