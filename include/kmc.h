@@ -25,6 +25,7 @@
  *   (addition: no equivalent in the reference)             kmc_graph / kmc_graph_device (de Bruijn graph of the table)
  *   (addition: no equivalent in the reference)             kmc_unitigs / kmc_unitigs_device (its unitig sequences)
  *   (addition: no equivalent in the reference)             kmc_unitig_links / kmc_unitig_links_device (the edges between them)
+ *   (addition: no equivalent in the reference)             kmc_unitig_clean / kmc_unitig_clean_device / kmc_unitig_clean_into (tips and islands removed)
  *
  * Conventions
  *   - Every function returns 0 (KMC_OK) or a negative kmc_status; no exception or abort crosses
@@ -442,6 +443,63 @@ int kmc_unitig_links_device(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count
  * call that computes, in between makes it compute again. */
 int kmc_unitig_links(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, uint64_t* link_offsets, uint64_t cap_ends,
                      uint32_t* link_to, uint64_t cap_links, uint64_t* n_unitigs, uint64_t* n_links, uint64_t* summary);
+
+/* ---- the compacted graph cleaned: tips clipped, islands dropped (additions, as above).  Everything refers to the unitigs
+ * and the link records of kmc_unitigs / kmc_unitig_links for the same view and range min_count..max_count.  For unitig u:
+ * m_u = offsets[u + 1] - offsets[u] - (k - 1) its number of keys, A_u = abund[u], rec(e) the record list of end e.
+ * ISLAND.  u is an island iff it is not circular, rec(2u) and rec(2u + 1) are both empty and m_u <= max_island_keys.
+ * TIP CANDIDATE.  u is a tip candidate iff it is not circular, m_u <= max_tip_keys, exactly one of its ends has no record and
+ *   the other, the attached end a, has exactly one.  (A stem that leads into a fork has two or more records at its attached
+ *   end: it is no candidate.)
+ * TIP.  Let t be the one record of a.  The siblings of u are the records s of rec(t) with s != a and s >> 1 != u.  u is a tip
+ *   iff it is a candidate and some sibling's unitig w = s >> 1 dominates it: w is not a tip candidate, or w is one and beats u
+ *   -- by higher mean abundance, compared exactly as the 128-bit products A_w * m_u > A_u * m_w; on a tie by m_w > m_u; on
+ *   a tie by w < u.  So of the dead-end arms that compete at one junction exactly the best survives, and beside any sibling
+ *   that is not a candidate (a long one, or one that continues) every candidate goes.  Hairpins get no special case (a
+ *   record from an end to itself gives no sibling), nor do the dropped or asymmetric records around palindromic keys: the
+ *   formula is the definition.
+ * VERDICT.  verdict[u], a uint8_t: KMC_CLEAN_KEEP, KMC_CLEAN_TIP or KMC_CLEAN_ISLAND.  (An island is never a candidate.)
+ * KEPT TABLE.  The solid keys whose unitig's verdict is KEEP, in view order, with their counts: key_hi (NULL / zeros when
+ *   keys fit one word), key_lo, count -- the shape of a view, as kmc_filter_device gives it, so that it goes straight into
+ *   another ctx through kmc_merge_pairs_device.
+ * summary[KMC_CLEAN_WORDS]: [0] unitigs, [1] tips, [2] islands, [3] keys kept, [4] keys of tips, [5] keys of islands, [6] tip
+ *   candidates (those that survive included), [7] the sum of the counts of the kept keys.  With t the kmc_unitigs summary of
+ *   the same range: [3] + [4] + [5] == t[2].
+ * LIMITS.  max_tip_keys == 0 clips nothing, max_island_keys == 0 drops nothing; with both 0 the kept table equals
+ *   kmc_export_filtered of the range.  A limit of 2^31 or more is unlimited.
+ * Rules: those of kmc_unitig_links (NULL ctx, KMC_MODE_LR, a non-zero max_count below min_count: KMC_ERR_ARG; no view:
+ * KMC_ERR_STATE; the capacity rules of the links: KMC_ERR_CAPACITY; an empty view gives zeros).
+ * RELATION TO THE OTHER VIEW CALLS.  A clean call counts as a kmc_unitig_links* call: it reuses the unitigs and links the ctx
+ * still holds for this view and range (and whose work arrays no kmc_graph* call has rewritten), otherwise it computes them
+ * and keeps them.  It rewrites neither of them, nor adj, nor the view, a partition, a filter result, a set-operation result
+ * or the query index: the arrays a preceding links or unitigs call of this range handed out stay valid.
+ * Diagnostic: with KMC_UNITIG_TRACE set, a clean pass prints "kmc_unitig_clean: keys N unitigs U tips T islands I kept K
+ * clean_ms .." to stderr, behind the lines of the unitigs and links it had to compute (tools/measure_clean.py reads it). ---- */
+#define KMC_CLEAN_WORDS 8
+#define KMC_CLEAN_KEEP 0
+#define KMC_CLEAN_TIP 1
+#define KMC_CLEAN_ISLAND 2
+/* The kept table and uint8_t verdict[n_unitigs] in ctx-owned device memory, valid until the next kmc_unitig_clean*,
+ * kmc_unitig_links*, kmc_unitigs* or kmc_graph* call / finalize / reset / destroy (same ordering contract as
+ * kmc_export_device).  Every output pointer may be NULL.  Always computes the clean pass. */
+int kmc_unitig_clean_device(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, uint64_t max_tip_keys, uint64_t max_island_keys,
+                            const void** d_key_hi, const void** d_key_lo, const void** d_count, const void** d_verdict,
+                            uint64_t* n_kept, uint64_t* n_unitigs, uint64_t* summary);
+/* The same, copied to the caller's arrays: key_hi / key_lo / count of cap_keys entries each, verdict of cap_unitigs bytes.
+ * Every output pointer may be NULL (an array that is NULL is not copied and its cap not looked at).  *n_kept and *n_unitigs
+ * are always set; a cap too small for an array that was given -> KMC_ERR_ARG and nothing is copied.  All arrays NULL is the
+ * sizing / summary-only call.  A call whose ctx still holds the clean result for this very view, range and pair of limits
+ * copies from it: the sizing call followed by the call that copies computes once. */
+int kmc_unitig_clean(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, uint64_t max_tip_keys, uint64_t max_island_keys,
+                     uint64_t* key_hi, uint64_t* key_lo, uint64_t* count, uint64_t cap_keys, uint8_t* verdict, uint64_t cap_unitigs,
+                     uint64_t* n_kept, uint64_t* n_unitigs, uint64_t* summary);
+/* One step of a cleaning round: kmc_unitig_clean_device on src, then the kept pairs merged into dst as
+ * kmc_merge_pairs_device(dst, ...) would; the merge has finished when the call returns.  dst must differ from src and agree
+ * with it in device, mode, k and canonical (KMC_ERR_ARG otherwise; errors are reported on src).  dst is left un-finalized,
+ * so several sources can be merged; kmc_finalize(dst) then gives the cleaned table, on which the next round's kmc_unitigs /
+ * kmc_unitig_links / kmc_unitig_clean_into run.  summary may be NULL. */
+int kmc_unitig_clean_into(kmc_ctx* src, kmc_ctx* dst, uint64_t min_count, uint64_t max_count, uint64_t max_tip_keys,
+                          uint64_t max_island_keys, uint64_t* summary);
 
 /* Multi-GPU reduce for small tables: ONE fixed-size all-gather instead of size exchange +
  * all-to-all (the reduce of main.rs:87's grouping across GPUs; for the generator's input a table is

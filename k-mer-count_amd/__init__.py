@@ -90,6 +90,7 @@ ABI_SYMBOLS = [
     "kmc_graph", "kmc_graph_device",
     "kmc_unitigs", "kmc_unitigs_device",
     "kmc_unitig_links", "kmc_unitig_links_device",
+    "kmc_unitig_clean", "kmc_unitig_clean_device", "kmc_unitig_clean_into",
 ]
 
 PROFILE_WORDS = 5  # KMC_PROFILE_WORDS: valid windows, present windows, min, max, sum
@@ -99,6 +100,8 @@ GRAPH_END_R, GRAPH_END_L, GRAPH_SOLID = 1 << 8, 1 << 9, 1 << 10   # bits of an a
 UNITIG_WORDS = 8   # KMC_UNITIG_WORDS: unitigs, bases, keys, circular, one-key, keys of the longest, unjoined sides, abundance
 UNITIG_CIRCULAR = 1  # KMC_UNITIG_CIRCULAR: bit 0 of a unitig's flags byte
 LINK_WORDS = 8     # KMC_LINK_WORDS: unitigs, records, ends without / with several records, self records, dropped, isolated unitigs, most at one end
+CLEAN_WORDS = 8    # KMC_CLEAN_WORDS: unitigs, tips, islands, keys kept / of tips / of islands, tip candidates, sum of the kept counts
+CLEAN_KEEP, CLEAN_TIP, CLEAN_ISLAND = 0, 1, 2   # KMC_CLEAN_*: a unitig's verdict byte
 SETOP_INTERSECT, SETOP_UNION, SETOP_SUBTRACT = 0, 1, 2
 COUNT_LEFT, COUNT_RIGHT, COUNT_MIN, COUNT_MAX, COUNT_SUM, COUNT_DIFF = 0, 1, 2, 3, 4, 5
 SETOP_NAMES = {"intersect": SETOP_INTERSECT, "union": SETOP_UNION, "subtract": SETOP_SUBTRACT}
@@ -170,6 +173,9 @@ def lib() -> C.CDLL:
     L.kmc_unitigs.argtypes = [vp, u64, u64, vp, u64, vp, vp, vp, u64, pu64, pu64, vp]
     L.kmc_unitig_links_device.argtypes = [vp, u64, u64, C.POINTER(vp), C.POINTER(vp), pu64, pu64, vp]
     L.kmc_unitig_links.argtypes = [vp, u64, u64, vp, u64, vp, u64, pu64, pu64, vp]
+    L.kmc_unitig_clean_device.argtypes = [vp, u64, u64, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), pu64, pu64, vp]
+    L.kmc_unitig_clean.argtypes = [vp, u64, u64, u64, u64, vp, vp, vp, u64, vp, u64, pu64, pu64, vp]
+    L.kmc_unitig_clean_into.argtypes = [vp, vp, u64, u64, u64, u64, vp]
     L.kmc_owner_of.argtypes = [u64, u64, u32]
     L.kmc_owner_of.restype = u32
     L.kmc_get_stats.argtypes = [vp, C.POINTER(Stats)]
@@ -486,6 +492,48 @@ class UnitigLinks:
                 yield i >> 1, "+" if i & 1 else "-", int(t) >> 1, "-" if int(t) & 1 else "+"
 
 
+_CLEAN_FIELDS = ("unitigs", "tips", "islands", "kept_keys", "tip_keys", "island_keys", "tip_candidates", "kept_count")
+
+
+@dataclass
+class CleanSummary:
+    """The eight words of kmc_unitig_clean: unitigs, those clipped as tips, those dropped as islands, the keys kept, the keys
+    of the tips, the keys of the islands, tip candidates (those that survive included), the sum of the counts of the kept keys."""
+    unitigs: int
+    tips: int
+    islands: int
+    kept_keys: int
+    tip_keys: int
+    island_keys: int
+    tip_candidates: int
+    kept_count: int
+
+    @classmethod
+    def from_words(cls, words) -> "CleanSummary":
+        return cls(*[int(w) for w in words])
+
+    def words(self) -> list:
+        return [getattr(self, f) for f in _CLEAN_FIELDS]
+
+    @property
+    def removed(self) -> int:
+        """Unitigs this pass takes out."""
+        return self.tips + self.islands
+
+    def to_text(self) -> str:
+        """``NAME\tVALUE`` lines."""
+        return "\n".join("%s\t%d" % (f, getattr(self, f)) for f in _CLEAN_FIELDS) + "\n"
+
+
+@dataclass
+class CleanedUnitigs:
+    """What KmerCounter.clean_unitigs returns: ``table`` (the keys of the kept unitigs with their counts, in view order),
+    ``verdict`` uint8[n unitigs] (CLEAN_KEEP / CLEAN_TIP / CLEAN_ISLAND, indexed as unitigs() numbers them), ``summary``."""
+    table: "Table"
+    verdict: np.ndarray
+    summary: CleanSummary
+
+
 def parse_fasta(path: str) -> Tuple[np.ndarray, np.ndarray]:
     """Host FASTA reader of libkmc (the reader the reference uses, main.rs:45-46,59-62).
     Returns (bases uint8[n_bases], offsets uint64[n_reads+1])."""
@@ -779,6 +827,71 @@ class KmerCounter:
         w = (C.c_uint64 * LINK_WORDS)()
         self._chk(self._L.kmc_unitig_links_device(self._h, int(min_count), int(max_count), *[C.byref(x) for x in p], C.byref(nu), C.byref(nl), w))
         return tuple(x.value or 0 for x in p) + (nu.value, nl.value, LinkSummary.from_words(list(w)))
+
+    # -- that graph cleaned: tips clipped, islands dropped (of the sorted view; finalize() first) --
+    def _clean_limits(self, max_tip_keys, max_island_keys) -> Tuple[int, int]:
+        return (self.k if max_tip_keys is None else int(max_tip_keys)), (self.k if max_island_keys is None else int(max_island_keys))
+
+    def clean_unitigs(self, min_count: int = 1, max_count: int = 0, max_tip_keys: Optional[int] = None,
+                      max_island_keys: Optional[int] = None) -> "CleanedUnitigs":
+        """kmc_unitig_clean: the verdict per unitig of unitigs() / unitig_links() with the same range -- dead-end arms of at
+        most max_tip_keys keys that lose against a sibling are tips, unconnected unitigs of at most max_island_keys keys
+        islands (None: k; 0: none) -- and the table of the keys of the kept unitigs.  Two calls, one computation."""
+        tip, isl = self._clean_limits(max_tip_keys, max_island_keys)
+        nk, nu = C.c_uint64(), C.c_uint64()
+        w = (C.c_uint64 * CLEAN_WORDS)()
+        lo, hi = int(min_count), int(max_count)
+        self._chk(self._L.kmc_unitig_clean(self._h, lo, hi, tip, isl, None, None, None, 0, None, 0, C.byref(nk), C.byref(nu), w))
+        khi, klo, cnt = (np.zeros(nk.value, np.uint64) for _ in range(3))
+        verdict = np.zeros(nu.value, np.uint8)
+        self._chk(self._L.kmc_unitig_clean(self._h, lo, hi, tip, isl, khi.ctypes.data if nk.value else None, klo.ctypes.data if nk.value else None,
+                                           cnt.ctypes.data if nk.value else None, nk.value, verdict.ctypes.data if nu.value else None, nu.value,
+                                           C.byref(nk), C.byref(nu), w))
+        return CleanedUnitigs(Table(khi, klo, cnt, self.k), verdict, CleanSummary.from_words(list(w)))
+
+    def clean_unitigs_device(self, min_count: int = 1, max_count: int = 0, max_tip_keys: Optional[int] = None,
+                             max_island_keys: Optional[int] = None):
+        """(d_key_hi or 0, d_key_lo, d_count, d_verdict, n_kept, n_unitigs, CleanSummary) of kmc_unitig_clean_device: ctx-owned
+        device arrays; the first three can be handed to another counter's merge_pairs_device."""
+        tip, isl = self._clean_limits(max_tip_keys, max_island_keys)
+        p = [C.c_void_p() for _ in range(4)]
+        nk, nu = C.c_uint64(), C.c_uint64()
+        w = (C.c_uint64 * CLEAN_WORDS)()
+        self._chk(self._L.kmc_unitig_clean_device(self._h, int(min_count), int(max_count), tip, isl, *[C.byref(x) for x in p], C.byref(nk), C.byref(nu), w))
+        return tuple(x.value or 0 for x in p) + (nk.value, nu.value, CleanSummary.from_words(list(w)))
+
+    def clean_into(self, dst: "KmerCounter", min_count: int = 1, max_count: int = 0, max_tip_keys: Optional[int] = None,
+                   max_island_keys: Optional[int] = None) -> "CleanSummary":
+        """kmc_unitig_clean_into: the kept keys of self merged into dst's table (dst is not finalized)."""
+        tip, isl = self._clean_limits(max_tip_keys, max_island_keys)
+        w = (C.c_uint64 * CLEAN_WORDS)()
+        self._chk(self._L.kmc_unitig_clean_into(self._h, dst._h, int(min_count), int(max_count), tip, isl, w))
+        return CleanSummary.from_words(list(w))
+
+    def cleaned(self, min_count: int = 1, max_count: int = 0, max_tip_keys: Optional[int] = None, max_island_keys: Optional[int] = None,
+                rounds: int = 1):
+        """(KmerCounter, [CleanSummary per round run]): a new finalized counter on this device, same k and canonical, that
+        holds this table cleaned ``rounds`` times -- round 2 and later run on the previous round's counter with the same
+        range.  Stops early after a round that removes nothing.  Intermediate counters are closed; self is left as it is."""
+        if rounds < 1:
+            raise ValueError("rounds must be at least 1")
+        src, out = self, []
+        for _ in range(int(rounds)):
+            dst = KmerCounter(k=self.k, canonical=self.canonical, mode=self.mode, device=self.device)
+            try:
+                out.append(src.clean_into(dst, min_count, max_count, max_tip_keys, max_island_keys))
+                dst.finalize()
+            except Exception:
+                dst.close()
+                if src is not self:
+                    src.close()
+                raise
+            if src is not self:
+                src.close()
+            src = dst
+            if out[-1].removed == 0:
+                break
+        return src, out
 
     # -- asking the table: key lookups and per-read profiles (of the sorted view; finalize() first) --
     def query(self, key_lo, key_hi=None) -> np.ndarray:

@@ -1540,8 +1540,8 @@ extern "C" void kmc_destroy(kmc_ctx* c) {
                       &c->so_pa, &c->so_pb, &c->g_adj, &c->g_ctl,
                       &c->u_bases, &c->u_offs, &c->u_abund, &c->u_flags, &c->u_link, &c->u_join, &c->u_ptr[0], &c->u_ptr[1],
                       &c->u_dist[0], &c->u_dist[1], &c->u_circ, &c->u_ctl,
-                      &c->l_offs, &c->l_to, &c->l_cnt, &c->l_pos, &c->l_tgt, &c->l_ctl};
-    KeyBufs* keys[] = {&c->o, &c->t, &c->p, &c->rx, &c->f, &c->so};
+                      &c->l_offs, &c->l_to, &c->l_cnt, &c->l_pos, &c->l_tgt, &c->l_ctl, &c->cl_verdict, &c->cl_row};
+    KeyBufs* keys[] = {&c->o, &c->t, &c->p, &c->rx, &c->f, &c->so, &c->cl};
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
     sk_free(c);
     try { free_runs(c, true); } catch (...) { /* (only the pool bookkeeping can throw; the buffers it could not list leak with the process) */ }

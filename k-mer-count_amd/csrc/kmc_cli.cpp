@@ -7,7 +7,7 @@
 //   k-mer-count [FASTA] [-k K] [--forward] [--expand] [--device N | --gpus N] [--algo auto|stream|walk|sort] [--stats]
 //               [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE]
 //               [--with FASTA2 (--compare | --setop intersect|union|subtract [--counts left|right|min|max|sum|diff])]
-//               [--graph | --graph-stats | --unitigs | --gfa]
+//               [--graph | --graph-stats | --unitigs | --gfa] [--clean ROUNDS [--tip-keys N] [--island-keys N]]
 //
 //   --gpus N  the file's chunks go round-robin to GPUs 0..N-1 of this process, tables reduced on GPU 0
 //             (there is no CPU backend: SURVEY.md's "--backend cpu" is deliberately absent)
@@ -47,6 +47,13 @@
 //               tab-separated: "H VN:Z:1.0", then per unitig in order "S INDEX SEQ LN:i:BASES KC:i:ABUND CL:i:0|1", then per link
 //               record in array order "L U +|- V +|- (K-1)M" (every link appears from both of its ends).  Same solidity range.
 //
+//   --clean ROUNDS       (with -k K) before whichever output was asked for -- the table, --histo, --graph*, --unitigs, --gfa -- the
+//               table is cleaned: up to ROUNDS times the unitigs of the solidity range are judged (kmc_unitig_clean_into), dead-end
+//               arms of at most --tip-keys keys that lose against a sibling and unconnected unitigs of at most --island-keys keys
+//               (default K each, 0: none) are taken out, and the keys of the others become the table of the next round and in the
+//               end of the output (--query-kmers / --profile ask the cleaned table too).  A round that removes nothing is the last.
+//               With --stats one line per round on stderr; the closing --stats line still describes the counting of the file.
+//
 // Errors: message on stderr, exit code 101 (what a Rust panic exits with), never partial stdout.
 #include <errno.h>
 #include <limits.h>
@@ -54,6 +61,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -97,6 +105,8 @@ int main(int argc, char** argv) {
     long long min_count = 1, max_count = 0;   // (max_count 0: no upper bound)
     const char *query_path = nullptr, *profile_path = nullptr, *with_path = nullptr;
     int compare = 0, setop = -1, count_mode = -1, graph = 0, graph_stats = 0, unitigs = 0, gfa = 0;
+    int clean = 0;
+    long long tip_keys = -1, island_keys = -1;   // (-1: K)
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         if (a == "-k" && i + 1 < argc) { if (!parse_int("-k", argv[++i], 1, 63, &k)) return 2; }
@@ -116,6 +126,9 @@ int main(int argc, char** argv) {
         else if (a == "--graph-stats") graph_stats = 1;
         else if (a == "--unitigs") unitigs = 1;
         else if (a == "--gfa") gfa = 1;
+        else if (a == "--clean" && i + 1 < argc) { if (!parse_int("--clean", argv[++i], 1, 1000, &clean)) return 2; }
+        else if (a == "--tip-keys" && i + 1 < argc) { if (!parse_count("--tip-keys", argv[++i], 0, LLONG_MAX, &tip_keys)) return 2; }
+        else if (a == "--island-keys" && i + 1 < argc) { if (!parse_count("--island-keys", argv[++i], 0, LLONG_MAX, &island_keys)) return 2; }
         else if (a == "--setop" && i + 1 < argc) {
             std::string v = argv[++i];
             setop = v == "intersect" ? KMC_SETOP_INTERSECT : v == "union" ? KMC_SETOP_UNION : v == "subtract" ? KMC_SETOP_SUBTRACT : -1;
@@ -132,10 +145,11 @@ int main(int argc, char** argv) {
             fprintf(stderr, "usage: k-mer-count [FASTA] [-k K] [--forward] [--expand] [--device N | --gpus N] [--algo auto|stream|walk|sort] [--stats]\n"
                             "                   [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE]\n"
                             "                   [--with FASTA2 (--compare | --setop intersect|union|subtract [--counts left|right|min|max|sum|diff])]\n"
-                            "                   [--graph | --graph-stats | --unitigs | --gfa]\n");
+                            "                   [--graph | --graph-stats | --unitigs | --gfa] [--clean ROUNDS [--tip-keys N] [--island-keys N]]\n");
             return 0;
         } else if (a == "-k" || a == "--device" || a == "--gpus" || a == "--algo" || a == "--min-count" || a == "--max-count" || a == "--histo" ||
-                   a == "--query-kmers" || a == "--profile" || a == "--with" || a == "--setop" || a == "--counts") {
+                   a == "--query-kmers" || a == "--profile" || a == "--with" || a == "--setop" || a == "--counts" ||
+                   a == "--clean" || a == "--tip-keys" || a == "--island-keys") {
             fprintf(stderr, "k-mer-count: %s needs a value\n", a.c_str());
             return 2;
         } else if (!a.empty() && a[0] != '-') path = argv[i];
@@ -212,6 +226,14 @@ int main(int argc, char** argv) {
         else if (expand) bad = "--expand exclude each other";
         if (bad) { fprintf(stderr, "k-mer-count: %s %s%s\n", opt, strncmp(bad, "needs", 5) ? "and " : "", bad); return 2; }
     }
+    // --clean / --tip-keys / --island-keys: the same
+    if (clean || tip_keys >= 0 || island_keys >= 0) {
+        const char* bad = nullptr;
+        if (!clean) bad = "--tip-keys / --island-keys need --clean ROUNDS";
+        else if (!k) bad = "--clean needs -k K";
+        else if (with_path || compare || setop >= 0) bad = "--clean and --with / --compare / --setop exclude each other";
+        if (bad) { fprintf(stderr, "k-mer-count: %s\n", bad); return 2; }
+    }
     const bool filtered = min_count > 1 || max_count != 0;
     kmc_config cfg;
     memset(&cfg, 0, sizeof(cfg));
@@ -236,9 +258,34 @@ int main(int argc, char** argv) {
     auto destroy_all = [&]() { for (kmc_ctx* x : ctxs) kmc_destroy(x); };
     if (rc) { int r = die("kmc_create", kmc_last_error(nullptr)); destroy_all(); return r; }
     kmc_ctx* ctx = ctxs[0];
+    kmc_ctx* const counted = ctx;   // (the ctx that read the file: --clean moves ctx on to the cleaned table)
     uint64_t nd = 0, nt = 0;
     rc = gpus == 1 ? kmc_count_file(ctx, path, &nd, &nt) : kmc_count_file_multi(ctxs.data(), (uint32_t)ctxs.size(), path, &nd, &nt);
     if (rc) { int r = die(path, kmc_last_error(ctx)); destroy_all(); return r; }
+    // --clean: round by round into a fresh ctx, which then is the table every output below reads
+    for (int round = 1; round <= clean; ++round) {
+        cfg.device = gpus == 1 ? device : (share ? atoi(share) : 0);
+        kmc_ctx* next = nullptr;
+        rc = kmc_create(&next, &cfg);
+        if (rc) { int r = die("kmc_create", kmc_last_error(nullptr)); destroy_all(); return r; }
+        ctxs.push_back(next);
+        uint64_t w[KMC_CLEAN_WORDS];
+        rc = kmc_unitig_clean_into(ctx, next, (uint64_t)min_count, (uint64_t)max_count, tip_keys < 0 ? (uint64_t)k : (uint64_t)tip_keys,
+                                   island_keys < 0 ? (uint64_t)k : (uint64_t)island_keys, w);
+        if (rc) { int r = die("kmc_unitig_clean_into", kmc_last_error(ctx)); destroy_all(); return r; }
+        rc = kmc_finalize(next, &nd, &nt);
+        if (rc) { int r = die("kmc_finalize", kmc_last_error(next)); destroy_all(); return r; }
+        if (stats)
+            fprintf(stderr, "clean round %d unitigs %llu tips %llu islands %llu kept_keys %llu tip_keys %llu island_keys %llu tip_candidates %llu kept_count %llu\n",
+                    round, (unsigned long long)w[0], (unsigned long long)w[1], (unsigned long long)w[2], (unsigned long long)w[3],
+                    (unsigned long long)w[4], (unsigned long long)w[5], (unsigned long long)w[6], (unsigned long long)w[7]);
+        if (ctx != counted) {   // (the table of the round before)
+            kmc_destroy(ctx);
+            ctxs.erase(std::find(ctxs.begin(), ctxs.end(), ctx));
+        }
+        ctx = next;
+        if (w[1] + w[2] == 0) break;
+    }
     std::vector<char> obuf(1 << 22);
     if (with_path) {
         cfg.device = device;
@@ -436,7 +483,7 @@ int main(int argc, char** argv) {
     fflush(stdout);
     if (stats) {
         kmc_stats s;
-        kmc_get_stats(ctx, &s);
+        kmc_get_stats(counted, &s);
         fprintf(stderr, "reads %llu bases %llu kmers %llu distinct %llu table_slots %llu spilled %llu kernel_ms %.3f algo %d\n",
                 (unsigned long long)s.n_reads, (unsigned long long)s.n_bases, (unsigned long long)s.n_kmers,
                 (unsigned long long)s.n_distinct, (unsigned long long)s.table_capacity, (unsigned long long)s.n_spilled,

@@ -189,6 +189,12 @@ struct kmc_ctx {
     bool u_live = false;
     DevBuf l_offs, l_to, l_cnt, l_pos, l_tgt, l_ctl;
     u64 l_gen = ~0ull, l_min = 0, l_max = 0, l_words[8] = {};
+    // kmc_unitig_clean* (kmc_clean.hip.h) reads the unitigs, the links and what the links pass reads.  Its result: the
+    // verdict per unitig and the kept table, with cl_gen / cl_min / cl_max / cl_tip / cl_isl / cl_words as above (nothing but
+    // the clean pass writes them), cl_kept keys; the class byte per view row between its two passes.
+    KeyBufs cl;
+    DevBuf cl_verdict, cl_row;
+    u64 cl_gen = ~0ull, cl_min = 0, cl_max = 0, cl_tip = 0, cl_isl = 0, cl_kept = 0, cl_words[8] = {};
 };
 
 #pragma GCC visibility push(hidden)   // what follows is shared between the translation units, never exported

@@ -13,6 +13,7 @@
 #include "kmc_graph.hip.h"
 #include "kmc_unitig.hip.h"
 #include "kmc_links.hip.h"
+#include "kmc_clean.hip.h"
 
 namespace {
 
@@ -409,6 +410,16 @@ static int kmc_profile_impl(kmc_ctx* c, const uint8_t* bases, const uint64_t* of
 }
 
 // ---- two tables compared: summary and set operations over the sorted views of two contexts (kmc_setops.hip.h) ----
+// a and b count the same kind of key on one device (the error is a's)
+static int same_kind(kmc_ctx* a, const kmc_ctx* b, const char* what) {
+    if (a->cfg.device != b->cfg.device) return fail(a, KMC_ERR_ARG, "%s: the contexts differ in device (%d / %d)", what, a->cfg.device, b->cfg.device);
+    if (a->cfg.mode != b->cfg.mode) return fail(a, KMC_ERR_ARG, "%s: the contexts differ in mode (%d / %d)", what, a->cfg.mode, b->cfg.mode);
+    if (a->klen != b->klen || a->KW != b->KW) return fail(a, KMC_ERR_ARG, "%s: the contexts differ in k (%d / %d)", what, a->klen, b->klen);
+    if ((a->cfg.canonical != 0) != (b->cfg.canonical != 0))
+        return fail(a, KMC_ERR_ARG, "%s: the contexts differ in canonical (%d / %d)", what, a->cfg.canonical, b->cfg.canonical);
+    return KMC_OK;
+}
+
 // What every set-operation call checks first: arguments, that a and b count the same kind of key on one device, both views.
 // b's view is only read, on a's stream: b is synchronised first where kmc_export_device would do so.
 static int setop_begin(kmc_ctx* a, kmc_ctx* b, const char* what, int op, int count_mode, uint64_t min_a, uint64_t max_a,
@@ -417,12 +428,9 @@ static int setop_begin(kmc_ctx* a, kmc_ctx* b, const char* what, int op, int cou
     if (count_mode < KMC_COUNT_LEFT || count_mode > KMC_COUNT_DIFF) return fail(a, KMC_ERR_ARG, "%s: unknown count_mode %d", what, count_mode);
     if (max_a && min_a > max_a) return fail(a, KMC_ERR_ARG, "%s: min_a %llu > max_a %llu", what, (unsigned long long)min_a, (unsigned long long)max_a);
     if (max_b && min_b > max_b) return fail(a, KMC_ERR_ARG, "%s: min_b %llu > max_b %llu", what, (unsigned long long)min_b, (unsigned long long)max_b);
-    if (a->cfg.device != b->cfg.device) return fail(a, KMC_ERR_ARG, "%s: the contexts differ in device (%d / %d)", what, a->cfg.device, b->cfg.device);
-    if (a->cfg.mode != b->cfg.mode) return fail(a, KMC_ERR_ARG, "%s: the contexts differ in mode (%d / %d)", what, a->cfg.mode, b->cfg.mode);
-    if (a->klen != b->klen || a->KW != b->KW) return fail(a, KMC_ERR_ARG, "%s: the contexts differ in k (%d / %d)", what, a->klen, b->klen);
-    if ((a->cfg.canonical != 0) != (b->cfg.canonical != 0))
-        return fail(a, KMC_ERR_ARG, "%s: the contexts differ in canonical (%d / %d)", what, a->cfg.canonical, b->cfg.canonical);
-    int rc = view_begin(a, what);
+    int rc = same_kind(a, b, what);
+    if (rc) return rc;
+    rc = view_begin(a, what);
     if (rc) return rc;
     if (b != a) {
         if ((rc = view_begin(b, what)) || (rc = sync_view(b))) return rc;
@@ -968,6 +976,144 @@ static int kmc_unitig_links_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_co
     return KMC_OK;
 }
 
+// ---- the compacted graph cleaned: a verdict per unitig, the table of the kept keys (kmc_clean.hip.h) ----
+static u64 clean_limit(uint64_t keys) { return keys >= (1ull << 31) ? ~0ull : (u64)keys; }   // 2^31 or more: unlimited
+
+static bool clean_kept(const kmc_ctx* c, u64 min_count, u64 max_count, u64 tip, u64 isl) {
+    return c->cl_gen == c->view_gen && c->cl_min == min_count && c->cl_max == max_count && c->cl_tip == tip && c->cl_isl == isl;
+}
+
+// The clean pass behind the unitigs and links of this view and range -- those the ctx holds if their work arrays are still
+// theirs, otherwise computed and kept -- into cl_verdict / cl, the summary into cl_words; finished when it returns.
+static int clean_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count, u64 tip, u64 isl) {
+    int rc;
+    u64 lw[KMC_LINK_WORDS];
+    const bool held = c->u_live && c->u_gen == c->view_gen && c->u_min == min_count && c->u_max == max_count;
+    if ((rc = links_result(c, what, min_count, max_count, held, lw))) return rc;
+    c->cl_gen = ~0ull;
+    const u64 n = c->n_sorted, nu = lw[0], nl = lw[1];
+    u64 h[KMC_C_CTL_WORDS] = {0};
+    if ((rc = ensure(c, c->cl_verdict, (size_t)std::max<u64>(nu, 8))) || (rc = ensure(c, c->cl_row, (size_t)std::max<u64>(n, 8)))) return rc;
+    UnitigTrace tr;
+    tr.mark(c->stream);
+    if (nu) {
+        if (nu > n || c->u_words[0] != nu) return fail(c, KMC_ERR_HIP, "internal error: %s holds %llu unitigs, its links %llu", what, (unsigned long long)c->u_words[0], (unsigned long long)nu);
+        const u64 n_tiles = (n + KMC_C_TILE - 1) / KMC_C_TILE;
+        if ((rc = compact_plan(c, n_tiles, KMC_C_CTL_WORDS))) return rc;
+        kmc_ull* ctl = (kmc_ull*)c->c_ctl.p;
+        CleanGraph g;
+        g.offsets = (const u64*)c->u_offs.p; g.abund = (const u64*)c->u_abund.p; g.flags = (const uint8_t*)c->u_flags.p;
+        g.link_offsets = (const u64*)c->l_offs.p; g.link_to = (const u32*)c->l_to.p;
+        g.n_unitigs = nu; g.n_links = nl; g.km1 = (u64)(c->klen - 1); g.max_tip = tip; g.max_island = isl;
+        hipLaunchKernelGGL(kmc_clean_verdict_kernel, dim3((u32)((nu + KMC_C_THREADS - 1) / KMC_C_THREADS)), dim3(KMC_C_THREADS), 0, c->stream,
+                           g, (uint8_t*)c->cl_verdict.p, ctl);
+        const u32 grid = (u32)std::min<u64>(n_tiles, (u64)c->n_cu * 8);
+        hipLaunchKernelGGL(kmc_clean_mark_kernel, dim3(grid), dim3(KMC_C_THREADS), 0, c->stream, c->v_cnt, n, n_tiles, (const uint16_t*)c->g_adj.p,
+                           (const u32*)c->u_ptr[c->u_cur].p, (const u32*)c->u_join.p, c->cfg.canonical ? 1 : 0,
+                           (const uint8_t*)c->cl_verdict.p, nu, (uint8_t*)c->cl_row.p, (u32*)c->c_tile.p, ctl);
+        if ((rc = compact_scan_and_read(c, n_tiles, h, KMC_C_CTL_WORDS))) return rc;
+        if (h[KMC_C_BAD] || h[0] != h[KMC_C_SUM + 3] || h[KMC_C_SUM + 3] + h[KMC_C_SUM + 4] + h[KMC_C_SUM + 5] != c->u_words[2])
+            return fail(c, KMC_ERR_HIP, "internal error: %s met %llu indices outside their arrays (%llu + %llu + %llu of %llu keys, %llu scanned)", what,
+                        (unsigned long long)h[KMC_C_BAD], (unsigned long long)h[KMC_C_SUM + 3], (unsigned long long)h[KMC_C_SUM + 4],
+                        (unsigned long long)h[KMC_C_SUM + 5], (unsigned long long)c->u_words[2], (unsigned long long)h[0]);
+    }
+    const u64 n_kept = h[0];
+    if ((rc = ensure_keys(c, c->cl, n_kept))) return rc;
+    if (n_kept) {
+        const KView v = view_of(c);
+        const u64 n_tiles = (n + KMC_C_TILE - 1) / KMC_C_TILE;
+        kmc_ull* ctl = (kmc_ull*)c->c_ctl.p;
+        with_kw(c, [&](auto KW) {
+            hipLaunchKernelGGL(kmc_clean_scatter_kernel<KW()>, dim3((u32)n_tiles), dim3(KMC_C_THREADS), 0, c->stream, v.hi, v.lo, v.cnt, v.n,
+                               (const uint8_t*)c->cl_row.p, (const u32*)c->c_tpos.p, n_kept, (u64*)c->cl.hi.p, (u64*)c->cl.lo.p, (u64*)c->cl.cnt.p, ctl);
+        });
+        HIPCHK(c, hipGetLastError());
+        u64 bad = 0;
+        HIPCHK(c, hipMemcpyAsync(&bad, ctl + KMC_C_BAD, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (bad) return fail(c, KMC_ERR_HIP, "internal error: %s could not place %llu kept keys", what, (unsigned long long)bad);
+    }
+    tr.mark(c->stream);
+    if (tr.on && tr.n_ev == 2) {
+        float ms = 0;
+        if (hipEventSynchronize(tr.ev[1]) == hipSuccess && hipEventElapsedTime(&ms, tr.ev[0], tr.ev[1]) == hipSuccess)
+            fprintf(stderr, "kmc_unitig_clean: keys %llu unitigs %llu tips %llu islands %llu kept %llu clean_ms %.4f\n", (unsigned long long)n,
+                    (unsigned long long)nu, (unsigned long long)h[KMC_C_SUM + 1], (unsigned long long)h[KMC_C_SUM + 2], (unsigned long long)n_kept, ms);
+    }
+    h[KMC_C_SUM + 0] = nu;
+    memcpy(c->cl_words, h + KMC_C_SUM, sizeof(c->cl_words));
+    c->cl_kept = n_kept;
+    c->cl_gen = c->view_gen; c->cl_min = min_count; c->cl_max = max_count; c->cl_tip = tip; c->cl_isl = isl;
+    return KMC_OK;
+}
+
+static int kmc_unitig_clean_device_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t max_tip_keys, uint64_t max_island_keys,
+                                        const void** d_key_hi, const void** d_key_lo, const void** d_count, const void** d_verdict,
+                                        uint64_t* n_kept, uint64_t* n_unitigs, uint64_t* summary, const char* what = "kmc_unitig_clean_device") {
+    if (!c) return KMC_ERR_ARG;
+    int rc;
+    if ((rc = unitig_begin(c, what, min_count, max_count)) ||
+        (rc = clean_run(c, what, min_count, max_count, clean_limit(max_tip_keys), clean_limit(max_island_keys)))) return rc;
+    publish_keys(c, c->cl, d_key_hi, d_key_lo, d_count);
+    if (d_verdict) *d_verdict = c->cl_verdict.p;
+    if (n_kept) *n_kept = c->cl_kept;
+    if (n_unitigs) *n_unitigs = c->cl_words[0];
+    if (summary) memcpy(summary, c->cl_words, sizeof(c->cl_words));
+    return KMC_OK;
+}
+
+static int kmc_unitig_clean_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t max_tip_keys, uint64_t max_island_keys,
+                                 uint64_t* key_hi, uint64_t* key_lo, uint64_t* count, uint64_t cap_keys, uint8_t* verdict, uint64_t cap_unitigs,
+                                 uint64_t* n_kept, uint64_t* n_unitigs, uint64_t* summary) {
+    if (n_kept) *n_kept = 0;
+    if (n_unitigs) *n_unitigs = 0;
+    if (!c) return KMC_ERR_ARG;
+    int rc;
+    if ((rc = unitig_begin(c, "kmc_unitig_clean", min_count, max_count))) return rc;
+    const u64 tip = clean_limit(max_tip_keys), isl = clean_limit(max_island_keys);
+    if (!clean_kept(c, min_count, max_count, tip, isl) && (rc = clean_run(c, "kmc_unitig_clean", min_count, max_count, tip, isl))) return rc;
+    const u64 nk = c->cl_kept, nu = c->cl_words[0];
+    if (n_kept) *n_kept = nk;
+    if (n_unitigs) *n_unitigs = nu;
+    if ((key_hi || key_lo || count) && cap_keys < nk)
+        return fail(c, KMC_ERR_ARG, "kmc_unitig_clean: capacity %llu < %llu kept keys", (unsigned long long)cap_keys, (unsigned long long)nk);
+    if (verdict && cap_unitigs < nu)
+        return fail(c, KMC_ERR_ARG, "kmc_unitig_clean: capacity %llu < %llu unitigs", (unsigned long long)cap_unitigs, (unsigned long long)nu);
+    if (nk) {
+        if (key_lo) HIPCHK(c, hipMemcpyAsync(key_lo, c->cl.lo.p, (size_t)nk * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+        if (count) HIPCHK(c, hipMemcpyAsync(count, c->cl.cnt.p, (size_t)nk * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+        if (key_hi) {
+            if (c->KW == 2) HIPCHK(c, hipMemcpyAsync(key_hi, c->cl.hi.p, (size_t)nk * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+            else memset(key_hi, 0, (size_t)nk * sizeof(u64));
+        }
+    }
+    if (verdict && nu) HIPCHK(c, hipMemcpyAsync(verdict, c->cl_verdict.p, (size_t)nu, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (summary) memcpy(summary, c->cl_words, sizeof(c->cl_words));
+    return KMC_OK;
+}
+
+// One step of a cleaning round: the kept pairs of src merged into dst's table (dst stays un-finalized).  dst's merge has
+// finished when this returns: src's result may be rewritten right after.
+static int kmc_unitig_clean_into_impl(kmc_ctx* src, kmc_ctx* dst, uint64_t min_count, uint64_t max_count, uint64_t max_tip_keys,
+                                      uint64_t max_island_keys, uint64_t* summary) {
+    if (!src || !dst) return src ? fail(src, KMC_ERR_ARG, "kmc_unitig_clean_into: null context") : KMC_ERR_ARG;
+    if (dst == src) return fail(src, KMC_ERR_ARG, "kmc_unitig_clean_into: dst is src");
+    int rc;
+    if ((rc = same_kind(src, dst, "kmc_unitig_clean_into"))) return rc;
+    const void *hi = nullptr, *lo = nullptr, *cnt = nullptr;
+    uint64_t nk = 0;
+    u64 h[KMC_CLEAN_WORDS];
+    if ((rc = kmc_unitig_clean_device_impl(src, min_count, max_count, max_tip_keys, max_island_keys, &hi, &lo, &cnt, nullptr, &nk, nullptr, h,
+                                           "kmc_unitig_clean_into"))) return rc;
+    if (nk) {
+        if ((rc = kmc_merge_pairs_device(dst, hi, lo, cnt, nk)) || (rc = kmc_sync(dst)))
+            return fail(src, rc, "kmc_unitig_clean_into: merging into dst failed: %s", kmc_last_error(dst));
+    }
+    if (summary) memcpy(summary, h, sizeof(h));
+    return KMC_OK;
+}
+
 // ---- the ABI proper (guarded: no C++ exception leaves the library) ----
 extern "C" int kmc_export(kmc_ctx* c, uint64_t* key_hi, uint64_t* key_lo, uint64_t* count, uint64_t cap) {
     return guarded(c, [&]() -> int { return kmc_export_impl(c, key_hi, key_lo, count, cap); });
@@ -1044,6 +1190,28 @@ extern "C" int kmc_unitig_links(kmc_ctx* c, uint64_t min_count, uint64_t max_cou
                                 uint32_t* link_to, uint64_t cap_links, uint64_t* n_unitigs, uint64_t* n_links, uint64_t* summary) {
     return guarded(c, [&]() -> int {
         return kmc_unitig_links_impl(c, min_count, max_count, link_offsets, cap_ends, link_to, cap_links, n_unitigs, n_links, summary);
+    });
+}
+extern "C" int kmc_unitig_clean_device(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t max_tip_keys, uint64_t max_island_keys,
+                                       const void** d_key_hi, const void** d_key_lo, const void** d_count, const void** d_verdict,
+                                       uint64_t* n_kept, uint64_t* n_unitigs, uint64_t* summary) {
+    return guarded(c, [&]() -> int {
+        return kmc_unitig_clean_device_impl(c, min_count, max_count, max_tip_keys, max_island_keys, d_key_hi, d_key_lo, d_count, d_verdict, n_kept,
+                                            n_unitigs, summary);
+    });
+}
+extern "C" int kmc_unitig_clean(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t max_tip_keys, uint64_t max_island_keys,
+                                uint64_t* key_hi, uint64_t* key_lo, uint64_t* count, uint64_t cap_keys, uint8_t* verdict, uint64_t cap_unitigs,
+                                uint64_t* n_kept, uint64_t* n_unitigs, uint64_t* summary) {
+    return guarded(c, [&]() -> int {
+        return kmc_unitig_clean_impl(c, min_count, max_count, max_tip_keys, max_island_keys, key_hi, key_lo, count, cap_keys, verdict, cap_unitigs,
+                                     n_kept, n_unitigs, summary);
+    });
+}
+extern "C" int kmc_unitig_clean_into(kmc_ctx* src, kmc_ctx* dst, uint64_t min_count, uint64_t max_count, uint64_t max_tip_keys,
+                                     uint64_t max_island_keys, uint64_t* summary) {
+    return guarded(src, [&]() -> int {
+        return kmc_unitig_clean_into_impl(src, dst, min_count, max_count, max_tip_keys, max_island_keys, summary);
     });
 }
 extern "C" int kmc_partition_device(kmc_ctx* c, uint32_t n_parts, uint64_t* part_begin, const void** d_key_hi,

@@ -32,6 +32,12 @@ pub const KMC_UNITIG_WORDS: usize = 8;
 pub const KMC_UNITIG_CIRCULAR: u8 = 1;
 /// summary words of `kmc_unitig_links`
 pub const KMC_LINK_WORDS: usize = 8;
+/// summary words of `kmc_unitig_clean`
+pub const KMC_CLEAN_WORDS: usize = 8;
+/// a unitig's verdict byte
+pub const KMC_CLEAN_KEEP: u8 = 0;
+pub const KMC_CLEAN_TIP: u8 = 1;
+pub const KMC_CLEAN_ISLAND: u8 = 2;
 
 // The structs and the extern block below are checked against include/kmc.h by
 // tests/test_abi_host.py::test_rust_binding_matches_the_header (names, arity, argument types, field
@@ -143,6 +149,9 @@ extern "C" {
     // the links between those unitigs: offsets per unitig end, target ends, summary
     pub fn kmc_unitig_links_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, d_link_offsets: *mut *const c_void, d_link_to: *mut *const c_void, n_unitigs: *mut u64, n_links: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_links(ctx: *mut KmcCtx, min_count: u64, max_count: u64, link_offsets: *mut u64, cap_ends: u64, link_to: *mut u32, cap_links: u64, n_unitigs: *mut u64, n_links: *mut u64, summary: *mut u64) -> c_int;
+    pub fn kmc_unitig_clean_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, max_tip_keys: u64, max_island_keys: u64, d_key_hi: *mut *const c_void, d_key_lo: *mut *const c_void, d_count: *mut *const c_void, d_verdict: *mut *const c_void, n_kept: *mut u64, n_unitigs: *mut u64, summary: *mut u64) -> c_int;
+    pub fn kmc_unitig_clean(ctx: *mut KmcCtx, min_count: u64, max_count: u64, max_tip_keys: u64, max_island_keys: u64, key_hi: *mut u64, key_lo: *mut u64, count: *mut u64, cap_keys: u64, verdict: *mut u8, cap_unitigs: u64, n_kept: *mut u64, n_unitigs: *mut u64, summary: *mut u64) -> c_int;
+    pub fn kmc_unitig_clean_into(src: *mut KmcCtx, dst: *mut KmcCtx, min_count: u64, max_count: u64, max_tip_keys: u64, max_island_keys: u64, summary: *mut u64) -> c_int;
     // multi-GPU reduce (one process per GPU; the collective itself is the host program's, e.g. RCCL)
     pub fn kmc_slab_words(ctx: *const KmcCtx, slab_entries: u64) -> u64;
     pub fn kmc_pack_slab_device(ctx: *mut KmcCtx, d_slab: *mut c_void, slab_entries: u64) -> c_int;
@@ -409,6 +418,50 @@ impl Counter {
             kmc_unitig_links(self.ctx, min_count, max_count, offsets.as_mut_ptr(), 2 * nu, to.as_mut_ptr(), nl, &mut nu, &mut nl, w.as_mut_ptr())
         })?;
         Ok((offsets, to, w))
+    }
+
+    /// That graph cleaned (`kmc_unitig_clean`): the keys of the kept unitigs with their counts, in the order of `table()`,
+    /// the verdict per unitig (`KMC_CLEAN_KEEP` / `KMC_CLEAN_TIP` / `KMC_CLEAN_ISLAND`, indexed as `unitigs` numbers them) and
+    /// the eight summary words [unitigs, tips, islands, keys kept, keys of tips, keys of islands, tip candidates, sum of the
+    /// kept counts].  A dead-end arm of at most `max_tip_keys` keys that loses against a sibling is a tip, an unconnected
+    /// unitig of at most `max_island_keys` keys an island; 0 switches a rule off.
+    pub fn clean_unitigs(&mut self, min_count: u64, max_count: u64, max_tip_keys: u64, max_island_keys: u64)
+                         -> Result<(Vec<(String, u64)>, Vec<u8>, [u64; KMC_CLEAN_WORDS]), KmcError> {
+        let (mut nd, mut nt) = (0u64, 0u64);
+        self.check(unsafe { kmc_finalize(self.ctx, &mut nd, &mut nt) })?;
+        let (mut nk, mut nu) = (0u64, 0u64);
+        let mut w = [0u64; KMC_CLEAN_WORDS];
+        let null64 = std::ptr::null_mut::<u64>();
+        self.check(unsafe {
+            kmc_unitig_clean(self.ctx, min_count, max_count, max_tip_keys, max_island_keys, null64, null64, null64, 0, std::ptr::null_mut::<u8>(), 0,
+                             &mut nk, &mut nu, w.as_mut_ptr())
+        })?;
+        let k = nk as usize;
+        let (mut hi, mut lo, mut cnt) = (vec![0u64; k], vec![0u64; k], vec![0u64; k]);
+        let mut verdict = vec![0u8; nu as usize];
+        self.check(unsafe {
+            kmc_unitig_clean(self.ctx, min_count, max_count, max_tip_keys, max_island_keys, hi.as_mut_ptr(), lo.as_mut_ptr(), cnt.as_mut_ptr(), nk,
+                             verdict.as_mut_ptr(), nu, &mut nk, &mut nu, w.as_mut_ptr())
+        })?;
+        let mut buf = vec![0u8; self.klen as usize];
+        let mut out = Vec::with_capacity(k);
+        for i in 0..k {
+            unsafe { kmc_decode_key(hi[i], lo[i], self.klen, buf.as_mut_ptr() as *mut c_char) };
+            out.push((String::from_utf8_lossy(&buf).into_owned(), cnt[i]));
+        }
+        Ok((out, verdict, w))
+    }
+
+    /// One step of a cleaning round (`kmc_unitig_clean_into`): the keys of the kept unitigs of `self` merged into the table
+    /// of `dst`, another counter of the same k, strand rule and device.  `dst` is not finalized, so several sources can be
+    /// merged; its `table()` is the cleaned table.  Returns the summary words of `clean_unitigs`.
+    pub fn clean_into(&mut self, dst: &mut Counter, min_count: u64, max_count: u64, max_tip_keys: u64, max_island_keys: u64)
+                      -> Result<[u64; KMC_CLEAN_WORDS], KmcError> {
+        let (mut nd, mut nt) = (0u64, 0u64);
+        self.check(unsafe { kmc_finalize(self.ctx, &mut nd, &mut nt) })?;
+        let mut w = [0u64; KMC_CLEAN_WORDS];
+        self.check(unsafe { kmc_unitig_clean_into(self.ctx, dst.ctx, min_count, max_count, max_tip_keys, max_island_keys, w.as_mut_ptr()) })?;
+        Ok(w)
     }
 }
 
