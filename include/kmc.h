@@ -127,6 +127,8 @@ typedef struct kmc_stats {
     uint64_t n_async_slabs_skipped; /* slabs they saw, both since kmc_create (as of the last call that synchronised): see kmc_finalize_async */
     uint64_t n_planner_stale;     /* debug invariant of the launch planner: risky launches whose table snapshot was armed on
                                      counters older than the last queued unfold / merge (must stay 0) */
+    uint64_t walk_uniform_launches; /* walk-kernel launches since kmc_create (kmc_reset does not clear it) that ran the
+                                       uniform-length variant: all reads of the batch equally long, no offsets read */
 } kmc_stats;
 
 const char* kmc_version(void);
@@ -149,7 +151,11 @@ int kmc_add_batch(kmc_ctx* ctx, const uint8_t* bases, const uint64_t* offsets, u
 /* Same, for buffers already resident in this ctx's GPU memory (HBM-resident timing, pipelines
  * that parse into pinned/device memory).  d_bases must be 16-byte aligned and readable up to the
  * next 16-byte boundary past the last base.  max_read_len: longest read in the batch, or 0 if
- * unknown (then it is computed on the device).  Asynchronous on the ctx stream.  The buffers must stay
+ * unknown (then it is computed on the device).  A non-zero max_read_len MUST be >= the length of every read
+ * of the batch, and the library relies on it: the launch planner's bounds and the walk kernel's 416-base staging
+ * area are sized by it, and a batch with n_bases == n_reads * max_read_len is taken to consist of reads of exactly
+ * that length each, whose bounds the walk kernel then computes instead of loading d_offsets (d_offsets must be
+ * valid all the same: other parts of the path read it).  Asynchronous on the ctx stream.  The buffers must stay
  * valid and unchanged until the next call on this ctx that synchronises (kmc_add_batch*, kmc_finalize,
  * kmc_poll, kmc_export): the batch may go out in one launch sized by what earlier batches looked like, and
  * if that prediction proves wrong (far more distinct k-mers than the table and its spill area hold) the

@@ -1287,6 +1287,9 @@ int count_walk(kmc_ctx* c, BatchPlan& bp, const uint8_t* d_bases, const u64* d_o
         if (rc) return rc;
         if (c->walk_ws.p != before) c->walk_ws_clean = false;  // fresh memory: the host clears header + counters once
     }
+    // all reads of one length: the kernels compute the reads' bounds and load no offsets (kmc_walk_uniform.h).  Everything
+    // else on this path -- recovery, the hand-over to the sort path, the log pipeline -- goes on reading d_offsets.
+    const u32 uni_len = !c->walk_no_uniform && kmc_walk_uniform(n_reads, n_bases, max_read_len) ? (u32)max_read_len : 0u;
     const u64 n_tiles = (n_v + 63) / 64;
     const u64 kpt = 64 * std::min<u64>(std::max<u64>(max_read_len, 1), KMC_WALK_MAX_READ);  // k-mers per tile, upper bound
     u64 done = 0, prev = 0;
@@ -1332,12 +1335,13 @@ int count_walk(kmc_ctx* c, BatchPlan& bp, const uint8_t* d_bases, const u64* d_o
         rc = launch_events(c, &we0, &we1);
         if (rc) return rc;
         rc = kmc_walk_launch(c->stream, c->n_cu, c->KW, c->cfg.k, c->cfg.canonical != 0, d_bases, d_vs, d_ve, n_v, n_bases,
-                             done, done + take, c->walk_ws.p, c->walk_memo.p, c->memo_parity, gtable_of(c, c->tab), skt, lg, 0, we0, we1);
+                             done, done + take, c->walk_ws.p, c->walk_memo.p, c->memo_parity, gtable_of(c, c->tab), skt, lg, 0, we0, we1, uni_len);
         if (rc) return fail(c, rc, "walk kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+        if (uni_len) c->st.walk_uniform_launches++;
         c->batch_pending = true;
         if (skt.key_lo) c->sk_dirty = true;
         rc = kmc_walk_launch(c->stream, c->n_cu, c->KW, c->cfg.k, c->cfg.canonical != 0, d_bases, d_vs, d_ve, n_v, n_bases,
-                             done, done + take, c->walk_ws.p, c->walk_memo.p, c->memo_parity, gtable_of(c, c->tab), skt, lg, 1, nullptr, nullptr);
+                             done, done + take, c->walk_ws.p, c->walk_memo.p, c->memo_parity, gtable_of(c, c->tab), skt, lg, 1, nullptr, nullptr, uni_len);
         if (rc) return fail(c, rc, "scalar/unfold kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
         if (lg.rec) {   // count what the launch logged: partition by hash, LDS tables, one unfold per distinct (k+16)-mer
             rc = launch_begin(c);
@@ -1579,6 +1583,7 @@ static int kmc_create_impl(kmc_ctx** out, const kmc_config* cfg) {
     };
     c->sort_sub_chunks = seam("KMC_SORT_SUB_CHUNKS", KMC_MSD_RANGE / KMC_CHUNK, c->sort_sub_chunks);
     c->lr_sub_starts = seam("KMC_LR_SUB_STARTS", KMC_LRX_POS, c->lr_sub_starts);
+    if (const char* e = getenv("KMC_WALK_NO_UNIFORM")) c->walk_no_uniform = e[0] != 0 && e[0] != '0';   // (A/B runs on one build, tests)
     int rc = KMC_OK;
     auto body = [&]() -> int {
         HIPCHK(c, hipSetDevice(cfg->device));
@@ -1659,6 +1664,7 @@ static int kmc_reset_impl(kmc_ctx* c) {
     c->st.kernel_ms_lifetime = keep.kernel_ms_lifetime;
     c->st.launches_lifetime = keep.launches_lifetime;
     c->st.n_planner_stale = keep.n_planner_stale;
+    c->st.walk_uniform_launches = keep.walk_uniform_launches;
     c->st.n_async_ok = keep.n_async_ok;
     c->st.n_async_slabs_skipped = keep.n_async_slabs_skipped;
     return KMC_OK;

@@ -68,6 +68,7 @@ struct kmc_ctx {
     DevBuf vr_reads, vr_cnt, vr_pos;  // pieces of long reads for the walk kernel: [starts | ends], per-read counts and their scan
     DevBuf walk_memo;  // two shared memo snapshots + dense counters, kept across launches (kmc_walk.hip.h)
     int memo_parity = 0;  // snapshot slot the next walk launch reads
+    bool walk_no_uniform = false;  // KMC_WALK_NO_UNIFORM=1 at kmc_create: uniform-length batches take the ragged kernels too
     bool walk_ws_clean = false;  // workspace header + dense counters are zero (left so by kmc_walk_tail_kernel)
     // KMC_ALGO_SORT: scratch for one sub-batch and the sorted (key,count) runs produced so far
     DevBuf s_lo[2], s_hi[2];

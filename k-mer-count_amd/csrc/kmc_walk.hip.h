@@ -26,19 +26,23 @@
 // rounds across tiles), packs every 16 ASCII bases into one 2-bit word in registers and parks the
 // words in its private LDS staging area (4x smaller than the ASCII); each lane then reads its own
 // read back 16 bases at a time, re-aligned with v_alignbit.  HBM traffic is the algorithmic
-// minimum: every base byte and offset once.  The waves of a workgroup DRAW their tiles from a
+// minimum: every base byte once, and every offset once -- or not at all: when all reads of the batch
+// have the same length L (every fixed-length read set; the host sees it from n_bases == n_reads *
+// max_read_len, kmc_walk_uniform.h) the UNI instantiations take read r as bases [r * L, (r + 1) * L),
+// load no offsets (2 % of the bytes at L = 400) and run the step loop on a scalar bound.  The waves
+// of a workgroup DRAW their tiles from a
 // counter in LDS (the SIMD arbiter favours older waves; with fixed shares half of them idled for
 // the last third of the kernel).  Reads longer than KMC_WALK_MAX_READ are walked as pieces that
 // overlap by k-1 bases (kmc_vreads_*).  Reads that contain a non-ACGT byte are diverted to a scalar
-// kernel (the scalar part of kmc_walk_tail_kernel).  Measured: 1.33 ms for 8.95 G bases = 6.8 TB/s, 85 % of the HBM
-// peak.
+// kernel (the scalar part of kmc_walk_tail_kernel).  Measured: 1.31 ms for 8.95 G bases = 6.8 TB/s of
+// bases, 85 % of the HBM peak.
 #pragma once
 #include "../../include/kmc.h"
 #include "kmc_device.hip.h"
+#include "kmc_walk_uniform.h"   // KMC_WALK_MAX_READ; uniform-length batches
 #include <hip/hip_ext.h>
 
 #define KMC_WALK_MAX_K 63
-#define KMC_WALK_MAX_READ 416
 #define KMC_WALK_WAVES 16
 #define KMC_WALK_THREADS (KMC_WALK_WAVES * 64)
 #define KMC_WALK_STAGE_WORDS (64 * KMC_WALK_MAX_READ / 16 + 4)
@@ -496,11 +500,12 @@ __device__ unsigned long long kmc_walk_stamps[256 * 24];
 #else
 #define WALK_STAMP(i) do { } while (0)
 #endif
-template <int KW, bool CANON>
+// UNI: every read of the batch is uni_len bases long -- tile geometry in closed form, vstart / vend are not read
+template <int KW, bool CANON, bool UNI>
 __global__ __launch_bounds__(KMC_WALK_THREADS)
 void kmc_walk_kernel(const uint8_t* __restrict__ bases, u64 n_bases, const u64* __restrict__ vstart, const u64* __restrict__ vend, u64 n_reads,
                      int k, u64 tile_begin, u64 tile_end, WalkWs* ws, u32* deferred, const WalkMemoSlot<KW>* memo,
-                     WalkMemoSlot<KW>* memo_out, u64* gcnt, GTable g, GTable sk, SkLog lg) {
+                     WalkMemoSlot<KW>* memo_out, u64* gcnt, GTable g, GTable sk, SkLog lg, u32 uni_len) {
     extern __shared__ __align__(16) unsigned char walk_smem[];
     WalkLds<KW>& L = *reinterpret_cast<WalkLds<KW>*>(walk_smem);
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -592,7 +597,16 @@ void kmc_walk_kernel(const uint8_t* __restrict__ bases, u64 n_bases, const u64* 
         t.n_pieces = (u32)((t.B - t.A16 + 15) >> 4);
         return t;
     };
-    auto tile_geo = [&](u64 tile) { return tile_finish(tile_load(tile)); };
+    // Uniform batches: nothing is loaded, so nothing is issued ahead either -- the successor's geometry is a handful of
+    // scalar multiplies at the entry of the tile before (kmc_walk_uniform.h).
+    auto tile_geo = [&](u64 tile) {
+        if constexpr (UNI) {
+            const KmcWalkTile u = kmc_walk_tile_uniform(n_reads, uni_len, tile, (u32)lane);
+            return TileGeo{u.a, u.e, u.A, u.B, u.A16, u.n_pieces, u.have};
+        } else {
+            return tile_finish(tile_load(tile));
+        }
+    };
     // One round = KMC_WALK_LPR coalesced 1 KiB wave-loads: pieces base + 64*u + lane of the byte range
     // that starts at A16.  Branch-free on purpose (straight-line code lets the compiler keep counted
     // s_waitcnt vmcnt(N) and two rounds in flight): a piece index past the end is clamped to the
@@ -699,15 +713,19 @@ void kmc_walk_kernel(const uint8_t* __restrict__ bases, u64 n_bases, const u64* 
         // the only LDS round trip on the step-to-step critical path is the node lookup
         const u32* sp = stage + (mine ? w0 : 0);
         u32 wc = sp[0], wn = sp[1];
+        // (uniform batches: every read has the same steps, so the loop's bound and "is this a full step" are scalars --
+        // no compare per lane and no wave-wide ballot per step)
+        const u32 nfull_u = uni_len >> 4, nsteps_u = __builtin_amdgcn_ballot_w64(mine) != 0 ? (uni_len + 15) >> 4 : 0u;
         for (u32 tstep = 0; tstep < KMC_WALK_MAX_READ / KMC_WALK_STRIDE + 1; ++tstep) {
-            const bool act = tstep < nsteps;
-            if (__builtin_amdgcn_ballot_w64(act) == 0) break;
+            const bool act = UNI ? mine : tstep < nsteps;
+            if constexpr (UNI) { if (tstep >= nsteps_u) break; }
+            else { if (__builtin_amdgcn_ballot_w64(act) == 0) break; }
             if (act) {
                 // next 16 bases of my read, re-aligned to its start
                 u32 label = alignbit(wn, wc, sh);
                 wc = wn;
                 wn = sp[tstep + 2];  // (at most 2 words past the read's last word: inside the staging area's slack; unused then)
-                const bool full = tstep < nfull;
+                const bool full = UNI ? tstep < nfull_u : tstep < nfull;
                 WalkNode* np = reinterpret_cast<WalkNode*>(reinterpret_cast<char*>(L.node) + s);
                 const u64 pe = __hip_atomic_load(&np->prim, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 if (full && (u32)pe == label && (u32)(pe >> 32) != 0) {
@@ -745,7 +763,7 @@ void kmc_walk_kernel(const uint8_t* __restrict__ bases, u64 n_bases, const u64* 
         // are older than the round about to be consumed anyway; in all others nothing.  Without it the
         // compiler has to put an s_waitcnt vmcnt(0) in front of tile_finish, which would drain the
         // round in flight at every tile's last round.
-        asm volatile("" ::"v"(nxt_raw.a), "v"(nxt_raw.e));
+        if constexpr (!UNI) asm volatile("" ::"v"(nxt_raw.a), "v"(nxt_raw.e));
         const bool last = rbase + RP >= np_u;  // wave-uniform: this is the tile's last round
         if (rbase == 0) {  // tile entry
             if (lane < KMC_WALK_BADWORDS) L.badbits[wv][lane] = 0;
@@ -754,14 +772,18 @@ void kmc_walk_kernel(const uint8_t* __restrict__ bases, u64 n_bases, const u64* 
             if (lane == 0) jn = atomicAdd(&L.qnext, 1u);
             nxt_tile = tile_of((u32)__builtin_amdgcn_readfirstlane((int)jn));
             has_next = nxt_tile < n_tiles;
-            if (has_next) nxt_raw = tile_load(nxt_tile);
-            // a one-round tile needs its successor's geometry right behind the loads and has to wait for them
-            if (last && has_next) { asm volatile("; tile_finish right behind tile_load"); nxt = tile_finish(nxt_raw); }
-        } else if (last && has_next) {
+            if constexpr (UNI) {
+                if (has_next) nxt = tile_geo(nxt_tile);
+            } else {
+                if (has_next) nxt_raw = tile_load(nxt_tile);
+                // a one-round tile needs its successor's geometry right behind the loads and has to wait for them
+                if (last && has_next) { asm volatile("; tile_finish right behind tile_load"); nxt = tile_finish(nxt_raw); }
+            }
+        } else if constexpr (!UNI) {
             // every other tile: rounds later, and no path from tile_load leads here except through the
             // use above (a second copy on purpose: merged with the one-round case, its s_waitcnt
             // vmcnt(0) would serve both)
-            nxt = tile_finish(nxt_raw);
+            if (last && has_next) nxt = tile_finish(nxt_raw);
         }
         const u32 cur_last = cur.n_pieces ? cur.n_pieces - 1 : 0, nxt_last = nxt.n_pieces ? nxt.n_pieces - 1 : 0;
         issue(y, last ? nxt.A16 : cur.A16, last ? nxt_last : cur_last, last ? 0u : rbase + RP);
@@ -898,9 +920,10 @@ __device__ __forceinline__ void walk_unfold_part(const WalkMemoSlot<KW>* memo, u
 }
 
 // One lane per listed read, byte by byte: reads diverted from the walk kernel (non-ACGT bytes).
-template <int KW, bool CANON>
+// UNI: read r is bases [r * uni_len, (r + 1) * uni_len), vstart / vend are not read.
+template <int KW, bool CANON, bool UNI>
 __device__ __forceinline__ void walk_scalar_part(const uint8_t* __restrict__ bases, const u64* __restrict__ vstart, const u64* __restrict__ vend,
-                                                 WalkWs* ws, const u32* __restrict__ list, int k, const GTable& g, u32 block, u32 n_blocks) {
+                                                 WalkWs* ws, const u32* __restrict__ list, int k, const GTable& g, u32 block, u32 n_blocks, u32 uni_len) {
     // every workgroup of this part reads the deferred-read counter; the last one to have read it leaves the
     // workspace clean for the next launch (no memset per launch)
     __shared__ u64 s_n;
@@ -924,10 +947,10 @@ __device__ __forceinline__ void walk_scalar_part(const uint8_t* __restrict__ bas
         const u64 r = list[i];
         u64 lo = 0, hi = 0;
         int run = 0;
-        for (u64 p = vstart[r]; p < vend[r]; ++p) {
+        auto base = [&](u64 p) {
             const uint8_t b = bases[p];
             int c = b == 'A' ? 0 : b == 'C' ? 1 : b == 'G' ? 2 : b == 'T' ? 3 : -1;
-            if (c < 0) { run = 0; lo = hi = 0; continue; }
+            if (c < 0) { run = 0; lo = hi = 0; return; }
             hi = ((hi << 2) | (lo >> 62)) & mask_hi;
             lo = ((lo << 2) | (u64)c) & mask_lo;
             if (++run >= k) {
@@ -940,6 +963,12 @@ __device__ __forceinline__ void walk_scalar_part(const uint8_t* __restrict__ bas
                 gtable_add<KW>(g, khi, klo, 1);
                 nk++;
             }
+        };
+        if constexpr (UNI) {
+            const u64 p0 = r * uni_len;
+            for (u64 p = p0; p < p0 + uni_len; ++p) base(p);
+        } else {
+            for (u64 p = vstart[r]; p < vend[r]; ++p) base(p);
         }
     }
     nk = wave_sum_u64(nk);
@@ -950,12 +979,12 @@ __device__ __forceinline__ void walk_scalar_part(const uint8_t* __restrict__ bas
 // workgroups turn the dense traversal counters into k-mer counts, the others count the diverted reads.
 // The two parts touch disjoint state (gcnt / the deferred list) and both only add to the count table.
 #define KMC_WALK_UNFOLD_BLOCKS ((KMC_WALK_NCAP + KMC_WALK_ECAP) * KMC_WALK_STRIDE / 256)
-template <int KW, bool CANON>
+template <int KW, bool CANON, bool UNI>
 __global__ __launch_bounds__(256)
 void kmc_walk_tail_kernel(const uint8_t* __restrict__ bases, const u64* __restrict__ vstart, const u64* __restrict__ vend,
-                          WalkWs* ws, const u32* __restrict__ list, const WalkMemoSlot<KW>* memo, u64* gcnt, int k, GTable g) {
+                          WalkWs* ws, const u32* __restrict__ list, const WalkMemoSlot<KW>* memo, u64* gcnt, int k, GTable g, u32 uni_len) {
     if (blockIdx.x < KMC_WALK_UNFOLD_BLOCKS) walk_unfold_part<KW, CANON>(memo, gcnt, k, g, blockIdx.x, KMC_WALK_UNFOLD_BLOCKS);
-    else walk_scalar_part<KW, CANON>(bases, vstart, vend, ws, list, k, g, blockIdx.x - KMC_WALK_UNFOLD_BLOCKS, gridDim.x - KMC_WALK_UNFOLD_BLOCKS);
+    else walk_scalar_part<KW, CANON, UNI>(bases, vstart, vend, ws, list, k, g, blockIdx.x - KMC_WALK_UNFOLD_BLOCKS, gridDim.x - KMC_WALK_UNFOLD_BLOCKS, uni_len);
 }
 
 // ---- host side ------------------------------------------------------------------------------
@@ -1002,23 +1031,23 @@ static inline size_t kmc_walk_slot_bytes(int KW) { return KW == 1 ? sizeof(WalkM
 static inline size_t kmc_walk_memo_bytes(int, int KW) { return 2 * kmc_walk_slot_bytes(KW); }
 static inline size_t kmc_walk_workspace_bytes(u64 n_reads) { return KMC_WALK_WS_PREFIX + (size_t)(n_reads + 16) * sizeof(u32); }
 
-template <int KW, bool CANON>
+template <int KW, bool CANON, bool UNI>
 static inline void kmc_walk_launch_t(hipStream_t st, int grid, int n_cu, const uint8_t* d_bases, const u64* d_vstart, const u64* d_vend,
                                      u64 n_reads, u64 n_bases, int k, u64 tile_begin, u64 tile_end, WalkWs* hdr, u32* list, u64* gcnt, void* memo, int parity, GTable g, GTable sk, SkLog lg, int phase,
-                                     hipEvent_t e0, hipEvent_t e1) {
+                                     hipEvent_t e0, hipEvent_t e1, u32 uni_len) {
     const size_t smem = sizeof(WalkLds<KW>);
     static std::atomic<unsigned long long> attr{0};  // one flag per instantiation and device
-    if (kmc_attr_once(attr)) (void)hipFuncSetAttribute((const void*)kmc_walk_kernel<KW, CANON>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (kmc_attr_once(attr)) (void)hipFuncSetAttribute((const void*)kmc_walk_kernel<KW, CANON, UNI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     WalkMemoSlot<KW>* slots = (WalkMemoSlot<KW>*)memo;
     if (phase == 0) {
         // the launch's own start / stop timestamps go to e0 / e1 (hipExtLaunchKernelGGL): what hipEventRecord in front of and
         // behind the launch measured too, without two more packets in the stream per step
-        hipExtLaunchKernelGGL((kmc_walk_kernel<KW, CANON>), dim3(grid), dim3(KMC_WALK_THREADS), (uint32_t)smem, st, e0, e1, 0u, d_bases, n_bases, d_vstart, d_vend, n_reads, k, tile_begin, tile_end, hdr, list,
-                              (const WalkMemoSlot<KW>*)&slots[parity], &slots[parity ^ 1], gcnt, g, sk, lg);
+        hipExtLaunchKernelGGL((kmc_walk_kernel<KW, CANON, UNI>), dim3(grid), dim3(KMC_WALK_THREADS), (uint32_t)smem, st, e0, e1, 0u, d_bases, n_bases, d_vstart, d_vend, n_reads, k, tile_begin, tile_end, hdr, list,
+                              (const WalkMemoSlot<KW>*)&slots[parity], &slots[parity ^ 1], gcnt, g, sk, lg, uni_len);
     } else {
         static_assert(((KMC_WALK_NCAP + KMC_WALK_ECAP) * KMC_WALK_STRIDE) % 256 == 0 && 256 % KMC_WALK_STRIDE == 0, "unfold grid must cover the items exactly");
-        hipLaunchKernelGGL((kmc_walk_tail_kernel<KW, CANON>), dim3(KMC_WALK_UNFOLD_BLOCKS + n_cu), dim3(256), 0, st,
-                           d_bases, d_vstart, d_vend, hdr, list, (const WalkMemoSlot<KW>*)&slots[parity], gcnt, k, g);
+        hipLaunchKernelGGL((kmc_walk_tail_kernel<KW, CANON, UNI>), dim3(KMC_WALK_UNFOLD_BLOCKS + n_cu), dim3(256), 0, st,
+                           d_bases, d_vstart, d_vend, hdr, list, (const WalkMemoSlot<KW>*)&slots[parity], gcnt, k, g, uni_len);
     }
 }
 
@@ -1041,6 +1070,7 @@ static inline int kmc_sk_unfold_launch(hipStream_t st, int n_cu, int KW, int k, 
 // it diverted + the unfold of the dense snapshot counters.  `parity` selects the snapshot slot read
 // by this launch (the other one is written); the caller flips it after phase 1.  The caller clears the workspace header (kmc_walk_prepare) before phase 0.
 // e0 / e1: the events phase 0 records its start and stop in (phase 1 ignores them).
+// uni_len != 0: every read is uni_len bases long (kmc_walk_uniform); both phases then run their UNI instantiation.
 static inline int kmc_walk_prepare(hipStream_t st, void* ws) {
     return hipMemsetAsync(ws, 0, KMC_WALK_WS_PREFIX, st) == hipSuccess ? KMC_OK : KMC_ERR_HIP;
 }
@@ -1052,19 +1082,22 @@ static inline int kmc_walk_grid(u64 n_tiles, int n_cu) {
 }
 static inline int kmc_walk_launch(hipStream_t st, int n_cu, int KW, int k, bool canon, const uint8_t* d_bases,
                                   const u64* d_vstart, const u64* d_vend, u64 n_reads, u64 n_bases, u64 tile_begin, u64 tile_end, void* ws, void* memo, int parity, GTable g, GTable sk, SkLog lg, int phase,
-                                  hipEvent_t e0, hipEvent_t e1) {
+                                  hipEvent_t e0, hipEvent_t e1, u32 uni_len) {
     if (n_reads >= (1ull << 32) || tile_end <= tile_begin) return KMC_ERR_ARG;
     WalkWs* hdr = (WalkWs*)ws;
     u32* list = (u32*)((char*)ws + KMC_WALK_WS_PREFIX);
     u64* gcnt_ws = (u64*)((char*)ws + sizeof(WalkWs));
     const u64 n_tiles = tile_end - tile_begin;
     const int grid = kmc_walk_grid(n_tiles, n_cu);
+#define KMC_WALK_GO(KWV, CN, UN) kmc_walk_launch_t<KWV, CN, UN>(st, grid, n_cu, d_bases, d_vstart, d_vend, n_reads, n_bases, k, tile_begin, tile_end, \
+                                                               hdr, list, gcnt_ws, memo, parity, g, sk, lg, phase, e0, e1, uni_len)
     if (KW == 1) {
-        if (canon) kmc_walk_launch_t<1, true>(st, grid, n_cu, d_bases, d_vstart, d_vend, n_reads, n_bases, k, tile_begin, tile_end, hdr, list, gcnt_ws, memo, parity, g, sk, lg, phase, e0, e1);
-        else kmc_walk_launch_t<1, false>(st, grid, n_cu, d_bases, d_vstart, d_vend, n_reads, n_bases, k, tile_begin, tile_end, hdr, list, gcnt_ws, memo, parity, g, sk, lg, phase, e0, e1);
+        if (canon) { if (uni_len) KMC_WALK_GO(1, true, true); else KMC_WALK_GO(1, true, false); }
+        else { if (uni_len) KMC_WALK_GO(1, false, true); else KMC_WALK_GO(1, false, false); }
     } else {
-        if (canon) kmc_walk_launch_t<2, true>(st, grid, n_cu, d_bases, d_vstart, d_vend, n_reads, n_bases, k, tile_begin, tile_end, hdr, list, gcnt_ws, memo, parity, g, sk, lg, phase, e0, e1);
-        else kmc_walk_launch_t<2, false>(st, grid, n_cu, d_bases, d_vstart, d_vend, n_reads, n_bases, k, tile_begin, tile_end, hdr, list, gcnt_ws, memo, parity, g, sk, lg, phase, e0, e1);
+        if (canon) { if (uni_len) KMC_WALK_GO(2, true, true); else KMC_WALK_GO(2, true, false); }
+        else { if (uni_len) KMC_WALK_GO(2, false, true); else KMC_WALK_GO(2, false, false); }
     }
+#undef KMC_WALK_GO
     return hipGetLastError() == hipSuccess ? KMC_OK : KMC_ERR_HIP;
 }

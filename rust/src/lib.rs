@@ -74,6 +74,7 @@ pub struct KmcStats {
     pub n_async_ok: u64,
     pub n_async_slabs_skipped: u64,
     pub n_planner_stale: u64,
+    pub walk_uniform_launches: u64,
 }
 
 #[repr(C)]
