@@ -183,7 +183,9 @@ int kmc_finalize(kmc_ctx* ctx, uint64_t* n_distinct, uint64_t* n_total);
  * the ordinary finalize; an addition puts the view's counts back into the table first.  A caller that queues many steps
  * (count -> kmc_finalize_async -> kmc_reset -> ...) checks afterwards that every step delivered:
  * kmc_stats.n_async_ok grows by one per finalize that produced its view, n_async_slabs_skipped by the oversize slabs
- * those finalizes saw (both valid after a synchronising call).  Larger tables are finalized synchronously, as by kmc_finalize. */
+ * those finalizes saw (both valid after a synchronising call).  An empty table (nothing spilled, nothing pending) produces
+ * its view too, the empty one: a reduce step whose owner holds no key counts as delivered, and the oversize slabs it saw
+ * are counted.  Larger tables are finalized synchronously, as by kmc_finalize. */
 int kmc_finalize_async(kmc_ctx* ctx);
 
 /* Copy the sorted table to caller-allocated host arrays of `cap` entries (cap >= n_distinct).

@@ -253,6 +253,43 @@ __global__ void kmc_merge_slabs_kernel(GTable g, const u64* __restrict__ slabs, 
 // (History: a single-workgroup bitonic network took 55-60 us for 3,350 keys whether it ran in LDS
 // with workgroup barriers, in LDS with wave-local passes, or in registers with wave shuffles.)
 #define KMC_FIN_CHUNK 16
+// The publishing workgroup's part (all 1024 threads of ONE workgroup, behind every read of the table): the counters to
+// the host's pinned mirror with the verdict "view written" (FASTFIN = 1, ticket[1] + 1, ticket[2] + the oversize slabs
+// this table's merges saw), FINSEQ last, then the n listed slots and the device counters cleared.  `empty`: the table
+// holds no key (n == 0) -- the view is the empty one and the sum of its counts is zero, whatever the device word says.
+template <int KW>
+__device__ __forceinline__ void kmc_fin_publish_and_drain(GTable g, const u64* __restrict__ sk_counters, u32* __restrict__ ticket,
+                                                          u64* __restrict__ host_mirror, u64 seq, u64 n, bool empty) {
+    const u32 tid = threadIdx.x;
+    // The host waits on mirror[FINSEQ] (kmc_api.hip: poll_fin), not on the end of the kernel: that word is written
+    // last, behind a system-scope fence; everything after it touches device memory only, in stream order before
+    // whatever the host launches next.
+    if (tid < KMC_CTR_FINSEQ && tid != KMC_CTR_SUM2 && tid != KMC_CTR_FASTFIN)
+        __hip_atomic_store(&host_mirror[tid], g.counters[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    else if (tid == KMC_CTR_FINSEQ) {
+        const u32 okn = ticket[1] + 1u, skn = ticket[2] + (u32)g.counters[KMC_CTR_SLABSKIP];
+        ticket[1] = okn;
+        ticket[2] = skn;
+        __hip_atomic_store(&host_mirror[KMC_CTR_FINOK], (u64)okn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(&host_mirror[KMC_CTR_FINSKIP], (u64)skn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        const u64 tot = empty ? 0ull : __hip_atomic_load(&g.counters[KMC_CTR_SUM2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&host_mirror[KMC_CTR_SUM2], tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(&host_mirror[KMC_CTR_FASTFIN], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    else if (tid >= 64 && tid < 64 + KMC_CTR_N)
+        __hip_atomic_store(&host_mirror[KMC_CTR_N + tid - 64], sk_counters[tid - 64], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __threadfence_system();
+    __syncthreads();
+    if (tid == 0) __hip_atomic_store(&host_mirror[KMC_CTR_FINSEQ], seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    for (u64 i = tid; i < n; i += 1024) {
+        const u64 slot = g.occ_list[i];
+        if (KW == 2) { g.key_hi[slot] = KMC_EMPTY64; g.key_lo[slot] = 0; } else g.key_lo[slot] = KMC_EMPTY64;
+        g.count[slot] = 0;
+    }
+    __syncthreads();   // (the counters above have been read)
+    if (tid < KMC_CTR_N) g.counters[tid] = 0;
+    if (tid == 0) *ticket = 0;
+}
 // host_mirror: the ctx's pinned mirror of [count-table counters | (k+16)-mer-table counters].  The host clears
 // mirror[KMC_CTR_FASTFIN] before the launch; 1 afterwards means: sorted view written, counters published
 // (mirror[KMC_CTR_SUM2] = sum of all counts), table drained; mirror[KMC_CTR_FINSEQ] = seq is written LAST (the host waits on it).
@@ -279,6 +316,16 @@ void kmc_small_finalize_kernel(GTable g, const u64* __restrict__ sk_counters, u3
     // behind the last ticket: all of them decide alike.  A workgroup past the table that starts that late may
     // read zeros -- it leaves either way.)
     if (!ok) {
+        // An EMPTY table with nothing spilled, no error and nothing pending is not a table the kernel refuses: an owner whose
+        // share of a reduce step is empty (tiny k, or every slab of the step oversize) has delivered its partition -- the
+        // empty view.  No workgroup would draw the last ticket (nb == 0), so workgroup 0 publishes here, in the branch it
+        // takes anyway: the counters (SLABSKIP among them) go to the mirror and are cleared exactly as behind a drain.
+        // (Every workgroup decides alike: the words this depends on are zero before and after workgroup 0 has cleared them.)
+        const bool empty = n == 0 && g.counters[KMC_CTR_SPILL] == 0 && g.counters[KMC_CTR_ERR] == 0 && sk_counters[KMC_CTR_KMERS] == 0;
+        if (empty) {
+            if (blockIdx.x == 0) kmc_fin_publish_and_drain<KW>(g, sk_counters, ticket, host_mirror, seq, 0, true);
+            return;
+        }
         if (blockIdx.x == 0 && tid == 0) {   // "gave up": the table is as it was
             __hip_atomic_store(&host_mirror[KMC_CTR_FASTFIN], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             __hip_atomic_store(&host_mirror[KMC_CTR_FINOK], (u64)ticket[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -380,32 +427,5 @@ void kmc_small_finalize_kernel(GTable g, const u64* __restrict__ sk_counters, u3
     __syncthreads();
     if (!s_last) return;
     // ---- the last workgroup: publish the counters, empty the table (every workgroup has finished READING it) ----
-    // The host waits on mirror[FINSEQ] (kmc_api.hip: poll_fin), not on the end of the kernel: that word is written
-    // last, behind a system-scope fence; everything after it touches device memory only, in stream order before
-    // whatever the host launches next.
-    if (tid < KMC_CTR_FINSEQ && tid != KMC_CTR_SUM2 && tid != KMC_CTR_FASTFIN)
-        __hip_atomic_store(&host_mirror[tid], g.counters[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    else if (tid == KMC_CTR_FINSEQ) {
-        const u32 okn = ticket[1] + 1u, skn = ticket[2] + (u32)g.counters[KMC_CTR_SLABSKIP];
-        ticket[1] = okn;
-        ticket[2] = skn;
-        __hip_atomic_store(&host_mirror[KMC_CTR_FINOK], (u64)okn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(&host_mirror[KMC_CTR_FINSKIP], (u64)skn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        const u64 tot = __hip_atomic_load(&g.counters[KMC_CTR_SUM2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&host_mirror[KMC_CTR_SUM2], tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(&host_mirror[KMC_CTR_FASTFIN], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    else if (tid >= 64 && tid < 64 + KMC_CTR_N)
-        __hip_atomic_store(&host_mirror[KMC_CTR_N + tid - 64], sk_counters[tid - 64], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __threadfence_system();
-    __syncthreads();
-    if (tid == 0) __hip_atomic_store(&host_mirror[KMC_CTR_FINSEQ], seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    for (u64 i = tid; i < n; i += 1024) {
-        const u64 slot = g.occ_list[i];
-        if (KW == 2) { g.key_hi[slot] = KMC_EMPTY64; g.key_lo[slot] = 0; } else g.key_lo[slot] = KMC_EMPTY64;
-        g.count[slot] = 0;
-    }
-    __syncthreads();   // (the counters above have been read)
-    if (tid < KMC_CTR_N) g.counters[tid] = 0;
-    if (tid == 0) *ticket = 0;
+    kmc_fin_publish_and_drain<KW>(g, sk_counters, ticket, host_mirror, seq, n, false);
 }

@@ -160,6 +160,11 @@ def _slab_buffers(words: int, world: int, dev):
     if key not in _slab_cache:
         _slab_cache[key] = (torch.zeros(words, dtype=torch.int64, device=dev),
                             torch.zeros(words * world, dtype=torch.int64, device=dev))
+        if torch.device(dev).type == "cuda":
+            # the zero fill runs on torch's current stream; a ctx created without stream= packs the slab on its OWN
+            # non-blocking stream, which does not wait for it: the fill could land on top of the packed slab (the header
+            # then reads "0 pairs, inline" and the rank's table is lost).  Once per buffer shape, not per step.
+            torch.cuda.current_stream(dev).synchronize()
     return _slab_cache[key]
 
 
@@ -192,7 +197,8 @@ def reduce_tables(local, owner, group=None, slab_entries: int = SLAB_ENTRIES, re
     are queued and the call returns (None, None).  Every such step still DELIVERS its sorted partition on the
     device; what is deferred is the host's look at it.  The caller synchronises when it wants (owner.finalize()
     returns the sizes of the last step's view) and then checks owner.stats(): n_async_ok must have grown by
-    one per step and n_async_slabs_skipped must not have grown -- otherwise some step's table did not fit its
+    one per step (also on a rank whose owned partition is empty: the empty view counts as delivered) and
+    n_async_slabs_skipped must not have grown -- otherwise some step's table did not fit its
     slab (or the small-table path) and that step has to be redone with finalize=True (which routes such tables
     through the all-to-all), after owner.reset(): the owner already holds the slabs that did travel inline,
     and merging them a second time would double their counts."""

@@ -134,6 +134,25 @@ def test_world2_reduce_equals_single_table(oracle, tmp_path, k):
     assert sum(len(p["lo"]) for p in parts) == want.n_distinct
 
 
+@pytest.mark.parametrize("n_parts", [1, 2, 3, 5, 8, 63, 64, 65, 257, 4096])
+def test_owner_function_three_ways(kmc, n_parts):
+    """kmc_owner_of (C), distributed.owner_np (numpy) and a restatement in plain Python integers (every product masked
+    to 64 bits) agree on 2000 keys with non-zero high words: C and numpy otherwise vouch only for each other."""
+    import partition_np
+    kd = importlib.import_module("k-mer-count_amd.distributed")
+    rng = np.random.default_rng(4242)
+    hi = rng.integers(1, 2**64, 2000, dtype=np.uint64)
+    lo = rng.integers(0, 2**64, 2000, dtype=np.uint64)
+    hi[:4] = [1, 2**63, 2**64 - 1, 2**32]         # (products that wrap, and the extremes)
+    lo[:4] = [0, 2**64 - 1, 2**64 - 1, 2**63]
+    vec = kd.owner_np(hi, lo, n_parts)
+    assert vec.min() >= 0 and vec.max() < n_parts
+    for h, l, o in zip(hi.tolist(), lo.tolist(), vec.tolist()):
+        assert partition_np.owner_py(h, l, n_parts) == o == kmc.owner_of(h, l, n_parts), (h, l, n_parts)
+    if n_parts >= 2:
+        assert len(set(vec.tolist())) > 1
+
+
 def test_shard_range_covers_everything():
     kd = importlib.import_module("k-mer-count_amd.distributed")
     for n in (0, 1, 7, 200, 22371032):

@@ -348,6 +348,9 @@ def test_poll_and_forget_source(kmc, oracle):
 
 def test_merge_and_partition(kmc, oracle):
     """Multi-GPU reduce building blocks on one GPU: owner partition + merge == counting everything."""
+    torch = pytest.importorskip("torch")
+    import partition_np
+    kd = importlib.import_module("k-mer-count_amd.distributed")
     rng = np.random.default_rng(21)
     for k in (21, 63):
         bases, offs = _random_reads(rng, 2000, 100, 300)
@@ -360,10 +363,14 @@ def test_merge_and_partition(kmc, oracle):
             for src in (a, b):
                 pb, dhi, dlo, dcnt = src.partition_device(4)
                 assert pb[0] == 0 and pb[4] == src.export_device()[3]
-                # every pair sits in its owner's range
+                # every pair sits in its owner's range: every entry of part p has owner p, and the parts are the table
                 t = src.export()
                 own = np.array([kmc.owner_of(int(h), int(l), 4) for h, l in zip(t.key_hi[:200], t.key_lo[:200])])
                 assert own.min() >= 0 and own.max() < 4
+                n = pb[4]
+                view = lambda ptr: kd.device_view(ptr, n, torch.device("cuda", 0)).cpu().numpy().view(np.uint64).copy()
+                partition_np.check_partition(pb, view(dhi) if k > 31 else np.zeros(n, np.uint64), view(dlo), view(dcnt),
+                                             t.key_hi, t.key_lo, t.count, 4)
                 for p in range(4):
                     n = pb[p + 1] - pb[p]
                     if n:
