@@ -1042,3 +1042,14 @@ def read_peak_device(d_buf: int, n_bytes: int, device: int = 0, stream: int = 0,
     if rc:
         raise KmcError(rc, "kmc_read_peak_device failed")
     return ms.value, x.value
+
+
+def debug_mem() -> Tuple[int, int, int, int, int]:
+    """The library's own allocation counters, process-wide (kmc_debug_mem): live device bytes, live pinned bytes, device
+    allocation calls, pinned allocation calls, frees that the runtime refused.  (Bound here, not in lib(): a build loaded
+    through KMC_LIB_PATH for an A/B run may be older than the call.)"""
+    f = lib().kmc_debug_mem
+    f.argtypes, f.restype = [C.POINTER(C.c_uint64 * 5)], None
+    out = (C.c_uint64 * 5)()
+    f(out)
+    return tuple(int(v) for v in out)

@@ -28,6 +28,7 @@
 #include "kmc_ingest.h"
 
 thread_local char g_create_err[512] = {0};
+MemStats g_mem;   // kmc_mem.hip.h: what kmc_debug_mem reports
 
 namespace {
 
@@ -36,34 +37,20 @@ int ensure_keep(kmc_ctx* c, DevBuf& b, size_t bytes, size_t keep) {
     if (b.bytes >= bytes && b.p) return KMC_OK;
     if (!b.p || !keep) return ensure(c, b, bytes);
     const size_t want = std::max(bytes + bytes / 8 + 256, b.bytes * 2);
-    void* np = nullptr;
-    HIPCHK(c, hipMalloc(&np, want));
-    if (hipMemcpyAsync(np, b.p, keep, hipMemcpyDeviceToDevice, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
-        (void)hipFree(np);
+    DevBuf np;
+    HIPCHK(c, np.alloc(want));
+    if (hipMemcpyAsync(np.p, b.p, keep, hipMemcpyDeviceToDevice, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
         return fail(c, KMC_ERR_HIP, "growing the key accumulator failed");
-    }
-    (void)hipFree(b.p);
-    b.p = np;
-    b.bytes = want;
+    b = std::move(np);
     return KMC_OK;
 }
 
-void free_runs(kmc_ctx* c, bool release);
-
-void free_table(Table& t) {
-    if (t.hi) (void)hipFree(t.hi);
-    if (t.lo) (void)hipFree(t.lo);
-    if (t.cnt) (void)hipFree(t.cnt);
-    if (t.mid) (void)hipFree(t.mid);
-    t = Table{};
-}
-
 int alloc_table(kmc_ctx* c, Table& t, u64 cap) {
-    t = Table{};
+    t.reset();
     t.cap = cap;
-    HIPCHK(c, hipMalloc((void**)&t.lo, cap * sizeof(u64)));
-    HIPCHK(c, hipMalloc((void**)&t.cnt, cap * sizeof(u64)));
-    if (c->KW == 2) HIPCHK(c, hipMalloc((void**)&t.hi, cap * sizeof(u64)));
+    HIPCHK(c, t.lo.alloc(cap * sizeof(u64)));
+    HIPCHK(c, t.cnt.alloc(cap * sizeof(u64)));
+    if (c->KW == 2) HIPCHK(c, t.hi.alloc(cap * sizeof(u64)));
     // EMPTY marker is all ones in the word that is CASed
     if (c->KW == 2) {
         HIPCHK(c, hipMemsetAsync(t.hi, 0xFF, cap * sizeof(u64), c->stream));
@@ -75,20 +62,20 @@ int alloc_table(kmc_ctx* c, Table& t, u64 cap) {
     return KMC_OK;
 }
 
-// drop the live runs; their buffers go back to the pool (release == true: really free everything)
-void free_runs(kmc_ctx* c, bool release = false) {
+// the previous finalize's merged view goes back to the pool
+void pool_view_run(kmc_ctx* c) {
+    if (!c->view_run.lo) return;
+    c->view_run.n = 0;
+    c->run_pool.push_back(std::move(c->view_run));
+    c->view_run = kmc_ctx::Run{};
+}
+
+// drop the live runs; their buffers go back to the pool
+void free_runs(kmc_ctx* c) {
     c->acc_n = 0;  // (keys extracted and not yet sorted go with the runs)
-    for (auto& r : c->runs) { r.n = 0; c->run_pool.push_back(r); }
+    for (auto& r : c->runs) { r.n = 0; c->run_pool.push_back(std::move(r)); }
     c->runs.clear();
-    if (c->view_run.lo) { c->view_run.n = 0; c->run_pool.push_back(c->view_run); c->view_run = kmc_ctx::Run{}; }
-    if (release) {
-        for (auto& r : c->run_pool) {
-            if (r.hi) (void)hipFree(r.hi);
-            if (r.lo) (void)hipFree(r.lo);
-            if (r.cnt) (void)hipFree(r.cnt);
-        }
-        c->run_pool.clear();
-    }
+    pool_view_run(c);
 }
 
 // a run with room for `cap` entries: the smallest fitting pooled one, else a new allocation
@@ -97,7 +84,7 @@ int take_run(kmc_ctx* c, u64 cap, kmc_ctx::Run* out) {
     for (size_t i = 0; i < c->run_pool.size(); ++i)
         if (c->run_pool[i].cap >= cap && (best < 0 || c->run_pool[i].cap < c->run_pool[(size_t)best].cap)) best = (int)i;
     if (best >= 0) {
-        *out = c->run_pool[(size_t)best];
+        *out = std::move(c->run_pool[(size_t)best]);
         c->run_pool.erase(c->run_pool.begin() + best);
         out->n = 0;
         out->total = 0;
@@ -107,18 +94,14 @@ int take_run(kmc_ctx* c, u64 cap, kmc_ctx::Run* out) {
     if (!c->run_pool.empty()) {  // nothing fits: recycle the memory of the largest pooled buffer
         size_t big = 0;
         for (size_t i = 1; i < c->run_pool.size(); ++i) if (c->run_pool[i].cap > c->run_pool[big].cap) big = i;
-        kmc_ctx::Run r = c->run_pool[big];
         c->run_pool.erase(c->run_pool.begin() + (long)big);
-        if (r.hi) (void)hipFree(r.hi);
-        (void)hipFree(r.lo);
-        (void)hipFree(r.cnt);
     }
     kmc_ctx::Run r;
     r.cap = cap + cap / 16 + 64;
-    HIPCHK(c, hipMalloc((void**)&r.lo, r.cap * sizeof(u64)));
-    if (hipMalloc((void**)&r.cnt, r.cap * sizeof(u64)) != hipSuccess) { (void)hipFree(r.lo); return fail(c, KMC_ERR_NOMEM, "out of device memory for a sorted run"); }
-    if (c->KW == 2 && hipMalloc((void**)&r.hi, r.cap * sizeof(u64)) != hipSuccess) { (void)hipFree(r.lo); (void)hipFree(r.cnt); return fail(c, KMC_ERR_NOMEM, "out of device memory for a sorted run"); }
-    *out = r;
+    HIPCHK(c, r.lo.alloc(r.cap * sizeof(u64)));
+    if (r.cnt.alloc(r.cap * sizeof(u64)) != hipSuccess || (c->KW == 2 && r.hi.alloc(r.cap * sizeof(u64)) != hipSuccess))
+        return fail(c, KMC_ERR_NOMEM, "out of device memory for a sorted run");
+    *out = std::move(r);
     return KMC_OK;
 }
 
@@ -175,26 +158,24 @@ int sk_clear(kmc_ctx* c) {
 // and is re-allocated sixteen times larger, once, when a poll finds it more than half full -- at a moment
 // when it is empty (right behind its unfold), so nothing has to be re-inserted.
 void sk_free(kmc_ctx* c) {
-    free_table(c->sk);
-    c->sk = Table{};
-    u64** p[] = {&c->sk_spill_hi, &c->sk_spill_lo, &c->sk_spill_cnt, &c->sk_spill_mid, &c->sk_occ};
-    for (u64** q : p) { if (*q) (void)hipFree(*q); *q = nullptr; }
+    c->sk.reset();
+    for (Dev<u64>* q : {&c->sk_spill_hi, &c->sk_spill_lo, &c->sk_spill_cnt, &c->sk_spill_mid, &c->sk_occ}) (void)q->reset();
 }
 int sk_alloc_parts(kmc_ctx* c, u64 cap) {
     const bool three = c->cfg.k > KMC_SK_MAX_K;  // a (k+16)-mer of more than 63 bases: three key words
     c->sk.cap = cap;
-    HIPCHK(c, hipMalloc((void**)&c->sk.hi, cap * sizeof(u64)));
-    HIPCHK(c, hipMalloc((void**)&c->sk.lo, cap * sizeof(u64)));
-    HIPCHK(c, hipMalloc((void**)&c->sk.cnt, cap * sizeof(u64)));
-    if (three) HIPCHK(c, hipMalloc((void**)&c->sk.mid, cap * sizeof(u64)));
+    HIPCHK(c, c->sk.hi.alloc(cap * sizeof(u64)));
+    HIPCHK(c, c->sk.lo.alloc(cap * sizeof(u64)));
+    HIPCHK(c, c->sk.cnt.alloc(cap * sizeof(u64)));
+    if (three) HIPCHK(c, c->sk.mid.alloc(cap * sizeof(u64)));
     c->d_sk_counters = c->d_counters + KMC_CTR_N;
     c->h_sk_counters = c->h_counters + KMC_CTR_N;
     c->sk_spill_cap = std::max<u64>(cap / 64, 4096);
-    HIPCHK(c, hipMalloc((void**)&c->sk_spill_hi, c->sk_spill_cap * sizeof(u64)));
-    HIPCHK(c, hipMalloc((void**)&c->sk_spill_lo, c->sk_spill_cap * sizeof(u64)));
-    HIPCHK(c, hipMalloc((void**)&c->sk_spill_cnt, c->sk_spill_cap * sizeof(u64)));
-    if (three) HIPCHK(c, hipMalloc((void**)&c->sk_spill_mid, c->sk_spill_cap * sizeof(u64)));
-    HIPCHK(c, hipMalloc((void**)&c->sk_occ, cap * sizeof(u64)));
+    HIPCHK(c, c->sk_spill_hi.alloc(c->sk_spill_cap * sizeof(u64)));
+    HIPCHK(c, c->sk_spill_lo.alloc(c->sk_spill_cap * sizeof(u64)));
+    HIPCHK(c, c->sk_spill_cnt.alloc(c->sk_spill_cap * sizeof(u64)));
+    if (three) HIPCHK(c, c->sk_spill_mid.alloc(c->sk_spill_cap * sizeof(u64)));
+    HIPCHK(c, c->sk_occ.alloc(cap * sizeof(u64)));
     return sk_clear(c);
 }
 // all or nothing: a table whose spill area or slot list is missing must never reach a kernel (kmc_spill writes
@@ -333,7 +314,7 @@ int recover_overflow(kmc_ctx* c);
 int grow_to(kmc_ctx* c, u64 newcap) {
     Table nt;
     int rc = alloc_table(c, nt, newcap);
-    if (rc) { free_table(nt); return rc; }
+    if (rc) return rc;
     // fresh occupancy count: rehash re-counts every claimed slot
     HIPCHK(c, hipMemsetAsync(&c->d_counters[KMC_CTR_OCCUPIED], 0, sizeof(u64), c->stream));
     GTable go = gtable_of(c, c->tab), gn = gtable_of(c, nt);
@@ -342,8 +323,7 @@ int grow_to(kmc_ctx* c, u64 newcap) {
     else hipLaunchKernelGGL(kmc_rehash_kernel<2>, dim3(grid), dim3(256), 0, c->stream, go, gn);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    free_table(c->tab);
-    c->tab = nt;
+    c->tab = std::move(nt);   // (frees the old arrays)
     c->st.table_capacity = newcap;
     return KMC_OK;
 }
@@ -373,10 +353,10 @@ int settle(kmc_ctx* c) {
             u64 n = spill;
             c->st.n_spilled += n;
             // the merge may itself spill (appends after position n); handled by the next iteration
-            u64 *sh = nullptr, *sl = nullptr, *sc = nullptr;
-            HIPCHK(c, hipMalloc((void**)&sl, n * sizeof(u64)));
-            HIPCHK(c, hipMalloc((void**)&sc, n * sizeof(u64)));
-            if (c->KW == 2) HIPCHK(c, hipMalloc((void**)&sh, n * sizeof(u64)));
+            Dev<u64> sh, sl, sc;   // (freed at the end of the iteration, behind the synchronisation)
+            HIPCHK(c, sl.alloc(n * sizeof(u64)));
+            HIPCHK(c, sc.alloc(n * sizeof(u64)));
+            if (c->KW == 2) HIPCHK(c, sh.alloc(n * sizeof(u64)));
             HIPCHK(c, hipMemcpyAsync(sl, c->spill_lo, n * sizeof(u64), hipMemcpyDeviceToDevice, c->stream));
             HIPCHK(c, hipMemcpyAsync(sc, c->spill_cnt, n * sizeof(u64), hipMemcpyDeviceToDevice, c->stream));
             if (sh) HIPCHK(c, hipMemcpyAsync(sh, c->spill_hi, n * sizeof(u64), hipMemcpyDeviceToDevice, c->stream));
@@ -384,7 +364,6 @@ int settle(kmc_ctx* c) {
             launch_merge_pairs(c, sh, sl, sc, n);
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            (void)hipFree(sl); (void)hipFree(sc); if (sh) (void)hipFree(sh);
         }
         int rc = poll(c);
         if (rc) return rc;
@@ -613,7 +592,7 @@ int msd_scratch(kmc_ctx* c, u64 max_ranges, u64 max_seg, u64 term_cap, u64 n_wor
     MSD_ENSURE(c->m_ctl, sizeof(MsdCtl));
     MSD_ENSURE(c->m_bsum, (std::max<u64>(n_words, term_cap) / KMC_SCAN_PER_BLOCK + 2) * sizeof(u32));
 #undef MSD_ENSURE
-    if (!c->h_ctl) HIPCHK(c, hipHostMalloc((void**)&c->h_ctl, sizeof(MsdCtl)));
+    if (!c->h_ctl) HIPCHK(c, c->h_ctl.alloc(sizeof(MsdCtl)));
     return KMC_OK;
 }
 
@@ -755,13 +734,14 @@ int msd_sort_to_run(kmc_ctx* c, u64* const hi[2], u64* const lo[2], u64* const w
     else MSD_LEAF(2, false, 1024, 128);
 #undef MSD_LEAF
     if (n_cnt) {
-        if (n_cnt > max_seg) { c->run_pool.push_back(run); return fail(c, KMC_ERR_HIP, "msd sort: more counted spans than segments (internal error)"); }
+        if (n_cnt > max_seg) return fail(c, KMC_ERR_HIP, "msd sort: more counted spans than segments (internal error)");
         if (KW == 1) hipLaunchKernelGGL(kmc_msd_count_kernel<1>, dim3(n_cnt), dim3(1024), 0, c->stream, (const u64*)hi[0], (const u64*)lo[0], (const u64*)hi[1], (const u64*)lo[1],
                                         (const MsdTerm*)c->m_ord.p, (const u32*)c->m_clist.p, n_cnt, run.hi, run.lo, run.cnt, (u32*)c->m_nd.p, ctl);
         else hipLaunchKernelGGL(kmc_msd_count_kernel<2>, dim3(n_cnt), dim3(1024), 0, c->stream, (const u64*)hi[0], (const u64*)lo[0], (const u64*)hi[1], (const u64*)lo[1],
                                 (const MsdTerm*)c->m_ord.p, (const u32*)c->m_clist.p, n_cnt, run.hi, run.lo, run.cnt, (u32*)c->m_nd.p, ctl);
     }
-    auto give_back = [&](int code, const char* what) { c->run_pool.push_back(run); return fail(c, code, "msd sort: %s", what); };
+    // (an error return from here on frees the run: its owner goes out of scope)
+    auto give_back = [&](int code, const char* what) { return fail(c, code, "msd sort: %s", what); };
     if (hipGetLastError() != hipSuccess) return give_back(KMC_ERR_HIP, "leaf launch failed");
     if (hipMemcpyAsync(c->h_ctl, ctl, sizeof(MsdCtl), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
         return give_back(KMC_ERR_HIP, "leaf kernel failed");
@@ -775,14 +755,14 @@ int msd_sort_to_run(kmc_ctx* c, u64* const hi[2], u64* const lo[2], u64* const w
         // together into a run of the right size (work proportional to the distinct keys), give the sparse one back
         kmc_ctx::Run dense;
         rc = take_run(c, std::max<u64>(n_pairs, 1), &dense);
-        if (rc) { c->run_pool.push_back(run); return rc; }
+        if (rc) return rc;
         launch_exclusive_scan<0>(c->stream, c->m_nd.p, n_term, (u32*)c->m_bsum.p, (u32*)c->m_base.p, &ctl->n_pairs);
         if (KW == 1) hipLaunchKernelGGL(kmc_msd_gather_kernel<1>, dim3(grid_for(c, (u64)n_term * 64, 256)), dim3(256), 0, c->stream, (const MsdTerm*)c->m_ord.p, n_term,
                                         (const u32*)c->m_nd.p, (const u32*)c->m_base.p, (const u64*)run.hi, (const u64*)run.lo, (const u64*)run.cnt, dense.hi, dense.lo, dense.cnt);
         else hipLaunchKernelGGL(kmc_msd_gather_kernel<2>, dim3(grid_for(c, (u64)n_term * 64, 256)), dim3(256), 0, c->stream, (const MsdTerm*)c->m_ord.p, n_term,
                                 (const u32*)c->m_nd.p, (const u32*)c->m_base.p, (const u64*)run.hi, (const u64*)run.lo, (const u64*)run.cnt, dense.hi, dense.lo, dense.cnt);
-        c->run_pool.push_back(run);   // (stream order: the gather is queued before anything can reuse it)
-        run = dense;
+        c->run_pool.push_back(std::move(run));   // (stream order: the gather is queued before anything can reuse it)
+        run = std::move(dense);
         if (hipGetLastError() != hipSuccess) return give_back(KMC_ERR_HIP, "gather launch failed");
     }
     if (n_pairs > run_cap) return give_back(KMC_ERR_HIP, "more pairs than keys (internal error)");
@@ -790,9 +770,9 @@ int msd_sort_to_run(kmc_ctx* c, u64* const hi[2], u64* const lo[2], u64* const w
     run.total = weights ? (u64)c->h_ctl->w_total : (u64)c->h_ctl->n_valid;  // what the run's counts sum to
     run.total_known = true;
     if (!weights && c->h_ctl->n_valid >= (1u << 20)) c->msd_dup_heavy = (u64)c->h_ctl->n_valid >= 4 * std::max<u64>(n_pairs, 1);
-    if (out) *out = run;
-    else if (n_pairs) c->runs.push_back(run);
-    else c->run_pool.push_back(run);
+    if (out) *out = std::move(run);
+    else if (n_pairs) c->runs.push_back(std::move(run));
+    else c->run_pool.push_back(std::move(run));
     return KMC_OK;
 }
 
@@ -988,7 +968,7 @@ int build_vreads(kmc_ctx* c, const u64* d_offsets, u64 n_reads, u64* n_v_out) {
     if (rc) return rc;
     rc = ensure(c, c->m_ctl, sizeof(MsdCtl));
     if (rc) return rc;
-    if (!c->h_ctl) HIPCHK(c, hipHostMalloc((void**)&c->h_ctl, sizeof(MsdCtl)));
+    if (!c->h_ctl) HIPCHK(c, c->h_ctl.alloc(sizeof(MsdCtl)));
     MsdCtl* ctl = (MsdCtl*)c->m_ctl.p;
     u32 *cnt = (u32*)c->vr_cnt.p, *pos = (u32*)c->vr_pos.p;
     hipLaunchKernelGGL(kmc_vreads_count_kernel, dim3(grid_for(c, n_reads, 256)), dim3(256), 0, c->stream, d_offsets, n_reads, c->cfg.k, cnt);
@@ -1213,15 +1193,15 @@ int count_lr(kmc_ctx* c, const uint8_t* d_bases, const u64* d_offsets, u64 n_rea
         if (n_distinct) {   // (no dictionary: the pair kernel wrote nothing but filler)
             kmc_ctx::Run run;
             rc = msd_sort_to_run(c, khi, klo, kwt, n, 2u * (unsigned)B, 1, &run, true);
-            if (rc) { c->run_pool.push_back(mers); return rc; }
+            if (rc) return rc;
             hipLaunchKernelGGL(kmc_lr_addcount_kernel, dim3(1), dim3(64), 0, c->stream, (const u32*)&((const MsdCtl*)c->m_ctl.p)->n_valid, c->d_counters);
             if (run.n) {
                 hipLaunchKernelGGL(kmc_lr_compose_kernel, dim3(grid_for(c, run.n, 256)), dim3(256), 0, c->stream, run.hi, run.lo, run.n, (const u64*)mers.lo, B);
                 HIPCHK(c, hipGetLastError());
-                c->runs.push_back(run);
-            } else if (run.lo) c->run_pool.push_back(run);
+                c->runs.push_back(std::move(run));
+            } else if (run.lo) c->run_pool.push_back(std::move(run));
         }
-        if (mers.lo) c->run_pool.push_back(mers);  // (stream order: the compose kernel is queued before any later use)
+        if (mers.lo) c->run_pool.push_back(std::move(mers));  // (stream order: the compose kernel is queued before any later use)
         rc = launch_end(c);
         if (rc) return rc;
         c->pending = true;
@@ -1518,43 +1498,20 @@ extern "C" const char* kmc_status_string(int s) {
 
 extern "C" const char* kmc_last_error(const kmc_ctx* ctx) { return ctx ? ctx->err : g_create_err; }
 
+// Every buffer of the ctx frees itself (kmc_mem.hip.h), so nothing is listed here.  The order: the stream is synchronised
+// before the first free; an owned stream is destroyed after the last, because it lives in the ctx's base (CtxStream), and
+// bases are destroyed behind all members.  Also the end of a ctx that kmc_create built only half of.
 extern "C" void kmc_destroy(kmc_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->cfg.device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    free_table(c->tab);
-    if (c->d_counters) (void)hipFree(c->d_counters);
-    if (c->h_counters) (void)hipHostFree(c->h_counters);
-    if (c->h_restore) (void)hipHostFree(c->h_restore);
-    if (c->h_pub) (void)hipHostFree(c->h_pub);
-    if (c->occ_list) (void)hipFree(c->occ_list);
-    if (c->occ_key_lo) (void)hipFree(c->occ_key_lo);
-    if (c->occ_key_hi) (void)hipFree(c->occ_key_hi);
-    if (c->fin_rank) (void)hipFree(c->fin_rank);
-    if (c->spill_hi) (void)hipFree(c->spill_hi);
-    if (c->spill_lo) (void)hipFree(c->spill_lo);
-    if (c->spill_cnt) (void)hipFree(c->spill_cnt);
-    DevBuf* bufs[] = {&c->st_bases, &c->st_offsets, &c->t_idx0, &c->walk_ws, &c->walk_memo, &c->vr_reads, &c->vr_cnt, &c->vr_pos,
-                      &c->s_lo[0], &c->s_lo[1], &c->s_hi[0], &c->s_hi[1], &c->lr_rank, &c->a_hist, &c->a_rand, &c->a_ror,
-                      &c->lg_rec, &c->lg_count, &c->lg_bins, &c->lg_cursor,
-                      &c->m_hist, &c->m_stot, &c->m_bsum, &c->m_rmin, &c->m_rmax, &c->m_seg[0], &c->m_seg[1], &c->m_first, &c->m_cbase, &c->m_skip, &c->m_term, &c->m_ord,
-                      &c->m_bitmap, &c->m_rank, &c->m_nd, &c->m_base, &c->m_ctl, &c->m_clist, &c->m_w[0], &c->m_w[1],
-                      &c->snap_hi, &c->snap_lo, &c->snap_cnt, &c->snap_n, &c->snap_occ, &c->h_hist, &c->c_tile, &c->c_tpos, &c->c_bsum, &c->c_ctl,
-                      &c->q_idx, &c->q_khi, &c->q_klo, &c->q_cnt, &c->q_bases, &c->q_offs, &c->q_win, &c->q_stats,
-                      &c->so_pa, &c->so_pb, &c->g_adj, &c->g_ctl,
-                      &c->u_bases, &c->u_offs, &c->u_abund, &c->u_flags, &c->u_link, &c->u_join, &c->u_ptr[0], &c->u_ptr[1],
-                      &c->u_dist[0], &c->u_dist[1], &c->u_circ, &c->u_ctl,
-                      &c->l_offs, &c->l_to, &c->l_cnt, &c->l_pos, &c->l_tgt, &c->l_ctl, &c->cl_verdict, &c->cl_row};
-    KeyBufs* keys[] = {&c->o, &c->t, &c->p, &c->rx, &c->f, &c->so, &c->cl};
-    if (c->h_ctl) (void)hipHostFree(c->h_ctl);
-    sk_free(c);
-    try { free_runs(c, true); } catch (...) { /* (only the pool bookkeeping can throw; the buffers it could not list leak with the process) */ }
-    for (DevBuf* b : bufs) free_buf(*b);
-    for (KeyBufs* k : keys) free_keys(*k);
     for (auto& b : c->tb) for (hipEvent_t e : b.ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ev_free) (void)hipEventDestroy(e);
-    if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
+}
+
+extern "C" void kmc_debug_mem(uint64_t out[5]) {
+    out[0] = g_mem.dev_live; out[1] = g_mem.pin_live; out[2] = g_mem.dev_allocs; out[3] = g_mem.pin_allocs; out[4] = g_mem.free_failed;
 }
 
 static int kmc_create_impl(kmc_ctx** out, const kmc_config* cfg) {
@@ -1592,24 +1549,24 @@ static int kmc_create_impl(kmc_ctx** out, const kmc_config* cfg) {
         c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
         if (cfg->stream) c->stream = (hipStream_t)cfg->stream;
         else { HIPCHK(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); c->own_stream = true; }
-        HIPCHK(c, hipMalloc((void**)&c->d_counters, 2 * KMC_CTR_N * sizeof(u64)));  // [count table | (k+16)-mer table]: one read-back
+        HIPCHK(c, c->d_counters.alloc(2 * KMC_CTR_N * sizeof(u64)));  // [count table | (k+16)-mer table]: one read-back
         HIPCHK(c, hipMemsetAsync(c->d_counters, 0, 2 * KMC_CTR_N * sizeof(u64), c->stream));
-        HIPCHK(c, hipHostMalloc((void**)&c->h_counters, 2 * KMC_CTR_N * sizeof(u64)));
+        HIPCHK(c, c->h_counters.alloc(2 * KMC_CTR_N * sizeof(u64)));
         memset(c->h_counters, 0, 2 * KMC_CTR_N * sizeof(u64));
-        HIPCHK(c, hipHostMalloc((void**)&c->h_pub, 2 * KMC_CTR_N * sizeof(u64)));
+        HIPCHK(c, c->h_pub.alloc(2 * KMC_CTR_N * sizeof(u64)));
         memset(c->h_pub, 0, 2 * KMC_CTR_N * sizeof(u64));
         HIPCHK(c, hipHostGetDevicePointer((void**)&c->d_mirror, c->h_pub, 0));
-        HIPCHK(c, hipHostMalloc((void**)&c->h_restore, KMC_CTR_N * sizeof(u64)));
+        HIPCHK(c, c->h_restore.alloc(KMC_CTR_N * sizeof(u64)));
         u64 cap = next_pow2(std::max<u64>(cfg->capacity_hint * 2, 1ull << 20));
         c->spill_cap = std::max<u64>(cap / 4, 1ull << 18);
-        HIPCHK(c, hipMalloc((void**)&c->occ_list, KMC_OCC_LIST_CAP * sizeof(u64)));
-        HIPCHK(c, hipMalloc((void**)&c->occ_key_lo, KMC_OCC_LIST_CAP * sizeof(u64)));
-        HIPCHK(c, hipMalloc((void**)&c->occ_key_hi, KMC_OCC_LIST_CAP * sizeof(u64)));
-        HIPCHK(c, hipMalloc((void**)&c->fin_rank, 16 * sizeof(u32)));
+        HIPCHK(c, c->occ_list.alloc(KMC_OCC_LIST_CAP * sizeof(u64)));
+        HIPCHK(c, c->occ_key_lo.alloc(KMC_OCC_LIST_CAP * sizeof(u64)));
+        HIPCHK(c, c->occ_key_hi.alloc(KMC_OCC_LIST_CAP * sizeof(u64)));
+        HIPCHK(c, c->fin_rank.alloc(16 * sizeof(u32)));
         HIPCHK(c, hipMemsetAsync(c->fin_rank, 0, 16 * sizeof(u32), c->stream));
-        HIPCHK(c, hipMalloc((void**)&c->spill_lo, c->spill_cap * sizeof(u64)));
-        HIPCHK(c, hipMalloc((void**)&c->spill_cnt, c->spill_cap * sizeof(u64)));
-        if (c->KW == 2) HIPCHK(c, hipMalloc((void**)&c->spill_hi, c->spill_cap * sizeof(u64)));
+        HIPCHK(c, c->spill_lo.alloc(c->spill_cap * sizeof(u64)));
+        HIPCHK(c, c->spill_cnt.alloc(c->spill_cap * sizeof(u64)));
+        if (c->KW == 2) HIPCHK(c, c->spill_hi.alloc(c->spill_cap * sizeof(u64)));
         int r = alloc_table(c, c->tab, cap);
         if (r) return r;
         c->st.table_capacity = cap;
@@ -1651,7 +1608,7 @@ static int kmc_reset_impl(kmc_ctx* c) {
     c->polled_epoch = c->table_epoch;   // (an empty table is a known state)
     c->sorted_valid = false;
     c->n_sorted = 0;
-    free_runs(c, false);
+    free_runs(c);
     c->direct_seen = c->kmers_seen = 0;
     c->batch_pending = false;
     c->unpolled_adds = 0;
@@ -1811,7 +1768,7 @@ static int kmc_finalize_impl(kmc_ctx* c, uint64_t* n_distinct, uint64_t* n_total
     u64 n = n_tab + n_runs_total;  // entries before merging duplicates across sources
     u64 n_kmers = 0;
     const bool single_run = n_tab == 0 && c->runs.size() == 1;
-    if (c->view_run.lo) { c->view_run.n = 0; c->run_pool.push_back(c->view_run); c->view_run = kmc_ctx::Run{}; }  // the previous finalize's view
+    pool_view_run(c);  // the previous finalize's view
     c->v_hi = c->KW == 2 ? (const u64*)c->o.hi.p : nullptr;
     c->v_lo = (const u64*)c->o.lo.p;
     c->v_cnt = (const u64*)c->o.cnt.p;
@@ -1830,7 +1787,6 @@ static int kmc_finalize_impl(kmc_ctx* c, uint64_t* n_distinct, uint64_t* n_total
         if (n >= (1ull << 32) - KMC_MSD_RANGE) return fail(c, KMC_ERR_ARG, "kmc_finalize: more than 2^32 table entries + run entries to merge in one pass");
         if (!c->runs.empty()) {
             // a merge of big runs needs room: give back the pooled buffers
-            for (auto& r : c->run_pool) { if (r.hi) (void)hipFree(r.hi); (void)hipFree(r.lo); (void)hipFree(r.cnt); }
             c->run_pool.clear();
         }
         if ((rc = ensure_keys(c, c->o, n)) || (rc = ensure_keys(c, c->t, n))) return rc;
@@ -1873,8 +1829,8 @@ static int kmc_finalize_impl(kmc_ctx* c, uint64_t* n_distinct, uint64_t* n_total
         // still queued -- wait for them (it is already a multi-synchronisation path).
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (c->runs.size() > before) {
-            c->view_run = c->runs.back();   // the merged view is not one of the ctx's runs (they stay as they are)
-            c->runs.pop_back();
+            c->view_run = std::move(c->runs.back());   // the merged view is not one of the ctx's runs (they stay as they are); the move
+            c->runs.pop_back();                       // takes the arrays along, so v_hi / v_lo / v_cnt below alias live memory
             n = c->view_run.n;
             n_kmers = c->view_run.total;
             c->v_hi = c->view_run.hi; c->v_lo = c->view_run.lo; c->v_cnt = c->view_run.cnt;
@@ -2055,18 +2011,22 @@ static int count_file_whole(kmc_ctx* c, const char* path, uint64_t* n_distinct, 
 }
 
 // A pinned host pair the FASTA reader parses a chunk into, and the event of its upload
-struct Pinned { uint8_t* bases = nullptr; u64* offs = nullptr; u64 offs_cap = 0; hipEvent_t ev = nullptr; bool busy = false; };
-
-static void free_pinned(Pinned& p) {
-    if (p.bases) (void)hipHostFree(p.bases);
-    if (p.offs) (void)hipHostFree(p.offs);
-    if (p.ev) (void)hipEventDestroy(p.ev);
-}
+struct Pinned {
+    Pin<uint8_t> bases;
+    Pin<u64> offs;
+    u64 offs_cap = 0;
+    hipEvent_t ev = nullptr;
+    bool busy = false;
+    Pinned() = default;
+    Pinned(const Pinned&) = delete;
+    Pinned& operator=(const Pinned&) = delete;
+    ~Pinned() { if (ev) (void)hipEventDestroy(ev); }
+};
 
 // A pinned pair ready for the reader: allocated at first use, its upload two rounds ago finished
 static int pinned_ready(kmc_ctx* c, Pinned& p, u64 cap) {
     if (!p.bases) {
-        HIPCHK(c, hipHostMalloc((void**)&p.bases, (size_t)cap));
+        HIPCHK(c, p.bases.alloc((size_t)cap));
         HIPCHK(c, hipEventCreateWithFlags(&p.ev, hipEventDisableTiming));
     }
     if (p.busy) { HIPCHK(c, hipEventSynchronize(p.ev)); p.busy = false; }
@@ -2078,9 +2038,8 @@ static int pinned_ready(kmc_ctx* c, Pinned& p, u64 cap) {
 // without waiting.
 static int upload_and_count(kmc_ctx* c, Pinned& p, const KmcIngestChunk& ck) {
     if (p.offs_cap < ck.n_reads + 1) {
-        if (p.offs) { HIPCHK(c, hipHostFree(p.offs)); p.offs = nullptr; }
         p.offs_cap = (ck.n_reads + 1) * 5 / 4 + 1024;
-        HIPCHK(c, hipHostMalloc((void**)&p.offs, (size_t)p.offs_cap * sizeof(u64)));
+        HIPCHK(c, p.offs.alloc((size_t)p.offs_cap * sizeof(u64)));   // (frees the smaller one first)
     }
     memcpy(p.offs, ck.offsets.data(), (size_t)(ck.n_reads + 1) * sizeof(u64));
     int r = stage_host_batch(c, ck.n_reads, ck.n_bases);
@@ -2155,7 +2114,7 @@ static int count_file_pipeline(kmc_ctx** ctxs, uint32_t n_ctx, const char* path,
     std::vector<Pinned> pin((size_t)n_ctx * 2);  // two per ctx
     auto cleanup = [&]() {
         for (uint32_t i = 0; i < n_ctx; ++i) { (void)hipSetDevice(ctxs[i]->cfg.device); (void)hipStreamSynchronize(ctxs[i]->stream); }
-        for (auto& p : pin) free_pinned(p);
+        pin.clear();
     };
     auto body = [&]() -> int {
         KmcIngestChunk ck;
@@ -2193,10 +2152,7 @@ static int count_file_pipeline(kmc_ctx** ctxs, uint32_t n_ctx, const char* path,
         auto feed = [&](uint32_t i) {
             kmc_ctx* c = ctxs[i];
             Pinned pp[2];
-            auto fin = [&]() {
-                (void)hipStreamSynchronize(c->stream);
-                for (auto& p : pp) free_pinned(p);
-            };
+            auto fin = [&]() { (void)hipStreamSynchronize(c->stream); };   // (pp is freed behind it, when feed returns)
             auto run = [&]() -> int {
                 HIPCHK(c, hipSetDevice(c->cfg.device));
                 KmcIngestChunk ck;
@@ -2294,24 +2250,23 @@ static int kmc_synth_reads_device_impl(const kmc_synth* s, uint64_t first_record
     hipStream_t st = (hipStream_t)stream;
     const u64 read_len = (u64)s->lines_per_record * s->line_len;
     const u64 n_bases = n_records * read_len;
-    uint8_t* d_pool = nullptr;
+    Dev<uint8_t> d_pool;
     if (s->pool) {
         std::vector<uint8_t> pool((size_t)s->pool * s->line_len);
         for (u32 p = 0; p < s->pool; ++p)
             for (u32 x = 0; x < s->line_len; ++x) pool[(size_t)p * s->line_len + x] = kmc_synth_pool_base(s->seed, s->line_len, p, x);
-        if (hipMalloc((void**)&d_pool, pool.size()) != hipSuccess) return KMC_ERR_NOMEM;
-        if (hipMemcpy(d_pool, pool.data(), pool.size(), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_pool); return KMC_ERR_HIP; }
+        if (d_pool.alloc(pool.size()) != hipSuccess) return KMC_ERR_NOMEM;
+        if (hipMemcpy(d_pool, pool.data(), pool.size(), hipMemcpyHostToDevice) != hipSuccess) return KMC_ERR_HIP;
     }
     u64 n16 = (n_bases + 15) / 16;
     int grid = (int)std::min<u64>((n16 + 255) / 256, 256 * 16);
     if (grid < 1) grid = 1;
     hipLaunchKernelGGL(kmc_synth_kernel, dim3(grid), dim3(256), 0, st, s->seed, s->pool, s->line_len, s->lines_per_record,
-                       first_record, n_bases, (const uint8_t*)d_pool, (uint8_t*)d_bases);
+                       first_record, n_bases, (const uint8_t*)d_pool.p, (uint8_t*)d_bases);
     int g2 = (int)std::min<u64>((n_records + 256) / 256, 256 * 16);
     hipLaunchKernelGGL(kmc_synth_offsets_kernel, dim3(g2), dim3(256), 0, st, n_records, read_len, (u64*)d_offsets);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (d_pool) (void)hipFree(d_pool);
     return e == hipSuccess ? KMC_OK : KMC_ERR_HIP;
 }
 
@@ -2325,7 +2280,7 @@ static int kmc_read_peak_device_impl(const void* d_buf, uint64_t n_bytes, int de
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) != hipSuccess) return KMC_ERR_HIP;
     const int n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    unsigned long long* d_out = nullptr;
+    Dev<unsigned long long> d_out;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     int rc = KMC_OK;
     float ms = 0.f;
@@ -2339,7 +2294,7 @@ static int kmc_read_peak_device_impl(const void* d_buf, uint64_t n_bytes, int de
             default: hipLaunchKernelGGL(kmc_read_peak_kernel<8>, dim3(n_cu * 4), dim3(512), 0, st, (const uint8_t*)d_buf, n16, d_out); break;
         }
     };
-    if (hipMalloc((void**)&d_out, sizeof(unsigned long long)) != hipSuccess) return KMC_ERR_NOMEM;
+    if (d_out.alloc(sizeof(unsigned long long)) != hipSuccess) return KMC_ERR_NOMEM;
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess || hipMemsetAsync(d_out, 0, sizeof(unsigned long long), st) != hipSuccess) rc = KMC_ERR_HIP;
     if (!rc) {
         launch();   // warm-up (clocks, code object)
@@ -2351,7 +2306,6 @@ static int kmc_read_peak_device_impl(const void* d_buf, uint64_t n_bytes, int de
     }
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    (void)hipFree(d_out);
     if (rc) return rc;
     *ms_avg = (double)ms / iters;
     if (xor_out) *xor_out = h;   // (iters + 1 launches: the xor of an even number of passes is 0, of an odd number the buffer's checksum)

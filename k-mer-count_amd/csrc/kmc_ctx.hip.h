@@ -13,38 +13,61 @@
 
 #include "../../include/kmc.h"
 #include "kmc_device.hip.h"
+#include "kmc_mem.hip.h"
 
 struct MsdCtl;   // kmc_msd.hip.h
 
-struct DevBuf { void* p = nullptr; size_t bytes = 0; };
+// Every buffer below is owned by its type (kmc_mem.hip.h): a ctx, a Table, a Run or a local that goes away frees what it
+// holds, and none of them can be copied.
+using DevBuf = Dev<void>;   // an untyped buffer that ensure() sizes: read through .p with the cast of the use
 
 // a (key, count) table the library hands out or keeps for itself; hi is allocated for two-word keys only
 struct KeyBufs { DevBuf hi, lo, cnt; };
 
 struct Table {
-    u64 *hi = nullptr, *lo = nullptr, *cnt = nullptr, *mid = nullptr;  // (mid: three-word keys of the (k+16)-mer table, k >= 48)
+    Dev<u64> hi, lo, cnt, mid;  // (mid: three-word keys of the (k+16)-mer table, k >= 48)
     u64 cap = 0;
+    void reset() { *this = Table{}; }
 };
 
-struct kmc_ctx {
+// "The result this ctx still holds": the view generation and the count range a derived result (unitigs, links, the clean
+// pass) was computed for.  A stage asks holds() before it computes again, keep()s when its result is complete, and
+// drop()s before it rewrites the result arrays.
+struct ResultKey {
+    u64 gen = ~0ull, min = 0, max = 0;
+    bool holds(u64 view_gen, u64 min_count, u64 max_count) const { return gen == view_gen && min == min_count && max == max_count; }
+    void keep(u64 view_gen, u64 min_count, u64 max_count) { gen = view_gen; min = min_count; max = max_count; }
+    void drop() { gen = ~0ull; }
+};
+
+// The stream is a base of kmc_ctx so that it outlives every buffer: members are destroyed before bases, so the last free
+// has happened when an owned stream is destroyed.  (kmc_destroy synchronises it before the first.)
+struct CtxStream {
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    CtxStream() = default;
+    CtxStream(const CtxStream&) = delete;
+    CtxStream& operator=(const CtxStream&) = delete;
+    ~CtxStream() { if (own_stream && stream) (void)hipStreamDestroy(stream); }
+};
+
+struct kmc_ctx : CtxStream {
     kmc_config cfg{};
     int KW = 1;     // key words
     int klen = 0;   // characters per key (k, or 54 in LR mode)
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
     char err[512] = {0};
 
     Table tab;
-    u64* d_counters = nullptr;      // KMC_CTR_N u64
-    u64* h_counters = nullptr;      // pinned mirror
-    u64* occ_list = nullptr;        // first KMC_OCC_LIST_CAP claimed slots (fast finalize of small tables)
-    u64 *occ_key_lo = nullptr, *occ_key_hi = nullptr;   // ... and their keys, dense (GTable::occ_key_*)
-    u32* fin_rank = nullptr;        // ticket counter of kmc_small_finalize_kernel (zero between launches)
-    u64* h_pub = nullptr;           // pinned, 2 * KMC_CTR_N: where kmc_small_finalize_kernel publishes its outcome + the counters.  Its
+    Dev<u64> d_counters;            // 2 * KMC_CTR_N u64: [count table | (k+16)-mer table]
+    Pin<u64> h_counters;            // pinned mirror
+    Dev<u64> occ_list;              // first KMC_OCC_LIST_CAP claimed slots (fast finalize of small tables)
+    Dev<u64> occ_key_lo, occ_key_hi;   // ... and their keys, dense (GTable::occ_key_*)
+    Dev<u32> fin_rank;              // ticket counter of kmc_small_finalize_kernel (zero between launches)
+    Pin<u64> h_pub;                 // pinned, 2 * KMC_CTR_N: where kmc_small_finalize_kernel publishes its outcome + the counters.  Its
                                     // own block: a kernel queued by kmc_finalize_async may publish after the host has reset or
                                     // polled h_counters; poll_fin copies what the awaited launch published into h_counters
-    u64* d_mirror = nullptr;        // h_pub as the device sees it
-    u64* h_restore = nullptr;       // pinned: the counters to put back when a drained table is filled again (undrain)
+    u64* d_mirror = nullptr;        // h_pub as the device sees it (an alias, not an owner)
+    Pin<u64> h_restore;             // pinned: the counters to put back when a drained table is filled again (undrain)
     // planner invariant (kmc_stats.n_planner_stale): every kernel queued OUTSIDE the count launches' own accounting that
     // changes the table -- the (k+16)-mer unfold, merges -- bumps table_epoch; a poll records the epoch it has seen; a
     // risky launch must save a table whose counters were polled at the current epoch
@@ -53,7 +76,7 @@ struct kmc_ctx {
     bool async_fin = false;         // kmc_finalize_async: a finalize is queued whose outcome the host has not looked at yet
     bool drained = false;           // the last kmc_finalize emptied the table into the sorted view (kmc_small_finalize_kernel):
                                     // table and device counters are as after kmc_reset, h_counters hold the true totals
-    u64 *spill_hi = nullptr, *spill_lo = nullptr, *spill_cnt = nullptr;
+    Dev<u64> spill_hi, spill_lo, spill_cnt;
     u64 spill_cap = 0;
 
     // staging for host batches
@@ -86,12 +109,12 @@ struct kmc_ctx {
     DevBuf lr_rank;  // LR mode: rank of every position's 27-mer among the batch's distinct 27-mers
     // hand-written MSD radix sort (kmc_msd.hip.h): per-range histograms, segment lists, terminals
     DevBuf m_hist, m_stot, m_bsum, m_rmin, m_rmax, m_seg[2], m_first, m_cbase, m_skip, m_term, m_ord, m_bitmap, m_rank, m_nd, m_base, m_ctl, m_clist, m_w[2];
-    MsdCtl* h_ctl = nullptr;  // pinned mirror of the sort's device counters
-    struct Run { u64 *hi = nullptr, *lo = nullptr, *cnt = nullptr; u64 n = 0, cap = 0; u64 total = 0; bool total_known = false; };
+    Pin<MsdCtl> h_ctl;        // pinned mirror of the sort's device counters
+    struct Run { Dev<u64> hi, lo, cnt; u64 n = 0, cap = 0; u64 total = 0; bool total_known = false; };
     std::vector<Run> runs;       // live runs
     std::vector<Run> run_pool;   // buffers of dropped runs, reused (multi-GB hipMalloc/hipFree per batch is slow)
     Run view_run;                // the merged, sorted view built by the last kmc_finalize (table entries + runs)
-    const u64 *v_hi = nullptr, *v_lo = nullptr, *v_cnt = nullptr;  // the sorted view of the last finalize
+    const u64 *v_hi = nullptr, *v_lo = nullptr, *v_cnt = nullptr;  // the sorted view of the last finalize: aliases of o, of runs[0] or of view_run, not owners
     bool msd_dup_heavy = false;  // the last large unweighted sort collapsed its keys more than fourfold (leaf size of two-word sorts)
     bool prefer_sort = false;  // AUTO: the data source proved high-cardinality  // per-workgroup memo slots, kept across launches (kmc_walk.hip.h)
 
@@ -145,11 +168,11 @@ struct kmc_ctx {
     DevBuf snap_hi, snap_lo, snap_cnt, snap_n, snap_occ;
     // second-level memo of the walk kernel: (k+16)-mer table (kmc_walk.hip.h); three key words for k >= 48
     Table sk;
-    u64* d_sk_counters = nullptr;
-    u64* h_sk_counters = nullptr;   // pinned mirror (valid after a poll)
-    u64 *sk_spill_hi = nullptr, *sk_spill_lo = nullptr, *sk_spill_cnt = nullptr, *sk_spill_mid = nullptr;
+    u64* d_sk_counters = nullptr;   // the second half of d_counters (an alias, not an owner)
+    u64* h_sk_counters = nullptr;   // the second half of h_counters, valid after a poll (an alias, not an owner)
+    Dev<u64> sk_spill_hi, sk_spill_lo, sk_spill_cnt, sk_spill_mid;
     u64 sk_spill_cap = 0;
-    u64* sk_occ = nullptr;          // list of its claimed slots (what the unfold kernel walks)
+    Dev<u64> sk_occ;                // list of its claimed slots (what the unfold kernel walks)
     bool recovered = false;  // the last poll found an overflow and recovered: the batch in flight is complete
     bool sk_dirty = false;   // walk launches since the last unfold of the (k+16)-mer table
     bool sk_fixed = false;   // its size was set by KMC_SK_SLOTS (tests): never re-allocated
@@ -175,27 +198,30 @@ struct kmc_ctx {
     DevBuf g_adj, g_ctl;
     // kmc_unitigs / kmc_unitigs_device (kmc_unitig.hip.h): the result (bases, offsets, abundances, flags), and the work
     // arrays over the 2n side states -- links, joins, two (pointer, distance) pairs of the ranking -- the cycle marks per
-    // key, the summary words and round counts.  u_gen / u_min / u_max / u_words: the view and the range the result arrays
-    // were computed for and their summary (u_gen != view_gen: none), so that kmc_unitigs' sizing call and the copy call that
-    // follows it compute once
+    // key, the summary words and round counts.  u_key / u_words: the view and the range the result arrays were computed
+    // for (ResultKey) and their summary, so that kmc_unitigs' sizing call and the copy call that follows it compute once
     DevBuf u_bases, u_offs, u_abund, u_flags;
-    u64 u_gen = ~0ull, u_min = 0, u_max = 0, u_words[8] = {};
+    ResultKey u_key;
+    u64 u_words[8] = {};
     DevBuf u_link, u_join, u_ptr[2], u_dist[2], u_circ, u_ctl;
     // kmc_unitig_links / kmc_unitig_links_device (kmc_links.hip.h) read what unitig_run left besides its result: adj, the
-    // final ranking u_ptr[u_cur] / u_dist[u_cur], the unitig ids in u_join.  u_live says those are still the ones of the
-    // result u_gen names: unitig_run sets it when it is through, anything that rewrites adj (graph_run) clears it.
-    // The result (offsets per end, targets) with l_gen / l_min / l_max / l_words as above, the work arrays per end
+    // final ranking u_ptr[u_cur] / u_dist[u_cur], the unitig ids in u_join.  u_live is a different fact from u_key: not
+    // "the result arrays hold this result" but "the WORK arrays are still this result's": unitig_run sets it when it is
+    // through, anything that rewrites adj (graph_run) clears it, and the result itself stays good.
+    // The result (offsets per end, targets) with l_key / l_words as above, the work arrays per end
     // (counts, their scan), the resolved targets per view row, the control words.
     int u_cur = 0;
     bool u_live = false;
     DevBuf l_offs, l_to, l_cnt, l_pos, l_tgt, l_ctl;
-    u64 l_gen = ~0ull, l_min = 0, l_max = 0, l_words[8] = {};
+    ResultKey l_key;
+    u64 l_words[8] = {};
     // kmc_unitig_clean* (kmc_clean.hip.h) reads the unitigs, the links and what the links pass reads.  Its result: the
-    // verdict per unitig and the kept table, with cl_gen / cl_min / cl_max / cl_tip / cl_isl / cl_words as above (nothing but
-    // the clean pass writes them), cl_kept keys; the class byte per view row between its two passes.
+    // verdict per unitig and the kept table, with cl_key plus its two limits cl_tip / cl_isl and cl_words as above (nothing
+    // but the clean pass writes them), cl_kept keys; the class byte per view row between its two passes.
     KeyBufs cl;
     DevBuf cl_verdict, cl_row;
-    u64 cl_gen = ~0ull, cl_min = 0, cl_max = 0, cl_tip = 0, cl_isl = 0, cl_kept = 0, cl_words[8] = {};
+    ResultKey cl_key;
+    u64 cl_tip = 0, cl_isl = 0, cl_kept = 0, cl_words[8] = {};
 };
 
 #pragma GCC visibility push(hidden)   // what follows is shared between the translation units, never exported
@@ -221,16 +247,8 @@ inline int fail(kmc_ctx* c, int code, const char* fmt, ...) {
 
 inline int ensure(kmc_ctx* c, DevBuf& b, size_t bytes) {
     if (b.bytes >= bytes && b.p) return KMC_OK;
-    if (b.p) { HIPCHK(c, hipFree(b.p)); b.p = nullptr; b.bytes = 0; }
-    size_t want = bytes + bytes / 8 + 256;
-    HIPCHK(c, hipMalloc(&b.p, want));
-    b.bytes = want;
+    HIPCHK(c, b.alloc(bytes + bytes / 8 + 256));
     return KMC_OK;
-}
-
-inline void free_buf(DevBuf& b) {
-    if (b.p) (void)hipFree(b.p);
-    b = DevBuf{};
 }
 
 // room for n entries (one at least), the high words for two-word keys only
@@ -248,8 +266,6 @@ inline void publish_keys(const kmc_ctx* c, const KeyBufs& k, const void** d_key_
     if (d_key_lo) *d_key_lo = k.lo.p;
     if (d_count) *d_count = k.cnt.p;
 }
-
-inline void free_keys(KeyBufs& k) { free_buf(k.hi); free_buf(k.lo); free_buf(k.cnt); }
 
 inline int grid_for(const kmc_ctx* c, u64 n, int threads) {
     return (int)std::max<u64>(1, std::min<u64>((n + threads - 1) / threads, (u64)c->n_cu * 8));

@@ -56,14 +56,19 @@ int view_begin(kmc_ctx* c, const char* what, uint64_t min_count = 0, uint64_t ma
     return KMC_OK;
 }
 
-// n entries of a table on the device into the caller's arrays (key_hi: optional, zeros for one-word keys)
-int copy_to_host(kmc_ctx* c, const void* hi, const void* lo, const void* cnt, u64 n, uint64_t* key_hi, uint64_t* key_lo, uint64_t* count) {
-    HIPCHK(c, hipMemcpyAsync(key_lo, lo, n * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(count, cnt, n * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+// n entries of a table on the device queued into the caller's arrays (each optional; key_hi: zeros for one-word keys)
+int queue_to_host(kmc_ctx* c, const void* hi, const void* lo, const void* cnt, u64 n, uint64_t* key_hi, uint64_t* key_lo, uint64_t* count) {
+    if (key_lo) HIPCHK(c, hipMemcpyAsync(key_lo, lo, n * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    if (count) HIPCHK(c, hipMemcpyAsync(count, cnt, n * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     if (key_hi) {
         if (c->KW == 2) HIPCHK(c, hipMemcpyAsync(key_hi, hi, n * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
         else memset(key_hi, 0, n * sizeof(u64));
     }
+    return KMC_OK;
+}
+// ... and waited for
+int copy_to_host(kmc_ctx* c, const void* hi, const void* lo, const void* cnt, u64 n, uint64_t* key_hi, uint64_t* key_lo, uint64_t* count) {
+    if (int rc = queue_to_host(c, hi, lo, cnt, n, key_hi, key_lo, count)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return KMC_OK;
 }
@@ -683,7 +688,7 @@ static int unitig_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count
     memset(h, 0, KMC_UNITIG_WORDS * sizeof(u64));
     const u64 n = c->n_sorted, n2 = 2 * n;
     int rc;
-    c->u_gen = c->l_gen = ~0ull;   // the result arrays are rewritten from here on (and the links of the old ones go with them)
+    c->u_key.drop(); c->l_key.drop();   // the result arrays are rewritten from here on (and the links of the old ones go with them)
     if ((rc = ensure(c, c->u_offs, sizeof(u64))) || (rc = ensure(c, c->u_bases, 64)) || (rc = ensure(c, c->u_abund, sizeof(u64))) ||
         (rc = ensure(c, c->u_flags, 8)))
         return rc;
@@ -787,7 +792,7 @@ static int unitig_begin(kmc_ctx* c, const char* what, uint64_t min_count, uint64
 
 // the result arrays now hold the unitigs of this view and range (nothing but unitig_run writes them)
 static void unitig_keep(kmc_ctx* c, uint64_t min_count, uint64_t max_count, const u64* h) {
-    c->u_gen = c->view_gen; c->u_min = min_count; c->u_max = max_count;
+    c->u_key.keep(c->view_gen, min_count, max_count);
     memcpy(c->u_words, h, sizeof(c->u_words));
 }
 
@@ -816,7 +821,7 @@ static int kmc_unitigs_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, 
     u64 h[KMC_UNITIG_WORDS];
     int rc;
     if ((rc = unitig_begin(c, "kmc_unitigs", min_count, max_count))) return rc;
-    if (c->u_gen == c->view_gen && c->u_min == min_count && c->u_max == max_count) {
+    if (c->u_key.holds(c->view_gen, min_count, max_count)) {
         memcpy(h, c->u_words, sizeof(h));   // the arrays of this view and range are still there: the call after a sizing call
     } else {
         if ((rc = unitig_run(c, "kmc_unitigs", min_count, max_count, h))) return rc;
@@ -866,7 +871,7 @@ static int links_run(kmc_ctx* c, const char* what, u64* h) {
     memset(h, 0, KMC_LINK_WORDS * sizeof(u64));
     const u64 n = c->n_sorted, nu = c->u_words[0], ne = 2 * nu;
     int rc;
-    c->l_gen = ~0ull;
+    c->l_key.drop();
     if ((rc = ensure(c, c->l_offs, (size_t)(ne + 1) * sizeof(u64))) || (rc = ensure(c, c->l_to, sizeof(u32)))) return rc;
     if (!nu) {   // an empty view, or one without a solid key
         HIPCHK(c, hipMemsetAsync(c->l_offs.p, 0, sizeof(u64), c->stream));
@@ -912,12 +917,12 @@ static int links_run(kmc_ctx* c, const char* what, u64* h) {
 // What both calls do once their arguments are in order: the kept links (host form only), or the links pass behind the
 // kept unitigs of this view and range if their work arrays are still theirs, or behind a unitig_run of its own.
 static int links_result(kmc_ctx* c, const char* what, u64 min_count, u64 max_count, bool may_reuse, u64* h) {
-    if (may_reuse && c->l_gen == c->view_gen && c->l_min == min_count && c->l_max == max_count) {
+    if (may_reuse && c->l_key.holds(c->view_gen, min_count, max_count)) {
         memcpy(h, c->l_words, sizeof(c->l_words));
         return KMC_OK;
     }
     int rc;
-    const bool kept = c->u_live && c->u_gen == c->view_gen && c->u_min == min_count && c->u_max == max_count;
+    const bool kept = c->u_live && c->u_key.holds(c->view_gen, min_count, max_count);
     if (!kept) {
         u64 t[KMC_UNITIG_WORDS];
         if ((rc = unitig_run(c, what, min_count, max_count, t))) return rc;
@@ -933,7 +938,7 @@ static int links_result(kmc_ctx* c, const char* what, u64 min_count, u64 max_cou
             fprintf(stderr, "kmc_unitig_links: keys %llu unitigs %llu records %llu unitigs_reused %d links_ms %.4f\n",
                     (unsigned long long)c->n_sorted, (unsigned long long)h[0], (unsigned long long)h[1], kept ? 1 : 0, ms);
     }
-    c->l_gen = c->view_gen; c->l_min = min_count; c->l_max = max_count;
+    c->l_key.keep(c->view_gen, min_count, max_count);
     memcpy(c->l_words, h, sizeof(c->l_words));
     return KMC_OK;
 }
@@ -980,7 +985,7 @@ static int kmc_unitig_links_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_co
 static u64 clean_limit(uint64_t keys) { return keys >= (1ull << 31) ? ~0ull : (u64)keys; }   // 2^31 or more: unlimited
 
 static bool clean_kept(const kmc_ctx* c, u64 min_count, u64 max_count, u64 tip, u64 isl) {
-    return c->cl_gen == c->view_gen && c->cl_min == min_count && c->cl_max == max_count && c->cl_tip == tip && c->cl_isl == isl;
+    return c->cl_key.holds(c->view_gen, min_count, max_count) && c->cl_tip == tip && c->cl_isl == isl;
 }
 
 // The clean pass behind the unitigs and links of this view and range -- those the ctx holds if their work arrays are still
@@ -988,9 +993,9 @@ static bool clean_kept(const kmc_ctx* c, u64 min_count, u64 max_count, u64 tip, 
 static int clean_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count, u64 tip, u64 isl) {
     int rc;
     u64 lw[KMC_LINK_WORDS];
-    const bool held = c->u_live && c->u_gen == c->view_gen && c->u_min == min_count && c->u_max == max_count;
+    const bool held = c->u_live && c->u_key.holds(c->view_gen, min_count, max_count);
     if ((rc = links_result(c, what, min_count, max_count, held, lw))) return rc;
-    c->cl_gen = ~0ull;
+    c->cl_key.drop();
     const u64 n = c->n_sorted, nu = lw[0], nl = lw[1];
     u64 h[KMC_C_CTL_WORDS] = {0};
     if ((rc = ensure(c, c->cl_verdict, (size_t)std::max<u64>(nu, 8))) || (rc = ensure(c, c->cl_row, (size_t)std::max<u64>(n, 8)))) return rc;
@@ -1043,7 +1048,7 @@ static int clean_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count,
     h[KMC_C_SUM + 0] = nu;
     memcpy(c->cl_words, h + KMC_C_SUM, sizeof(c->cl_words));
     c->cl_kept = n_kept;
-    c->cl_gen = c->view_gen; c->cl_min = min_count; c->cl_max = max_count; c->cl_tip = tip; c->cl_isl = isl;
+    c->cl_key.keep(c->view_gen, min_count, max_count); c->cl_tip = tip; c->cl_isl = isl;
     return KMC_OK;
 }
 
@@ -1079,14 +1084,7 @@ static int kmc_unitig_clean_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_co
         return fail(c, KMC_ERR_ARG, "kmc_unitig_clean: capacity %llu < %llu kept keys", (unsigned long long)cap_keys, (unsigned long long)nk);
     if (verdict && cap_unitigs < nu)
         return fail(c, KMC_ERR_ARG, "kmc_unitig_clean: capacity %llu < %llu unitigs", (unsigned long long)cap_unitigs, (unsigned long long)nu);
-    if (nk) {
-        if (key_lo) HIPCHK(c, hipMemcpyAsync(key_lo, c->cl.lo.p, (size_t)nk * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-        if (count) HIPCHK(c, hipMemcpyAsync(count, c->cl.cnt.p, (size_t)nk * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-        if (key_hi) {
-            if (c->KW == 2) HIPCHK(c, hipMemcpyAsync(key_hi, c->cl.hi.p, (size_t)nk * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-            else memset(key_hi, 0, (size_t)nk * sizeof(u64));
-        }
-    }
+    if (nk && (rc = queue_to_host(c, c->cl.hi.p, c->cl.lo.p, c->cl.cnt.p, nk, key_hi, key_lo, count))) return rc;
     if (verdict && nu) HIPCHK(c, hipMemcpyAsync(verdict, c->cl_verdict.p, (size_t)nu, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (summary) memcpy(summary, c->cl_words, sizeof(c->cl_words));
