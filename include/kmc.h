@@ -26,6 +26,7 @@
  *   (addition: no equivalent in the reference)             kmc_unitigs / kmc_unitigs_device (its unitig sequences)
  *   (addition: no equivalent in the reference)             kmc_unitig_links / kmc_unitig_links_device (the edges between them)
  *   (addition: no equivalent in the reference)             kmc_unitig_clean / kmc_unitig_clean_device / kmc_unitig_clean_into (tips and islands removed)
+ *   (addition: no equivalent in the reference)             kmc_unitig_simplify / kmc_unitig_simplify_device / kmc_unitig_simplify_into (and simple bubbles popped)
  *
  * Conventions
  *   - Every function returns 0 (KMC_OK) or a negative kmc_status; no exception or abort crosses
@@ -508,6 +509,56 @@ int kmc_unitig_clean(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, uint6
  * kmc_unitig_links / kmc_unitig_clean_into run.  summary may be NULL. */
 int kmc_unitig_clean_into(kmc_ctx* src, kmc_ctx* dst, uint64_t min_count, uint64_t max_count, uint64_t max_tip_keys,
                           uint64_t max_island_keys, uint64_t* summary);
+
+/* ---- the same with simple bubbles popped: the third shape a sequencing error leaves (additions, as above).  A substitution
+ * in the interior of a read gives k erroneous keys: one short unitig that leaves the true path at a fork and rejoins it k keys
+ * later, beside the true arm of the same length.  It has one record at each end, so it is neither a tip nor an island.
+ * Everything refers to the unitigs and the link records of kmc_unitigs / kmc_unitig_links for the same view and range; m_u,
+ * A_u and rec(e) are as in the clean block above.
+ * BUBBLE CANDIDATE.  u is a bubble candidate iff it is not circular, m_u <= max_bubble_keys, rec(2u) has exactly one record
+ *   p and rec(2u + 1) exactly one record q, p != q, p >> 1 != u and q >> 1 != u.  ends(u) = {p, q}.
+ * PARALLEL.  Candidates u and w != u are parallel iff ends(w) == ends(u) as sets.  Orientation may differ: in a canonical
+ *   ctx the other arm is often spelled the other way round.
+ * BUBBLE.  u is a bubble iff it is a candidate and, among the records s of rec(p) -- p the one record of u's START end --
+ *   with s >> 1 != u, some unitig w = s >> 1 is a candidate parallel to u that beats u, in the order of the tip rule:
+ *   A_w * m_u > A_u * m_w as 128-bit products; on a tie m_w > m_u; on a tie w < u.  The order is strict, so two parallel
+ *   arms are never both popped; where the records are symmetric exactly the best of the parallel arms survives and the two
+ *   junctions stay connected.  Around palindromic keys (even k, canonical) records can be missing or asymmetric; no special
+ *   case is made: the formula is the definition, as for tips.  Arms of more than one unitig (nested or complex bubbles) are
+ *   not looked for.
+ * TIPS AND ISLANDS are decided exactly as by kmc_unitig_clean.  The three classes exclude one another by their record
+ *   counts (0 + 0, 0 + 1, 1 + 1).  A bubble arm is not a tip candidate, so it dominates a tip at its junction as before,
+ *   also when the same pass pops the arm: its surviving parallel arm stays.
+ * VERDICT.  KMC_CLEAN_KEEP, KMC_CLEAN_TIP, KMC_CLEAN_ISLAND or KMC_CLEAN_BUBBLE.  The kept table is that of the clean block.
+ * ABUNDANCE.  The counts of a popped arm's keys are NOT added to the surviving arm: they leave the table and summary[11]
+ *   says how much left.
+ * summary[KMC_SIMPLIFY_WORDS]: [0..7] as in KMC_CLEAN_WORDS, [3] and [7] counting what is kept after all three removals;
+ *   [8] bubbles popped, [9] keys of popped bubbles, [10] bubble candidates (those that survive included), [11] the sum of the
+ *   counts of the popped bubbles' keys.  With t the kmc_unitigs summary of the same range: [3] + [4] + [5] + [9] == t[2].
+ * LIMITS.  max_bubble_keys == 0 pops nothing: verdicts, kept table and words [0..7] are those of kmc_unitig_clean with the
+ *   same arguments and words [8..11] are 0.  2^31 or more is unlimited.
+ * Rules, ordering contract, pointer lifetimes, NULL-able outputs and the sizing call are those of kmc_unitig_clean*.
+ * RELATION TO THE OTHER VIEW CALLS.  A simplify call counts as a clean call: it reuses the unitigs and links under the same
+ *   conditions, writes the buffers a clean call writes (so it ends the validity of a clean result's pointers and the other
+ *   way round) and rewrites nothing else.  The result a ctx holds is keyed by view, range and the three limits, a clean call
+ *   having bubble limit 0: kmc_unitig_clean behind a simplify with a non-zero bubble limit computes again, and the other
+ *   way round; a simplify with limit 0 and a clean with the same arguments share one result.
+ * Diagnostic: with KMC_UNITIG_TRACE set, a simplify pass that computes prints "kmc_unitig_simplify: keys N unitigs U tips T
+ * islands I bubbles B kept K clean_ms .." to stderr, behind the lines of the unitigs and links it had to compute
+ * (tools/measure_simplify.py reads it); a kmc_unitig_clean* call prints its own line as before. ---- */
+#define KMC_SIMPLIFY_WORDS 12
+#define KMC_CLEAN_BUBBLE 3
+/* kmc_unitig_clean_device with the bubble rule.  Always computes the pass. */
+int kmc_unitig_simplify_device(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, uint64_t max_tip_keys, uint64_t max_island_keys,
+                               uint64_t max_bubble_keys, const void** d_key_hi, const void** d_key_lo, const void** d_count,
+                               const void** d_verdict, uint64_t* n_kept, uint64_t* n_unitigs, uint64_t* summary);
+/* kmc_unitig_clean with the bubble rule; the sizing call followed by the call that copies computes once. */
+int kmc_unitig_simplify(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, uint64_t max_tip_keys, uint64_t max_island_keys,
+                        uint64_t max_bubble_keys, uint64_t* key_hi, uint64_t* key_lo, uint64_t* count, uint64_t cap_keys,
+                        uint8_t* verdict, uint64_t cap_unitigs, uint64_t* n_kept, uint64_t* n_unitigs, uint64_t* summary);
+/* kmc_unitig_clean_into with the bubble rule: one step of a round that also pops bubbles. */
+int kmc_unitig_simplify_into(kmc_ctx* src, kmc_ctx* dst, uint64_t min_count, uint64_t max_count, uint64_t max_tip_keys,
+                             uint64_t max_island_keys, uint64_t max_bubble_keys, uint64_t* summary);
 
 /* Multi-GPU reduce for small tables: ONE fixed-size all-gather instead of size exchange +
  * all-to-all (the reduce of main.rs:87's grouping across GPUs; for the generator's input a table is

@@ -92,6 +92,7 @@ ABI_SYMBOLS = [
     "kmc_unitigs", "kmc_unitigs_device",
     "kmc_unitig_links", "kmc_unitig_links_device",
     "kmc_unitig_clean", "kmc_unitig_clean_device", "kmc_unitig_clean_into",
+    "kmc_unitig_simplify", "kmc_unitig_simplify_device", "kmc_unitig_simplify_into",
 ]
 
 PROFILE_WORDS = 5  # KMC_PROFILE_WORDS: valid windows, present windows, min, max, sum
@@ -103,6 +104,8 @@ UNITIG_CIRCULAR = 1  # KMC_UNITIG_CIRCULAR: bit 0 of a unitig's flags byte
 LINK_WORDS = 8     # KMC_LINK_WORDS: unitigs, records, ends without / with several records, self records, dropped, isolated unitigs, most at one end
 CLEAN_WORDS = 8    # KMC_CLEAN_WORDS: unitigs, tips, islands, keys kept / of tips / of islands, tip candidates, sum of the kept counts
 CLEAN_KEEP, CLEAN_TIP, CLEAN_ISLAND = 0, 1, 2   # KMC_CLEAN_*: a unitig's verdict byte
+SIMPLIFY_WORDS = 12  # KMC_SIMPLIFY_WORDS: the clean words, then bubbles, their keys, bubble candidates, the counts of their keys
+CLEAN_BUBBLE = 3     # KMC_CLEAN_BUBBLE: the fourth verdict, of a simplify call
 SETOP_INTERSECT, SETOP_UNION, SETOP_SUBTRACT = 0, 1, 2
 COUNT_LEFT, COUNT_RIGHT, COUNT_MIN, COUNT_MAX, COUNT_SUM, COUNT_DIFF = 0, 1, 2, 3, 4, 5
 SETOP_NAMES = {"intersect": SETOP_INTERSECT, "union": SETOP_UNION, "subtract": SETOP_SUBTRACT}
@@ -177,6 +180,9 @@ def lib() -> C.CDLL:
     L.kmc_unitig_clean_device.argtypes = [vp, u64, u64, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), pu64, pu64, vp]
     L.kmc_unitig_clean.argtypes = [vp, u64, u64, u64, u64, vp, vp, vp, u64, vp, u64, pu64, pu64, vp]
     L.kmc_unitig_clean_into.argtypes = [vp, vp, u64, u64, u64, u64, vp]
+    L.kmc_unitig_simplify_device.argtypes = [vp, u64, u64, u64, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), pu64, pu64, vp]
+    L.kmc_unitig_simplify.argtypes = [vp, u64, u64, u64, u64, u64, vp, vp, vp, u64, vp, u64, pu64, pu64, vp]
+    L.kmc_unitig_simplify_into.argtypes = [vp, vp, u64, u64, u64, u64, u64, vp]
     L.kmc_owner_of.argtypes = [u64, u64, u32]
     L.kmc_owner_of.restype = u32
     L.kmc_get_stats.argtypes = [vp, C.POINTER(Stats)]
@@ -535,6 +541,53 @@ class CleanedUnitigs:
     summary: CleanSummary
 
 
+_SIMPLIFY_FIELDS = _CLEAN_FIELDS + ("bubbles", "bubble_keys", "bubble_candidates", "bubble_count")
+
+
+@dataclass
+class SimplifySummary:
+    """The twelve words of kmc_unitig_simplify: those of CleanSummary (kept_keys and kept_count after all three removals),
+    then the bubbles popped, their keys, bubble candidates (those that survive included), the sum of the counts of the
+    popped bubbles' keys."""
+    unitigs: int
+    tips: int
+    islands: int
+    kept_keys: int
+    tip_keys: int
+    island_keys: int
+    tip_candidates: int
+    kept_count: int
+    bubbles: int
+    bubble_keys: int
+    bubble_candidates: int
+    bubble_count: int
+
+    @classmethod
+    def from_words(cls, words) -> "SimplifySummary":
+        return cls(*[int(w) for w in words])
+
+    def words(self) -> list:
+        return [getattr(self, f) for f in _SIMPLIFY_FIELDS]
+
+    @property
+    def removed(self) -> int:
+        """Unitigs this pass takes out."""
+        return self.tips + self.islands + self.bubbles
+
+    def to_text(self) -> str:
+        """``NAME\tVALUE`` lines."""
+        return "\n".join("%s\t%d" % (f, getattr(self, f)) for f in _SIMPLIFY_FIELDS) + "\n"
+
+
+@dataclass
+class SimplifiedUnitigs:
+    """What KmerCounter.simplify_unitigs returns: ``table``, ``verdict`` uint8[n unitigs] (CLEAN_KEEP / CLEAN_TIP /
+    CLEAN_ISLAND / CLEAN_BUBBLE), ``summary``."""
+    table: "Table"
+    verdict: np.ndarray
+    summary: SimplifySummary
+
+
 def parse_fasta(path: str) -> Tuple[np.ndarray, np.ndarray]:
     """Host FASTA reader of libkmc (the reader the reference uses, main.rs:45-46,59-62).
     Returns (bases uint8[n_bases], offsets uint64[n_reads+1])."""
@@ -881,6 +934,71 @@ class KmerCounter:
             dst = KmerCounter(k=self.k, canonical=self.canonical, mode=self.mode, device=self.device)
             try:
                 out.append(src.clean_into(dst, min_count, max_count, max_tip_keys, max_island_keys))
+                dst.finalize()
+            except Exception:
+                dst.close()
+                if src is not self:
+                    src.close()
+                raise
+            if src is not self:
+                src.close()
+            src = dst
+            if out[-1].removed == 0:
+                break
+        return src, out
+
+    # -- and simple bubbles popped: the arm of a fork-and-rejoin that loses against its parallel arm --
+    def _simplify_limits(self, max_tip_keys, max_island_keys, max_bubble_keys) -> Tuple[int, int, int]:
+        return self._clean_limits(max_tip_keys, max_island_keys) + (self.k if max_bubble_keys is None else int(max_bubble_keys),)
+
+    def simplify_unitigs(self, min_count: int = 1, max_count: int = 0, max_tip_keys: Optional[int] = None,
+                         max_island_keys: Optional[int] = None, max_bubble_keys: Optional[int] = None) -> "SimplifiedUnitigs":
+        """kmc_unitig_simplify: clean_unitigs with a fourth verdict -- a unitig of at most max_bubble_keys keys (None: k; 0:
+        none) with one link at each end that loses against a parallel unitig between the same two ends is a bubble.  The
+        counts of a popped arm are not added to the survivor.  Two calls, one computation."""
+        tip, isl, bub = self._simplify_limits(max_tip_keys, max_island_keys, max_bubble_keys)
+        nk, nu = C.c_uint64(), C.c_uint64()
+        w = (C.c_uint64 * SIMPLIFY_WORDS)()
+        lo, hi = int(min_count), int(max_count)
+        self._chk(self._L.kmc_unitig_simplify(self._h, lo, hi, tip, isl, bub, None, None, None, 0, None, 0, C.byref(nk), C.byref(nu), w))
+        khi, klo, cnt = (np.zeros(nk.value, np.uint64) for _ in range(3))
+        verdict = np.zeros(nu.value, np.uint8)
+        self._chk(self._L.kmc_unitig_simplify(self._h, lo, hi, tip, isl, bub, khi.ctypes.data if nk.value else None,
+                                              klo.ctypes.data if nk.value else None, cnt.ctypes.data if nk.value else None, nk.value,
+                                              verdict.ctypes.data if nu.value else None, nu.value, C.byref(nk), C.byref(nu), w))
+        return SimplifiedUnitigs(Table(khi, klo, cnt, self.k), verdict, SimplifySummary.from_words(list(w)))
+
+    def simplify_unitigs_device(self, min_count: int = 1, max_count: int = 0, max_tip_keys: Optional[int] = None,
+                                max_island_keys: Optional[int] = None, max_bubble_keys: Optional[int] = None):
+        """(d_key_hi or 0, d_key_lo, d_count, d_verdict, n_kept, n_unitigs, SimplifySummary) of kmc_unitig_simplify_device:
+        ctx-owned device arrays, as clean_unitigs_device gives them."""
+        tip, isl, bub = self._simplify_limits(max_tip_keys, max_island_keys, max_bubble_keys)
+        p = [C.c_void_p() for _ in range(4)]
+        nk, nu = C.c_uint64(), C.c_uint64()
+        w = (C.c_uint64 * SIMPLIFY_WORDS)()
+        self._chk(self._L.kmc_unitig_simplify_device(self._h, int(min_count), int(max_count), tip, isl, bub, *[C.byref(x) for x in p],
+                                                     C.byref(nk), C.byref(nu), w))
+        return tuple(x.value or 0 for x in p) + (nk.value, nu.value, SimplifySummary.from_words(list(w)))
+
+    def simplify_into(self, dst: "KmerCounter", min_count: int = 1, max_count: int = 0, max_tip_keys: Optional[int] = None,
+                      max_island_keys: Optional[int] = None, max_bubble_keys: Optional[int] = None) -> "SimplifySummary":
+        """kmc_unitig_simplify_into: the kept keys of self merged into dst's table (dst is not finalized)."""
+        tip, isl, bub = self._simplify_limits(max_tip_keys, max_island_keys, max_bubble_keys)
+        w = (C.c_uint64 * SIMPLIFY_WORDS)()
+        self._chk(self._L.kmc_unitig_simplify_into(self._h, dst._h, int(min_count), int(max_count), tip, isl, bub, w))
+        return SimplifySummary.from_words(list(w))
+
+    def simplified(self, min_count: int = 1, max_count: int = 0, max_tip_keys: Optional[int] = None, max_island_keys: Optional[int] = None,
+                   max_bubble_keys: Optional[int] = None, rounds: int = 1):
+        """(KmerCounter, [SimplifySummary per round run]): cleaned() with bubbles popped in every round.  Stops early after a
+        round that removes nothing.  Intermediate counters are closed; self is left as it is."""
+        if rounds < 1:
+            raise ValueError("rounds must be at least 1")
+        src, out = self, []
+        for _ in range(int(rounds)):
+            dst = KmerCounter(k=self.k, canonical=self.canonical, mode=self.mode, device=self.device)
+            try:
+                out.append(src.simplify_into(dst, min_count, max_count, max_tip_keys, max_island_keys, max_bubble_keys))
                 dst.finalize()
             except Exception:
                 dst.close()

@@ -7,7 +7,7 @@
 //   k-mer-count [FASTA] [-k K] [--forward] [--expand] [--device N | --gpus N] [--algo auto|stream|walk|sort] [--stats]
 //               [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE]
 //               [--with FASTA2 (--compare | --setop intersect|union|subtract [--counts left|right|min|max|sum|diff])]
-//               [--graph | --graph-stats | --unitigs | --gfa] [--clean ROUNDS [--tip-keys N] [--island-keys N]]
+//               [--graph | --graph-stats | --unitigs | --gfa] [--clean ROUNDS [--tip-keys N] [--island-keys N] [--bubble-keys N]]
 //
 //   --gpus N  the file's chunks go round-robin to GPUs 0..N-1 of this process, tables reduced on GPU 0
 //             (there is no CPU backend: SURVEY.md's "--backend cpu" is deliberately absent)
@@ -53,6 +53,10 @@
 //               (default K each, 0: none) are taken out, and the keys of the others become the table of the next round and in the
 //               end of the output (--query-kmers / --profile ask the cleaned table too).  A round that removes nothing is the last.
 //               With --stats one line per round on stderr; the closing --stats line still describes the counting of the file.
+//   --bubble-keys N      (with --clean ROUNDS) every round also pops simple bubbles (kmc_unitig_simplify_into): a unitig of at
+//               most N keys with one link at each end that loses against a parallel unitig between the same two ends (0: none).
+//               Without the option nothing is popped.  The per-round --stats line gains "bubbles B bubble_keys K
+//               bubble_candidates C"; a round that removes nothing, bubbles included, is the last.
 //
 // Errors: message on stderr, exit code 101 (what a Rust panic exits with), never partial stdout.
 #include <errno.h>
@@ -107,6 +111,7 @@ int main(int argc, char** argv) {
     int compare = 0, setop = -1, count_mode = -1, graph = 0, graph_stats = 0, unitigs = 0, gfa = 0;
     int clean = 0;
     long long tip_keys = -1, island_keys = -1;   // (-1: K)
+    long long bubble_keys = -1;                  // (-1: no bubble is popped, the rounds are kmc_unitig_clean_into's)
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         if (a == "-k" && i + 1 < argc) { if (!parse_int("-k", argv[++i], 1, 63, &k)) return 2; }
@@ -129,6 +134,7 @@ int main(int argc, char** argv) {
         else if (a == "--clean" && i + 1 < argc) { if (!parse_int("--clean", argv[++i], 1, 1000, &clean)) return 2; }
         else if (a == "--tip-keys" && i + 1 < argc) { if (!parse_count("--tip-keys", argv[++i], 0, LLONG_MAX, &tip_keys)) return 2; }
         else if (a == "--island-keys" && i + 1 < argc) { if (!parse_count("--island-keys", argv[++i], 0, LLONG_MAX, &island_keys)) return 2; }
+        else if (a == "--bubble-keys" && i + 1 < argc) { if (!parse_count("--bubble-keys", argv[++i], 0, LLONG_MAX, &bubble_keys)) return 2; }
         else if (a == "--setop" && i + 1 < argc) {
             std::string v = argv[++i];
             setop = v == "intersect" ? KMC_SETOP_INTERSECT : v == "union" ? KMC_SETOP_UNION : v == "subtract" ? KMC_SETOP_SUBTRACT : -1;
@@ -145,11 +151,11 @@ int main(int argc, char** argv) {
             fprintf(stderr, "usage: k-mer-count [FASTA] [-k K] [--forward] [--expand] [--device N | --gpus N] [--algo auto|stream|walk|sort] [--stats]\n"
                             "                   [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE]\n"
                             "                   [--with FASTA2 (--compare | --setop intersect|union|subtract [--counts left|right|min|max|sum|diff])]\n"
-                            "                   [--graph | --graph-stats | --unitigs | --gfa] [--clean ROUNDS [--tip-keys N] [--island-keys N]]\n");
+                            "                   [--graph | --graph-stats | --unitigs | --gfa] [--clean ROUNDS [--tip-keys N] [--island-keys N] [--bubble-keys N]]\n");
             return 0;
         } else if (a == "-k" || a == "--device" || a == "--gpus" || a == "--algo" || a == "--min-count" || a == "--max-count" || a == "--histo" ||
                    a == "--query-kmers" || a == "--profile" || a == "--with" || a == "--setop" || a == "--counts" ||
-                   a == "--clean" || a == "--tip-keys" || a == "--island-keys") {
+                   a == "--clean" || a == "--tip-keys" || a == "--island-keys" || a == "--bubble-keys") {
             fprintf(stderr, "k-mer-count: %s needs a value\n", a.c_str());
             return 2;
         } else if (!a.empty() && a[0] != '-') path = argv[i];
@@ -226,10 +232,10 @@ int main(int argc, char** argv) {
         else if (expand) bad = "--expand exclude each other";
         if (bad) { fprintf(stderr, "k-mer-count: %s %s%s\n", opt, strncmp(bad, "needs", 5) ? "and " : "", bad); return 2; }
     }
-    // --clean / --tip-keys / --island-keys: the same
-    if (clean || tip_keys >= 0 || island_keys >= 0) {
+    // --clean / --tip-keys / --island-keys / --bubble-keys: the same
+    if (clean || tip_keys >= 0 || island_keys >= 0 || bubble_keys >= 0) {
         const char* bad = nullptr;
-        if (!clean) bad = "--tip-keys / --island-keys need --clean ROUNDS";
+        if (!clean) bad = "--tip-keys / --island-keys / --bubble-keys need --clean ROUNDS";
         else if (!k) bad = "--clean needs -k K";
         else if (with_path || compare || setop >= 0) bad = "--clean and --with / --compare / --setop exclude each other";
         if (bad) { fprintf(stderr, "k-mer-count: %s\n", bad); return 2; }
@@ -269,22 +275,32 @@ int main(int argc, char** argv) {
         rc = kmc_create(&next, &cfg);
         if (rc) { int r = die("kmc_create", kmc_last_error(nullptr)); destroy_all(); return r; }
         ctxs.push_back(next);
-        uint64_t w[KMC_CLEAN_WORDS];
-        rc = kmc_unitig_clean_into(ctx, next, (uint64_t)min_count, (uint64_t)max_count, tip_keys < 0 ? (uint64_t)k : (uint64_t)tip_keys,
-                                   island_keys < 0 ? (uint64_t)k : (uint64_t)island_keys, w);
-        if (rc) { int r = die("kmc_unitig_clean_into", kmc_last_error(ctx)); destroy_all(); return r; }
+        uint64_t w[KMC_SIMPLIFY_WORDS] = {0};
+        const uint64_t tip = tip_keys < 0 ? (uint64_t)k : (uint64_t)tip_keys, isl = island_keys < 0 ? (uint64_t)k : (uint64_t)island_keys;
+        if (bubble_keys < 0) {
+            rc = kmc_unitig_clean_into(ctx, next, (uint64_t)min_count, (uint64_t)max_count, tip, isl, w);
+            if (rc) { int r = die("kmc_unitig_clean_into", kmc_last_error(ctx)); destroy_all(); return r; }
+        } else {
+            rc = kmc_unitig_simplify_into(ctx, next, (uint64_t)min_count, (uint64_t)max_count, tip, isl, (uint64_t)bubble_keys, w);
+            if (rc) { int r = die("kmc_unitig_simplify_into", kmc_last_error(ctx)); destroy_all(); return r; }
+        }
         rc = kmc_finalize(next, &nd, &nt);
         if (rc) { int r = die("kmc_finalize", kmc_last_error(next)); destroy_all(); return r; }
-        if (stats)
-            fprintf(stderr, "clean round %d unitigs %llu tips %llu islands %llu kept_keys %llu tip_keys %llu island_keys %llu tip_candidates %llu kept_count %llu\n",
+        if (stats) {
+            fprintf(stderr, "clean round %d unitigs %llu tips %llu islands %llu kept_keys %llu tip_keys %llu island_keys %llu tip_candidates %llu kept_count %llu",
                     round, (unsigned long long)w[0], (unsigned long long)w[1], (unsigned long long)w[2], (unsigned long long)w[3],
                     (unsigned long long)w[4], (unsigned long long)w[5], (unsigned long long)w[6], (unsigned long long)w[7]);
+            if (bubble_keys >= 0)
+                fprintf(stderr, " bubbles %llu bubble_keys %llu bubble_candidates %llu", (unsigned long long)w[8], (unsigned long long)w[9],
+                        (unsigned long long)w[10]);
+            fprintf(stderr, "\n");
+        }
         if (ctx != counted) {   // (the table of the round before)
             kmc_destroy(ctx);
             ctxs.erase(std::find(ctxs.begin(), ctxs.end(), ctx));
         }
         ctx = next;
-        if (w[1] + w[2] == 0) break;
+        if (w[1] + w[2] + w[8] == 0) break;
     }
     std::vector<char> obuf(1 << 22);
     if (with_path) {

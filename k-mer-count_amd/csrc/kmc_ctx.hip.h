@@ -215,13 +215,15 @@ struct kmc_ctx : CtxStream {
     DevBuf l_offs, l_to, l_cnt, l_pos, l_tgt, l_ctl;
     ResultKey l_key;
     u64 l_words[8] = {};
-    // kmc_unitig_clean* (kmc_clean.hip.h) reads the unitigs, the links and what the links pass reads.  Its result: the
-    // verdict per unitig and the kept table, with cl_key plus its two limits cl_tip / cl_isl and cl_words as above (nothing
-    // but the clean pass writes them), cl_kept keys; the class byte per view row between its two passes.
+    // kmc_unitig_clean* and kmc_unitig_simplify* (kmc_clean.hip.h) read the unitigs, the links and what the links pass
+    // reads.  Their result: the verdict per unitig and the kept table, with cl_key plus its three limits cl_tip / cl_isl /
+    // cl_bub (0 for a clean call) and cl_words as above (nothing but the clean pass writes them; a clean call hands out the
+    // first 8), cl_kept keys; the class byte per view row between its two passes; the totals per workgroup of a mark
+    // pass that pops bubbles.
     KeyBufs cl;
-    DevBuf cl_verdict, cl_row;
+    DevBuf cl_verdict, cl_row, cl_part;
     ResultKey cl_key;
-    u64 cl_tip = 0, cl_isl = 0, cl_kept = 0, cl_words[8] = {};
+    u64 cl_tip = 0, cl_isl = 0, cl_bub = 0, cl_kept = 0, cl_words[12] = {};
 };
 
 #pragma GCC visibility push(hidden)   // what follows is shared between the translation units, never exported

@@ -984,13 +984,14 @@ static int kmc_unitig_links_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_co
 // ---- the compacted graph cleaned: a verdict per unitig, the table of the kept keys (kmc_clean.hip.h) ----
 static u64 clean_limit(uint64_t keys) { return keys >= (1ull << 31) ? ~0ull : (u64)keys; }   // 2^31 or more: unlimited
 
-static bool clean_kept(const kmc_ctx* c, u64 min_count, u64 max_count, u64 tip, u64 isl) {
-    return c->cl_key.holds(c->view_gen, min_count, max_count) && c->cl_tip == tip && c->cl_isl == isl;
+static bool clean_kept(const kmc_ctx* c, u64 min_count, u64 max_count, u64 tip, u64 isl, u64 bub) {
+    return c->cl_key.holds(c->view_gen, min_count, max_count) && c->cl_tip == tip && c->cl_isl == isl && c->cl_bub == bub;
 }
 
 // The clean pass behind the unitigs and links of this view and range -- those the ctx holds if their work arrays are still
 // theirs, otherwise computed and kept -- into cl_verdict / cl, the summary into cl_words; finished when it returns.
-static int clean_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count, u64 tip, u64 isl) {
+// bub != 0 runs the kernels that also pop bubbles; simplify says whose trace line the pass prints.
+static int clean_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count, u64 tip, u64 isl, u64 bub = 0, bool simplify = false) {
     int rc;
     u64 lw[KMC_LINK_WORDS];
     const bool held = c->u_live && c->u_key.holds(c->view_gen, min_count, max_count);
@@ -1009,18 +1010,26 @@ static int clean_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count,
         CleanGraph g;
         g.offsets = (const u64*)c->u_offs.p; g.abund = (const u64*)c->u_abund.p; g.flags = (const uint8_t*)c->u_flags.p;
         g.link_offsets = (const u64*)c->l_offs.p; g.link_to = (const u32*)c->l_to.p;
-        g.n_unitigs = nu; g.n_links = nl; g.km1 = (u64)(c->klen - 1); g.max_tip = tip; g.max_island = isl;
-        hipLaunchKernelGGL(kmc_clean_verdict_kernel, dim3((u32)((nu + KMC_C_THREADS - 1) / KMC_C_THREADS)), dim3(KMC_C_THREADS), 0, c->stream,
-                           g, (uint8_t*)c->cl_verdict.p, ctl);
+        g.n_unitigs = nu; g.n_links = nl; g.km1 = (u64)(c->klen - 1); g.max_tip = tip; g.max_island = isl; g.max_bubble = bub;
         const u32 grid = (u32)std::min<u64>(n_tiles, (u64)c->n_cu * 8);
-        hipLaunchKernelGGL(kmc_clean_mark_kernel, dim3(grid), dim3(KMC_C_THREADS), 0, c->stream, c->v_cnt, n, n_tiles, (const uint16_t*)c->g_adj.p,
-                           (const u32*)c->u_ptr[c->u_cur].p, (const u32*)c->u_join.p, c->cfg.canonical ? 1 : 0,
-                           (const uint8_t*)c->cl_verdict.p, nu, (uint8_t*)c->cl_row.p, (u32*)c->c_tile.p, ctl);
+        if (bub && (rc = ensure(c, c->cl_part, (size_t)grid * KMC_C_PART * sizeof(u64)))) return rc;
+        auto launch = [&](auto BUBBLES) {
+            hipLaunchKernelGGL(kmc_clean_verdict_kernel<BUBBLES()>, dim3((u32)((nu + KMC_C_THREADS - 1) / KMC_C_THREADS)), dim3(KMC_C_THREADS), 0,
+                               c->stream, g, (uint8_t*)c->cl_verdict.p, ctl);
+            hipLaunchKernelGGL(kmc_clean_mark_kernel<BUBBLES()>, dim3(grid), dim3(KMC_C_THREADS), 0, c->stream, c->v_cnt, n, n_tiles,
+                               (const uint16_t*)c->g_adj.p, (const u32*)c->u_ptr[c->u_cur].p, (const u32*)c->u_join.p, c->cfg.canonical ? 1 : 0,
+                               (const uint8_t*)c->cl_verdict.p, nu, (uint8_t*)c->cl_row.p, (u32*)c->c_tile.p, ctl, (kmc_ull*)c->cl_part.p);
+            if (BUBBLES())
+                hipLaunchKernelGGL(kmc_clean_reduce_kernel, dim3(KMC_C_PART_USED), dim3(KMC_C_THREADS), 0, c->stream, (const kmc_ull*)c->cl_part.p, grid, ctl);
+        };
+        if (bub) launch(std::true_type{}); else launch(std::false_type{});
         if ((rc = compact_scan_and_read(c, n_tiles, h, KMC_C_CTL_WORDS))) return rc;
-        if (h[KMC_C_BAD] || h[0] != h[KMC_C_SUM + 3] || h[KMC_C_SUM + 3] + h[KMC_C_SUM + 4] + h[KMC_C_SUM + 5] != c->u_words[2])
-            return fail(c, KMC_ERR_HIP, "internal error: %s met %llu indices outside their arrays (%llu + %llu + %llu of %llu keys, %llu scanned)", what,
-                        (unsigned long long)h[KMC_C_BAD], (unsigned long long)h[KMC_C_SUM + 3], (unsigned long long)h[KMC_C_SUM + 4],
-                        (unsigned long long)h[KMC_C_SUM + 5], (unsigned long long)c->u_words[2], (unsigned long long)h[0]);
+        if (h[KMC_C_BAD] || h[0] != h[KMC_C_SUM + 3] ||
+            h[KMC_C_SUM + 3] + h[KMC_C_SUM + 4] + h[KMC_C_SUM + 5] + h[KMC_C_SUM2 + 1] != c->u_words[2])
+            return fail(c, KMC_ERR_HIP, "internal error: %s met %llu indices outside their arrays (%llu + %llu + %llu + %llu of %llu keys, %llu scanned)",
+                        what, (unsigned long long)h[KMC_C_BAD], (unsigned long long)h[KMC_C_SUM + 3], (unsigned long long)h[KMC_C_SUM + 4],
+                        (unsigned long long)h[KMC_C_SUM + 5], (unsigned long long)h[KMC_C_SUM2 + 1], (unsigned long long)c->u_words[2],
+                        (unsigned long long)h[0]);
     }
     const u64 n_kept = h[0];
     if ((rc = ensure_keys(c, c->cl, n_kept))) return rc;
@@ -1041,74 +1050,90 @@ static int clean_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count,
     tr.mark(c->stream);
     if (tr.on && tr.n_ev == 2) {
         float ms = 0;
-        if (hipEventSynchronize(tr.ev[1]) == hipSuccess && hipEventElapsedTime(&ms, tr.ev[0], tr.ev[1]) == hipSuccess)
-            fprintf(stderr, "kmc_unitig_clean: keys %llu unitigs %llu tips %llu islands %llu kept %llu clean_ms %.4f\n", (unsigned long long)n,
-                    (unsigned long long)nu, (unsigned long long)h[KMC_C_SUM + 1], (unsigned long long)h[KMC_C_SUM + 2], (unsigned long long)n_kept, ms);
+        if (hipEventSynchronize(tr.ev[1]) == hipSuccess && hipEventElapsedTime(&ms, tr.ev[0], tr.ev[1]) == hipSuccess) {
+            if (simplify)
+                fprintf(stderr, "kmc_unitig_simplify: keys %llu unitigs %llu tips %llu islands %llu bubbles %llu kept %llu clean_ms %.4f\n",
+                        (unsigned long long)n, (unsigned long long)nu, (unsigned long long)h[KMC_C_SUM + 1], (unsigned long long)h[KMC_C_SUM + 2],
+                        (unsigned long long)h[KMC_C_SUM2 + 0], (unsigned long long)n_kept, ms);
+            else
+                fprintf(stderr, "kmc_unitig_clean: keys %llu unitigs %llu tips %llu islands %llu kept %llu clean_ms %.4f\n", (unsigned long long)n,
+                        (unsigned long long)nu, (unsigned long long)h[KMC_C_SUM + 1], (unsigned long long)h[KMC_C_SUM + 2], (unsigned long long)n_kept, ms);
+        }
     }
     h[KMC_C_SUM + 0] = nu;
-    memcpy(c->cl_words, h + KMC_C_SUM, sizeof(c->cl_words));
+    memcpy(c->cl_words, h + KMC_C_SUM, KMC_CLEAN_WORDS * sizeof(u64));
+    memcpy(c->cl_words + KMC_CLEAN_WORDS, h + KMC_C_SUM2, (KMC_SIMPLIFY_WORDS - KMC_CLEAN_WORDS) * sizeof(u64));
     c->cl_kept = n_kept;
-    c->cl_key.keep(c->view_gen, min_count, max_count); c->cl_tip = tip; c->cl_isl = isl;
+    c->cl_key.keep(c->view_gen, min_count, max_count); c->cl_tip = tip; c->cl_isl = isl; c->cl_bub = bub;
     return KMC_OK;
 }
 
+// what a clean and a simplify call differ in: the bubble limit, how many summary words go out, whose name errors carry
+struct CleanForm { uint64_t max_bubble_keys; int words; bool simplify; const char* what; };
+
 static int kmc_unitig_clean_device_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t max_tip_keys, uint64_t max_island_keys,
                                         const void** d_key_hi, const void** d_key_lo, const void** d_count, const void** d_verdict,
-                                        uint64_t* n_kept, uint64_t* n_unitigs, uint64_t* summary, const char* what = "kmc_unitig_clean_device") {
+                                        uint64_t* n_kept, uint64_t* n_unitigs, uint64_t* summary,
+                                        CleanForm f = {0, KMC_CLEAN_WORDS, false, "kmc_unitig_clean_device"}) {
     if (!c) return KMC_ERR_ARG;
     int rc;
+    const char* what = f.what;
     if ((rc = unitig_begin(c, what, min_count, max_count)) ||
-        (rc = clean_run(c, what, min_count, max_count, clean_limit(max_tip_keys), clean_limit(max_island_keys)))) return rc;
+        (rc = clean_run(c, what, min_count, max_count, clean_limit(max_tip_keys), clean_limit(max_island_keys), clean_limit(f.max_bubble_keys),
+                        f.simplify))) return rc;
     publish_keys(c, c->cl, d_key_hi, d_key_lo, d_count);
     if (d_verdict) *d_verdict = c->cl_verdict.p;
     if (n_kept) *n_kept = c->cl_kept;
     if (n_unitigs) *n_unitigs = c->cl_words[0];
-    if (summary) memcpy(summary, c->cl_words, sizeof(c->cl_words));
+    if (summary) memcpy(summary, c->cl_words, (size_t)f.words * sizeof(u64));
     return KMC_OK;
 }
 
 static int kmc_unitig_clean_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t max_tip_keys, uint64_t max_island_keys,
                                  uint64_t* key_hi, uint64_t* key_lo, uint64_t* count, uint64_t cap_keys, uint8_t* verdict, uint64_t cap_unitigs,
-                                 uint64_t* n_kept, uint64_t* n_unitigs, uint64_t* summary) {
+                                 uint64_t* n_kept, uint64_t* n_unitigs, uint64_t* summary,
+                                 CleanForm f = {0, KMC_CLEAN_WORDS, false, "kmc_unitig_clean"}) {
     if (n_kept) *n_kept = 0;
     if (n_unitigs) *n_unitigs = 0;
     if (!c) return KMC_ERR_ARG;
     int rc;
-    if ((rc = unitig_begin(c, "kmc_unitig_clean", min_count, max_count))) return rc;
-    const u64 tip = clean_limit(max_tip_keys), isl = clean_limit(max_island_keys);
-    if (!clean_kept(c, min_count, max_count, tip, isl) && (rc = clean_run(c, "kmc_unitig_clean", min_count, max_count, tip, isl))) return rc;
+    const char* what = f.what;
+    if ((rc = unitig_begin(c, what, min_count, max_count))) return rc;
+    const u64 tip = clean_limit(max_tip_keys), isl = clean_limit(max_island_keys), bub = clean_limit(f.max_bubble_keys);
+    if (!clean_kept(c, min_count, max_count, tip, isl, bub) && (rc = clean_run(c, what, min_count, max_count, tip, isl, bub, f.simplify))) return rc;
     const u64 nk = c->cl_kept, nu = c->cl_words[0];
     if (n_kept) *n_kept = nk;
     if (n_unitigs) *n_unitigs = nu;
     if ((key_hi || key_lo || count) && cap_keys < nk)
-        return fail(c, KMC_ERR_ARG, "kmc_unitig_clean: capacity %llu < %llu kept keys", (unsigned long long)cap_keys, (unsigned long long)nk);
+        return fail(c, KMC_ERR_ARG, "%s: capacity %llu < %llu kept keys", what, (unsigned long long)cap_keys, (unsigned long long)nk);
     if (verdict && cap_unitigs < nu)
-        return fail(c, KMC_ERR_ARG, "kmc_unitig_clean: capacity %llu < %llu unitigs", (unsigned long long)cap_unitigs, (unsigned long long)nu);
+        return fail(c, KMC_ERR_ARG, "%s: capacity %llu < %llu unitigs", what, (unsigned long long)cap_unitigs, (unsigned long long)nu);
     if (nk && (rc = queue_to_host(c, c->cl.hi.p, c->cl.lo.p, c->cl.cnt.p, nk, key_hi, key_lo, count))) return rc;
     if (verdict && nu) HIPCHK(c, hipMemcpyAsync(verdict, c->cl_verdict.p, (size_t)nu, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (summary) memcpy(summary, c->cl_words, sizeof(c->cl_words));
+    if (summary) memcpy(summary, c->cl_words, (size_t)f.words * sizeof(u64));
     return KMC_OK;
 }
 
 // One step of a cleaning round: the kept pairs of src merged into dst's table (dst stays un-finalized).  dst's merge has
 // finished when this returns: src's result may be rewritten right after.
 static int kmc_unitig_clean_into_impl(kmc_ctx* src, kmc_ctx* dst, uint64_t min_count, uint64_t max_count, uint64_t max_tip_keys,
-                                      uint64_t max_island_keys, uint64_t* summary) {
-    if (!src || !dst) return src ? fail(src, KMC_ERR_ARG, "kmc_unitig_clean_into: null context") : KMC_ERR_ARG;
-    if (dst == src) return fail(src, KMC_ERR_ARG, "kmc_unitig_clean_into: dst is src");
+                                      uint64_t max_island_keys, uint64_t* summary,
+                                      CleanForm f = {0, KMC_CLEAN_WORDS, false, "kmc_unitig_clean_into"}) {
+    if (!src || !dst) return src ? fail(src, KMC_ERR_ARG, "%s: null context", f.what) : KMC_ERR_ARG;
+    if (dst == src) return fail(src, KMC_ERR_ARG, "%s: dst is src", f.what);
     int rc;
-    if ((rc = same_kind(src, dst, "kmc_unitig_clean_into"))) return rc;
+    if ((rc = same_kind(src, dst, f.what))) return rc;
     const void *hi = nullptr, *lo = nullptr, *cnt = nullptr;
     uint64_t nk = 0;
-    u64 h[KMC_CLEAN_WORDS];
-    if ((rc = kmc_unitig_clean_device_impl(src, min_count, max_count, max_tip_keys, max_island_keys, &hi, &lo, &cnt, nullptr, &nk, nullptr, h,
-                                           "kmc_unitig_clean_into"))) return rc;
+    u64 h[KMC_SIMPLIFY_WORDS];
+    if ((rc = kmc_unitig_clean_device_impl(src, min_count, max_count, max_tip_keys, max_island_keys, &hi, &lo, &cnt, nullptr, &nk, nullptr, h, f)))
+        return rc;
     if (nk) {
         if ((rc = kmc_merge_pairs_device(dst, hi, lo, cnt, nk)) || (rc = kmc_sync(dst)))
-            return fail(src, rc, "kmc_unitig_clean_into: merging into dst failed: %s", kmc_last_error(dst));
+            return fail(src, rc, "%s: merging into dst failed: %s", f.what, kmc_last_error(dst));
     }
-    if (summary) memcpy(summary, h, sizeof(h));
+    if (summary) memcpy(summary, h, (size_t)f.words * sizeof(u64));
     return KMC_OK;
 }
 
@@ -1210,6 +1235,29 @@ extern "C" int kmc_unitig_clean_into(kmc_ctx* src, kmc_ctx* dst, uint64_t min_co
                                      uint64_t max_island_keys, uint64_t* summary) {
     return guarded(src, [&]() -> int {
         return kmc_unitig_clean_into_impl(src, dst, min_count, max_count, max_tip_keys, max_island_keys, summary);
+    });
+}
+extern "C" int kmc_unitig_simplify_device(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t max_tip_keys, uint64_t max_island_keys,
+                                          uint64_t max_bubble_keys, const void** d_key_hi, const void** d_key_lo, const void** d_count,
+                                          const void** d_verdict, uint64_t* n_kept, uint64_t* n_unitigs, uint64_t* summary) {
+    return guarded(c, [&]() -> int {
+        return kmc_unitig_clean_device_impl(c, min_count, max_count, max_tip_keys, max_island_keys, d_key_hi, d_key_lo, d_count, d_verdict, n_kept,
+                                            n_unitigs, summary, {max_bubble_keys, KMC_SIMPLIFY_WORDS, true, "kmc_unitig_simplify_device"});
+    });
+}
+extern "C" int kmc_unitig_simplify(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t max_tip_keys, uint64_t max_island_keys,
+                                   uint64_t max_bubble_keys, uint64_t* key_hi, uint64_t* key_lo, uint64_t* count, uint64_t cap_keys,
+                                   uint8_t* verdict, uint64_t cap_unitigs, uint64_t* n_kept, uint64_t* n_unitigs, uint64_t* summary) {
+    return guarded(c, [&]() -> int {
+        return kmc_unitig_clean_impl(c, min_count, max_count, max_tip_keys, max_island_keys, key_hi, key_lo, count, cap_keys, verdict, cap_unitigs,
+                                     n_kept, n_unitigs, summary, {max_bubble_keys, KMC_SIMPLIFY_WORDS, true, "kmc_unitig_simplify"});
+    });
+}
+extern "C" int kmc_unitig_simplify_into(kmc_ctx* src, kmc_ctx* dst, uint64_t min_count, uint64_t max_count, uint64_t max_tip_keys,
+                                        uint64_t max_island_keys, uint64_t max_bubble_keys, uint64_t* summary) {
+    return guarded(src, [&]() -> int {
+        return kmc_unitig_clean_into_impl(src, dst, min_count, max_count, max_tip_keys, max_island_keys, summary,
+                                          {max_bubble_keys, KMC_SIMPLIFY_WORDS, true, "kmc_unitig_simplify_into"});
     });
 }
 extern "C" int kmc_partition_device(kmc_ctx* c, uint32_t n_parts, uint64_t* part_begin, const void** d_key_hi,

@@ -38,6 +38,10 @@ pub const KMC_CLEAN_WORDS: usize = 8;
 pub const KMC_CLEAN_KEEP: u8 = 0;
 pub const KMC_CLEAN_TIP: u8 = 1;
 pub const KMC_CLEAN_ISLAND: u8 = 2;
+/// the fourth verdict, of `kmc_unitig_simplify`
+pub const KMC_CLEAN_BUBBLE: u8 = 3;
+/// summary words of `kmc_unitig_simplify`
+pub const KMC_SIMPLIFY_WORDS: usize = 12;
 
 // The structs and the extern block below are checked against include/kmc.h by
 // tests/test_abi_host.py::test_rust_binding_matches_the_header (names, arity, argument types, field
@@ -153,6 +157,9 @@ extern "C" {
     pub fn kmc_unitig_clean_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, max_tip_keys: u64, max_island_keys: u64, d_key_hi: *mut *const c_void, d_key_lo: *mut *const c_void, d_count: *mut *const c_void, d_verdict: *mut *const c_void, n_kept: *mut u64, n_unitigs: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_clean(ctx: *mut KmcCtx, min_count: u64, max_count: u64, max_tip_keys: u64, max_island_keys: u64, key_hi: *mut u64, key_lo: *mut u64, count: *mut u64, cap_keys: u64, verdict: *mut u8, cap_unitigs: u64, n_kept: *mut u64, n_unitigs: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_clean_into(src: *mut KmcCtx, dst: *mut KmcCtx, min_count: u64, max_count: u64, max_tip_keys: u64, max_island_keys: u64, summary: *mut u64) -> c_int;
+    pub fn kmc_unitig_simplify_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, max_tip_keys: u64, max_island_keys: u64, max_bubble_keys: u64, d_key_hi: *mut *const c_void, d_key_lo: *mut *const c_void, d_count: *mut *const c_void, d_verdict: *mut *const c_void, n_kept: *mut u64, n_unitigs: *mut u64, summary: *mut u64) -> c_int;
+    pub fn kmc_unitig_simplify(ctx: *mut KmcCtx, min_count: u64, max_count: u64, max_tip_keys: u64, max_island_keys: u64, max_bubble_keys: u64, key_hi: *mut u64, key_lo: *mut u64, count: *mut u64, cap_keys: u64, verdict: *mut u8, cap_unitigs: u64, n_kept: *mut u64, n_unitigs: *mut u64, summary: *mut u64) -> c_int;
+    pub fn kmc_unitig_simplify_into(src: *mut KmcCtx, dst: *mut KmcCtx, min_count: u64, max_count: u64, max_tip_keys: u64, max_island_keys: u64, max_bubble_keys: u64, summary: *mut u64) -> c_int;
     // multi-GPU reduce (one process per GPU; the collective itself is the host program's, e.g. RCCL)
     pub fn kmc_slab_words(ctx: *const KmcCtx, slab_entries: u64) -> u64;
     pub fn kmc_pack_slab_device(ctx: *mut KmcCtx, d_slab: *mut c_void, slab_entries: u64) -> c_int;
@@ -462,6 +469,50 @@ impl Counter {
         self.check(unsafe { kmc_finalize(self.ctx, &mut nd, &mut nt) })?;
         let mut w = [0u64; KMC_CLEAN_WORDS];
         self.check(unsafe { kmc_unitig_clean_into(self.ctx, dst.ctx, min_count, max_count, max_tip_keys, max_island_keys, w.as_mut_ptr()) })?;
+        Ok(w)
+    }
+
+    /// `clean_unitigs` with simple bubbles popped (`kmc_unitig_simplify`): a unitig of at most `max_bubble_keys` keys with one
+    /// link at each end that loses against a parallel unitig between the same two ends gets `KMC_CLEAN_BUBBLE`; 0 pops
+    /// nothing.  Twelve summary words: those of `clean_unitigs`, then [bubbles, their keys, bubble candidates, the sum of
+    /// the counts of their keys].  The counts of a popped arm are not added to the survivor.
+    pub fn simplify_unitigs(&mut self, min_count: u64, max_count: u64, max_tip_keys: u64, max_island_keys: u64, max_bubble_keys: u64)
+                            -> Result<(Vec<(String, u64)>, Vec<u8>, [u64; KMC_SIMPLIFY_WORDS]), KmcError> {
+        let (mut nd, mut nt) = (0u64, 0u64);
+        self.check(unsafe { kmc_finalize(self.ctx, &mut nd, &mut nt) })?;
+        let (mut nk, mut nu) = (0u64, 0u64);
+        let mut w = [0u64; KMC_SIMPLIFY_WORDS];
+        let null64 = std::ptr::null_mut::<u64>();
+        self.check(unsafe {
+            kmc_unitig_simplify(self.ctx, min_count, max_count, max_tip_keys, max_island_keys, max_bubble_keys, null64, null64, null64, 0,
+                                std::ptr::null_mut::<u8>(), 0, &mut nk, &mut nu, w.as_mut_ptr())
+        })?;
+        let k = nk as usize;
+        let (mut hi, mut lo, mut cnt) = (vec![0u64; k], vec![0u64; k], vec![0u64; k]);
+        let mut verdict = vec![0u8; nu as usize];
+        self.check(unsafe {
+            kmc_unitig_simplify(self.ctx, min_count, max_count, max_tip_keys, max_island_keys, max_bubble_keys, hi.as_mut_ptr(), lo.as_mut_ptr(),
+                                cnt.as_mut_ptr(), nk, verdict.as_mut_ptr(), nu, &mut nk, &mut nu, w.as_mut_ptr())
+        })?;
+        let mut buf = vec![0u8; self.klen as usize];
+        let mut out = Vec::with_capacity(k);
+        for i in 0..k {
+            unsafe { kmc_decode_key(hi[i], lo[i], self.klen, buf.as_mut_ptr() as *mut c_char) };
+            out.push((String::from_utf8_lossy(&buf).into_owned(), cnt[i]));
+        }
+        Ok((out, verdict, w))
+    }
+
+    /// One step of a round that also pops bubbles (`kmc_unitig_simplify_into`): as `clean_into`, with the twelve words of
+    /// `simplify_unitigs`.
+    pub fn simplify_into(&mut self, dst: &mut Counter, min_count: u64, max_count: u64, max_tip_keys: u64, max_island_keys: u64,
+                         max_bubble_keys: u64) -> Result<[u64; KMC_SIMPLIFY_WORDS], KmcError> {
+        let (mut nd, mut nt) = (0u64, 0u64);
+        self.check(unsafe { kmc_finalize(self.ctx, &mut nd, &mut nt) })?;
+        let mut w = [0u64; KMC_SIMPLIFY_WORDS];
+        self.check(unsafe {
+            kmc_unitig_simplify_into(self.ctx, dst.ctx, min_count, max_count, max_tip_keys, max_island_keys, max_bubble_keys, w.as_mut_ptr())
+        })?;
         Ok(w)
     }
 }
