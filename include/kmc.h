@@ -27,6 +27,7 @@
  *   (addition: no equivalent in the reference)             kmc_unitig_links / kmc_unitig_links_device (the edges between them)
  *   (addition: no equivalent in the reference)             kmc_unitig_clean / kmc_unitig_clean_device / kmc_unitig_clean_into (tips and islands removed)
  *   (addition: no equivalent in the reference)             kmc_unitig_simplify / kmc_unitig_simplify_device / kmc_unitig_simplify_into (and simple bubbles popped)
+ *   (addition: no equivalent in the reference)             kmc_unitig_map / kmc_unitig_map_device (reads threaded through the unitigs)
  *
  * Conventions
  *   - Every function returns 0 (KMC_OK) or a negative kmc_status; no exception or abort crosses
@@ -452,6 +453,66 @@ int kmc_unitig_links_device(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count
  * call that computes, in between makes it compute again. */
 int kmc_unitig_links(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, uint64_t* link_offsets, uint64_t cap_ends,
                      uint32_t* link_to, uint64_t cap_links, uint64_t* n_unitigs, uint64_t* n_links, uint64_t* summary);
+
+/* ---- reads threaded through those unitigs: where every window of a read lies in the compacted graph (additions, as
+ * above).  Everything refers to the unitigs of kmc_unitigs for the same view and range min_count..max_count: their
+ * numbering, their spelling S_u, their m_u keys.  KMC_MODE_CONTIG only; every k, in a canonical or a forward ctx.
+ * WINDOW.  The k bases that start at base j of read r, as the string f: the window kmc_profile counts.  A window is VALID iff
+ *   it lies inside the read and holds only upper-case ACGT.
+ * PLACED.  A valid window is placed iff x = canon(f) (f itself in a forward ctx) is solid, by the ctx's own key rule and the
+ *   range rule of kmc_graph.  x then occurs in exactly one unitig u, at exactly one key position pos in 0..m_u-1, and
+ *   S_u[pos : pos+k] is f or its reverse complement.  o = 0 iff f == S_u[pos : pos+k] -- so a palindromic f has o = 0 --
+ *   and o = 1 otherwise; in a forward ctx o is always 0.
+ * PLACE WORD.  place[offsets[r] + j], a uint64_t: the low 32 bits are uni = 2u + o, the high 32 bits are pos.  A window that
+ *   is not placed has uni = KMC_MAP_NONE and pos = 0: the last k-1 positions of a read, every position of a read shorter
+ *   than k, invalid windows, windows that are not solid.
+ * CONTINUES.  Window j of a read continues window j-1 iff both are placed, their uni is equal, and pos_j == pos_{j-1} + 1
+ *   when o = 0, pos_j == pos_{j-1} - 1 when o = 1.  Nothing else counts: a homopolymer read over a one-key circular unitig
+ *   does not continue itself, nor does a wrap across a cycle's cut.  The formula is the definition.
+ * SEGMENT.  A maximal run of windows of one read, each continuing the one before it, recorded as four uint32_t: start (the
+ *   window start relative to the read), len (its number of windows), uni, pos (the position of its first window).  Segments
+ *   are listed per read in read order; seg_offsets[n_reads + 1], uint64_t, seg_offsets[0] == 0: the segments of read r are
+ *   segs[4 * seg_offsets[r] .. 4 * seg_offsets[r+1]).
+ * CROSSING.  A segment whose first window is not the read's first window and whose preceding window is placed: the read
+ *   stepped from one unitig end to another without a gap.
+ * read_stats[n_reads * KMC_MAP_READ_WORDS], uint32_t: [0] valid windows, [1] placed windows, [2] segments, [3] crossings.
+ * support[n_unitigs], uint64_t: placed windows per unitig, on either strand, over the batch.
+ * summary[KMC_MAP_WORDS]: [0] reads, [1] valid windows, [2] placed windows, [3] segments, [4] crossings, [5] reads with at
+ *   least one valid window, all of them placed, [6] reads with no placed window, [7] the most segments in one read.
+ *   [2] equals the sum of support, [3] equals seg_offsets[n_reads].
+ * Rules: NULL ctx, KMC_MODE_LR, a non-zero max_count below min_count: KMC_ERR_ARG; no view: KMC_ERR_STATE (where kmc_export
+ * says so); the capacity rules of kmc_unitigs: KMC_ERR_CAPACITY; a read of 2^32 bases or more: KMC_ERR_ARG; 2^32 segments or
+ * more in a batch: KMC_ERR_CAPACITY.  n_reads == 0 and an empty view give zeros (an empty view places nothing; its valid
+ * windows are still counted).
+ * RELATION TO THE OTHER VIEW CALLS.  A map call counts as a kmc_unitigs* call: it reuses the unitigs the ctx holds for this
+ * view and range if no kmc_graph* call has rewritten their work arrays (the condition of kmc_unitig_links), otherwise it
+ * computes them and keeps them.  It rewrites none of: the unitig arrays, links, a clean result, adj, the view, a partition,
+ * a filter or set-operation result, the query index.  Behind the unitigs it keeps one 8-byte word per view row (unitig,
+ * position, strand), built once per unitig result and dropped with it.
+ * Diagnostic: with KMC_UNITIG_TRACE set, a map call prints "kmc_unitig_map: keys N unitigs U reads R windows W placed P
+ * segments S unitigs_reused 0|1 index_ms .. place_ms .. segs_ms .." to stderr (tools/measure_map.py reads it). ---- */
+#define KMC_MAP_WORDS 8
+#define KMC_MAP_READ_WORDS 4
+#define KMC_MAP_NONE 0xFFFFFFFFu
+/* The batch in device memory, by the layout and alignment rules of kmc_profile_device (d_bases 16-byte aligned and readable
+ * up to the next 16-byte boundary, d_offsets uint64_t[n_reads + 1]).  The results in ctx-owned device arrays -- uint64_t
+ * place[n_bases], uint32_t read_stats[n_reads * 4], uint64_t seg_offsets[n_reads + 1], uint32_t segs[4 * n_segs], uint64_t
+ * support[n_unitigs] -- valid until the next kmc_unitig_map*, kmc_unitigs* or kmc_graph* call / finalize / reset / destroy
+ * (same ordering contract as kmc_export_device).  Every output pointer may be NULL. */
+int kmc_unitig_map_device(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, const void* d_bases, const void* d_offsets,
+                          uint64_t n_reads, uint64_t n_bases, const void** d_place, const void** d_read_stats,
+                          const void** d_seg_offsets, const void** d_segs, const void** d_support, uint64_t* n_segs,
+                          uint64_t* n_unitigs, uint64_t* summary);
+/* The same on host buffers (the batch as kmc_profile takes it).  The caller supplies place[offsets[n_reads]],
+ * read_stats[n_reads * 4], seg_offsets[n_reads + 1], segs with room for cap_segs records and support with cap_unitigs
+ * entries.  *n_segs and *n_unitigs are always set; a cap too small for an array that was given -> KMC_ERR_ARG and nothing
+ * is copied; an array that is NULL is not copied and its cap not looked at.  All arrays NULL is the sizing call.  The host
+ * form computes on EVERY call -- it cannot recognise a batch it has seen -- so a caller that sizes first maps twice; the
+ * device form, which hands out the arrays themselves, needs no sizing call. */
+int kmc_unitig_map(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, const uint8_t* bases, const uint64_t* offsets,
+                   uint64_t n_reads, uint64_t* place, uint32_t* read_stats, uint64_t* seg_offsets, uint32_t* segs,
+                   uint64_t cap_segs, uint64_t* support, uint64_t cap_unitigs, uint64_t* n_segs, uint64_t* n_unitigs,
+                   uint64_t* summary);
 
 /* ---- the compacted graph cleaned: tips clipped, islands dropped (additions, as above).  Everything refers to the unitigs
  * and the link records of kmc_unitigs / kmc_unitig_links for the same view and range min_count..max_count.  For unitig u:

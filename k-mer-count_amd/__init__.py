@@ -93,6 +93,7 @@ ABI_SYMBOLS = [
     "kmc_unitig_links", "kmc_unitig_links_device",
     "kmc_unitig_clean", "kmc_unitig_clean_device", "kmc_unitig_clean_into",
     "kmc_unitig_simplify", "kmc_unitig_simplify_device", "kmc_unitig_simplify_into",
+    "kmc_unitig_map", "kmc_unitig_map_device",
 ]
 
 PROFILE_WORDS = 5  # KMC_PROFILE_WORDS: valid windows, present windows, min, max, sum
@@ -106,6 +107,9 @@ CLEAN_WORDS = 8    # KMC_CLEAN_WORDS: unitigs, tips, islands, keys kept / of tip
 CLEAN_KEEP, CLEAN_TIP, CLEAN_ISLAND = 0, 1, 2   # KMC_CLEAN_*: a unitig's verdict byte
 SIMPLIFY_WORDS = 12  # KMC_SIMPLIFY_WORDS: the clean words, then bubbles, their keys, bubble candidates, the counts of their keys
 CLEAN_BUBBLE = 3     # KMC_CLEAN_BUBBLE: the fourth verdict, of a simplify call
+MAP_WORDS = 8        # KMC_MAP_WORDS: reads, valid windows, placed windows, segments, crossings, fully placed reads, unplaced reads, most segments
+MAP_READ_WORDS = 4   # KMC_MAP_READ_WORDS: a read's valid windows, placed windows, segments, crossings
+MAP_NONE = 0xFFFFFFFF  # KMC_MAP_NONE: the low half of the place word of a window that is not placed
 SETOP_INTERSECT, SETOP_UNION, SETOP_SUBTRACT = 0, 1, 2
 COUNT_LEFT, COUNT_RIGHT, COUNT_MIN, COUNT_MAX, COUNT_SUM, COUNT_DIFF = 0, 1, 2, 3, 4, 5
 SETOP_NAMES = {"intersect": SETOP_INTERSECT, "union": SETOP_UNION, "subtract": SETOP_SUBTRACT}
@@ -183,6 +187,8 @@ def lib() -> C.CDLL:
     L.kmc_unitig_simplify_device.argtypes = [vp, u64, u64, u64, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), pu64, pu64, vp]
     L.kmc_unitig_simplify.argtypes = [vp, u64, u64, u64, u64, u64, vp, vp, vp, u64, vp, u64, pu64, pu64, vp]
     L.kmc_unitig_simplify_into.argtypes = [vp, vp, u64, u64, u64, u64, u64, vp]
+    L.kmc_unitig_map_device.argtypes = [vp, u64, u64, vp, vp, u64, u64] + [C.POINTER(vp)] * 5 + [pu64, pu64, vp]
+    L.kmc_unitig_map.argtypes = [vp, u64, u64, vp, vp, u64, vp, vp, vp, vp, u64, vp, u64, pu64, pu64, vp]
     L.kmc_owner_of.argtypes = [u64, u64, u32]
     L.kmc_owner_of.restype = u32
     L.kmc_get_stats.argtypes = [vp, C.POINTER(Stats)]
@@ -497,6 +503,78 @@ class UnitigLinks:
         for i in range(len(o) - 1):
             for t in self.to[int(o[i]):int(o[i + 1])]:
                 yield i >> 1, "+" if i & 1 else "-", int(t) >> 1, "-" if int(t) & 1 else "+"
+
+
+_MAP_FIELDS = ("reads", "valid_windows", "placed_windows", "segments", "crossings", "reads_fully_placed", "reads_unplaced", "max_segments")
+
+
+@dataclass
+class MapSummary:
+    """The eight words of kmc_unitig_map: reads, valid windows, placed windows, segments, crossings, reads with at least one
+    valid window and all of them placed, reads with no placed window, the most segments in one read."""
+    reads: int
+    valid_windows: int
+    placed_windows: int
+    segments: int
+    crossings: int
+    reads_fully_placed: int
+    reads_unplaced: int
+    max_segments: int
+
+    @classmethod
+    def from_words(cls, words) -> "MapSummary":
+        return cls(*[int(w) for w in words])
+
+    def words(self) -> list:
+        return [getattr(self, f) for f in _MAP_FIELDS]
+
+    def to_text(self) -> str:
+        """``NAME\tVALUE`` lines."""
+        return "\n".join("%s\t%d" % (f, getattr(self, f)) for f in _MAP_FIELDS) + "\n"
+
+
+@dataclass
+class ReadMap:
+    """What KmerCounter.map_reads returns: ``place`` uint64[n_bases] (low half 2 * unitig + orientation or MAP_NONE, high
+    half the key position), ``stats`` uint32[n_reads, 4], ``seg_offsets`` uint64[n_reads + 1], ``segments`` uint32[n, 4]
+    (start, len, 2 * unitig + orientation, pos), ``support`` uint64[n_unitigs], ``summary``.  The segments of read r are
+    ``segments[seg_offsets[r]:seg_offsets[r + 1]]``."""
+    place: np.ndarray
+    stats: np.ndarray
+    seg_offsets: np.ndarray
+    segments: np.ndarray
+    support: np.ndarray
+    summary: MapSummary
+
+    def __len__(self) -> int:
+        return len(self.seg_offsets) - 1
+
+    def walks(self) -> list:
+        """Per read a list of stretches; a stretch is a list of ``(unitig, orientation, pos, len)`` in which each element is
+        a crossing of the one before it (it starts at the window right behind it), and a gap starts a new stretch."""
+        out = []
+        so = self.seg_offsets
+        for r in range(len(self)):
+            stretches, end = [], None
+            for start, ln, uni, pos in self.segments[int(so[r]):int(so[r + 1])].tolist():
+                if end is None or start != end:
+                    stretches.append([])
+                stretches[-1].append((uni >> 1, uni & 1, pos, ln))
+                end = start + ln
+            out.append(stretches)
+        return out
+
+    def walk_text(self, r: int) -> str:
+        """The WALK column of ``k-mer-count --map`` for read r: ``>U:POS:LEN`` / ``<U:POS:LEN`` per segment, a crossing written
+        directly behind its predecessor, ``,`` at a gap, ``*`` for a read without a segment."""
+        so = self.seg_offsets
+        parts, end = [], None
+        for start, ln, uni, pos in self.segments[int(so[r]):int(so[r + 1])].tolist():
+            if end is not None and start != end:
+                parts.append(",")
+            parts.append("%s%d:%d:%d" % ("<" if uni & 1 else ">", uni >> 1, pos, ln))
+            end = start + ln
+        return "".join(parts) or "*"
 
 
 _CLEAN_FIELDS = ("unitigs", "tips", "islands", "kept_keys", "tip_keys", "island_keys", "tip_candidates", "kept_count")
@@ -881,6 +959,50 @@ class KmerCounter:
         w = (C.c_uint64 * LINK_WORDS)()
         self._chk(self._L.kmc_unitig_links_device(self._h, int(min_count), int(max_count), *[C.byref(x) for x in p], C.byref(nu), C.byref(nl), w))
         return tuple(x.value or 0 for x in p) + (nu.value, nl.value, LinkSummary.from_words(list(w)))
+
+    # -- reads threaded through those unitigs: placements, segments, support (of the sorted view; finalize() first) --
+    def map_reads_device(self, d_bases: int, d_offsets: int, n_reads: int, n_bases: int, min_count: int = 1, max_count: int = 0):
+        """(d_place, d_read_stats, d_seg_offsets, d_segs, d_support, n_segs, n_unitigs, MapSummary) of kmc_unitig_map_device for
+        a batch in device memory (raw addresses, laid out as for profile_device): ctx-owned device arrays of n_bases uint64,
+        n_reads * 4 uint32, n_reads + 1 uint64, n_segs * 4 uint32 and n_unitigs uint64."""
+        p = [C.c_void_p() for _ in range(5)]
+        ns, nu = C.c_uint64(), C.c_uint64()
+        w = (C.c_uint64 * MAP_WORDS)()
+        self._chk(self._L.kmc_unitig_map_device(self._h, int(min_count), int(max_count), d_bases or None, d_offsets or None, int(n_reads),
+                                                int(n_bases), *[C.byref(x) for x in p], C.byref(ns), C.byref(nu), w))
+        return tuple(x.value or 0 for x in p) + (ns.value, nu.value, MapSummary.from_words(list(w)))
+
+    def map_reads_tensors(self, bases, offsets, min_count: int = 1, max_count: int = 0):
+        """map_reads_device for torch tensors on this ctx's GPU (bases uint8[n_bases], padded as for add_batch_tensors;
+        offsets int64[n_reads + 1])."""
+        assert bases.is_cuda and offsets.is_cuda and bases.is_contiguous() and offsets.is_contiguous()
+        return self.map_reads_device(bases.data_ptr(), offsets.data_ptr(), max(offsets.numel() - 1, 0), bases.numel(), min_count, max_count)
+
+    def map_reads(self, bases: np.ndarray, offsets: np.ndarray, min_count: int = 1, max_count: int = 0) -> "ReadMap":
+        """kmc_unitig_map_device for a host batch (the batch is not counted): where every window of every read lies in the
+        unitigs of unitigs() with the same range.  The batch goes to the device as tensors and the result arrays are read
+        back from the ctx, so the library computes once (the host form kmc_unitig_map would need a sizing call first)."""
+        import torch
+        from .distributed import device_view
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n_reads, n_bases = max(int(offsets.shape[0]) - 1, 0), int(bases.shape[0])
+        if n_reads and (int(offsets[0]) != 0 or int(offsets[-1]) != n_bases or (np.diff(offsets.astype(np.int64)) < 0).any()):
+            raise ValueError("offsets must start at 0, not decrease, and end at len(bases)")
+        if n_reads and int(np.diff(offsets.astype(np.int64)).max()) >= 1 << 32:
+            raise KmcError(ERR_ARG, "a read of 2^32 bases or more")
+        dev = torch.device("cuda", self.device)
+        d_bases = torch.zeros(n_bases + 64, dtype=torch.uint8, device=dev)   # (readable past the end, 16-byte aligned)
+        d_bases[:n_bases] = torch.from_numpy(bases.copy())
+        d_offs = torch.from_numpy(offsets.view(np.int64).copy()).to(dev)
+        torch.cuda.synchronize(dev)
+        dp, ds, do, dg, du, ns, nu, summary = self.map_reads_device(d_bases.data_ptr(), d_offs.data_ptr(), n_reads, n_bases, min_count, max_count)
+
+        def words(ptr, n_bytes):
+            return device_view(ptr, (n_bytes + 7) // 8, dev).cpu().numpy().view(np.uint8)[:n_bytes].copy()
+        return ReadMap(words(dp, 8 * n_bases).view(np.uint64), words(ds, 16 * n_reads).view(np.uint32).reshape(n_reads, MAP_READ_WORDS),
+                       words(do, 8 * (n_reads + 1)).view(np.uint64), words(dg, 16 * ns).view(np.uint32).reshape(ns, 4),
+                       words(du, 8 * nu).view(np.uint64), summary)
 
     # -- that graph cleaned: tips clipped, islands dropped (of the sorted view; finalize() first) --
     def _clean_limits(self, max_tip_keys, max_island_keys) -> Tuple[int, int]:

@@ -5,7 +5,7 @@
 // test.py:15-18 takes the FASTA path as its only positional argument.  This tool keeps both:
 //
 //   k-mer-count [FASTA] [-k K] [--forward] [--expand] [--device N | --gpus N] [--algo auto|stream|walk|sort] [--stats]
-//               [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE]
+//               [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE | --map FILE]
 //               [--with FASTA2 (--compare | --setop intersect|union|subtract [--counts left|right|min|max|sum|diff])]
 //               [--graph | --graph-stats | --unitigs | --gfa] [--clean ROUNDS [--tip-keys N] [--island-keys N] [--bubble-keys N]]
 //
@@ -26,6 +26,13 @@
 //   --profile FILE       (with -k K) instead of the table: for every read of FILE (FASTA / FASTQ), in file order,
 //               "INDEX<TAB>WINDOWS<TAB>PRESENT<TAB>MIN<TAB>MAX<TAB>SUM": its valid K-mer windows, how many of them the
 //               counted input holds --min-count times or more, and the smallest / largest / summed count over them
+//   --map FILE           (with -k K) instead of the table: every read of FILE (FASTA / FASTQ) threaded through the unitigs of the
+//               counted input (kmc_unitig_map; --min-count / --max-count are the solidity range), in file order
+//               "INDEX<TAB>WINDOWS<TAB>PLACED<TAB>SEGMENTS<TAB>WALK": its valid K-mer windows, how many of them lie on a unitig, the
+//               number of segments, and the segments as ">U:POS:LEN" (read along unitig U from key position POS, LEN windows) or
+//               "<U:POS:LEN" (against it).  A segment that starts at the window right behind its predecessor -- the read crossed
+//               from one unitig end to another -- is written directly behind it, one behind a gap after a ","; "*" for a read
+//               with no segment.  With --clean the reads are laid on the cleaned graph.
 //
 //   --with FASTA2        (with -k K) a second file, counted into a second table on the same device; one of:
 //     --compare          instead of the table: "NAME<TAB>VALUE" lines -- the eight words of kmc_compare (n_a, n_b, n_both, sum_a,
@@ -107,7 +114,7 @@ int main(int argc, char** argv) {
     const char* path = "sample.fasta";  // main.rs:44
     int k = 0, canonical = 1, expand = 0, device = 0, algo = KMC_ALGO_AUTO, stats = 0, gpus = 1, histo = 0;
     long long min_count = 1, max_count = 0;   // (max_count 0: no upper bound)
-    const char *query_path = nullptr, *profile_path = nullptr, *with_path = nullptr;
+    const char *query_path = nullptr, *profile_path = nullptr, *with_path = nullptr, *map_path = nullptr;
     int compare = 0, setop = -1, count_mode = -1, graph = 0, graph_stats = 0, unitigs = 0, gfa = 0;
     int clean = 0;
     long long tip_keys = -1, island_keys = -1;   // (-1: K)
@@ -125,6 +132,7 @@ int main(int argc, char** argv) {
         else if (a == "--histo" && i + 1 < argc) { if (!parse_int("--histo", argv[++i], 1, (1 << 24) - 1, &histo)) return 2; }
         else if (a == "--query-kmers" && i + 1 < argc) query_path = argv[++i];
         else if (a == "--profile" && i + 1 < argc) profile_path = argv[++i];
+        else if (a == "--map" && i + 1 < argc) map_path = argv[++i];
         else if (a == "--with" && i + 1 < argc) with_path = argv[++i];
         else if (a == "--compare") compare = 1;
         else if (a == "--graph") graph = 1;
@@ -149,12 +157,12 @@ int main(int argc, char** argv) {
             algo = v == "stream" ? KMC_ALGO_STREAM : v == "walk" ? KMC_ALGO_WALK : v == "sort" ? KMC_ALGO_SORT : KMC_ALGO_AUTO;
         } else if (a == "-h" || a == "--help") {
             fprintf(stderr, "usage: k-mer-count [FASTA] [-k K] [--forward] [--expand] [--device N | --gpus N] [--algo auto|stream|walk|sort] [--stats]\n"
-                            "                   [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE]\n"
+                            "                   [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE | --map FILE]\n"
                             "                   [--with FASTA2 (--compare | --setop intersect|union|subtract [--counts left|right|min|max|sum|diff])]\n"
                             "                   [--graph | --graph-stats | --unitigs | --gfa] [--clean ROUNDS [--tip-keys N] [--island-keys N] [--bubble-keys N]]\n");
             return 0;
         } else if (a == "-k" || a == "--device" || a == "--gpus" || a == "--algo" || a == "--min-count" || a == "--max-count" || a == "--histo" ||
-                   a == "--query-kmers" || a == "--profile" || a == "--with" || a == "--setop" || a == "--counts" ||
+                   a == "--query-kmers" || a == "--profile" || a == "--map" || a == "--with" || a == "--setop" || a == "--counts" ||
                    a == "--clean" || a == "--tip-keys" || a == "--island-keys" || a == "--bubble-keys") {
             fprintf(stderr, "k-mer-count: %s needs a value\n", a.c_str());
             return 2;
@@ -175,6 +183,17 @@ int main(int argc, char** argv) {
         if (query_path && profile_path) { fprintf(stderr, "k-mer-count: --query-kmers and --profile exclude each other\n"); return 2; }
         if (!k) { fprintf(stderr, "k-mer-count: %s needs -k K\n", opt); return 2; }
         if (histo) { fprintf(stderr, "k-mer-count: %s and --histo exclude each other\n", opt); return 2; }
+    }
+    // --map: the same (it shares the parsed reads with --profile, which it excludes)
+    if (map_path) {
+        const char* bad = nullptr;
+        if (!k) bad = "needs -k K";
+        else if (query_path || profile_path) bad = "--query-kmers / --profile exclude each other";
+        else if (histo) bad = "--histo exclude each other";
+        else if (with_path || compare || setop >= 0) bad = "--with / --compare / --setop exclude each other";
+        else if (graph || graph_stats || unitigs || gfa) bad = "--graph / --graph-stats / --unitigs / --gfa exclude each other";
+        else if (expand) bad = "--expand exclude each other";
+        if (bad) { fprintf(stderr, "k-mer-count: --map %s%s\n", strncmp(bad, "needs", 5) ? "and " : "", bad); return 2; }
     }
     if (query_path) {
         FILE* f = fopen(query_path, "r");
@@ -200,10 +219,11 @@ int main(int argc, char** argv) {
         }
         fclose(f);
     }
-    if (profile_path) {
+    if (profile_path || map_path) {
+        const char* reads_path = profile_path ? profile_path : map_path;
         char eb[256] = {0};
-        const int prc = kmc_parse_fasta(profile_path, &prof, eb, sizeof(eb));
-        if (prc) return die(profile_path, eb[0] ? eb : kmc_status_string(prc));
+        const int prc = kmc_parse_fasta(reads_path, &prof, eb, sizeof(eb));
+        if (prc) return die(reads_path, eb[0] ? eb : kmc_status_string(prc));
     }
     // --with / --compare / --setop: bad combinations end here, before a GPU is touched
     {
@@ -215,6 +235,7 @@ int main(int argc, char** argv) {
         else if (count_mode >= 0 && setop < 0) bad = "--counts needs --setop";
         else if (with_path && !k) bad = "--with needs -k K";
         else if (with_path && (histo || query_path || profile_path)) bad = "--with and --histo / --query-kmers / --profile exclude each other";
+        else if (with_path && map_path) bad = "--with and --map exclude each other";
         else if (with_path && gpus != 1) bad = "--with and --gpus exclude each other";
         if (bad) { fprintf(stderr, "k-mer-count: %s\n", bad); return 2; }
     }
@@ -370,6 +391,38 @@ int main(int argc, char** argv) {
             const uint64_t* w = &rs[(size_t)r * KMC_PROFILE_WORDS];
             printf("%llu\t%llu\t%llu\t%llu\t%llu\t%llu\n", (unsigned long long)r, (unsigned long long)w[0], (unsigned long long)w[1],
                    (unsigned long long)w[2], (unsigned long long)w[3], (unsigned long long)w[4]);
+        }
+        fflush(stdout);
+        destroy_all();
+        return 0;
+    }
+    if (map_path) {
+        // the host form computes on every call: the first call sizes the segment list (and fills the arrays that need no
+        // size), the second copies it
+        const uint64_t n_map = prof.n_reads, lo_c = (uint64_t)min_count, hi_c = (uint64_t)max_count;
+        std::vector<uint32_t> rs((size_t)n_map * KMC_MAP_READ_WORDS + 1), sg(4);
+        std::vector<uint64_t> so((size_t)n_map + 1);
+        uint64_t ns = 0, nu = 0;
+        rc = kmc_unitig_map(ctx, lo_c, hi_c, prof.bases, prof.offsets, n_map, nullptr, rs.data(), so.data(), nullptr, 0, nullptr, 0, &ns, &nu, nullptr);
+        if (!rc && ns) {
+            sg.resize((size_t)ns * 4);
+            rc = kmc_unitig_map(ctx, lo_c, hi_c, prof.bases, prof.offsets, n_map, nullptr, nullptr, nullptr, sg.data(), ns, nullptr, 0, &ns, &nu, nullptr);
+        }
+        kmc_free_reads(&prof);
+        if (rc) { int r = die("kmc_unitig_map", kmc_last_error(ctx)); destroy_all(); return r; }
+        setvbuf(stdout, obuf.data(), _IOFBF, obuf.size());
+        for (uint64_t r = 0; r < n_map; ++r) {
+            const uint32_t* w = &rs[(size_t)r * KMC_MAP_READ_WORDS];
+            printf("%llu\t%u\t%u\t%u\t", (unsigned long long)r, w[0], w[1], w[2]);
+            uint64_t end = 0;
+            for (uint64_t i = so[r]; i < so[r + 1] && i < ns; ++i) {
+                const uint32_t* g = &sg[(size_t)i * 4];
+                if (i > so[r] && g[0] != end) fputc(',', stdout);
+                printf("%c%u:%u:%u", (g[2] & 1) ? '<' : '>', g[2] >> 1, g[3], g[1]);
+                end = (uint64_t)g[0] + g[1];
+            }
+            if (so[r] == so[r + 1]) fputc('*', stdout);
+            fputc('\n', stdout);
         }
         fflush(stdout);
         destroy_all();

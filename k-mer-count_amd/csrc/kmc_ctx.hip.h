@@ -215,6 +215,13 @@ struct kmc_ctx : CtxStream {
     DevBuf l_offs, l_to, l_cnt, l_pos, l_tgt, l_ctl;
     ResultKey l_key;
     u64 l_words[8] = {};
+    // kmc_unitig_map / kmc_unitig_map_device (kmc_map.hip.h) read the same work arrays.  m_idx is the row index built from
+    // them -- per view row the unitig, the key position and the strand -- and m_idx_live says it is still theirs: map_run
+    // sets it, graph_run (which every unitig_run goes through) clears it.  The result of the last call: place words, per-read
+    // rows, segment offsets and records, support per unitig; between the passes the read-start and valid-window bits of
+    // the batch and the tails' positions.
+    DevBuf m_idx, m_place, m_stats, m_soffs, m_segs, m_support, m_sbits, m_vbits, m_tail;
+    bool m_idx_live = false;
     // kmc_unitig_clean* and kmc_unitig_simplify* (kmc_clean.hip.h) read the unitigs, the links and what the links pass
     // reads.  Their result: the verdict per unitig and the kept table, with cl_key plus its three limits cl_tip / cl_isl /
     // cl_bub (0 for a clean call) and cl_words as above (nothing but the clean pass writes them; a clean call hands out the

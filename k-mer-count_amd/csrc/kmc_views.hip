@@ -14,6 +14,7 @@
 #include "kmc_unitig.hip.h"
 #include "kmc_links.hip.h"
 #include "kmc_clean.hip.h"
+#include "kmc_map.hip.h"
 
 namespace {
 
@@ -562,6 +563,7 @@ static int graph_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count,
     const u64 n = c->n_sorted;
     int rc;
     c->u_live = false;   // adj is rewritten from here on: a kept unitig result no longer has its work arrays
+    c->m_idx_live = false;   // ... and the row index built from them (kmc_map.hip.h) goes with them
     if ((rc = ensure(c, c->g_adj, (size_t)std::max<u64>(n, 1) * sizeof(uint16_t))) || (rc = ensure(c, c->g_ctl, KMC_GRAPH_WORDS * sizeof(u64)))) return rc;
     if (!n) return KMC_OK;
     QView v;
@@ -981,6 +983,191 @@ static int kmc_unitig_links_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_co
     return KMC_OK;
 }
 
+// ---- reads threaded through those unitigs: place words, segments, per-read and per-unitig totals (kmc_map.hip.h) ----
+// KMC_MAP_NO_INDEX in the environment makes the place kernel gather adj, the ranking and uid_of per window instead of the
+// row index -- a diagnostic for tools/measure_map.py, the result is the same.
+template <int PASS>
+static void map_segs_launch(kmc_ctx* c, const MapBatch& b, u64 n_segs, u64 nu) {
+    const u32 grid = (u32)std::min<u64>(b.n_tiles, (u64)c->n_cu * 8);
+    hipLaunchKernelGGL(kmc_map_segs_kernel<PASS>, dim3(grid), dim3(KMC_M_THREADS), 0, c->stream, b, (u32*)c->c_tile.p, (const u32*)c->c_tpos.p,
+                       n_segs, nu, (u32*)c->m_tail.p, (uint4*)c->m_segs.p, (u64*)c->m_soffs.p, (u32*)c->m_stats.p, (kmc_ull*)c->m_support.p,
+                       (kmc_ull*)c->c_ctl.p);
+}
+
+// The batch (device arrays) laid on the unitigs of this view and range -- those the ctx holds if their work arrays are
+// still theirs, otherwise computed and kept -- into the m_* buffers; h[KMC_MAP_WORDS] the summary.  Finished when it returns.
+static int map_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count, const uint8_t* d_bases, const u64* d_offsets, u64 n_reads,
+                   u64 n_bases, u64* h, u64* n_segs, u64* n_unitigs) {
+    memset(h, 0, KMC_MAP_WORDS * sizeof(u64));
+    *n_segs = *n_unitigs = 0;
+    int rc;
+    const bool kept = c->u_live && c->u_key.holds(c->view_gen, min_count, max_count);
+    if (!kept) {
+        u64 t[KMC_UNITIG_WORDS];
+        if ((rc = unitig_run(c, what, min_count, max_count, t))) return rc;
+        unitig_keep(c, min_count, max_count, t);
+    }
+    const u64 n = c->n_sorted, nu = c->u_words[0];
+    *n_unitigs = nu;
+    if (nu > n) return fail(c, KMC_ERR_HIP, "internal error: %s holds %llu unitigs of %llu keys", what, (unsigned long long)nu, (unsigned long long)n);
+    const int k = c->klen;
+    const u64 n_chunks = (n_bases + (u64)k - 1 + KMC_CHUNK - 1) / KMC_CHUNK;
+    const u64 n_tiles = (n_bases + 1 + KMC_M_TILE - 1) / KMC_M_TILE;
+    if (n_tiles >= (1ull << 31)) return fail(c, KMC_ERR_ARG, "%s: batch too large for one call", what);
+    const size_t stb = (size_t)std::max<u64>(n_reads, 1) * KMC_MAP_READ_WORDS * sizeof(u32), spb = (size_t)std::max<u64>(nu, 1) * sizeof(u64);
+    const size_t bitb = (size_t)std::max<u64>(n_chunks, 1) * 64 * sizeof(uint16_t);
+    if ((rc = ensure(c, c->m_soffs, (size_t)(n_reads + 1) * sizeof(u64))) || (rc = ensure(c, c->m_stats, stb)) || (rc = ensure(c, c->m_support, spb)) ||
+        (rc = ensure(c, c->m_segs, 16)) || (rc = ensure(c, c->m_tail, 4)) || (rc = ensure(c, c->m_idx, (size_t)std::max<u64>(n, 1) * sizeof(u64))) ||
+        (rc = ensure(c, c->m_place, (size_t)std::max<u64>(n_bases, 1) * sizeof(u64))) || (rc = ensure(c, c->m_sbits, bitb)) ||
+        (rc = ensure(c, c->m_vbits, bitb)) || (rc = compact_plan(c, n_tiles, KMC_M_CTL_WORDS)))
+        return rc;
+    HIPCHK(c, hipMemsetAsync(c->m_stats.p, 0, stb, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->m_support.p, 0, spb, c->stream));
+    if (!n_reads) {
+        HIPCHK(c, hipMemsetAsync(c->m_soffs.p, 0, sizeof(u64), c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return KMC_OK;
+    }
+    QView v;
+    if ((rc = query_view(c, what, &v))) return rc;
+    kmc_ull* ctl = (kmc_ull*)c->c_ctl.p;
+    const int canon = c->cfg.canonical ? 1 : 0;
+    const bool use_index = getenv("KMC_MAP_NO_INDEX") == nullptr;
+    UnitigTrace tr;
+    tr.mark(c->stream);
+    if (n && use_index && !c->m_idx_live) {   // once per unitig result: graph_run, which every unitig_run goes through, clears m_idx_live
+        hipLaunchKernelGGL(kmc_map_index_kernel, dim3((u32)((n + KMC_M_THREADS - 1) / KMC_M_THREADS)), dim3(KMC_M_THREADS), 0, c->stream, n,
+                           (const uint16_t*)c->g_adj.p, (const u32*)c->u_ptr[c->u_cur].p, (const u32*)c->u_dist[c->u_cur].p, (const u32*)c->u_join.p,
+                           canon, nu, (u64*)c->m_idx.p, ctl);
+        HIPCHK(c, hipGetLastError());
+        c->m_idx_live = true;
+    }
+    tr.mark(c->stream);
+    {
+        MapSrc src;
+        src.idx = (const u64*)c->m_idx.p; src.adj = (const uint16_t*)c->g_adj.p;
+        src.ptr = (const u32*)c->u_ptr[c->u_cur].p; src.dist = (const u32*)c->u_dist[c->u_cur].p; src.uid_of = (const u32*)c->u_join.p;
+        src.n_unitigs = nu;
+        const u64 want_waves = (u64)c->n_cu * 16;   // four waves on each SIMD
+        const u64 cpw = std::min<u64>(64, std::max<u64>(1, (n_chunks + want_waves - 1) / want_waves));
+        const u64 waves = (n_chunks + cpw - 1) / cpw;
+        const u64 grid = (waves + KMC_Q_WAVES - 1) / KMC_Q_WAVES;
+        if (grid > 0x7FFFFFFFull) return fail(c, KMC_ERR_ARG, "%s: batch too large for one call", what);
+        if (n_chunks) with_kw_canon(c, [&](auto KW, auto CANON) {
+            auto go = [&](auto INDEX) {
+                hipLaunchKernelGGL((kmc_map_place_kernel<KW(), CANON(), INDEX()>), dim3((u32)grid), dim3(KMC_Q_THREADS), 0, c->stream, d_bases, n_bases,
+                                   d_offsets, n_reads, k, n_chunks, cpw, v, src, (u64*)c->m_place.p, (uint16_t*)c->m_sbits.p, (uint16_t*)c->m_vbits.p, ctl);
+            };
+            if (use_index) go(std::true_type{}); else go(std::false_type{});
+        });
+        HIPCHK(c, hipGetLastError());
+    }
+    tr.mark(c->stream);
+    MapBatch b;
+    b.place = (const u64*)c->m_place.p; b.start_bits = (const uint16_t*)c->m_sbits.p; b.valid_bits = (const uint16_t*)c->m_vbits.p;
+    b.offsets = d_offsets; b.n_reads = n_reads; b.n_bases = n_bases; b.n_tiles = n_tiles; b.k = k;
+    map_segs_launch<0>(c, b, 0, nu);
+    u64 w[KMC_M_CTL_WORDS];
+    if ((rc = compact_scan_and_read(c, n_tiles, w, KMC_M_CTL_WORDS))) return rc;
+    if (w[KMC_M_BAD]) return fail(c, KMC_ERR_HIP, "internal error: %s met %llu indices outside their arrays", what, (unsigned long long)w[KMC_M_BAD]);
+    const u64 ns = w[KMC_M_HEADS];
+    if (ns >= (1ull << 32)) return fail(c, KMC_ERR_CAPACITY, "%s: 2^32 segments or more", what);
+    if ((w[0] & 0xFFFFFFFFull) != ns)
+        return fail(c, KMC_ERR_HIP, "internal error: %s scanned %llu of %llu segments", what, (unsigned long long)(w[0] & 0xFFFFFFFFull), (unsigned long long)ns);
+    if ((rc = ensure(c, c->m_segs, (size_t)std::max<u64>(ns, 1) * 4 * sizeof(u32))) || (rc = ensure(c, c->m_tail, (size_t)std::max<u64>(ns, 1) * sizeof(u32))))
+        return rc;
+    map_segs_launch<1>(c, b, ns, nu);
+    hipLaunchKernelGGL(kmc_map_reads_kernel, dim3((u32)grid_for(c, n_reads, KMC_M_THREADS)), dim3(KMC_M_THREADS), 0, c->stream,
+                       (const u32*)c->m_stats.p, d_offsets, n_reads, ctl);
+    if (ns) map_segs_launch<2>(c, b, ns, nu);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(w, ctl, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    tr.mark(c->stream);
+    if (w[KMC_M_BAD]) return fail(c, KMC_ERR_HIP, "internal error: %s met %llu indices outside their arrays", what, (unsigned long long)w[KMC_M_BAD]);
+    if (w[KMC_M_LONG]) return fail(c, KMC_ERR_ARG, "%s: %llu reads of 2^32 bases or more", what, (unsigned long long)w[KMC_M_LONG]);
+    h[0] = n_reads; h[1] = w[KMC_M_VALID]; h[2] = w[KMC_M_PLACED]; h[3] = ns; h[4] = w[KMC_M_CROSS];
+    h[5] = w[KMC_M_FULL]; h[6] = w[KMC_M_EMPTY]; h[7] = w[KMC_M_MOST];
+    *n_segs = ns;
+    if (tr.on && tr.n_ev == 4) {
+        float ms[3] = {0, 0, 0};
+        bool ok = hipEventSynchronize(tr.ev[3]) == hipSuccess;
+        for (int i = 0; ok && i < 3; ++i) ok = hipEventElapsedTime(&ms[i], tr.ev[i], tr.ev[i + 1]) == hipSuccess;
+        if (ok)
+            fprintf(stderr, "kmc_unitig_map: keys %llu unitigs %llu reads %llu windows %llu placed %llu segments %llu unitigs_reused %d "
+                    "index_ms %.4f place_ms %.4f segs_ms %.4f\n", (unsigned long long)n, (unsigned long long)nu, (unsigned long long)n_reads,
+                    (unsigned long long)h[1], (unsigned long long)h[2], (unsigned long long)ns, kept ? 1 : 0, ms[0], ms[1], ms[2]);
+    }
+    return KMC_OK;
+}
+
+static int map_begin(kmc_ctx* c, const char* what, uint64_t min_count, uint64_t max_count) { return unitig_begin(c, what, min_count, max_count); }
+
+static int kmc_unitig_map_device_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, const void* d_bases, const void* d_offsets,
+                                      uint64_t n_reads, uint64_t n_bases, const void** d_place, const void** d_read_stats,
+                                      const void** d_seg_offsets, const void** d_segs, const void** d_support, uint64_t* n_segs,
+                                      uint64_t* n_unitigs, uint64_t* summary) {
+    if (!c) return KMC_ERR_ARG;
+    const char* what = "kmc_unitig_map_device";
+    int rc;
+    if ((rc = map_begin(c, what, min_count, max_count))) return rc;
+    if (n_reads) {
+        if (!d_bases || !d_offsets) return fail(c, KMC_ERR_ARG, "%s: null device pointer", what);
+        if (((uintptr_t)d_bases & 15) != 0) return fail(c, KMC_ERR_ARG, "%s: d_bases must be 16-byte aligned", what);
+        if (((uintptr_t)d_offsets & 7) != 0) return fail(c, KMC_ERR_ARG, "%s: d_offsets must be 8-byte aligned", what);
+    }
+    u64 h[KMC_MAP_WORDS], ns = 0, nu = 0;
+    if ((rc = map_run(c, what, min_count, max_count, (const uint8_t*)d_bases, (const u64*)d_offsets, n_reads, n_reads ? n_bases : 0, h, &ns, &nu)))
+        return rc;
+    if (d_place) *d_place = c->m_place.p;
+    if (d_read_stats) *d_read_stats = c->m_stats.p;
+    if (d_seg_offsets) *d_seg_offsets = c->m_soffs.p;
+    if (d_segs) *d_segs = c->m_segs.p;
+    if (d_support) *d_support = c->m_support.p;
+    if (n_segs) *n_segs = ns;
+    if (n_unitigs) *n_unitigs = nu;
+    if (summary) memcpy(summary, h, sizeof(h));
+    return KMC_OK;
+}
+
+static int kmc_unitig_map_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads,
+                               uint64_t* place, uint32_t* read_stats, uint64_t* seg_offsets, uint32_t* segs, uint64_t cap_segs,
+                               uint64_t* support, uint64_t cap_unitigs, uint64_t* n_segs, uint64_t* n_unitigs, uint64_t* summary) {
+    if (n_segs) *n_segs = 0;
+    if (n_unitigs) *n_unitigs = 0;
+    if (!c) return KMC_ERR_ARG;
+    const char* what = "kmc_unitig_map";
+    int rc;
+    if ((rc = map_begin(c, what, min_count, max_count))) return rc;
+    u64 n_bases = 0;
+    if (n_reads) {
+        if (!bases || !offsets) return fail(c, KMC_ERR_ARG, "%s: null buffer", what);
+        if (offsets[0] != 0) return fail(c, KMC_ERR_ARG, "%s: offsets[0] must be 0", what);
+        for (u64 i = 0; i < n_reads; ++i) {
+            if (offsets[i + 1] < offsets[i]) return fail(c, KMC_ERR_ARG, "%s: offsets must be non-decreasing (read %llu)", what, (unsigned long long)i);
+            if (offsets[i + 1] - offsets[i] >= (1ull << 32)) return fail(c, KMC_ERR_ARG, "%s: read %llu has 2^32 bases or more", what, (unsigned long long)i);
+        }
+        n_bases = offsets[n_reads];
+        if ((rc = ensure(c, c->q_bases, n_bases + 64)) || (rc = ensure(c, c->q_offs, (n_reads + 1) * sizeof(u64)))) return rc;
+        if (n_bases) HIPCHK(c, hipMemcpyAsync(c->q_bases.p, bases, n_bases, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->q_offs.p, offsets, (n_reads + 1) * sizeof(u64), hipMemcpyHostToDevice, c->stream));
+    }
+    u64 h[KMC_MAP_WORDS], ns = 0, nu = 0;
+    if ((rc = map_run(c, what, min_count, max_count, (const uint8_t*)c->q_bases.p, (const u64*)c->q_offs.p, n_reads, n_bases, h, &ns, &nu))) return rc;
+    if (n_segs) *n_segs = ns;
+    if (n_unitigs) *n_unitigs = nu;
+    if (segs && cap_segs < ns) return fail(c, KMC_ERR_ARG, "%s: capacity %llu < %llu segments", what, (unsigned long long)cap_segs, (unsigned long long)ns);
+    if (support && cap_unitigs < nu) return fail(c, KMC_ERR_ARG, "%s: capacity %llu < %llu unitigs", what, (unsigned long long)cap_unitigs, (unsigned long long)nu);
+    if (place && n_bases) HIPCHK(c, hipMemcpyAsync(place, c->m_place.p, (size_t)n_bases * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    if (read_stats && n_reads) HIPCHK(c, hipMemcpyAsync(read_stats, c->m_stats.p, (size_t)n_reads * KMC_MAP_READ_WORDS * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+    if (seg_offsets) HIPCHK(c, hipMemcpyAsync(seg_offsets, c->m_soffs.p, (size_t)(n_reads + 1) * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    if (segs && ns) HIPCHK(c, hipMemcpyAsync(segs, c->m_segs.p, (size_t)ns * 4 * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+    if (support && nu) HIPCHK(c, hipMemcpyAsync(support, c->m_support.p, (size_t)nu * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (summary) memcpy(summary, h, sizeof(h));
+    return KMC_OK;
+}
+
 // ---- the compacted graph cleaned: a verdict per unitig, the table of the kept keys (kmc_clean.hip.h) ----
 static u64 clean_limit(uint64_t keys) { return keys >= (1ull << 31) ? ~0ull : (u64)keys; }   // 2^31 or more: unlimited
 
@@ -1213,6 +1400,22 @@ extern "C" int kmc_unitig_links(kmc_ctx* c, uint64_t min_count, uint64_t max_cou
                                 uint32_t* link_to, uint64_t cap_links, uint64_t* n_unitigs, uint64_t* n_links, uint64_t* summary) {
     return guarded(c, [&]() -> int {
         return kmc_unitig_links_impl(c, min_count, max_count, link_offsets, cap_ends, link_to, cap_links, n_unitigs, n_links, summary);
+    });
+}
+extern "C" int kmc_unitig_map_device(kmc_ctx* c, uint64_t min_count, uint64_t max_count, const void* d_bases, const void* d_offsets, uint64_t n_reads,
+                                     uint64_t n_bases, const void** d_place, const void** d_read_stats, const void** d_seg_offsets,
+                                     const void** d_segs, const void** d_support, uint64_t* n_segs, uint64_t* n_unitigs, uint64_t* summary) {
+    return guarded(c, [&]() -> int {
+        return kmc_unitig_map_device_impl(c, min_count, max_count, d_bases, d_offsets, n_reads, n_bases, d_place, d_read_stats, d_seg_offsets,
+                                          d_segs, d_support, n_segs, n_unitigs, summary);
+    });
+}
+extern "C" int kmc_unitig_map(kmc_ctx* c, uint64_t min_count, uint64_t max_count, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads,
+                              uint64_t* place, uint32_t* read_stats, uint64_t* seg_offsets, uint32_t* segs, uint64_t cap_segs,
+                              uint64_t* support, uint64_t cap_unitigs, uint64_t* n_segs, uint64_t* n_unitigs, uint64_t* summary) {
+    return guarded(c, [&]() -> int {
+        return kmc_unitig_map_impl(c, min_count, max_count, bases, offsets, n_reads, place, read_stats, seg_offsets, segs, cap_segs, support,
+                                   cap_unitigs, n_segs, n_unitigs, summary);
     });
 }
 extern "C" int kmc_unitig_clean_device(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t max_tip_keys, uint64_t max_island_keys,

@@ -32,6 +32,11 @@ pub const KMC_UNITIG_WORDS: usize = 8;
 pub const KMC_UNITIG_CIRCULAR: u8 = 1;
 /// summary words of `kmc_unitig_links`
 pub const KMC_LINK_WORDS: usize = 8;
+/// summary words of `kmc_unitig_map`, words per read of its `read_stats`, the low half of the place word of a window
+/// that is not placed
+pub const KMC_MAP_WORDS: usize = 8;
+pub const KMC_MAP_READ_WORDS: usize = 4;
+pub const KMC_MAP_NONE: u32 = 0xFFFF_FFFF;
 /// summary words of `kmc_unitig_clean`
 pub const KMC_CLEAN_WORDS: usize = 8;
 /// a unitig's verdict byte
@@ -154,6 +159,8 @@ extern "C" {
     // the links between those unitigs: offsets per unitig end, target ends, summary
     pub fn kmc_unitig_links_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, d_link_offsets: *mut *const c_void, d_link_to: *mut *const c_void, n_unitigs: *mut u64, n_links: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_links(ctx: *mut KmcCtx, min_count: u64, max_count: u64, link_offsets: *mut u64, cap_ends: u64, link_to: *mut u32, cap_links: u64, n_unitigs: *mut u64, n_links: *mut u64, summary: *mut u64) -> c_int;
+    pub fn kmc_unitig_map_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, d_bases: *const c_void, d_offsets: *const c_void, n_reads: u64, n_bases: u64, d_place: *mut *const c_void, d_read_stats: *mut *const c_void, d_seg_offsets: *mut *const c_void, d_segs: *mut *const c_void, d_support: *mut *const c_void, n_segs: *mut u64, n_unitigs: *mut u64, summary: *mut u64) -> c_int;
+    pub fn kmc_unitig_map(ctx: *mut KmcCtx, min_count: u64, max_count: u64, bases: *const u8, offsets: *const u64, n_reads: u64, place: *mut u64, read_stats: *mut u32, seg_offsets: *mut u64, segs: *mut u32, cap_segs: u64, support: *mut u64, cap_unitigs: u64, n_segs: *mut u64, n_unitigs: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_clean_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, max_tip_keys: u64, max_island_keys: u64, d_key_hi: *mut *const c_void, d_key_lo: *mut *const c_void, d_count: *mut *const c_void, d_verdict: *mut *const c_void, n_kept: *mut u64, n_unitigs: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_clean(ctx: *mut KmcCtx, min_count: u64, max_count: u64, max_tip_keys: u64, max_island_keys: u64, key_hi: *mut u64, key_lo: *mut u64, count: *mut u64, cap_keys: u64, verdict: *mut u8, cap_unitigs: u64, n_kept: *mut u64, n_unitigs: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_clean_into(src: *mut KmcCtx, dst: *mut KmcCtx, min_count: u64, max_count: u64, max_tip_keys: u64, max_island_keys: u64, summary: *mut u64) -> c_int;
@@ -426,6 +433,43 @@ impl Counter {
             kmc_unitig_links(self.ctx, min_count, max_count, offsets.as_mut_ptr(), 2 * nu, to.as_mut_ptr(), nl, &mut nu, &mut nl, w.as_mut_ptr())
         })?;
         Ok((offsets, to, w))
+    }
+
+    /// A batch of reads threaded through those unitigs (`kmc_unitig_map`; the batch is not counted).  Returns the place
+    /// word of every base position (low half `2 * unitig + orientation` or `KMC_MAP_NONE`, high half the key position),
+    /// per read [valid windows, placed windows, segments, crossings], `seg_offsets[n_reads + 1]`, the segments as
+    /// [start, len, 2 * unitig + orientation, pos], the placed windows per unitig, and the eight summary words.  The host
+    /// form of the library computes on every call, so the sizing call below maps the batch once more.
+    #[allow(clippy::type_complexity)]
+    pub fn map_reads(&mut self, bases: &[u8], offsets: &[u64], min_count: u64, max_count: u64)
+                     -> Result<(Vec<u64>, Vec<[u32; KMC_MAP_READ_WORDS]>, Vec<u64>, Vec<[u32; 4]>, Vec<u64>, [u64; KMC_MAP_WORDS]), KmcError> {
+        let (mut nd, mut nt) = (0u64, 0u64);
+        self.check(unsafe { kmc_finalize(self.ctx, &mut nd, &mut nt) })?;
+        let n_reads = offsets.len().saturating_sub(1);
+        if n_reads > 0 && offsets[n_reads] as usize != bases.len() {
+            return Err(KmcError(-1, "offsets do not end at the number of bases".into()));
+        }
+        let n_bases = if n_reads > 0 { bases.len() } else { 0 };
+        let (mut ns, mut nu) = (0u64, 0u64);
+        let mut w = [0u64; KMC_MAP_WORDS];
+        let mut place = vec![0u64; n_bases];
+        let mut stats = vec![[0u32; KMC_MAP_READ_WORDS]; n_reads];
+        let mut seg_offsets = vec![0u64; n_reads + 1];
+        self.check(unsafe {
+            kmc_unitig_map(self.ctx, min_count, max_count, bases.as_ptr(), offsets.as_ptr(), n_reads as u64, place.as_mut_ptr(),
+                           stats.as_mut_ptr() as *mut u32, seg_offsets.as_mut_ptr(), std::ptr::null_mut::<u32>(), 0,
+                           std::ptr::null_mut::<u64>(), 0, &mut ns, &mut nu, w.as_mut_ptr())
+        })?;
+        let mut segs = vec![[0u32; 4]; ns as usize];
+        let mut support = vec![0u64; nu as usize];
+        if ns > 0 || nu > 0 {
+            self.check(unsafe {
+                kmc_unitig_map(self.ctx, min_count, max_count, bases.as_ptr(), offsets.as_ptr(), n_reads as u64, std::ptr::null_mut::<u64>(),
+                               std::ptr::null_mut::<u32>(), std::ptr::null_mut::<u64>(), segs.as_mut_ptr() as *mut u32, ns,
+                               support.as_mut_ptr(), nu, &mut ns, &mut nu, w.as_mut_ptr())
+            })?;
+        }
+        Ok((place, stats, seg_offsets, segs, support, w))
     }
 
     /// That graph cleaned (`kmc_unitig_clean`): the keys of the kept unitigs with their counts, in the order of `table()`,
