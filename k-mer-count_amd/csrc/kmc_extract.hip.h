@@ -10,9 +10,9 @@
 // equal" and "which is the highest bit in which two keys differ", and min ^ max and AND ^ OR answer both alike.
 //
 // Work split: a workgroup of 16 waves takes whole ranges (64 chunks of 1024 positions); wave w extracts chunks
-// 4 w .. 4 w + 3 of the range (plus one warm-up chunk for the halo, as kmc_stream_kernel does), all waves count into one
-// LDS histogram, and the row leaves with one coalesced 4 KB store.  Window extraction, validity (read starts, non-ACGT
-// bytes) and canonical strand are those of kmc_stream_kernel (same helper functions).
+// 4 w .. 4 w + 3 of the range (plus one warm-up chunk for the halo), all waves count into one LDS histogram, and the row
+// leaves with one coalesced 4 KB store.  Window extraction, validity (read starts, non-ACGT bytes) and canonical strand
+// are the chunk front end's (kmc_chunks.hip.h).
 //
 // Stores: a lane owns 16 consecutive positions.  One-word keys leave through the 16-key LDS transpose of
 // kmc_stream.hip.h (512 contiguous bytes per store instruction).  Two-word keys go half a lane's keys at a time (8 low
@@ -73,10 +73,7 @@ void kmc_extract_hist_kernel(const uint8_t* __restrict__ bases, u64 n_bases, con
     ExtractLds<KW>& L = *reinterpret_cast<ExtractLds<KW>*>(extract_smem);
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int kb = 2 * k;
-    const u64 mask_lo = kb >= 64 ? ~0ull : ((1ull << kb) - 1);
-    const u64 mask_hi = kb <= 64 ? 0ull : ((1ull << (kb - 64)) - 1);
-    const int P = 32 * NW - 30 - kb;   // rc pre-shift
-    const int Pq = P >> 5, Pr = P & 31;
+    const ChunkKeys<KW> K(k);
     // level-0 digit of the sort: bits [kb - w, kb) with w = min(kb, 10)
     const int dshift = kb > KMC_MSD_BITS ? kb - KMC_MSD_BITS : 0;
     const u32 dmask = kb >= KMC_MSD_BITS ? (u32)KMC_MSD_ND - 1u : (1u << kb) - 1u;
@@ -89,126 +86,22 @@ void kmc_extract_hist_kernel(const uint8_t* __restrict__ bases, u64 n_bases, con
         u64 a_lo = ~0ull, a_hi = ~0ull, o_lo = 0, o_hi = 0;   // AND / OR of this lane's valid keys
         const u64 c0 = chunk_begin + (u64)r * (KMC_MSD_RANGE / KMC_CHUNK) + 4u * (u64)wv, c1 = c0 + 4;
         const u64 cfirst = c0 > 0 ? c0 - 1 : 0;  // warm-up chunk supplies the halo of chunk c0
-        // first read start >= first position (binary search, wave-uniform)
-        u64 rbase;
-        {
-            const u64 target = cfirst * KMC_CHUNK;
-            u64 lo_i = 0, hi_i = n_reads + 1;  // offsets has n_reads + 1 entries
-            while (lo_i < hi_i) {
-                const u64 mid = (lo_i + hi_i) >> 1;
-                if (offsets[mid] < target) lo_i = mid + 1; else hi_i = mid;
-            }
-            rbase = lo_i;
-        }
-        u64 held = (rbase + lane <= n_reads) ? offsets[rbase + lane] : ~0ull;
-        u32 consumed = 0;
-        u32 pw = 0, pzb = 0;  // previous chunk's big-endian word and (z | b << 16)
+        ChunkWalk W(offsets, n_reads, cfirst, lane);
         for (u64 c = cfirst; c < c1; ++c) {
-            const u64 cb = c * KMC_CHUNK;
-            const u64 pp = cb + 16u * lane;  // this lane's piece
-            const bool live = c < chunk_end;  // (wave-uniform) padding chunks of the last range: filler only
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (live && pp < n_bases) v = *reinterpret_cast<const uint4*>(bases + pp);
-            Enc16 e = encode16(v);
-            u32 bad = 0;
-            if (__builtin_amdgcn_ballot_w64((e.x0 | e.x1 | e.x2 | e.x3) != 0) != 0) bad = bad16_from(e);
-            if (!live) bad = 0xFFFFu;
-            else if (pp + 16 > n_bases) {  // bytes past the end of the batch never form windows
-                const u32 nvalid = pp < n_bases ? (u32)(n_bases - pp) : 0;
-                bad |= (0xFFFFu << nvalid) & 0xFFFFu;
-            }
-            const u32 wbe = le_to_be(e.wle);
-            // read starts of this chunk -> per-lane 16-bit mask, through the wave's LDS bitmap
-            L.sbits[wv][lane] = 0;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            const u64 cend = cb + KMC_CHUNK;
-            for (;;) {
-                const bool in = (lane >= consumed) && (held < cend);
-                if (in) {
-                    const u32 rel = (u32)(held - cb);
-                    atomicOr(&L.sbits[wv][rel >> 4], 1u << (rel & 15));
-                }
-                consumed += (u32)__popcll(__builtin_amdgcn_ballot_w64(in));
-                if (consumed < 64) break;
-                rbase += 64;
-                consumed = 0;
-                held = (rbase + lane <= n_reads) ? offsets[rbase + lane] : ~0ull;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            const u32 st = __hip_atomic_load(&L.sbits[wv][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            __builtin_amdgcn_wave_barrier();
-            const u32 zb = ((st | bad) & 0xFFFFu) | (bad << 16);
+            // (wave-uniform) padding chunks of the last range, at or past chunk_end: filler only
+            W.step(bases, n_bases, c, c < chunk_end, L.sbits[wv]);
             if (c >= c0) {
-                // window words X[d] = word of lane - d (previous chunk for lane < d)
-                u32 X[NW], ZB[NW];
-                X[0] = wbe; ZB[0] = zb;
-#pragma unroll
-                for (int d = 1; d < NW; ++d) {
-                    const int src = (lane - d) & 63;
-                    const u32 a = __shfl(wbe, src), b = __shfl(pw, src);
-                    const u32 za = __shfl(zb, src), zbb = __shfl(pzb, src);
-                    X[d] = lane >= d ? a : b;
-                    ZB[d] = lane >= d ? za : zbb;
-                }
-                // validity: a window is invalid if a break (bad byte or read start) lies in its last k - 1 positions,
-                // or a bad byte in its first position
-                u32 inv16;
-                {
-                    u64 zl = 0, zh = 0, bl = 0, bh = 0;
-#pragma unroll
-                    for (int d = 0; d < NW; ++d) {
-                        const int pos = 16 * (NW - 1 - d);
-                        const u64 z = ZB[d] & 0xFFFFu, b = ZB[d] >> 16;
-                        if (pos < 64) { zl |= z << pos; bl |= b << pos; } else { zh |= z << (pos - 64); bh |= b << (pos - 64); }
-                    }
-                    const WMask<KW> Z = WMask<KW>::make(zl, zh), B = WMask<KW>::make(bl, bh);
-                    const WMask<KW> inv = smear<KW>(Z, k - 1) | B.shl(k - 1);
-                    inv16 = inv.bits16_at(16 * (NW - 1));
-                }
-                if (pp < range_begin) {  // windows ending before range_begin belong to an earlier launch
-                    const u64 nskip = range_begin - pp;
+                u32 X[NW], Yp[NW + 1];
+                u32 inv16 = chunk_windows<KW>(W, k, X);
+                if (W.pp < range_begin) {  // windows ending before range_begin belong to an earlier launch
+                    const u64 nskip = range_begin - W.pp;
                     inv16 |= nskip >= 16 ? 0xFFFFu : ((1u << (u32)nskip) - 1u);
                 }
-                // rc stream words from the LSB end
-                u32 Yp[NW + 1];
-                if (CANON) {
-                    u32 Yw[2 * NW + 1];
-#pragma unroll
-                    for (int m = 0; m < NW; ++m) Yw[m] = rc_word_be(X[NW - 1 - m]);
-#pragma unroll
-                    for (int m = NW; m < 2 * NW + 1; ++m) Yw[m] = 0;
-#pragma unroll
-                    for (int m = 0; m < NW; ++m) {
-                        u32 rr = 0;
-#pragma unroll
-                        for (int q = 0; q < NW; ++q)
-                            if (q == Pq) rr = alignbit(Yw[m + q + 1], Yw[m + q], Pr);
-                        Yp[m] = rr;
-                    }
-                    Yp[NW] = 0;
-                }
+                chunk_rc_stream<KW, CANON>(K, X, Yp);
                 // the wave's 1024 keys of this chunk start at the position of lane 0's first key
-                const u64 obase = cb - chunk_begin * KMC_CHUNK;
+                const u64 obase = W.cb - chunk_begin * KMC_CHUNK;
                 auto key_at = [&](int j, u64& khi, u64& klo) -> bool {
-                    const int s = 30 - 2 * j;
-                    u32 f[2 * KW];
-#pragma unroll
-                    for (int m = 0; m < 2 * KW; ++m) f[m] = alignbit(X[m + 1], X[m], s);
-                    const u64 flo = ((u64)f[1] << 32 | f[0]) & mask_lo;
-                    u64 fhi = 0;
-                    if constexpr (KW == 2) fhi = ((u64)f[3] << 32 | f[2]) & mask_hi;
-                    klo = flo; khi = fhi;
-                    if (CANON) {
-                        u32 rw[2 * KW];
-#pragma unroll
-                        for (int m = 0; m < 2 * KW; ++m) rw[m] = alignbit(Yp[m + 1], Yp[m], 2 * j);
-                        const u64 rlo = ((u64)rw[1] << 32 | rw[0]) & mask_lo;
-                        u64 rhi = 0;
-                        if constexpr (KW == 2) rhi = ((u64)rw[3] << 32 | rw[2]) & mask_hi;
-                        if (key_less(rhi, rlo, fhi, flo)) { klo = rlo; khi = rhi; }
-                    }
+                    chunk_key<KW, CANON>(K, X, Yp, j, khi, klo);
                     const bool ok = !((inv16 >> j) & 1);
                     // level-0 bookkeeping of the sort while the key is in registers
                     const u32 d = ok ? (msd_bits<KW>(khi, klo, dshift) & dmask) : (u32)KMC_MSD_ND;
@@ -237,8 +130,6 @@ void kmc_extract_hist_kernel(const uint8_t* __restrict__ bases, u64 n_bases, con
                     }
                 }
             }
-            pw = wbe;
-            pzb = zb;
         }
         // the range's AND / OR words
 #pragma unroll

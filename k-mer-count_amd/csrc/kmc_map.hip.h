@@ -6,8 +6,8 @@
 //   row index   one 8-byte word per view row (kmc_map_index_kernel): low half 2 * unitig + (read on its other strand),
 //               high half the key position; a row that is not solid holds KMC_M_NONE in the low half.  A batch has far more
 //               windows than the view has rows, so a placement is q_find plus ONE gather instead of adj, ptr / dist, uid_of.
-//   place       kmc_profile_kernel's walk over the batch (chunks of 1024 positions behind a warm-up chunk, 16 positions per
-//               lane, the same extraction, validity and canonical helpers) with q_find in the place of the count lookup.
+//   place       kmc_profile_kernel's walk over the batch (the chunk front end of kmc_chunks.hip.h: chunks of 1024 positions
+//               behind a warm-up chunk, 16 positions per lane) with q_find in the place of the count lookup.
 //               The place word goes to the window's START through two LDS transposes (one store instruction = 512
 //               contiguous bytes).  The kernel also leaves two bits per position for the passes behind it: "a read starts
 //               here" and "the window that ENDS here is valid".
@@ -82,7 +82,7 @@ struct MapSrc {
 };
 
 // place[p] for every p < n_bases, start_bits / valid_bits: one u16 per 16 positions, n_chunks * 64 of each (bit j of word
-// p / 16: a read starts at p + j / the window ending at p + j is valid).  The structure is kmc_profile_kernel's; see there.
+// p / 16: a read starts at p + j / the window ending at p + j is valid).  The walk over the batch is the chunk front end's (kmc_chunks.hip.h).
 template <int KW, bool CANON, bool INDEX>
 __global__ __launch_bounds__(KMC_Q_THREADS)
 void kmc_map_place_kernel(const uint8_t* __restrict__ bases, u64 n_bases, const u64* __restrict__ offsets, u64 n_reads, int k,
@@ -96,108 +96,19 @@ void kmc_map_place_kernel(const uint8_t* __restrict__ bases, u64 n_bases, const 
     u64 c1 = c0 + chunks_per_wave;
     if (c1 > n_chunks) c1 = n_chunks;
     if (c0 >= c1) return;
-    const int kb = 2 * k;
-    const u64 mask_lo = kb >= 64 ? ~0ull : ((1ull << kb) - 1);
-    const u64 mask_hi = kb <= 64 ? 0ull : ((1ull << (kb - 64)) - 1);
-    const int P = 32 * NW - 30 - kb;   // rc pre-shift
-    const int Pq = P >> 5, Pr = P & 31;
+    const ChunkKeys<KW> K(k);
     u32 n_bad = 0;
 
     const u64 cfirst = c0 > 0 ? c0 - 1 : 0;  // warm-up chunk supplies the halo of chunk c0
-    u64 rbase;
-    {
-        const u64 target = cfirst * KMC_CHUNK;
-        u64 lo_i = 0, hi_i = n_reads + 1;  // offsets has n_reads + 1 entries
-        while (lo_i < hi_i) {
-            const u64 mid = (lo_i + hi_i) >> 1;
-            if (offsets[mid] < target) lo_i = mid + 1; else hi_i = mid;
-        }
-        rbase = lo_i;
-    }
-    u64 held = (rbase + lane <= n_reads) ? offsets[rbase + lane] : ~0ull;
-    u32 consumed = 0;
-    u32 pw = 0, pzb = 0;  // previous chunk's big-endian word and (z | b << 16)
+    ChunkWalk W(offsets, n_reads, cfirst, lane);
     for (u64 c = cfirst; c < c1; ++c) {
-        const u64 cb = c * KMC_CHUNK;
-        const u64 pp = cb + 16u * lane;  // this lane's piece
-        uint4 w4 = make_uint4(0, 0, 0, 0);
-        if (pp < n_bases) w4 = *reinterpret_cast<const uint4*>(bases + pp);
-        Enc16 e = encode16(w4);
-        u32 bad = 0;
-        if (__builtin_amdgcn_ballot_w64((e.x0 | e.x1 | e.x2 | e.x3) != 0) != 0) bad = bad16_from(e);
-        if (pp + 16 > n_bases) {  // bytes past the end of the batch never form windows
-            const u32 nvalid = pp < n_bases ? (u32)(n_bases - pp) : 0;
-            bad |= (0xFFFFu << nvalid) & 0xFFFFu;
-        }
-        const u32 wbe = le_to_be(e.wle);
-        // read starts of this chunk -> per-lane 16-bit mask, through the wave's LDS bitmap
-        L.sbits[wv][lane] = 0;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        const u64 cend = cb + KMC_CHUNK;
-        for (;;) {
-            const bool in = (lane >= (int)consumed) && (held < cend);
-            if (in) {
-                const u32 rel = (u32)(held - cb);
-                atomicOr(&L.sbits[wv][rel >> 4], 1u << (rel & 15));
-            }
-            consumed += (u32)__popcll(__builtin_amdgcn_ballot_w64(in));
-            if (consumed < 64) break;
-            rbase += 64;
-            consumed = 0;
-            held = (rbase + lane <= n_reads) ? offsets[rbase + lane] : ~0ull;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        const u32 st = __hip_atomic_load(&L.sbits[wv][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __builtin_amdgcn_wave_barrier();
-        const u32 zb = ((st | bad) & 0xFFFFu) | (bad << 16);
+        W.step(bases, n_bases, c, true, L.sbits[wv]);
         if (c >= c0) {
-            u32 X[NW], ZB[NW];
-            X[0] = wbe; ZB[0] = zb;
-#pragma unroll
-            for (int d = 1; d < NW; ++d) {
-                const int s = (lane - d) & 63;
-                const u32 a = __shfl(wbe, s), b = __shfl(pw, s);
-                const u32 za = __shfl(zb, s), zbb = __shfl(pzb, s);
-                X[d] = lane >= d ? a : b;
-                ZB[d] = lane >= d ? za : zbb;
-            }
-            // validity: a window is invalid if a break (bad byte or read start) lies in its last k - 1 positions,
-            // or a bad byte in its first position
-            u32 inv16;
-            {
-                u64 zl = 0, zh = 0, bl = 0, bh = 0;
-#pragma unroll
-                for (int d = 0; d < NW; ++d) {
-                    const int pos = 16 * (NW - 1 - d);
-                    const u64 z = ZB[d] & 0xFFFFu, b = ZB[d] >> 16;
-                    if (pos < 64) { zl |= z << pos; bl |= b << pos; } else { zh |= z << (pos - 64); bh |= b << (pos - 64); }
-                }
-                const WMask<KW> Z = WMask<KW>::make(zl, zh), B = WMask<KW>::make(bl, bh);
-                const WMask<KW> inv = smear<KW>(Z, k - 1) | B.shl(k - 1);
-                inv16 = inv.bits16_at(16 * (NW - 1));
-            }
-            start_bits[c * 64 + lane] = (uint16_t)(st & 0xFFFFu);     // (c < n_chunks: inside both arrays)
+            u32 X[NW], Yp[NW + 1];
+            const u32 inv16 = chunk_windows<KW>(W, k, X);
+            start_bits[c * 64 + lane] = (uint16_t)(W.st & 0xFFFFu);     // (c < n_chunks: inside both arrays)
             valid_bits[c * 64 + lane] = (uint16_t)(~inv16 & 0xFFFFu);
-            // rc stream words from the LSB end
-            u32 Yp[NW + 1];
-            if (CANON) {
-                u32 Yw[2 * NW + 1];
-#pragma unroll
-                for (int m = 0; m < NW; ++m) Yw[m] = rc_word_be(X[NW - 1 - m]);
-#pragma unroll
-                for (int m = NW; m < 2 * NW + 1; ++m) Yw[m] = 0;
-#pragma unroll
-                for (int m = 0; m < NW; ++m) {
-                    u32 rr = 0;
-#pragma unroll
-                    for (int q = 0; q < NW; ++q)
-                        if (q == Pq) rr = alignbit(Yw[m + q + 1], Yw[m + q], Pr);
-                    Yp[m] = rr;
-                }
-                Yp[NW] = 0;
-            }
+            chunk_rc_stream<KW, CANON>(K, X, Yp);
             u32 uni16[16], pos16[16];
 #pragma unroll
             for (int h = 0; h < 16 / KMC_Q_U; ++h) {
@@ -206,24 +117,9 @@ void kmc_map_place_kernel(const uint8_t* __restrict__ bases, u64 n_bases, const 
                 u32 flip = 0, pal = 0;   // bit u: canon took the other strand / the window is its own reverse complement
 #pragma unroll
                 for (int u = 0; u < KMC_Q_U; ++u) {
-                    const int j = KMC_Q_U * h + u;
-                    const int s = 30 - 2 * j;
-                    u32 f[2 * KW];
-#pragma unroll
-                    for (int m = 0; m < 2 * KW; ++m) f[m] = alignbit(X[m + 1], X[m], s);
-                    u64 qlo = ((u64)f[1] << 32 | f[0]) & mask_lo, qhi = 0;
-                    if constexpr (KW == 2) qhi = ((u64)f[3] << 32 | f[2]) & mask_hi;
-                    if (CANON) {
-                        u32 rw[2 * KW];
-#pragma unroll
-                        for (int m = 0; m < 2 * KW; ++m) rw[m] = alignbit(Yp[m + 1], Yp[m], 2 * j);
-                        const u64 rlo = ((u64)rw[1] << 32 | rw[0]) & mask_lo;
-                        u64 rhi = 0;
-                        if constexpr (KW == 2) rhi = ((u64)rw[3] << 32 | rw[2]) & mask_hi;
-                        if (key_equal(rhi, rlo, qhi, qlo)) pal |= 1u << u;
-                        if (key_less(rhi, rlo, qhi, qlo)) { qlo = rlo; qhi = rhi; flip |= 1u << u; }
-                    }
-                    klo[u] = qlo; khi[u] = qhi;
+                    const ChunkStrand s = chunk_key<KW, CANON>(K, X, Yp, KMC_Q_U * h + u, khi[u], klo[u]);
+                    if (s.pal) pal |= 1u << u;
+                    if (s.flip) flip |= 1u << u;
                 }
                 q_find<KW, KMC_Q_U>(v, khi, klo, (~inv16 >> (KMC_Q_U * h)) & ((1u << KMC_Q_U) - 1u), row);
                 u64 w[KMC_Q_U];
@@ -282,7 +178,7 @@ void kmc_map_place_kernel(const uint8_t* __restrict__ bases, u64 n_bases, const 
                 for (int i = 0; i < 16; ++i) {
                     const int r = 4 * i + (lane >> 4), col = lane & 15;
                     const u32 xl = trl[r * 16 + ((col + r) & 15)], xh = trh[r * 16 + ((col + r) & 15)];
-                    const u64 endp = cb + 64u * i + lane;   // the window ends here and starts k - 1 earlier
+                    const u64 endp = W.cb + 64u * i + lane;   // the window ends here and starts k - 1 earlier
                     if (endp + 1 >= (u64)k && endp + 1 - (u64)k < n_bases) place[endp + 1 - (u64)k] = m_word(xl, xh);
                 }
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -290,8 +186,6 @@ void kmc_map_place_kernel(const uint8_t* __restrict__ bases, u64 n_bases, const 
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             }
         }
-        pw = wbe;
-        pzb = zb;
     }
     const u64 sb = wave_sum_u64((u64)n_bad);
     if (lane == 0 && sb) atomicAdd(&ctl[KMC_M_BAD], (kmc_ull)sb);

@@ -249,8 +249,8 @@ struct ProfLds {
 };
 
 // Chunks of 1024 positions, a wave walks chunks_per_wave of them in order behind one warm-up chunk for the halo; per chunk a
-// lane owns 16 positions.  Window extraction, validity (read starts, non-ACGT bytes) and canonical strand are those of
-// kmc_stream_kernel / kmc_extract_hist_kernel (the helpers of kmc_device.hip.h and kmc_stream.hip.h): they give the key of the
+// lane owns 16 positions.  Window extraction, validity (read starts, non-ACGT bytes) and canonical strand are the chunk
+// front end's (kmc_chunks.hip.h, which describes the layout, the halo and the validity rule): it gives the key of the
 // window ENDING at a position.  Its count is stored at the window's START, k - 1 positions earlier, through an LDS transpose
 // (one store instruction = 256 contiguous bytes); invalid windows store 0, and n_chunks covers k - 1 positions past the
 // batch's end, whose windows are all invalid: that is what zero-fills the last k - 1 slots of every read and of the batch.
@@ -271,131 +271,21 @@ void kmc_profile_kernel(const uint8_t* __restrict__ bases, u64 n_bases, const u6
     u64 c1 = c0 + chunks_per_wave;
     if (c1 > n_chunks) c1 = n_chunks;
     if (c0 >= c1) return;
-    const int kb = 2 * k;
-    const u64 mask_lo = kb >= 64 ? ~0ull : ((1ull << kb) - 1);
-    const u64 mask_hi = kb <= 64 ? 0ull : ((1ull << (kb - 64)) - 1);
-    const int P = 32 * NW - 30 - kb;   // rc pre-shift
-    const int Pq = P >> 5, Pr = P & 31;
-
+    const ChunkKeys<KW> K(k);
     const u64 cfirst = c0 > 0 ? c0 - 1 : 0;  // warm-up chunk supplies the halo of chunk c0
-    u64 rbase;
-    {
-        const u64 target = cfirst * KMC_CHUNK;
-        u64 lo_i = 0, hi_i = n_reads + 1;  // offsets has n_reads + 1 entries
-        while (lo_i < hi_i) {
-            const u64 mid = (lo_i + hi_i) >> 1;
-            if (offsets[mid] < target) lo_i = mid + 1; else hi_i = mid;
-        }
-        rbase = lo_i;
-    }
-    u64 held = (rbase + lane <= n_reads) ? offsets[rbase + lane] : ~0ull;
-    u32 consumed = 0;
-    u32 pw = 0, pzb = 0;  // previous chunk's big-endian word and (z | b << 16)
+    ChunkWalk W(offsets, n_reads, cfirst, lane);
     for (u64 c = cfirst; c < c1; ++c) {
-        const u64 cb = c * KMC_CHUNK;
-        const u64 pp = cb + 16u * lane;  // this lane's piece
-        uint4 w4 = make_uint4(0, 0, 0, 0);
-        if (pp < n_bases) w4 = *reinterpret_cast<const uint4*>(bases + pp);
-        Enc16 e = encode16(w4);
-        u32 bad = 0;
-        if (__builtin_amdgcn_ballot_w64((e.x0 | e.x1 | e.x2 | e.x3) != 0) != 0) bad = bad16_from(e);
-        if (pp + 16 > n_bases) {  // bytes past the end of the batch never form windows
-            const u32 nvalid = pp < n_bases ? (u32)(n_bases - pp) : 0;
-            bad |= (0xFFFFu << nvalid) & 0xFFFFu;
-        }
-        const u32 wbe = le_to_be(e.wle);
-        // read starts of this chunk -> per-lane 16-bit mask, through the wave's LDS bitmap
-        const u64 r_first = rbase + consumed;   // index of the first offset >= cb
-        L.sbits[wv][lane] = 0;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        const u64 cend = cb + KMC_CHUNK;
-        for (;;) {
-            const bool in = (lane >= (int)consumed) && (held < cend);
-            if (in) {
-                const u32 rel = (u32)(held - cb);
-                atomicOr(&L.sbits[wv][rel >> 4], 1u << (rel & 15));
-            }
-            consumed += (u32)__popcll(__builtin_amdgcn_ballot_w64(in));
-            if (consumed < 64) break;
-            rbase += 64;
-            consumed = 0;
-            held = (rbase + lane <= n_reads) ? offsets[rbase + lane] : ~0ull;
-        }
-        const u64 r_end = rbase + consumed;     // index of the first offset >= cend
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        const u32 st = __hip_atomic_load(&L.sbits[wv][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __builtin_amdgcn_wave_barrier();
-        const u32 zb = ((st | bad) & 0xFFFFu) | (bad << 16);
+        W.step(bases, n_bases, c, true, L.sbits[wv]);
         if (c >= c0) {
-            u32 X[NW], ZB[NW];
-            X[0] = wbe; ZB[0] = zb;
-#pragma unroll
-            for (int d = 1; d < NW; ++d) {
-                const int src = (lane - d) & 63;
-                const u32 a = __shfl(wbe, src), b = __shfl(pw, src);
-                const u32 za = __shfl(zb, src), zbb = __shfl(pzb, src);
-                X[d] = lane >= d ? a : b;
-                ZB[d] = lane >= d ? za : zbb;
-            }
-            // validity: a window is invalid if a break (bad byte or read start) lies in its last k - 1 positions,
-            // or a bad byte in its first position
-            u32 inv16;
-            {
-                u64 zl = 0, zh = 0, bl = 0, bh = 0;
-#pragma unroll
-                for (int d = 0; d < NW; ++d) {
-                    const int pos = 16 * (NW - 1 - d);
-                    const u64 z = ZB[d] & 0xFFFFu, b = ZB[d] >> 16;
-                    if (pos < 64) { zl |= z << pos; bl |= b << pos; } else { zh |= z << (pos - 64); bh |= b << (pos - 64); }
-                }
-                const WMask<KW> Z = WMask<KW>::make(zl, zh), B = WMask<KW>::make(bl, bh);
-                const WMask<KW> inv = smear<KW>(Z, k - 1) | B.shl(k - 1);
-                inv16 = inv.bits16_at(16 * (NW - 1));
-            }
-            // rc stream words from the LSB end
-            u32 Yp[NW + 1];
-            if (CANON) {
-                u32 Yw[2 * NW + 1];
-#pragma unroll
-                for (int m = 0; m < NW; ++m) Yw[m] = rc_word_be(X[NW - 1 - m]);
-#pragma unroll
-                for (int m = NW; m < 2 * NW + 1; ++m) Yw[m] = 0;
-#pragma unroll
-                for (int m = 0; m < NW; ++m) {
-                    u32 rr = 0;
-#pragma unroll
-                    for (int q = 0; q < NW; ++q)
-                        if (q == Pq) rr = alignbit(Yw[m + q + 1], Yw[m + q], Pr);
-                    Yp[m] = rr;
-                }
-                Yp[NW] = 0;
-            }
+            u32 X[NW], Yp[NW + 1];
+            const u32 inv16 = chunk_windows<KW>(W, k, X);
+            chunk_rc_stream<KW, CANON>(K, X, Yp);
             u64 cnt16[16];
 #pragma unroll
             for (int h = 0; h < 16 / KMC_Q_U; ++h) {
                 u64 khi[KMC_Q_U], klo[KMC_Q_U], out[KMC_Q_U];
 #pragma unroll
-                for (int u = 0; u < KMC_Q_U; ++u) {
-                    const int j = KMC_Q_U * h + u;
-                    const int s = 30 - 2 * j;
-                    u32 f[2 * KW];
-#pragma unroll
-                    for (int m = 0; m < 2 * KW; ++m) f[m] = alignbit(X[m + 1], X[m], s);
-                    u64 qlo = ((u64)f[1] << 32 | f[0]) & mask_lo, qhi = 0;
-                    if constexpr (KW == 2) qhi = ((u64)f[3] << 32 | f[2]) & mask_hi;
-                    if (CANON) {
-                        u32 rw[2 * KW];
-#pragma unroll
-                        for (int m = 0; m < 2 * KW; ++m) rw[m] = alignbit(Yp[m + 1], Yp[m], 2 * j);
-                        const u64 rlo = ((u64)rw[1] << 32 | rw[0]) & mask_lo;
-                        u64 rhi = 0;
-                        if constexpr (KW == 2) rhi = ((u64)rw[3] << 32 | rw[2]) & mask_hi;
-                        if (key_less(rhi, rlo, qhi, qlo)) { qlo = rlo; qhi = rhi; }
-                    }
-                    klo[u] = qlo; khi[u] = qhi;
-                }
+                for (int u = 0; u < KMC_Q_U; ++u) chunk_key<KW, CANON>(K, X, Yp, KMC_Q_U * h + u, khi[u], klo[u]);
                 q_lookup<KW, KMC_Q_U>(v, khi, klo, (~inv16 >> (KMC_Q_U * h)) & ((1u << KMC_Q_U) - 1u), out);
 #pragma unroll
                 for (int u = 0; u < KMC_Q_U; ++u) cnt16[KMC_Q_U * h + u] = out[u];
@@ -411,7 +301,7 @@ void kmc_profile_kernel(const uint8_t* __restrict__ bases, u64 n_bases, const u6
                 for (int i = 0; i < 16; ++i) {
                     const int row = 4 * i + (lane >> 4), col = lane & 15;
                     const u32 x = tr[row * 16 + ((col + row) & 15)];
-                    const u64 endp = cb + 64u * i + lane;   // the window ends here and starts k - 1 earlier
+                    const u64 endp = W.cb + 64u * i + lane;   // the window ends here and starts k - 1 earlier
                     if (endp + 1 >= (u64)k && endp + 1 - (u64)k < n_bases) window_count[endp + 1 - (u64)k] = x;
                 }
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -420,20 +310,20 @@ void kmc_profile_kernel(const uint8_t* __restrict__ bases, u64 n_bases, const u6
             }
             if (read_stats && __builtin_amdgcn_ballot_w64((~inv16 & 0xFFFFu) != 0) != 0) {
                 // read of this lane's first position: offsets[0 .. r_first) lie before the chunk
-                u64 a = r_first, b = r_end;
+                u64 a = W.r_first, b = W.r_end;
                 while (a < b) {
                     const u64 mid = (a + b) >> 1;
-                    if (offsets[mid] <= pp) a = mid + 1; else b = mid;
+                    if (offsets[mid] <= W.pp) a = mid + 1; else b = mid;
                 }
                 u64 rid = a - 1;   // (pp < n_bases has offsets[0] = 0 <= pp; lanes past the end hold no valid window)
                 ProfAcc acc;
                 acc.clear();
 #pragma unroll
                 for (int j = 0; j < 16; ++j) {
-                    if (j > 0 && ((st >> j) & 1)) {   // reads start here (several, if empty ones lie between)
+                    if (j > 0 && ((W.st >> j) & 1)) {   // reads start here (several, if empty ones lie between)
                         acc.flush(read_stats, rid);
                         acc.clear();
-                        while (rid + 1 < r_end && offsets[rid + 1] <= pp + j) ++rid;
+                        while (rid + 1 < W.r_end && offsets[rid + 1] <= W.pp + j) ++rid;
                     }
                     if (!((inv16 >> j) & 1)) acc.add(cnt16[j], thr);
                 }
@@ -451,7 +341,5 @@ void kmc_profile_kernel(const uint8_t* __restrict__ bases, u64 n_bases, const u6
                 if (lane == 0 || prid != rid) acc.flush(read_stats, rid);
             }
         }
-        pw = wbe;
-        pzb = zb;
     }
 }

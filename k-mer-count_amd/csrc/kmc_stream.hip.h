@@ -3,30 +3,23 @@
 // Replaces the reference's window loop + grouping, k-mer-count/src/main.rs:63-87, for
 // contiguous k.
 //
-// Data layout.  The batch is the concatenation of all reads as ASCII (1 B/base) plus
-// offsets[n_reads+1].  The stream is cut into 1024-base chunks; a wave owns a contiguous run of
-// chunks and walks them in order.  Per chunk every lane loads ONE 16-byte piece (a fully
-// coalesced 1 KiB global_load_dwordx4 per wave), packs it to one 32-bit 2-bit word in
-// registers, and obtains the words of the 2 (k<=31) or 4 (k<=63) preceding lanes with wave
-// shuffles -- the bases never pass through LDS.  The 16 windows ending in the lane's piece are
-// static funnel shifts (v_alignbit_b32) of that register window; the reverse-complement window
-// comes from the complemented little-endian words the same way, so there is no per-base
-// rolling dependency.  Read starts inside a chunk are scattered from the offsets array into a
-// per-wave 64-word LDS bitmap; windows that cross a read start or contain a non-ACGT byte are
-// masked with a shift-OR smear of those bits.
+// Data layout.  The batch is cut into 1024-base chunks; a wave owns a contiguous run of chunks and walks them in
+// order through the chunk front end of kmc_chunks.hip.h (the one description of the chunk layout, the halo and the
+// validity rule): per chunk a lane gets the register window of its 16 positions and the mask of windows that cross a
+// read start or contain a non-ACGT byte.
 //
 // Accumulation.  Each workgroup owns an LDS partial histogram of FORWARD-strand keys in buckets of two slots
 // (StreamLds below): the hot path reads a key's two home slots and adds on a hit, with no loop and no CAS;
 // first sights and keys that do not fit their home bucket go through a per-wave miss buffer and a probing
 // insert once per chunk; what fits nowhere goes to the global table with device-scope atomics; at the end
 // the LDS table is flushed with one global atomic per distinct key, the canonical strand chosen there.
-// (The extraction front end of KMC_ALGO_SORT, which shares this file's window helpers, is kmc_extract.hip.h.)
+// (The extraction kernel of KMC_ALGO_SORT, which shares this file's transposed store, is kmc_extract.hip.h.)
 #pragma once
 #include "kmc_device.hip.h"
+#include "kmc_chunks.hip.h"
 
 #define KMC_STREAM_THREADS 1024
 #define KMC_STREAM_WAVES (KMC_STREAM_THREADS / 64)
-#define KMC_CHUNK 1024
 
 // LDS partial table of one workgroup.  A slot holds a FORWARD-strand key; the canonical strand is
 // chosen once per distinct key at the flush (counting is additive, so the table is the same as with
@@ -192,41 +185,6 @@ __device__ __forceinline__ bool stream_finish1(StreamLds<1>& L, const StreamProb
     return ok && !hit;
 }
 
-// wide bit masks for the validity smear: 64 bits cover the 48-base window of KW==1,
-// 128 bits the 80-base window of KW==2
-template <int KW> struct WMask;
-template <> struct WMask<1> {
-    u64 v;
-    __device__ __forceinline__ static WMask make(u64 lo, u64) { return {lo}; }
-    __device__ __forceinline__ WMask shl(int s) const { return {s >= 64 ? 0 : v << s}; }
-    __device__ __forceinline__ WMask operator|(WMask o) const { return {v | o.v}; }
-    __device__ __forceinline__ u32 bits16_at(int pos) const { return (u32)(v >> pos) & 0xFFFFu; }
-};
-template <> struct WMask<2> {
-    u64 lo, hi;
-    __device__ __forceinline__ static WMask make(u64 l, u64 h) { return {l, h}; }
-    __device__ __forceinline__ WMask shl(int s) const {
-        if (s == 0) return *this;
-        if (s >= 128) return {0, 0};
-        if (s >= 64) return {0, lo << (s - 64)};
-        return {lo << s, (hi << s) | (lo >> (64 - s))};
-    }
-    __device__ __forceinline__ WMask operator|(WMask o) const { return {lo | o.lo, hi | o.hi}; }
-    __device__ __forceinline__ u32 bits16_at(int pos) const {  // pos == 64 here
-        return (u32)(hi >> (pos - 64)) & 0xFFFFu;
-    }
-};
-
-// OR of m << i for i in [0, t)
-template <int KW>
-__device__ __forceinline__ WMask<KW> smear(WMask<KW> m, int t) {
-    if (t <= 0) return WMask<KW>::make(0, 0);
-    int cur = 1;
-    while (cur * 2 <= t) { m = m | m.shl(cur); cur *= 2; }
-    if (cur < t) m = m | m.shl(t - cur);
-    return m;
-}
-
 // A wave holds 16 consecutive keys per lane (lane l: positions 16 l .. 16 l + 15 of its 1024-position chunk);
 // stored as they are, one store instruction touches 64 lines of 128 B with 8 B each.  Transposed through LDS
 // (rows of 32 lanes, 32 bits at a time, column index rotated by the row: two-way conflicts writing, none
@@ -284,153 +242,63 @@ void kmc_stream_kernel(const uint8_t* __restrict__ bases, u64 n_bases, const u64
 
     u64 nk = 0, nglobal = 0;
     if (c0 < c1) {
-        // uniform key masks
-        const int kb = 2 * k;
-        const u64 mask_lo = kb >= 64 ? ~0ull : ((1ull << kb) - 1);
-        const u64 mask_hi = kb <= 64 ? 0ull : ((1ull << (kb - 64)) - 1);
-
+        const ChunkKeys<KW> K(k);
         const u64 cfirst = c0 > 0 ? c0 - 1 : 0;  // warm-up chunk supplies the halo of chunk c0
-        // first read-start >= first position (binary search, wave-uniform)
-        u64 rbase;
-        {
-            const u64 target = cfirst * KMC_CHUNK;
-            u64 lo_i = 0, hi_i = n_reads + 1;  // offsets has n_reads+1 entries
-            while (lo_i < hi_i) {
-                u64 mid = (lo_i + hi_i) >> 1;
-                if (offsets[mid] < target) lo_i = mid + 1; else hi_i = mid;
-            }
-            rbase = lo_i;
-        }
-        u64 held = (rbase + lane <= n_reads) ? offsets[rbase + lane] : ~0ull;
-        u32 consumed = 0;
-
-        u32 pw = 0, pzb = 0;  // previous chunk's big-endian word and (z | b<<16)
-
+        ChunkWalk W(offsets, n_reads, cfirst, lane);
         for (u64 c = cfirst; c < c1; ++c) {
-            const u64 cb = c * KMC_CHUNK;
-            const u64 pp = cb + 16u * lane;  // this lane's piece
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (pp < n_bases) v = *reinterpret_cast<const uint4*>(bases + pp);
-            Enc16 e = encode16(v);
-            u32 bad = 0;
-            if (__builtin_amdgcn_ballot_w64((e.x0 | e.x1 | e.x2 | e.x3) != 0) != 0) bad = bad16_from(e);
-            if (pp + 16 > n_bases) {  // bytes past the end of the batch never form windows
-                u32 nvalid = pp < n_bases ? (u32)(n_bases - pp) : 0;
-                bad |= (0xFFFFu << nvalid) & 0xFFFFu;
-            }
-            const u32 wbe = le_to_be(e.wle);
-
-            // read starts of this chunk -> per-lane 16-bit mask, through the wave's LDS bitmap
-            L.sbits[wv][lane] = 0;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            const u64 cend = cb + KMC_CHUNK;
-            for (;;) {
-                bool in = (lane >= consumed) && (held < cend);
-                if (in) {
-                    u32 rel = (u32)(held - cb);
-                    atomicOr(&L.sbits[wv][rel >> 4], 1u << (rel & 15));
-                }
-                consumed += (u32)__popcll(__builtin_amdgcn_ballot_w64(in));
-                if (consumed < 64) break;
-                rbase += 64;
-                consumed = 0;
-                held = (rbase + lane <= n_reads) ? offsets[rbase + lane] : ~0ull;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            const u32 st = __hip_atomic_load(&L.sbits[wv][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            __builtin_amdgcn_wave_barrier();
-            const u32 zb = ((st | bad) & 0xFFFFu) | (bad << 16);
-
+            W.step(bases, n_bases, c, true, L.sbits[wv]);
             if (c >= c0) {
-                // window words X[d] = word of lane-d (previous chunk for lane < d)
-                u32 X[NW], ZB[NW];
-                X[0] = wbe; ZB[0] = zb;
-#pragma unroll
-                for (int d = 1; d < NW; ++d) {
-                    int src = (lane - d) & 63;
-                    u32 a = __shfl(wbe, src), b = __shfl(pw, src);
-                    u32 za = __shfl(zb, src), zbb = __shfl(pzb, src);
-                    X[d] = lane >= d ? a : b;
-                    ZB[d] = lane >= d ? za : zbb;
-                }
-                // validity: window invalid if a break (bad byte or read start) lies in its last
-                // k-1 positions, or a bad byte in its first position
-                u32 inv16;
-                {
-                    u64 zl = 0, zh = 0, bl = 0, bh = 0;
-#pragma unroll
-                    for (int d = 0; d < NW; ++d) {
-                        int pos = 16 * (NW - 1 - d);
-                        u64 z = ZB[d] & 0xFFFFu, b = ZB[d] >> 16;
-                        if (pos < 64) { zl |= z << pos; bl |= b << pos; } else { zh |= z << (pos - 64); bh |= b << (pos - 64); }
-                    }
-                    WMask<KW> Z = WMask<KW>::make(zl, zh), B = WMask<KW>::make(bl, bh);
-                    WMask<KW> inv = smear<KW>(Z, k - 1) | B.shl(k - 1);
-                    inv16 = inv.bits16_at(16 * (NW - 1));
-                }
-                if (pp < range_begin) {  // windows ending before range_begin belong to an earlier launch
-                    u64 nskip = range_begin - pp;
+                u32 X[NW];
+                u32 inv16 = chunk_windows<KW>(W, k, X);
+                if (W.pp < range_begin) {  // windows ending before range_begin belong to an earlier launch
+                    u64 nskip = range_begin - W.pp;
                     inv16 |= nskip >= 16 ? 0xFFFFu : ((1u << (u32)nskip) - 1u);
                 }
-                {  // (no per-lane skip of lanes without a valid window: the drain inside needs the whole wave)
-                    // forward keys are counted; the flush picks the strand
-                    u32 missmask = 0;  // bit j: this lane's window j missed both home slots
-                    if constexpr (KW == 1) {
-                        auto window = [&](int j) { return ((u64)alignbit(X[2], X[1], 30 - 2 * j) << 32 | alignbit(X[1], X[0], 30 - 2 * j)) & mask_lo; };
-                        u64 cur = window(0);
-                        StreamProbe1 pc = stream_issue1(L, cur);
-#pragma unroll
-                        for (int j = 0; j < 16; ++j) {
-                            u64 nxt = 0;
-                            StreamProbe1 pn = pc;
-                            if (j + 1 < 16) { nxt = window(j + 1); pn = stream_issue1(L, nxt); }
-                            missmask |= stream_finish1(L, pc, cur, !((inv16 >> j) & 1)) ? (1u << j) : 0u;
-                            cur = nxt; pc = pn;
-                        }
-                    } else {
+                // (no per-lane skip of lanes without a valid window: the drain below needs the whole wave)
+                // forward keys are counted; the flush picks the strand
+                u32 missmask = 0;  // bit j: this lane's window j missed both home slots
+                if constexpr (KW == 1) {
+                    auto window = [&](int j) { u64 hi, lo; chunk_fwd_key<KW>(K, X, j, hi, lo); return lo; };
+                    u64 cur = window(0);
+                    StreamProbe1 pc = stream_issue1(L, cur);
 #pragma unroll
                     for (int j = 0; j < 16; ++j) {
-                        const int s = 30 - 2 * j;
-                        u32 f[2 * KW];
+                        u64 nxt = 0;
+                        StreamProbe1 pn = pc;
+                        if (j + 1 < 16) { nxt = window(j + 1); pn = stream_issue1(L, nxt); }
+                        missmask |= stream_finish1(L, pc, cur, !((inv16 >> j) & 1)) ? (1u << j) : 0u;
+                        cur = nxt; pc = pn;
+                    }
+                } else {
 #pragma unroll
-                        for (int m = 0; m < 2 * KW; ++m) f[m] = alignbit(X[m + 1], X[m], s);
-                        const u64 flo = ((u64)f[1] << 32 | f[0]) & mask_lo;
-                        u64 fhi = 0;
-                        if constexpr (KW == 2) fhi = ((u64)f[3] << 32 | f[2]) & mask_hi;
+                    for (int j = 0; j < 16; ++j) {
+                        u64 fhi, flo;
+                        chunk_fwd_key<KW>(K, X, j, fhi, flo);
                         const bool ok = !((inv16 >> j) & 1);
                         missmask |= stream_probe<KW>(L, fhi, flo, ok) ? (1u << j) : 0u;
                     }
+                }
+                nk += (u32)__popc(~inv16 & 0xFFFFu);
+                // the chunk's misses (first sight of a key, keys that did not fit their home bucket):
+                // one per lane and round into the wave's miss buffer; the drain inserts them
+                u64 mb;
+                while ((mb = __builtin_amdgcn_ballot_w64(missmask != 0)) != 0) {
+                    if (missmask != 0) {
+                        const int jm = __ffs((int)missmask) - 1;
+                        missmask &= missmask - 1;
+                        u64 fhi, flo;
+                        chunk_fwd_key<KW>(K, X, jm, fhi, flo);
+                        const u32 idx = nbuf + __builtin_amdgcn_mbcnt_hi((u32)(mb >> 32), __builtin_amdgcn_mbcnt_lo((u32)mb, 0u));
+                        L.miss[wv][idx].lo = flo;
+                        if constexpr (KW == 2) L.miss[wv][idx].hi = fhi;
                     }
-                    {
-                        nk += (u32)__popc(~inv16 & 0xFFFFu);
-                        // the chunk's misses (first sight of a key, keys that did not fit their home bucket):
-                        // one per lane and round into the wave's miss buffer; the drain inserts them
-                        u64 mb;
-                        while ((mb = __builtin_amdgcn_ballot_w64(missmask != 0)) != 0) {
-                            if (missmask != 0) {
-                                const int jm = __ffs((int)missmask) - 1;
-                                missmask &= missmask - 1;
-                                const u32 sh = 30u - 2u * (u32)jm;
-                                u32 f[2 * KW];
-#pragma unroll
-                                for (int m = 0; m < 2 * KW; ++m) f[m] = alignbit(X[m + 1], X[m], sh);
-                                const u32 idx = nbuf + __builtin_amdgcn_mbcnt_hi((u32)(mb >> 32), __builtin_amdgcn_mbcnt_lo((u32)mb, 0u));
-                                L.miss[wv][idx].lo = ((u64)f[1] << 32 | f[0]) & mask_lo;
-                                if constexpr (KW == 2) L.miss[wv][idx].hi = ((u64)f[3] << 32 | f[2]) & mask_hi;
-                            }
-                            nbuf += (u32)__popcll(mb);
-                            if (nbuf > KMC_STREAM_MISSBUF - 64) {  // no room for another round
-                                nglobal += stream_drain<KW, CANON>(L, g, wv, lane, nbuf, k);
-                                nbuf = 0;
-                            }
-                        }
+                    nbuf += (u32)__popcll(mb);
+                    if (nbuf > KMC_STREAM_MISSBUF - 64) {  // no room for another round
+                        nglobal += stream_drain<KW, CANON>(L, g, wv, lane, nbuf, k);
+                        nbuf = 0;
                     }
                 }
             }
-            pw = wbe;
-            pzb = zb;
         }
         if (nbuf) { nglobal += stream_drain<KW, CANON>(L, g, wv, lane, nbuf, k); nbuf = 0; }
     }

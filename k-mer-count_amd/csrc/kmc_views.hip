@@ -344,6 +344,45 @@ static int kmc_query_impl(kmc_ctx* c, const uint64_t* key_hi, const uint64_t* ke
     return KMC_OK;
 }
 
+// ---- a batch of reads for the kernels that walk it in chunks (kmc_chunks.hip.h): kmc_profile*, kmc_unitig_map* ----
+// The launch that walks a batch whose results go to window STARTS: windows END up to k - 1 positions past the batch, and
+// those (invalid) windows zero the last k - 1 slots.  A wave takes cpw chunks; grid workgroups of KMC_Q_THREADS.
+struct ChunkGrid { u64 n_chunks, cpw, grid; };
+static int chunk_grid(kmc_ctx* c, const char* what, u64 n_bases, int k, ChunkGrid* g) {
+    g->n_chunks = (n_bases + (u64)k - 1 + KMC_CHUNK - 1) / KMC_CHUNK;
+    const u64 want_waves = (u64)c->n_cu * 16;   // four waves on each SIMD
+    g->cpw = std::min<u64>(64, std::max<u64>(1, (g->n_chunks + want_waves - 1) / want_waves));
+    const u64 waves = (g->n_chunks + g->cpw - 1) / g->cpw;
+    g->grid = (waves + KMC_Q_WAVES - 1) / KMC_Q_WAVES;
+    if (g->grid > 0x7FFFFFFFull) return fail(c, KMC_ERR_ARG, "%s: batch too large for one call", what);
+    return KMC_OK;
+}
+
+// a caller's device batch: d_bases is read 16 bytes at a time, d_offsets 8
+static int check_device_batch(kmc_ctx* c, const char* what, const void* d_bases, const void* d_offsets) {
+    if (!d_bases || !d_offsets) return fail(c, KMC_ERR_ARG, "%s: null device pointer", what);
+    if (((uintptr_t)d_bases & 15) != 0) return fail(c, KMC_ERR_ARG, "%s: d_bases must be 16-byte aligned", what);
+    if (((uintptr_t)d_offsets & 7) != 0) return fail(c, KMC_ERR_ARG, "%s: d_offsets must be 8-byte aligned", what);
+    return KMC_OK;
+}
+
+// a host batch (n_reads > 0) checked and on its way into q_bases / q_offs; u32_reads: no read may have 2^32 bases or more
+static int stage_batch(kmc_ctx* c, const char* what, const uint8_t* bases, const uint64_t* offsets, u64 n_reads, bool u32_reads, u64* n_bases) {
+    if (!bases || !offsets) return fail(c, KMC_ERR_ARG, "%s: null buffer", what);
+    if (offsets[0] != 0) return fail(c, KMC_ERR_ARG, "%s: offsets[0] must be 0", what);
+    for (u64 i = 0; i < n_reads; ++i) {
+        if (offsets[i + 1] < offsets[i]) return fail(c, KMC_ERR_ARG, "%s: offsets must be non-decreasing (read %llu)", what, (unsigned long long)i);
+        if (u32_reads && offsets[i + 1] - offsets[i] >= (1ull << 32)) return fail(c, KMC_ERR_ARG, "%s: read %llu has 2^32 bases or more", what, (unsigned long long)i);
+    }
+    *n_bases = offsets[n_reads];
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    int rc;
+    if ((rc = ensure(c, c->q_bases, *n_bases + 64)) || (rc = ensure(c, c->q_offs, (n_reads + 1) * sizeof(u64)))) return rc;
+    if (*n_bases) HIPCHK(c, hipMemcpyAsync(c->q_bases.p, bases, *n_bases, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->q_offs.p, offsets, (n_reads + 1) * sizeof(u64), hipMemcpyHostToDevice, c->stream));
+    return KMC_OK;
+}
+
 // the profile launches (device arrays; either output may be null)
 static int profile_launch(kmc_ctx* c, const uint8_t* d_bases, const u64* d_offsets, u64 n_reads, u64 n_bases, u64 min_count,
                           u32* d_win, u64* d_stats) {
@@ -353,18 +392,13 @@ static int profile_launch(kmc_ctx* c, const uint8_t* d_bases, const u64* d_offse
     const u64 n_words = n_reads * KMC_PROFILE_WORDS;
     const u32 sgrid = (u32)((n_words + KMC_PROF_INIT_THREADS - 1) / KMC_PROF_INIT_THREADS);
     if (d_stats) hipLaunchKernelGGL(kmc_profile_init_kernel, dim3(sgrid), dim3(KMC_PROF_INIT_THREADS), 0, c->stream, (kmc_ull*)d_stats, n_reads);
-    // windows END up to k - 1 positions past the batch: those (invalid) windows zero the last k - 1 slots
-    const u64 n_chunks = (n_bases + (u64)k - 1 + KMC_CHUNK - 1) / KMC_CHUNK;
-    if (n_chunks && (d_win || d_stats)) {
-        const u64 want_waves = (u64)c->n_cu * 16;   // four waves on each SIMD
-        const u64 cpw = std::min<u64>(64, std::max<u64>(1, (n_chunks + want_waves - 1) / want_waves));
-        const u64 waves = (n_chunks + cpw - 1) / cpw;
-        const u64 grid = (waves + KMC_Q_WAVES - 1) / KMC_Q_WAVES;
-        if (grid > 0x7FFFFFFFull) return fail(c, KMC_ERR_ARG, "kmc_profile: batch too large for one call");
+    ChunkGrid g;
+    if (int rc = chunk_grid(c, "kmc_profile", n_bases, k, &g)) return rc;
+    if (g.n_chunks && (d_win || d_stats)) {
         const u64 thr = std::max<u64>(min_count, 1);
         with_kw_canon(c, [&](auto KW, auto CANON) {
-            hipLaunchKernelGGL((kmc_profile_kernel<KW(), CANON()>), dim3((u32)grid), dim3(KMC_Q_THREADS), 0, c->stream, d_bases, n_bases,
-                               d_offsets, n_reads, k, n_chunks, cpw, v, thr, d_win, (kmc_ull*)d_stats);
+            hipLaunchKernelGGL((kmc_profile_kernel<KW(), CANON()>), dim3((u32)g.grid), dim3(KMC_Q_THREADS), 0, c->stream, d_bases, n_bases,
+                               d_offsets, n_reads, k, g.n_chunks, g.cpw, v, thr, d_win, (kmc_ull*)d_stats);
         });
     }
     if (d_stats) hipLaunchKernelGGL(kmc_profile_fix_kernel, dim3((u32)((n_reads + KMC_PROF_INIT_THREADS - 1) / KMC_PROF_INIT_THREADS)),
@@ -379,10 +413,9 @@ static int kmc_profile_device_impl(kmc_ctx* c, const void* d_bases, const void* 
     if (c->cfg.mode != KMC_MODE_CONTIG) return fail(c, KMC_ERR_ARG, "kmc_profile_device: contiguous k-mers only (not KMC_MODE_LR)");
     if (int rc = view_begin(c, "kmc_profile_device")) return rc;
     if (!n_reads) return KMC_OK;
-    if (!d_bases || !d_offsets) return fail(c, KMC_ERR_ARG, "kmc_profile_device: null device pointer");
-    if (((uintptr_t)d_bases & 15) != 0) return fail(c, KMC_ERR_ARG, "kmc_profile_device: d_bases must be 16-byte aligned");
-    if (((uintptr_t)d_offsets & 7) != 0 || ((uintptr_t)d_read_stats & 7) != 0 || ((uintptr_t)d_window_count & 3) != 0)
-        return fail(c, KMC_ERR_ARG, "kmc_profile_device: d_offsets / d_read_stats must be 8-byte, d_window_count 4-byte aligned");
+    if (int rc = check_device_batch(c, "kmc_profile_device", d_bases, d_offsets)) return rc;
+    if (((uintptr_t)d_read_stats & 7) != 0 || ((uintptr_t)d_window_count & 3) != 0)
+        return fail(c, KMC_ERR_ARG, "kmc_profile_device: d_read_stats must be 8-byte, d_window_count 4-byte aligned");
     HIPCHK(c, hipSetDevice(c->cfg.device));
     return profile_launch(c, (const uint8_t*)d_bases, (const u64*)d_offsets, n_reads, n_bases, min_count, (u32*)d_window_count, (u64*)d_read_stats);
 }
@@ -394,18 +427,11 @@ static int kmc_profile_impl(kmc_ctx* c, const uint8_t* bases, const uint64_t* of
     int rc = view_begin(c, "kmc_profile");
     if (rc) return rc;
     if (!n_reads) return KMC_OK;
-    if (!bases || !offsets) return fail(c, KMC_ERR_ARG, "kmc_profile: null buffer");
-    if (offsets[0] != 0) return fail(c, KMC_ERR_ARG, "kmc_profile: offsets[0] must be 0");
-    for (u64 i = 0; i < n_reads; ++i)
-        if (offsets[i + 1] < offsets[i]) return fail(c, KMC_ERR_ARG, "kmc_profile: offsets must be non-decreasing (read %llu)", (unsigned long long)i);
-    const u64 n_bases = offsets[n_reads];
-    HIPCHK(c, hipSetDevice(c->cfg.device));
+    u64 n_bases;
+    if ((rc = stage_batch(c, "kmc_profile", bases, offsets, n_reads, false, &n_bases))) return rc;
     const size_t sb = (size_t)n_reads * KMC_PROFILE_WORDS * sizeof(u64), wb = (size_t)n_bases * sizeof(u32);
-    if ((rc = ensure(c, c->q_bases, n_bases + 64)) || (rc = ensure(c, c->q_offs, (n_reads + 1) * sizeof(u64)))) return rc;
     if (window_count && n_bases && (rc = ensure(c, c->q_win, wb))) return rc;
     if (read_stats && (rc = ensure(c, c->q_stats, sb))) return rc;
-    if (n_bases) HIPCHK(c, hipMemcpyAsync(c->q_bases.p, bases, n_bases, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->q_offs.p, offsets, (n_reads + 1) * sizeof(u64), hipMemcpyHostToDevice, c->stream));
     rc = profile_launch(c, (const uint8_t*)c->q_bases.p, (const u64*)c->q_offs.p, n_reads, n_bases, min_count,
                         window_count && n_bases ? (u32*)c->q_win.p : nullptr, read_stats ? (u64*)c->q_stats.p : nullptr);
     if (rc) return rc;
@@ -1011,11 +1037,12 @@ static int map_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count, c
     *n_unitigs = nu;
     if (nu > n) return fail(c, KMC_ERR_HIP, "internal error: %s holds %llu unitigs of %llu keys", what, (unsigned long long)nu, (unsigned long long)n);
     const int k = c->klen;
-    const u64 n_chunks = (n_bases + (u64)k - 1 + KMC_CHUNK - 1) / KMC_CHUNK;
     const u64 n_tiles = (n_bases + 1 + KMC_M_TILE - 1) / KMC_M_TILE;
     if (n_tiles >= (1ull << 31)) return fail(c, KMC_ERR_ARG, "%s: batch too large for one call", what);
+    ChunkGrid g;
+    if ((rc = chunk_grid(c, what, n_bases, k, &g))) return rc;
     const size_t stb = (size_t)std::max<u64>(n_reads, 1) * KMC_MAP_READ_WORDS * sizeof(u32), spb = (size_t)std::max<u64>(nu, 1) * sizeof(u64);
-    const size_t bitb = (size_t)std::max<u64>(n_chunks, 1) * 64 * sizeof(uint16_t);
+    const size_t bitb = (size_t)std::max<u64>(g.n_chunks, 1) * 64 * sizeof(uint16_t);
     if ((rc = ensure(c, c->m_soffs, (size_t)(n_reads + 1) * sizeof(u64))) || (rc = ensure(c, c->m_stats, stb)) || (rc = ensure(c, c->m_support, spb)) ||
         (rc = ensure(c, c->m_segs, 16)) || (rc = ensure(c, c->m_tail, 4)) || (rc = ensure(c, c->m_idx, (size_t)std::max<u64>(n, 1) * sizeof(u64))) ||
         (rc = ensure(c, c->m_place, (size_t)std::max<u64>(n_bases, 1) * sizeof(u64))) || (rc = ensure(c, c->m_sbits, bitb)) ||
@@ -1048,15 +1075,10 @@ static int map_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count, c
         src.idx = (const u64*)c->m_idx.p; src.adj = (const uint16_t*)c->g_adj.p;
         src.ptr = (const u32*)c->u_ptr[c->u_cur].p; src.dist = (const u32*)c->u_dist[c->u_cur].p; src.uid_of = (const u32*)c->u_join.p;
         src.n_unitigs = nu;
-        const u64 want_waves = (u64)c->n_cu * 16;   // four waves on each SIMD
-        const u64 cpw = std::min<u64>(64, std::max<u64>(1, (n_chunks + want_waves - 1) / want_waves));
-        const u64 waves = (n_chunks + cpw - 1) / cpw;
-        const u64 grid = (waves + KMC_Q_WAVES - 1) / KMC_Q_WAVES;
-        if (grid > 0x7FFFFFFFull) return fail(c, KMC_ERR_ARG, "%s: batch too large for one call", what);
-        if (n_chunks) with_kw_canon(c, [&](auto KW, auto CANON) {
+        if (g.n_chunks) with_kw_canon(c, [&](auto KW, auto CANON) {
             auto go = [&](auto INDEX) {
-                hipLaunchKernelGGL((kmc_map_place_kernel<KW(), CANON(), INDEX()>), dim3((u32)grid), dim3(KMC_Q_THREADS), 0, c->stream, d_bases, n_bases,
-                                   d_offsets, n_reads, k, n_chunks, cpw, v, src, (u64*)c->m_place.p, (uint16_t*)c->m_sbits.p, (uint16_t*)c->m_vbits.p, ctl);
+                hipLaunchKernelGGL((kmc_map_place_kernel<KW(), CANON(), INDEX()>), dim3((u32)g.grid), dim3(KMC_Q_THREADS), 0, c->stream, d_bases, n_bases,
+                                   d_offsets, n_reads, k, g.n_chunks, g.cpw, v, src, (u64*)c->m_place.p, (uint16_t*)c->m_sbits.p, (uint16_t*)c->m_vbits.p, ctl);
             };
             if (use_index) go(std::true_type{}); else go(std::false_type{});
         });
@@ -1111,11 +1133,7 @@ static int kmc_unitig_map_device_impl(kmc_ctx* c, uint64_t min_count, uint64_t m
     const char* what = "kmc_unitig_map_device";
     int rc;
     if ((rc = map_begin(c, what, min_count, max_count))) return rc;
-    if (n_reads) {
-        if (!d_bases || !d_offsets) return fail(c, KMC_ERR_ARG, "%s: null device pointer", what);
-        if (((uintptr_t)d_bases & 15) != 0) return fail(c, KMC_ERR_ARG, "%s: d_bases must be 16-byte aligned", what);
-        if (((uintptr_t)d_offsets & 7) != 0) return fail(c, KMC_ERR_ARG, "%s: d_offsets must be 8-byte aligned", what);
-    }
+    if (n_reads && (rc = check_device_batch(c, what, d_bases, d_offsets))) return rc;
     u64 h[KMC_MAP_WORDS], ns = 0, nu = 0;
     if ((rc = map_run(c, what, min_count, max_count, (const uint8_t*)d_bases, (const u64*)d_offsets, n_reads, n_reads ? n_bases : 0, h, &ns, &nu)))
         return rc;
@@ -1140,18 +1158,7 @@ static int kmc_unitig_map_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_coun
     int rc;
     if ((rc = map_begin(c, what, min_count, max_count))) return rc;
     u64 n_bases = 0;
-    if (n_reads) {
-        if (!bases || !offsets) return fail(c, KMC_ERR_ARG, "%s: null buffer", what);
-        if (offsets[0] != 0) return fail(c, KMC_ERR_ARG, "%s: offsets[0] must be 0", what);
-        for (u64 i = 0; i < n_reads; ++i) {
-            if (offsets[i + 1] < offsets[i]) return fail(c, KMC_ERR_ARG, "%s: offsets must be non-decreasing (read %llu)", what, (unsigned long long)i);
-            if (offsets[i + 1] - offsets[i] >= (1ull << 32)) return fail(c, KMC_ERR_ARG, "%s: read %llu has 2^32 bases or more", what, (unsigned long long)i);
-        }
-        n_bases = offsets[n_reads];
-        if ((rc = ensure(c, c->q_bases, n_bases + 64)) || (rc = ensure(c, c->q_offs, (n_reads + 1) * sizeof(u64)))) return rc;
-        if (n_bases) HIPCHK(c, hipMemcpyAsync(c->q_bases.p, bases, n_bases, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->q_offs.p, offsets, (n_reads + 1) * sizeof(u64), hipMemcpyHostToDevice, c->stream));
-    }
+    if (n_reads && (rc = stage_batch(c, what, bases, offsets, n_reads, true, &n_bases))) return rc;
     u64 h[KMC_MAP_WORDS], ns = 0, nu = 0;
     if ((rc = map_run(c, what, min_count, max_count, (const uint8_t*)c->q_bases.p, (const u64*)c->q_offs.p, n_reads, n_bases, h, &ns, &nu))) return rc;
     if (n_segs) *n_segs = ns;
