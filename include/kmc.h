@@ -28,6 +28,7 @@
  *   (addition: no equivalent in the reference)             kmc_unitig_clean / kmc_unitig_clean_device / kmc_unitig_clean_into (tips and islands removed)
  *   (addition: no equivalent in the reference)             kmc_unitig_simplify / kmc_unitig_simplify_device / kmc_unitig_simplify_into (and simple bubbles popped)
  *   (addition: no equivalent in the reference)             kmc_unitig_map / kmc_unitig_map_device (reads threaded through the unitigs)
+ *   (addition: no equivalent in the reference)             kmc_correct / kmc_correct_device (substitution errors of reads repaired from the table)
  *
  * Conventions
  *   - Every function returns 0 (KMC_OK) or a negative kmc_status; no exception or abort crosses
@@ -513,6 +514,71 @@ int kmc_unitig_map(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, const u
                    uint64_t n_reads, uint64_t* place, uint32_t* read_stats, uint64_t* seg_offsets, uint32_t* segs,
                    uint64_t cap_segs, uint64_t* support, uint64_t cap_unitigs, uint64_t* n_segs, uint64_t* n_unitigs,
                    uint64_t* summary);
+
+/* ---- reads corrected against the table: substitution errors repaired from the solid keys (additions, as above).
+ * KMC_MODE_CONTIG only; every k, in a canonical or a forward ctx.  Reads the sorted view of the last kmc_finalize (a view
+ * queued by kmc_finalize_async counts as one).  A key is SOLID by the range rule of kmc_graph (min_count, max_count, 0 = no
+ * upper bound).  The batch is NOT counted.
+ * WINDOW.  For a read R of L bases, window j (0 <= j <= L - k) is f = R[j : j+k].  It is VALID iff f holds only upper-case
+ *   ACGT (kmc_profile's rule), WEAK iff valid and canon(f) is not solid (canon: the ctx's own key rule), STRONG iff valid and
+ *   solid.
+ * WEAK RUN.  A maximal run [a, b] of consecutive weak windows of one read, n = b - a + 1.  Its left border is START if
+ *   a == 0, SOLID if window a - 1 is strong, INVALID otherwise; its right border is END if b == L - k, SOLID if window b + 1
+ *   is strong, INVALID otherwise.
+ * CANDIDATE.  A weak run is a candidate with suspect position p (relative to the read) iff one of:
+ *     kind 0, KMC_CORRECT_INTERIOR: left SOLID, right SOLID, n == k; p = b.
+ *     kind 1, KMC_CORRECT_HEAD:     left START, right SOLID, n <= k; p = b.
+ *     kind 2, KMC_CORRECT_TAIL:     left SOLID, right END,   n <= k; p = a + k - 1.
+ *   Nothing else is: not a run with an INVALID border, not an interior run of any other length (two errors closer than k, an
+ *   error whose windows are partly solid by chance), not a read that is weak from end to end.  In all three kinds the
+ *   windows a..b are exactly the windows of the read that contain p.
+ * ACCEPTED.  For each base c of ACGT other than R[p]: c is accepted iff every window a..b of R with R[p] replaced by c is
+ *   strong.  The accepted mask has bit code(c) set per accepted base.  Exactly one accepted base: the candidate is CORRECTED
+ *   and the corrected read carries c at p.  None: it stays.  Two or three: it is AMBIGUOUS and stays.  The formula is the
+ *   definition; no count-weighted choice is made.
+ * INDEPENDENCE.  Two candidates of one read have suspect positions more than k - 1 apart, and no candidate's windows contain
+ *   another candidate's suspect position.  So testing every candidate against the read as it came gives the same result as
+ *   testing them in any order on the partly corrected read; a correction turns exactly its n windows strong and changes no
+ *   other window; correcting the corrected batch again corrects nothing.
+ * Outputs.  bases[n_bases]: the batch with the corrected positions replaced; every other byte is copied as given, N and
+ *   lower case included; the offsets are the caller's own.  cand_offsets[n_reads + 1], uint64_t, [0] == 0, and
+ *   cands[4 * n_cands], uint32_t: one record per candidate, in read order and by position within a read:
+ *   [0] p, [1] old ASCII byte | new ASCII byte << 8 (new == old unless corrected) | kind << 16 | accepted mask << 24, [2] a,
+ *   [3] n.  read_stats[n_reads * KMC_CORRECT_READ_WORDS], uint32_t: [0] valid windows, [1] weak windows, [2] candidates,
+ *   [3] corrected.  summary[KMC_CORRECT_WORDS]: [0] reads, [1] valid windows, [2] weak windows, [3] weak runs, [4] candidates,
+ *   [5] corrected, [6] ambiguous, [7] weak windows left = [2] minus the sum of n over the corrected candidates.
+ *   [4] == cand_offsets[n_reads], and [7] equals word [2] of a second call on the corrected batch.
+ * Rules: NULL ctx, KMC_MODE_LR, a non-zero max_count below min_count: KMC_ERR_ARG; no view: KMC_ERR_STATE (where kmc_export
+ * says so); a view of 2^32 keys or more: KMC_ERR_CAPACITY (the index's rule); a read of 2^32 bases or more: KMC_ERR_ARG; 2^32
+ * candidates or more: KMC_ERR_CAPACITY.  n_reads == 0 gives zeros.  An empty view gives no candidate and the batch back as
+ * it came; its valid windows are all weak and are counted.
+ * What the call changes: it builds or reuses the query index.  It rewrites none of: the view, a partition, a filter or
+ * set-operation result, adj, the unitigs, links, a clean result, a map result.  Left out on purpose: insertions and
+ * deletions, an N replaced by a base, two errors within k of each other, a choice among ambiguous bases by count.
+ * Diagnostic: with KMC_UNITIG_TRACE set, a call prints "kmc_correct: keys N reads R windows W weak X runs U cands C fixed F
+ * mark_ms .. runs_ms .. try_ms .." to stderr (tools/measure_correct.py reads it). ---- */
+#define KMC_CORRECT_WORDS 8
+#define KMC_CORRECT_READ_WORDS 4
+#define KMC_CORRECT_INTERIOR 0u
+#define KMC_CORRECT_HEAD 1u
+#define KMC_CORRECT_TAIL 2u
+/* The batch in device memory, by the layout and alignment rules of kmc_profile_device.  The results in ctx-owned device
+ * arrays -- uint8_t corrected[n_bases], uint32_t read_stats[n_reads * 4], uint64_t cand_offsets[n_reads + 1], uint32_t
+ * cands[4 * n_cands] -- valid until the next kmc_correct* call / finalize / reset / destroy (same ordering contract as
+ * kmc_export_device: the call has finished when it returns).  d_corrected obeys the alignment and padding rule of
+ * kmc_add_batch_device: with the caller's d_offsets it goes straight into kmc_add_batch_device, kmc_profile_device or
+ * kmc_unitig_map_device of this or another ctx on this device, and back into kmc_correct_device.  Every output pointer may
+ * be NULL. */
+int kmc_correct_device(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, const void* d_bases, const void* d_offsets,
+                       uint64_t n_reads, uint64_t n_bases, const void** d_corrected, const void** d_read_stats,
+                       const void** d_cand_offsets, const void** d_cands, uint64_t* n_cands, uint64_t* summary);
+/* The same on host buffers (the batch as kmc_profile takes it).  The caller supplies out_bases[offsets[n_reads]],
+ * read_stats[n_reads * 4], cand_offsets[n_reads + 1] and cands with room for cap_cands records.  *n_cands is always set; a
+ * cap too small for cands when it is given -> KMC_ERR_ARG and nothing is written; an array that is NULL is not copied and
+ * has no cap.  All arrays NULL is the sizing call.  The host form computes on EVERY call. */
+int kmc_correct(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, const uint8_t* bases, const uint64_t* offsets,
+                uint64_t n_reads, uint8_t* out_bases, uint32_t* read_stats, uint64_t* cand_offsets, uint32_t* cands,
+                uint64_t cap_cands, uint64_t* n_cands, uint64_t* summary);
 
 /* ---- the compacted graph cleaned: tips clipped, islands dropped (additions, as above).  Everything refers to the unitigs
  * and the link records of kmc_unitigs / kmc_unitig_links for the same view and range min_count..max_count.  For unitig u:

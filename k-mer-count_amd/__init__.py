@@ -94,6 +94,7 @@ ABI_SYMBOLS = [
     "kmc_unitig_clean", "kmc_unitig_clean_device", "kmc_unitig_clean_into",
     "kmc_unitig_simplify", "kmc_unitig_simplify_device", "kmc_unitig_simplify_into",
     "kmc_unitig_map", "kmc_unitig_map_device",
+    "kmc_correct", "kmc_correct_device",
 ]
 
 PROFILE_WORDS = 5  # KMC_PROFILE_WORDS: valid windows, present windows, min, max, sum
@@ -110,6 +111,9 @@ CLEAN_BUBBLE = 3     # KMC_CLEAN_BUBBLE: the fourth verdict, of a simplify call
 MAP_WORDS = 8        # KMC_MAP_WORDS: reads, valid windows, placed windows, segments, crossings, fully placed reads, unplaced reads, most segments
 MAP_READ_WORDS = 4   # KMC_MAP_READ_WORDS: a read's valid windows, placed windows, segments, crossings
 MAP_NONE = 0xFFFFFFFF  # KMC_MAP_NONE: the low half of the place word of a window that is not placed
+CORRECT_WORDS = 8       # KMC_CORRECT_WORDS: reads, valid windows, weak windows, weak runs, candidates, corrected, ambiguous, weak windows left
+CORRECT_READ_WORDS = 4  # KMC_CORRECT_READ_WORDS: a read's valid windows, weak windows, candidates, corrected
+CORRECT_INTERIOR, CORRECT_HEAD, CORRECT_TAIL = 0, 1, 2   # KMC_CORRECT_*: a candidate's kind
 SETOP_INTERSECT, SETOP_UNION, SETOP_SUBTRACT = 0, 1, 2
 COUNT_LEFT, COUNT_RIGHT, COUNT_MIN, COUNT_MAX, COUNT_SUM, COUNT_DIFF = 0, 1, 2, 3, 4, 5
 SETOP_NAMES = {"intersect": SETOP_INTERSECT, "union": SETOP_UNION, "subtract": SETOP_SUBTRACT}
@@ -189,6 +193,8 @@ def lib() -> C.CDLL:
     L.kmc_unitig_simplify_into.argtypes = [vp, vp, u64, u64, u64, u64, u64, vp]
     L.kmc_unitig_map_device.argtypes = [vp, u64, u64, vp, vp, u64, u64] + [C.POINTER(vp)] * 5 + [pu64, pu64, vp]
     L.kmc_unitig_map.argtypes = [vp, u64, u64, vp, vp, u64, vp, vp, vp, vp, u64, vp, u64, pu64, pu64, vp]
+    L.kmc_correct_device.argtypes = [vp, u64, u64, vp, vp, u64, u64] + [C.POINTER(vp)] * 4 + [pu64, vp]
+    L.kmc_correct.argtypes = [vp, u64, u64, vp, vp, u64, vp, vp, vp, vp, u64, pu64, vp]
     L.kmc_owner_of.argtypes = [u64, u64, u32]
     L.kmc_owner_of.restype = u32
     L.kmc_get_stats.argtypes = [vp, C.POINTER(Stats)]
@@ -575,6 +581,68 @@ class ReadMap:
             parts.append("%s%d:%d:%d" % ("<" if uni & 1 else ">", uni >> 1, pos, ln))
             end = start + ln
         return "".join(parts) or "*"
+
+
+_CORRECT_FIELDS = ("reads", "valid_windows", "weak_windows", "weak_runs", "candidates", "corrected", "ambiguous", "weak_windows_left")
+
+
+@dataclass
+class CorrectSummary:
+    """The eight words of kmc_correct: reads, valid windows, weak windows, weak runs, candidates, corrected candidates,
+    ambiguous candidates, weak windows left behind the corrections."""
+    reads: int
+    valid_windows: int
+    weak_windows: int
+    weak_runs: int
+    candidates: int
+    corrected: int
+    ambiguous: int
+    weak_windows_left: int
+
+    @classmethod
+    def from_words(cls, words) -> "CorrectSummary":
+        return cls(*[int(w) for w in words])
+
+    def words(self) -> list:
+        return [getattr(self, f) for f in _CORRECT_FIELDS]
+
+    def to_text(self) -> str:
+        """``NAME\tVALUE`` lines."""
+        return "\n".join("%s\t%d" % (f, getattr(self, f)) for f in _CORRECT_FIELDS) + "\n"
+
+
+@dataclass
+class CorrectedReads:
+    """What KmerCounter.correct_reads returns: ``bases`` uint8[n_bases] (the batch with the corrected positions replaced) and
+    the caller's ``offsets``, ``stats`` uint32[n_reads, 4] (valid windows, weak windows, candidates, corrected),
+    ``cand_offsets`` uint64[n_reads + 1], ``cands`` uint32[n, 4] (p, old | new << 8 | kind << 16 | accepted mask << 24, a, n),
+    ``summary``.  The candidates of read r are ``cands[cand_offsets[r]:cand_offsets[r + 1]]``."""
+    bases: np.ndarray
+    offsets: np.ndarray
+    stats: np.ndarray
+    cand_offsets: np.ndarray
+    cands: np.ndarray
+    summary: CorrectSummary
+
+    def __len__(self) -> int:
+        return len(self.offsets) - 1
+
+    def strings(self) -> list:
+        """The corrected reads as str."""
+        o, b = self.offsets, self.bases.tobytes()
+        return [b[int(o[i]):int(o[i + 1])].decode("latin-1") for i in range(len(self))]
+
+    def fixes(self):
+        """``(read, pos, old, new, kind)`` of every corrected candidate, in array order."""
+        co = self.cand_offsets
+        for r in range(len(self)):
+            for p, word, _, _ in self.cands[int(co[r]):int(co[r + 1])].tolist():
+                if (word & 255) != (word >> 8 & 255):
+                    yield r, p, chr(word & 255), chr(word >> 8 & 255), word >> 16 & 255
+
+    def to_fasta(self) -> str:
+        """What ``k-mer-count --correct`` prints: ``>INDEX WINDOWS WEAK CANDIDATES FIXED`` and the corrected read."""
+        return "".join(">%d %d %d %d %d\n%s\n" % (i, s[0], s[1], s[2], s[3], r) for i, (s, r) in enumerate(zip(self.stats.tolist(), self.strings())))
 
 
 _CLEAN_FIELDS = ("unitigs", "tips", "islands", "kept_keys", "tip_keys", "island_keys", "tip_candidates", "kept_count")
@@ -1003,6 +1071,50 @@ class KmerCounter:
         return ReadMap(words(dp, 8 * n_bases).view(np.uint64), words(ds, 16 * n_reads).view(np.uint32).reshape(n_reads, MAP_READ_WORDS),
                        words(do, 8 * (n_reads + 1)).view(np.uint64), words(dg, 16 * ns).view(np.uint32).reshape(ns, 4),
                        words(du, 8 * nu).view(np.uint64), summary)
+
+    # -- reads corrected against the solid keys of the table (of the sorted view; finalize() first) --
+    def correct_reads_device(self, d_bases: int, d_offsets: int, n_reads: int, n_bases: int, min_count: int = 2, max_count: int = 0):
+        """(d_corrected, d_read_stats, d_cand_offsets, d_cands, n_cands, CorrectSummary) of kmc_correct_device for a batch in
+        device memory (raw addresses, laid out as for profile_device): ctx-owned device arrays of n_bases uint8 (padded as
+        add_batch_device asks), n_reads * 4 uint32, n_reads + 1 uint64 and n_cands * 4 uint32."""
+        p = [C.c_void_p() for _ in range(4)]
+        nc = C.c_uint64()
+        w = (C.c_uint64 * CORRECT_WORDS)()
+        self._chk(self._L.kmc_correct_device(self._h, int(min_count), int(max_count), d_bases or None, d_offsets or None, int(n_reads), int(n_bases),
+                                             *[C.byref(x) for x in p], C.byref(nc), w))
+        return tuple(x.value or 0 for x in p) + (nc.value, CorrectSummary.from_words(list(w)))
+
+    def correct_reads_tensors(self, bases, offsets, min_count: int = 2, max_count: int = 0):
+        """correct_reads_device for torch tensors on this ctx's GPU (bases uint8[n_bases], padded as for add_batch_tensors;
+        offsets int64[n_reads + 1])."""
+        assert bases.is_cuda and offsets.is_cuda and bases.is_contiguous() and offsets.is_contiguous()
+        return self.correct_reads_device(bases.data_ptr(), offsets.data_ptr(), max(offsets.numel() - 1, 0), bases.numel(), min_count, max_count)
+
+    def correct_reads(self, bases: np.ndarray, offsets: np.ndarray, min_count: int = 2, max_count: int = 0) -> "CorrectedReads":
+        """kmc_correct_device for a host batch (the batch is not counted): every substitution error that leaves one clean run
+        of weak windows is replaced by the one base that makes all windows over it solid (count in min_count..max_count).
+        The batch goes to the device as tensors and the result arrays are read back from the ctx."""
+        import torch
+        from .distributed import device_view
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n_reads, n_bases = max(int(offsets.shape[0]) - 1, 0), int(bases.shape[0])
+        if n_reads and (int(offsets[0]) != 0 or int(offsets[-1]) != n_bases or (np.diff(offsets.astype(np.int64)) < 0).any()):
+            raise ValueError("offsets must start at 0, not decrease, and end at len(bases)")
+        if n_reads and int(np.diff(offsets.astype(np.int64)).max()) >= 1 << 32:
+            raise KmcError(ERR_ARG, "a read of 2^32 bases or more")
+        dev = torch.device("cuda", self.device)
+        d_bases = torch.zeros(n_bases + 64, dtype=torch.uint8, device=dev)   # (readable past the end, 16-byte aligned)
+        d_bases[:n_bases] = torch.from_numpy(bases.copy())
+        d_offs = torch.from_numpy(offsets.view(np.int64).copy()).to(dev)
+        torch.cuda.synchronize(dev)
+        db, ds, do, dc, nc, summary = self.correct_reads_device(d_bases.data_ptr(), d_offs.data_ptr(), n_reads, n_bases, min_count, max_count)
+
+        def words(ptr, n_bytes):
+            return device_view(ptr, (n_bytes + 7) // 8, dev).cpu().numpy().view(np.uint8)[:n_bytes].copy()
+        out = words(db, n_bases) if n_reads else bases.copy()
+        return CorrectedReads(out, offsets.copy() if n_reads else np.zeros(1, np.uint64), words(ds, 16 * n_reads).view(np.uint32).reshape(n_reads, CORRECT_READ_WORDS),
+                              words(do, 8 * (n_reads + 1)).view(np.uint64), words(dc, 16 * nc).view(np.uint32).reshape(nc, 4), summary)
 
     # -- that graph cleaned: tips clipped, islands dropped (of the sorted view; finalize() first) --
     def _clean_limits(self, max_tip_keys, max_island_keys) -> Tuple[int, int]:

@@ -5,7 +5,7 @@
 // test.py:15-18 takes the FASTA path as its only positional argument.  This tool keeps both:
 //
 //   k-mer-count [FASTA] [-k K] [--forward] [--expand] [--device N | --gpus N] [--algo auto|stream|walk|sort] [--stats]
-//               [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE | --map FILE]
+//               [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE | --map FILE | --correct FILE]
 //               [--with FASTA2 (--compare | --setop intersect|union|subtract [--counts left|right|min|max|sum|diff])]
 //               [--graph | --graph-stats | --unitigs | --gfa] [--clean ROUNDS [--tip-keys N] [--island-keys N] [--bubble-keys N]]
 //
@@ -33,6 +33,11 @@
 //               "<U:POS:LEN" (against it).  A segment that starts at the window right behind its predecessor -- the read crossed
 //               from one unitig end to another -- is written directly behind it, one behind a gap after a ","; "*" for a read
 //               with no segment.  With --clean the reads are laid on the cleaned graph.
+//   --correct FILE       (with -k K) instead of the table: every read of FILE (FASTA / FASTQ) corrected against the solid keys of
+//               the counted input (kmc_correct; --min-count / --max-count are the solidity range), as FASTA in file order:
+//               ">INDEX WINDOWS WEAK CANDIDATES FIXED" -- its valid K-mer windows, how many of them are not solid, the weak
+//               runs that qualify as one substitution, how many of those were repaired -- then the corrected read on one
+//               line.  With --clean the reads are corrected against the cleaned table.
 //
 //   --with FASTA2        (with -k K) a second file, counted into a second table on the same device; one of:
 //     --compare          instead of the table: "NAME<TAB>VALUE" lines -- the eight words of kmc_compare (n_a, n_b, n_both, sum_a,
@@ -114,7 +119,7 @@ int main(int argc, char** argv) {
     const char* path = "sample.fasta";  // main.rs:44
     int k = 0, canonical = 1, expand = 0, device = 0, algo = KMC_ALGO_AUTO, stats = 0, gpus = 1, histo = 0;
     long long min_count = 1, max_count = 0;   // (max_count 0: no upper bound)
-    const char *query_path = nullptr, *profile_path = nullptr, *with_path = nullptr, *map_path = nullptr;
+    const char *query_path = nullptr, *profile_path = nullptr, *with_path = nullptr, *map_path = nullptr, *correct_path = nullptr;
     int compare = 0, setop = -1, count_mode = -1, graph = 0, graph_stats = 0, unitigs = 0, gfa = 0;
     int clean = 0;
     long long tip_keys = -1, island_keys = -1;   // (-1: K)
@@ -133,6 +138,7 @@ int main(int argc, char** argv) {
         else if (a == "--query-kmers" && i + 1 < argc) query_path = argv[++i];
         else if (a == "--profile" && i + 1 < argc) profile_path = argv[++i];
         else if (a == "--map" && i + 1 < argc) map_path = argv[++i];
+        else if (a == "--correct" && i + 1 < argc) correct_path = argv[++i];
         else if (a == "--with" && i + 1 < argc) with_path = argv[++i];
         else if (a == "--compare") compare = 1;
         else if (a == "--graph") graph = 1;
@@ -157,12 +163,12 @@ int main(int argc, char** argv) {
             algo = v == "stream" ? KMC_ALGO_STREAM : v == "walk" ? KMC_ALGO_WALK : v == "sort" ? KMC_ALGO_SORT : KMC_ALGO_AUTO;
         } else if (a == "-h" || a == "--help") {
             fprintf(stderr, "usage: k-mer-count [FASTA] [-k K] [--forward] [--expand] [--device N | --gpus N] [--algo auto|stream|walk|sort] [--stats]\n"
-                            "                   [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE | --map FILE]\n"
+                            "                   [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE | --map FILE | --correct FILE]\n"
                             "                   [--with FASTA2 (--compare | --setop intersect|union|subtract [--counts left|right|min|max|sum|diff])]\n"
                             "                   [--graph | --graph-stats | --unitigs | --gfa] [--clean ROUNDS [--tip-keys N] [--island-keys N] [--bubble-keys N]]\n");
             return 0;
         } else if (a == "-k" || a == "--device" || a == "--gpus" || a == "--algo" || a == "--min-count" || a == "--max-count" || a == "--histo" ||
-                   a == "--query-kmers" || a == "--profile" || a == "--map" || a == "--with" || a == "--setop" || a == "--counts" ||
+                   a == "--query-kmers" || a == "--profile" || a == "--map" || a == "--correct" || a == "--with" || a == "--setop" || a == "--counts" ||
                    a == "--clean" || a == "--tip-keys" || a == "--island-keys" || a == "--bubble-keys") {
             fprintf(stderr, "k-mer-count: %s needs a value\n", a.c_str());
             return 2;
@@ -195,6 +201,18 @@ int main(int argc, char** argv) {
         else if (expand) bad = "--expand exclude each other";
         if (bad) { fprintf(stderr, "k-mer-count: --map %s%s\n", strncmp(bad, "needs", 5) ? "and " : "", bad); return 2; }
     }
+    // --correct: the same again
+    if (correct_path) {
+        const char* bad = nullptr;
+        if (!k) bad = "needs -k K";
+        else if (map_path) bad = "--map exclude each other";
+        else if (query_path || profile_path) bad = "--query-kmers / --profile exclude each other";
+        else if (histo) bad = "--histo exclude each other";
+        else if (with_path || compare || setop >= 0) bad = "--with / --compare / --setop exclude each other";
+        else if (graph || graph_stats || unitigs || gfa) bad = "--graph / --graph-stats / --unitigs / --gfa exclude each other";
+        else if (expand) bad = "--expand exclude each other";
+        if (bad) { fprintf(stderr, "k-mer-count: --correct %s%s\n", strncmp(bad, "needs", 5) ? "and " : "", bad); return 2; }
+    }
     if (query_path) {
         FILE* f = fopen(query_path, "r");
         if (!f) return die(query_path, strerror(errno));
@@ -219,8 +237,8 @@ int main(int argc, char** argv) {
         }
         fclose(f);
     }
-    if (profile_path || map_path) {
-        const char* reads_path = profile_path ? profile_path : map_path;
+    if (profile_path || map_path || correct_path) {
+        const char* reads_path = profile_path ? profile_path : map_path ? map_path : correct_path;
         char eb[256] = {0};
         const int prc = kmc_parse_fasta(reads_path, &prof, eb, sizeof(eb));
         if (prc) return die(reads_path, eb[0] ? eb : kmc_status_string(prc));
@@ -425,6 +443,26 @@ int main(int argc, char** argv) {
             fputc('\n', stdout);
         }
         fflush(stdout);
+        destroy_all();
+        return 0;
+    }
+    if (correct_path) {
+        // the records are not printed: one call fills everything this needs
+        const uint64_t n_cor = prof.n_reads;
+        std::vector<uint32_t> rs((size_t)n_cor * KMC_CORRECT_READ_WORDS + 1);
+        std::vector<uint8_t> cb((size_t)(n_cor ? prof.offsets[n_cor] : 0) + 1);
+        uint64_t nc = 0;
+        rc = kmc_correct(ctx, (uint64_t)min_count, (uint64_t)max_count, prof.bases, prof.offsets, n_cor, cb.data(), rs.data(), nullptr, nullptr, 0, &nc, nullptr);
+        if (rc) { kmc_free_reads(&prof); int r = die("kmc_correct", kmc_last_error(ctx)); destroy_all(); return r; }
+        setvbuf(stdout, obuf.data(), _IOFBF, obuf.size());
+        for (uint64_t r = 0; r < n_cor; ++r) {
+            const uint32_t* w = &rs[(size_t)r * KMC_CORRECT_READ_WORDS];
+            printf(">%llu %u %u %u %u\n", (unsigned long long)r, w[0], w[1], w[2], w[3]);
+            fwrite(cb.data() + prof.offsets[r], 1, (size_t)(prof.offsets[r + 1] - prof.offsets[r]), stdout);
+            fputc('\n', stdout);
+        }
+        fflush(stdout);
+        kmc_free_reads(&prof);
         destroy_all();
         return 0;
     }

@@ -222,6 +222,10 @@ struct kmc_ctx : CtxStream {
     // the batch and the tails' positions.
     DevBuf m_idx, m_place, m_stats, m_soffs, m_segs, m_support, m_sbits, m_vbits, m_tail;
     bool m_idx_live = false;
+    // kmc_correct / kmc_correct_device (kmc_correct.hip.h) read the view and the query index alone.  The result of the last
+    // call: the corrected copy of the batch, per-read rows, candidate offsets and records; between the passes the
+    // read-start, valid-window and weak-window bits of the batch and, per candidate, its batch position and read.
+    DevBuf cr_out, cr_stats, cr_coffs, cr_cands, cr_where, cr_sbits, cr_vbits, cr_wbits;
     // kmc_unitig_clean* and kmc_unitig_simplify* (kmc_clean.hip.h) read the unitigs, the links and what the links pass
     // reads.  Their result: the verdict per unitig and the kept table, with cl_key plus its three limits cl_tip / cl_isl /
     // cl_bub (0 for a clean call) and cl_words as above (nothing but the clean pass writes them; a clean call hands out the

@@ -15,6 +15,7 @@
 #include "kmc_links.hip.h"
 #include "kmc_clean.hip.h"
 #include "kmc_map.hip.h"
+#include "kmc_correct.hip.h"
 
 namespace {
 
@@ -1175,6 +1176,139 @@ static int kmc_unitig_map_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_coun
     return KMC_OK;
 }
 
+// ---- reads corrected against the solid keys of the view: weak runs, candidates, replacements (kmc_correct.hip.h) ----
+template <int PASS>
+static void correct_runs_launch(kmc_ctx* c, const CorrBatch& b, u64 n_cands) {
+    const u32 grid = (u32)std::min<u64>(b.n_tiles, (u64)c->n_cu * 8);
+    hipLaunchKernelGGL(kmc_correct_runs_kernel<PASS>, dim3(grid), dim3(KMC_CR_THREADS), 0, c->stream, b, (u32*)c->c_tile.p, (const u32*)c->c_tpos.p,
+                       n_cands, (uint4*)c->cr_cands.p, (u64*)c->cr_where.p, (u64*)c->cr_coffs.p, (u32*)c->cr_stats.p, (kmc_ull*)c->c_ctl.p);
+}
+
+// The batch (device arrays) corrected against the keys of this view inside the range, into the cr_* buffers;
+// h[KMC_CORRECT_WORDS] the summary.  Finished when it returns.
+static int correct_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count, const uint8_t* d_bases, const u64* d_offsets, u64 n_reads,
+                       u64 n_bases, u64* h, u64* n_cands) {
+    memset(h, 0, KMC_CORRECT_WORDS * sizeof(u64));
+    *n_cands = 0;
+    int rc;
+    const u64 n = c->n_sorted;
+    const int k = c->klen;
+    const u64 n_tiles = (n_bases + 1 + KMC_CR_TILE - 1) / KMC_CR_TILE;
+    if (n_tiles >= (1ull << 31)) return fail(c, KMC_ERR_ARG, "%s: batch too large for one call", what);
+    ChunkGrid g;
+    if ((rc = chunk_grid(c, what, n_bases, k, &g))) return rc;
+    const size_t stb = (size_t)std::max<u64>(n_reads, 1) * KMC_CORRECT_READ_WORDS * sizeof(u32);
+    const size_t bitb = (size_t)std::max<u64>(g.n_chunks, 1) * 64 * sizeof(uint16_t);
+    if ((rc = ensure(c, c->cr_out, (size_t)n_bases + 64)) || (rc = ensure(c, c->cr_stats, stb)) ||
+        (rc = ensure(c, c->cr_coffs, (size_t)(n_reads + 1) * sizeof(u64))) || (rc = ensure(c, c->cr_cands, 16)) || (rc = ensure(c, c->cr_where, 16)) ||
+        (rc = ensure(c, c->cr_sbits, bitb)) || (rc = ensure(c, c->cr_vbits, bitb)) || (rc = ensure(c, c->cr_wbits, bitb)) ||
+        (rc = compact_plan(c, n_tiles, KMC_CR_CTL_WORDS)))
+        return rc;
+    HIPCHK(c, hipMemsetAsync(c->cr_stats.p, 0, stb, c->stream));
+    if (!n_reads) {
+        HIPCHK(c, hipMemsetAsync(c->cr_coffs.p, 0, sizeof(u64), c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return KMC_OK;
+    }
+    QView v;
+    if ((rc = query_view(c, what, &v))) return rc;
+    kmc_ull* ctl = (kmc_ull*)c->c_ctl.p;
+    const u64 lo_c = std::max<u64>(min_count, 1), hi_c = count_hi(max_count);
+    // the copy that takes the corrections (a caller may hand the last call's own result back in)
+    if (n_bases && (const void*)d_bases != c->cr_out.p) HIPCHK(c, hipMemcpyAsync(c->cr_out.p, d_bases, (size_t)n_bases, hipMemcpyDeviceToDevice, c->stream));
+    UnitigTrace tr;
+    tr.mark(c->stream);
+    if (g.n_chunks) with_kw_canon(c, [&](auto KW, auto CANON) {
+        hipLaunchKernelGGL((kmc_correct_mark_kernel<KW(), CANON()>), dim3((u32)g.grid), dim3(KMC_Q_THREADS), 0, c->stream, d_bases, n_bases, d_offsets,
+                           n_reads, k, g.n_chunks, g.cpw, v, lo_c, hi_c, (uint16_t*)c->cr_sbits.p, (uint16_t*)c->cr_vbits.p, (uint16_t*)c->cr_wbits.p);
+    });
+    HIPCHK(c, hipGetLastError());
+    tr.mark(c->stream);
+    CorrBatch b;
+    b.start_bits = (const uint16_t*)c->cr_sbits.p; b.valid_bits = (const uint16_t*)c->cr_vbits.p; b.weak_bits = (const uint16_t*)c->cr_wbits.p;
+    b.bases = d_bases; b.offsets = d_offsets; b.n_reads = n_reads; b.n_bases = n_bases; b.n_words = g.n_chunks * 64; b.n_tiles = n_tiles; b.k = k;
+    correct_runs_launch<0>(c, b, 0);
+    u64 w[KMC_CR_CTL_WORDS];
+    if ((rc = compact_scan_and_read(c, n_tiles, w, KMC_CR_CTL_WORDS))) return rc;
+    const u64 nc = w[KMC_CR_CANDS];
+    if (nc >= (1ull << 32)) return fail(c, KMC_ERR_CAPACITY, "%s: 2^32 candidates or more", what);
+    if ((w[0] & 0xFFFFFFFFull) != nc)
+        return fail(c, KMC_ERR_HIP, "internal error: %s scanned %llu of %llu candidates", what, (unsigned long long)(w[0] & 0xFFFFFFFFull), (unsigned long long)nc);
+    if ((rc = ensure(c, c->cr_cands, (size_t)std::max<u64>(nc, 1) * 4 * sizeof(u32))) || (rc = ensure(c, c->cr_where, (size_t)std::max<u64>(nc, 1) * 2 * sizeof(u64))))
+        return rc;
+    correct_runs_launch<1>(c, b, nc);
+    hipLaunchKernelGGL(kmc_correct_reads_kernel, dim3((u32)grid_for(c, n_reads, KMC_CR_THREADS)), dim3(KMC_CR_THREADS), 0, c->stream, d_offsets, n_reads, ctl);
+    HIPCHK(c, hipGetLastError());
+    tr.mark(c->stream);
+    if (nc) with_kw_canon(c, [&](auto KW, auto CANON) {
+        const u32 grid = (u32)std::min<u64>((nc + KMC_CR_WAVES - 1) / KMC_CR_WAVES, (u64)c->n_cu * 16);
+        hipLaunchKernelGGL((kmc_correct_try_kernel<KW(), CANON()>), dim3(grid), dim3(KMC_CR_THREADS), 0, c->stream, d_bases, n_bases, n_reads, k, v, lo_c,
+                           hi_c, nc, (uint4*)c->cr_cands.p, (const u64*)c->cr_where.p, (uint8_t*)c->cr_out.p, (u32*)c->cr_stats.p, ctl);
+    });
+    HIPCHK(c, hipGetLastError());
+    tr.mark(c->stream);
+    HIPCHK(c, hipMemcpyAsync(w, ctl, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (w[KMC_CR_BAD]) return fail(c, KMC_ERR_HIP, "internal error: %s met %llu indices outside their arrays", what, (unsigned long long)w[KMC_CR_BAD]);
+    if (w[KMC_CR_LONG]) return fail(c, KMC_ERR_ARG, "%s: %llu reads of 2^32 bases or more", what, (unsigned long long)w[KMC_CR_LONG]);
+    h[0] = n_reads; h[1] = w[KMC_CR_VALID]; h[2] = w[KMC_CR_WEAK]; h[3] = w[KMC_CR_RUNS]; h[4] = nc; h[5] = w[KMC_CR_FIXED]; h[6] = w[KMC_CR_AMBIG];
+    h[7] = w[KMC_CR_WEAK] - w[KMC_CR_FIXED_WIN];
+    *n_cands = nc;
+    if (tr.on && tr.n_ev == 4) {
+        float ms[3] = {0, 0, 0};
+        bool ok = hipEventSynchronize(tr.ev[3]) == hipSuccess;
+        for (int i = 0; ok && i < 3; ++i) ok = hipEventElapsedTime(&ms[i], tr.ev[i], tr.ev[i + 1]) == hipSuccess;
+        if (ok)
+            fprintf(stderr, "kmc_correct: keys %llu reads %llu windows %llu weak %llu runs %llu cands %llu fixed %llu mark_ms %.4f runs_ms %.4f try_ms %.4f\n",
+                    (unsigned long long)n, (unsigned long long)n_reads, (unsigned long long)h[1], (unsigned long long)h[2], (unsigned long long)h[3],
+                    (unsigned long long)nc, (unsigned long long)h[5], ms[0], ms[1], ms[2]);
+    }
+    return KMC_OK;
+}
+
+static int kmc_correct_device_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, const void* d_bases, const void* d_offsets, uint64_t n_reads,
+                                   uint64_t n_bases, const void** d_corrected, const void** d_read_stats, const void** d_cand_offsets,
+                                   const void** d_cands, uint64_t* n_cands, uint64_t* summary) {
+    if (n_cands) *n_cands = 0;
+    if (!c) return KMC_ERR_ARG;
+    const char* what = "kmc_correct_device";
+    int rc;
+    if ((rc = graph_begin(c, what, min_count, max_count))) return rc;
+    if (n_reads && (rc = check_device_batch(c, what, d_bases, d_offsets))) return rc;
+    u64 h[KMC_CORRECT_WORDS], nc = 0;
+    if ((rc = correct_run(c, what, min_count, max_count, (const uint8_t*)d_bases, (const u64*)d_offsets, n_reads, n_reads ? n_bases : 0, h, &nc))) return rc;
+    if (d_corrected) *d_corrected = c->cr_out.p;
+    if (d_read_stats) *d_read_stats = c->cr_stats.p;
+    if (d_cand_offsets) *d_cand_offsets = c->cr_coffs.p;
+    if (d_cands) *d_cands = c->cr_cands.p;
+    if (n_cands) *n_cands = nc;
+    if (summary) memcpy(summary, h, sizeof(h));
+    return KMC_OK;
+}
+
+static int kmc_correct_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads,
+                            uint8_t* out_bases, uint32_t* read_stats, uint64_t* cand_offsets, uint32_t* cands, uint64_t cap_cands,
+                            uint64_t* n_cands, uint64_t* summary) {
+    if (n_cands) *n_cands = 0;
+    if (!c) return KMC_ERR_ARG;
+    const char* what = "kmc_correct";
+    int rc;
+    if ((rc = graph_begin(c, what, min_count, max_count))) return rc;
+    u64 n_bases = 0;
+    if (n_reads && (rc = stage_batch(c, what, bases, offsets, n_reads, true, &n_bases))) return rc;
+    u64 h[KMC_CORRECT_WORDS], nc = 0;
+    if ((rc = correct_run(c, what, min_count, max_count, (const uint8_t*)c->q_bases.p, (const u64*)c->q_offs.p, n_reads, n_bases, h, &nc))) return rc;
+    if (n_cands) *n_cands = nc;
+    if (cands && cap_cands < nc) return fail(c, KMC_ERR_ARG, "%s: capacity %llu < %llu candidates", what, (unsigned long long)cap_cands, (unsigned long long)nc);
+    if (out_bases && n_bases) HIPCHK(c, hipMemcpyAsync(out_bases, c->cr_out.p, (size_t)n_bases, hipMemcpyDeviceToHost, c->stream));
+    if (read_stats && n_reads) HIPCHK(c, hipMemcpyAsync(read_stats, c->cr_stats.p, (size_t)n_reads * KMC_CORRECT_READ_WORDS * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+    if (cand_offsets) HIPCHK(c, hipMemcpyAsync(cand_offsets, c->cr_coffs.p, (size_t)(n_reads + 1) * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    if (cands && nc) HIPCHK(c, hipMemcpyAsync(cands, c->cr_cands.p, (size_t)nc * 4 * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (summary) memcpy(summary, h, sizeof(h));
+    return KMC_OK;
+}
+
 // ---- the compacted graph cleaned: a verdict per unitig, the table of the kept keys (kmc_clean.hip.h) ----
 static u64 clean_limit(uint64_t keys) { return keys >= (1ull << 31) ? ~0ull : (u64)keys; }   // 2^31 or more: unlimited
 
@@ -1423,6 +1557,21 @@ extern "C" int kmc_unitig_map(kmc_ctx* c, uint64_t min_count, uint64_t max_count
     return guarded(c, [&]() -> int {
         return kmc_unitig_map_impl(c, min_count, max_count, bases, offsets, n_reads, place, read_stats, seg_offsets, segs, cap_segs, support,
                                    cap_unitigs, n_segs, n_unitigs, summary);
+    });
+}
+extern "C" int kmc_correct_device(kmc_ctx* c, uint64_t min_count, uint64_t max_count, const void* d_bases, const void* d_offsets, uint64_t n_reads,
+                                  uint64_t n_bases, const void** d_corrected, const void** d_read_stats, const void** d_cand_offsets,
+                                  const void** d_cands, uint64_t* n_cands, uint64_t* summary) {
+    return guarded(c, [&]() -> int {
+        return kmc_correct_device_impl(c, min_count, max_count, d_bases, d_offsets, n_reads, n_bases, d_corrected, d_read_stats, d_cand_offsets, d_cands,
+                                       n_cands, summary);
+    });
+}
+extern "C" int kmc_correct(kmc_ctx* c, uint64_t min_count, uint64_t max_count, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads,
+                           uint8_t* out_bases, uint32_t* read_stats, uint64_t* cand_offsets, uint32_t* cands, uint64_t cap_cands, uint64_t* n_cands,
+                           uint64_t* summary) {
+    return guarded(c, [&]() -> int {
+        return kmc_correct_impl(c, min_count, max_count, bases, offsets, n_reads, out_bases, read_stats, cand_offsets, cands, cap_cands, n_cands, summary);
     });
 }
 extern "C" int kmc_unitig_clean_device(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t max_tip_keys, uint64_t max_island_keys,

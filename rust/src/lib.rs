@@ -37,6 +37,12 @@ pub const KMC_LINK_WORDS: usize = 8;
 pub const KMC_MAP_WORDS: usize = 8;
 pub const KMC_MAP_READ_WORDS: usize = 4;
 pub const KMC_MAP_NONE: u32 = 0xFFFF_FFFF;
+/// summary words of `kmc_correct`, words per read of its `read_stats`, the kinds of a candidate
+pub const KMC_CORRECT_WORDS: usize = 8;
+pub const KMC_CORRECT_READ_WORDS: usize = 4;
+pub const KMC_CORRECT_INTERIOR: u32 = 0;
+pub const KMC_CORRECT_HEAD: u32 = 1;
+pub const KMC_CORRECT_TAIL: u32 = 2;
 /// summary words of `kmc_unitig_clean`
 pub const KMC_CLEAN_WORDS: usize = 8;
 /// a unitig's verdict byte
@@ -161,6 +167,8 @@ extern "C" {
     pub fn kmc_unitig_links(ctx: *mut KmcCtx, min_count: u64, max_count: u64, link_offsets: *mut u64, cap_ends: u64, link_to: *mut u32, cap_links: u64, n_unitigs: *mut u64, n_links: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_map_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, d_bases: *const c_void, d_offsets: *const c_void, n_reads: u64, n_bases: u64, d_place: *mut *const c_void, d_read_stats: *mut *const c_void, d_seg_offsets: *mut *const c_void, d_segs: *mut *const c_void, d_support: *mut *const c_void, n_segs: *mut u64, n_unitigs: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_map(ctx: *mut KmcCtx, min_count: u64, max_count: u64, bases: *const u8, offsets: *const u64, n_reads: u64, place: *mut u64, read_stats: *mut u32, seg_offsets: *mut u64, segs: *mut u32, cap_segs: u64, support: *mut u64, cap_unitigs: u64, n_segs: *mut u64, n_unitigs: *mut u64, summary: *mut u64) -> c_int;
+    pub fn kmc_correct_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, d_bases: *const c_void, d_offsets: *const c_void, n_reads: u64, n_bases: u64, d_corrected: *mut *const c_void, d_read_stats: *mut *const c_void, d_cand_offsets: *mut *const c_void, d_cands: *mut *const c_void, n_cands: *mut u64, summary: *mut u64) -> c_int;
+    pub fn kmc_correct(ctx: *mut KmcCtx, min_count: u64, max_count: u64, bases: *const u8, offsets: *const u64, n_reads: u64, out_bases: *mut u8, read_stats: *mut u32, cand_offsets: *mut u64, cands: *mut u32, cap_cands: u64, n_cands: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_clean_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, max_tip_keys: u64, max_island_keys: u64, d_key_hi: *mut *const c_void, d_key_lo: *mut *const c_void, d_count: *mut *const c_void, d_verdict: *mut *const c_void, n_kept: *mut u64, n_unitigs: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_clean(ctx: *mut KmcCtx, min_count: u64, max_count: u64, max_tip_keys: u64, max_island_keys: u64, key_hi: *mut u64, key_lo: *mut u64, count: *mut u64, cap_keys: u64, verdict: *mut u8, cap_unitigs: u64, n_kept: *mut u64, n_unitigs: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_clean_into(src: *mut KmcCtx, dst: *mut KmcCtx, min_count: u64, max_count: u64, max_tip_keys: u64, max_island_keys: u64, summary: *mut u64) -> c_int;
@@ -470,6 +478,41 @@ impl Counter {
             })?;
         }
         Ok((place, stats, seg_offsets, segs, support, w))
+    }
+
+    /// A batch of reads corrected against the solid keys of the table (`kmc_correct`; the batch is not counted): every
+    /// substitution error that leaves one clean run of weak windows is replaced by the one base that makes all windows
+    /// over it solid.  Returns the corrected bases (the offsets are the caller's), per read [valid windows, weak windows,
+    /// candidates, corrected], `cand_offsets[n_reads + 1]`, the candidates as [p, old | new << 8 | kind << 16 | accepted
+    /// mask << 24, a, n], and the eight summary words.  The host form computes on every call, so the sizing call below
+    /// corrects the batch once more.
+    #[allow(clippy::type_complexity)]
+    pub fn correct_reads(&mut self, bases: &[u8], offsets: &[u64], min_count: u64, max_count: u64)
+                         -> Result<(Vec<u8>, Vec<[u32; KMC_CORRECT_READ_WORDS]>, Vec<u64>, Vec<[u32; 4]>, [u64; KMC_CORRECT_WORDS]), KmcError> {
+        let (mut nd, mut nt) = (0u64, 0u64);
+        self.check(unsafe { kmc_finalize(self.ctx, &mut nd, &mut nt) })?;
+        let n_reads = offsets.len().saturating_sub(1);
+        if n_reads > 0 && offsets[n_reads] as usize != bases.len() {
+            return Err(KmcError(-1, "offsets do not end at the number of bases".into()));
+        }
+        let n_bases = if n_reads > 0 { bases.len() } else { 0 };
+        let mut nc = 0u64;
+        let mut w = [0u64; KMC_CORRECT_WORDS];
+        let mut out = vec![0u8; n_bases];
+        let mut stats = vec![[0u32; KMC_CORRECT_READ_WORDS]; n_reads];
+        let mut cand_offsets = vec![0u64; n_reads + 1];
+        self.check(unsafe {
+            kmc_correct(self.ctx, min_count, max_count, bases.as_ptr(), offsets.as_ptr(), n_reads as u64, out.as_mut_ptr(),
+                        stats.as_mut_ptr() as *mut u32, cand_offsets.as_mut_ptr(), std::ptr::null_mut::<u32>(), 0, &mut nc, w.as_mut_ptr())
+        })?;
+        let mut cands = vec![[0u32; 4]; nc as usize];
+        if nc > 0 {
+            self.check(unsafe {
+                kmc_correct(self.ctx, min_count, max_count, bases.as_ptr(), offsets.as_ptr(), n_reads as u64, std::ptr::null_mut::<u8>(),
+                            std::ptr::null_mut::<u32>(), std::ptr::null_mut::<u64>(), cands.as_mut_ptr() as *mut u32, nc, &mut nc, w.as_mut_ptr())
+            })?;
+        }
+        Ok((out, stats, cand_offsets, cands, w))
     }
 
     /// That graph cleaned (`kmc_unitig_clean`): the keys of the kept unitigs with their counts, in the order of `table()`,
