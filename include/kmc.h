@@ -27,6 +27,9 @@
  *   (addition: no equivalent in the reference)             kmc_unitig_links / kmc_unitig_links_device (the edges between them)
  *   (addition: no equivalent in the reference)             kmc_unitig_clean / kmc_unitig_clean_device / kmc_unitig_clean_into (tips and islands removed)
  *   (addition: no equivalent in the reference)             kmc_unitig_simplify / kmc_unitig_simplify_device / kmc_unitig_simplify_into (and simple bubbles popped)
+ *   (addition: no equivalent in the reference)             kmc_unitig_components (connected components of the unitig graph, the small ones dropped)
+ *   (addition: no equivalent in the reference)             kmc_unitig_components_device (the same in ctx-owned device memory)
+ *   (addition: no equivalent in the reference)             kmc_unitig_components_into (the table without small components, into another ctx)
  *   (addition: no equivalent in the reference)             kmc_unitig_map / kmc_unitig_map_device (reads threaded through the unitigs)
  *   (addition: no equivalent in the reference)             kmc_correct / kmc_correct_device (substitution errors of reads repaired from the table)
  *
@@ -686,6 +689,77 @@ int kmc_unitig_simplify(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, ui
 /* kmc_unitig_clean_into with the bubble rule: one step of a round that also pops bubbles. */
 int kmc_unitig_simplify_into(kmc_ctx* src, kmc_ctx* dst, uint64_t min_count, uint64_t max_count, uint64_t max_tip_keys,
                              uint64_t max_island_keys, uint64_t max_bubble_keys, uint64_t* summary);
+
+/* ---- the compacted graph as a whole: its connected components labelled, the small ones dropped (additions, as above).
+ * Everything refers to the unitigs and the link records of kmc_unitigs / kmc_unitig_links for the same view and range
+ * min_count..max_count; m_u, A_u and rec(e) are as in the clean block above.
+ * ADJACENT.  Unitigs u and v are adjacent iff some record of an end of u targets an end of v, or some record of an end of v
+ *   targets an end of u.  The union matters: around palindromic keys (even k, canonical) the record set need not be
+ *   symmetric.  No special case is made: the formula is the definition.  Self records (hairpins, the END -> START record of a
+ *   cut cycle) relate a unitig to itself and change nothing.
+ * COMPONENT.  An equivalence class of the reflexive-transitive closure of ADJACENT.  Every unitig is in exactly one.
+ * ROOT.  The smallest unitig id of a component.
+ * NUMBERING.  Components are numbered 0..n_comps-1 by ascending ROOT, so component 0 contains unitig 0.  The numbering
+ *   depends on the view and the range alone.
+ * Per component c: unitigs(c), keys(c) = the sum of m_u, abund(c) = the sum of A_u (exact, uint64_t).
+ * SMALL.  c is small iff keys(c) <= max_component_keys.  max_component_keys == 0 makes nothing small, 2^31 or more is
+ *   unlimited (the rule of the clean limits).  There is NO exemption for circular unitigs -- the one place where this rule
+ *   differs from ISLAND: a one-unitig cycle of m <= max_component_keys keys is a small component, while kmc_unitig_clean
+ *   never calls a circular unitig an island.
+ * VERDICT.  verdict[u], a uint8_t: KMC_CLEAN_KEEP, or KMC_CLEAN_COMPONENT when u's component is small.
+ * KEPT TABLE.  The solid keys whose unitig's verdict is KEEP, in view order, with their counts: the shape of a view, exactly
+ *   as kmc_unitig_clean* hands one out, so that it goes straight into kmc_merge_pairs_device.
+ * Outputs.  comp_of[n_unitigs], uint32_t: the component number of each unitig.  comp_stats[n_comps *
+ *   KMC_COMPONENT_STAT_WORDS], uint64_t, four words per component: [0] ROOT, [1] unitigs, [2] keys, [3] abund.
+ *   verdict[n_unitigs].  The kept table.
+ * summary[KMC_COMPONENT_WORDS]: [0] unitigs, [1] components, [2] components of one unitig, [3] the most keys in one
+ *   component, [4] the most unitigs in one component, [5] small components, [6] keys kept, [7] the sum of the counts of the
+ *   kept keys.
+ * IDENTITIES.  With t the kmc_unitigs summary and l the kmc_unitig_links summary of the same range: the sum of
+ *   comp_stats[.][1] == [0] == t[0]; the sum of comp_stats[.][2] == t[2]; the sum of comp_stats[.][3] == t[7]; [2] >= l[6]
+ *   (an isolated unitig is a one-unitig component, and so is a unitig that has only self records).  With limit 0 the kept
+ *   table equals kmc_export_filtered of the range.  With limits (tip 0, island N) every unitig kmc_unitig_clean calls ISLAND
+ *   is KMC_CLEAN_COMPONENT here with max_component_keys = N.
+ * Rules: those of kmc_unitig_links (NULL ctx, KMC_MODE_LR, a non-zero max_count below min_count: KMC_ERR_ARG; no view:
+ * KMC_ERR_STATE; the capacity rules of the links: KMC_ERR_CAPACITY).  An empty view or a range with nothing solid gives zeros
+ * and n_comps == 0.
+ * RELATION TO THE OTHER VIEW CALLS.  A components call counts as a kmc_unitig_links* call: it reuses the unitigs and links the
+ *   ctx still holds for this view and range under the condition of a clean call, otherwise it computes them and keeps them.  It
+ *   rewrites none of: the unitig arrays, the links, adj, the view, a partition, a filter or set-operation result, the query
+ *   index, a map or correct result, a clean / simplify result -- in particular the pointers a preceding
+ *   kmc_unitig_simplify_device handed out stay valid and unchanged.  Its own result is keyed by view, range and limit;
+ *   whatever drops the links (a kmc_unitigs* or kmc_unitig_links_device call, any call that computes them again) drops it.
+ * Diagnostic: with KMC_UNITIG_TRACE set, a components pass that computes prints "kmc_unitig_components: keys N unitigs U
+ * records R components C small S kept K rounds T label_ms .. number_ms .. stats_ms .. keep_ms .." to stderr, behind the lines
+ * of the unitigs and links it had to compute (tools/measure_components.py reads it); T counts the label rounds up to and
+ * including the one that hooked nothing. ---- */
+#define KMC_COMPONENT_WORDS 8
+#define KMC_COMPONENT_STAT_WORDS 4
+#define KMC_CLEAN_COMPONENT 4
+/* comp_of, comp_stats, verdict and the kept table in ctx-owned device memory, valid until the next kmc_unitig_components*,
+ * kmc_unitig_links*, kmc_unitigs* or kmc_graph* call / finalize / reset / destroy (same ordering contract as
+ * kmc_export_device; a clean or simplify call shares scratch with this one but leaves these arrays alone).  Every output
+ * pointer may be NULL.  Always computes the components pass. */
+int kmc_unitig_components_device(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, uint64_t max_component_keys,
+                                 const void** d_comp_of, const void** d_comp_stats, const void** d_verdict,
+                                 const void** d_key_hi, const void** d_key_lo, const void** d_count,
+                                 uint64_t* n_comps, uint64_t* n_unitigs, uint64_t* n_kept, uint64_t* summary);
+/* The same, copied to the caller's arrays: comp_of (uint32_t) and verdict of cap_unitigs entries each, comp_stats of
+ * cap_comps * KMC_COMPONENT_STAT_WORDS words, key_hi / key_lo / count of cap_keys entries each.  Every output pointer may be
+ * NULL (an array that is NULL is not copied and its cap not looked at).  *n_comps, *n_unitigs and *n_kept are always set; a
+ * cap too small for an array that was given -> KMC_ERR_ARG and nothing is copied.  All arrays NULL is the sizing /
+ * summary-only call.  A call whose ctx still holds the result for this very view, range and limit copies from it: the sizing
+ * call followed by the call that copies computes once. */
+int kmc_unitig_components(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, uint64_t max_component_keys,
+                          uint32_t* comp_of, uint8_t* verdict, uint64_t cap_unitigs, uint64_t* comp_stats, uint64_t cap_comps,
+                          uint64_t* key_hi, uint64_t* key_lo, uint64_t* count, uint64_t cap_keys,
+                          uint64_t* n_comps, uint64_t* n_unitigs, uint64_t* n_kept, uint64_t* summary);
+/* kmc_unitig_clean_into with this rule: kmc_unitig_components_device on src, then the kept pairs merged into dst as
+ * kmc_merge_pairs_device(dst, ...) would; the merge has finished when the call returns.  dst must differ from src and agree
+ * with it in device, mode, k and canonical (KMC_ERR_ARG otherwise; errors are reported on src); dst is left un-finalized.
+ * summary may be NULL. */
+int kmc_unitig_components_into(kmc_ctx* src, kmc_ctx* dst, uint64_t min_count, uint64_t max_count,
+                               uint64_t max_component_keys, uint64_t* summary);
 
 /* Multi-GPU reduce for small tables: ONE fixed-size all-gather instead of size exchange +
  * all-to-all (the reduce of main.rs:87's grouping across GPUs; for the generator's input a table is

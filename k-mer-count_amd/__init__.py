@@ -93,6 +93,7 @@ ABI_SYMBOLS = [
     "kmc_unitig_links", "kmc_unitig_links_device",
     "kmc_unitig_clean", "kmc_unitig_clean_device", "kmc_unitig_clean_into",
     "kmc_unitig_simplify", "kmc_unitig_simplify_device", "kmc_unitig_simplify_into",
+    "kmc_unitig_components", "kmc_unitig_components_device", "kmc_unitig_components_into",
     "kmc_unitig_map", "kmc_unitig_map_device",
     "kmc_correct", "kmc_correct_device",
 ]
@@ -108,6 +109,9 @@ CLEAN_WORDS = 8    # KMC_CLEAN_WORDS: unitigs, tips, islands, keys kept / of tip
 CLEAN_KEEP, CLEAN_TIP, CLEAN_ISLAND = 0, 1, 2   # KMC_CLEAN_*: a unitig's verdict byte
 SIMPLIFY_WORDS = 12  # KMC_SIMPLIFY_WORDS: the clean words, then bubbles, their keys, bubble candidates, the counts of their keys
 CLEAN_BUBBLE = 3     # KMC_CLEAN_BUBBLE: the fourth verdict, of a simplify call
+COMPONENT_WORDS = 8       # KMC_COMPONENT_WORDS: unitigs, components, those of one unitig, most keys / unitigs in one, small ones, keys kept, their counts
+COMPONENT_STAT_WORDS = 4  # KMC_COMPONENT_STAT_WORDS: a component's root, unitigs, keys, abundance
+CLEAN_COMPONENT = 4       # KMC_CLEAN_COMPONENT: the verdict of a unitig in a small component, of a components call
 MAP_WORDS = 8        # KMC_MAP_WORDS: reads, valid windows, placed windows, segments, crossings, fully placed reads, unplaced reads, most segments
 MAP_READ_WORDS = 4   # KMC_MAP_READ_WORDS: a read's valid windows, placed windows, segments, crossings
 MAP_NONE = 0xFFFFFFFF  # KMC_MAP_NONE: the low half of the place word of a window that is not placed
@@ -191,6 +195,9 @@ def lib() -> C.CDLL:
     L.kmc_unitig_simplify_device.argtypes = [vp, u64, u64, u64, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), pu64, pu64, vp]
     L.kmc_unitig_simplify.argtypes = [vp, u64, u64, u64, u64, u64, vp, vp, vp, u64, vp, u64, pu64, pu64, vp]
     L.kmc_unitig_simplify_into.argtypes = [vp, vp, u64, u64, u64, u64, u64, vp]
+    L.kmc_unitig_components_device.argtypes = [vp, u64, u64, u64] + [C.POINTER(vp)] * 6 + [pu64, pu64, pu64, vp]
+    L.kmc_unitig_components.argtypes = [vp, u64, u64, u64, vp, vp, u64, vp, u64, vp, vp, vp, u64, pu64, pu64, pu64, vp]
+    L.kmc_unitig_components_into.argtypes = [vp, vp, u64, u64, u64, vp]
     L.kmc_unitig_map_device.argtypes = [vp, u64, u64, vp, vp, u64, u64] + [C.POINTER(vp)] * 5 + [pu64, pu64, vp]
     L.kmc_unitig_map.argtypes = [vp, u64, u64, vp, vp, u64, vp, vp, vp, vp, u64, vp, u64, pu64, pu64, vp]
     L.kmc_correct_device.argtypes = [vp, u64, u64, vp, vp, u64, u64] + [C.POINTER(vp)] * 4 + [pu64, vp]
@@ -734,6 +741,60 @@ class SimplifiedUnitigs:
     summary: SimplifySummary
 
 
+_COMPONENT_FIELDS = ("unitigs", "components", "single_unitig", "max_keys", "max_unitigs", "small", "kept_keys", "kept_count")
+
+
+@dataclass
+class ComponentSummary:
+    """The eight words of kmc_unitig_components: unitigs, components, components of one unitig, the most keys and the most
+    unitigs in one component, small components, the keys kept, the sum of the counts of the kept keys."""
+    unitigs: int
+    components: int
+    single_unitig: int
+    max_keys: int
+    max_unitigs: int
+    small: int
+    kept_keys: int
+    kept_count: int
+
+    @classmethod
+    def from_words(cls, words) -> "ComponentSummary":
+        return cls(*[int(w) for w in words])
+
+    def words(self) -> list:
+        return [getattr(self, f) for f in _COMPONENT_FIELDS]
+
+    @property
+    def removed(self) -> int:
+        """Components this pass takes out."""
+        return self.small
+
+    def to_text(self) -> str:
+        """``NAME\tVALUE`` lines."""
+        return "\n".join("%s\t%d" % (f, getattr(self, f)) for f in _COMPONENT_FIELDS) + "\n"
+
+
+@dataclass
+class Components:
+    """What KmerCounter.components returns: ``comp_of`` uint32[n unitigs] (the component of each unitig, indexed as
+    unitigs() numbers them; components are numbered by their smallest unitig), ``stats`` uint64[n components, 4] (root,
+    unitigs, keys, abundance), ``verdict`` uint8[n unitigs] (CLEAN_KEEP / CLEAN_COMPONENT), ``table`` (the keys of the kept
+    unitigs with their counts, in view order), ``summary``."""
+    comp_of: np.ndarray
+    stats: np.ndarray
+    verdict: np.ndarray
+    table: "Table"
+    summary: ComponentSummary
+
+    def members(self, c: int) -> np.ndarray:
+        """The unitigs of component ``c``, ascending."""
+        return np.flatnonzero(self.comp_of == c)
+
+    def to_text(self) -> str:
+        """What ``k-mer-count --components`` prints: ``COMPONENT\tROOT\tUNITIGS\tKEYS\tABUND`` lines."""
+        return "".join("%d\t%d\t%d\t%d\t%d\n" % ((i,) + tuple(r)) for i, r in enumerate(self.stats.tolist()))
+
+
 def parse_fasta(path: str) -> Tuple[np.ndarray, np.ndarray]:
     """Host FASTA reader of libkmc (the reader the reference uses, main.rs:45-46,59-62).
     Returns (bases uint8[n_bases], offsets uint64[n_reads+1])."""
@@ -1180,6 +1241,41 @@ class KmerCounter:
             if out[-1].removed == 0:
                 break
         return src, out
+
+    # -- that graph as a whole: connected components labelled, the small ones dropped --
+    def components(self, min_count: int = 1, max_count: int = 0, max_component_keys: int = 0) -> "Components":
+        """kmc_unitig_components: the connected component of every unitig of unitigs() / unitig_links() with the same range,
+        root / unitigs / keys / abundance per component, and the table without the components of at most
+        max_component_keys keys (0: none is dropped).  Two calls, one computation."""
+        lo, hi, lim = int(min_count), int(max_count), int(max_component_keys)
+        nc, nu, nk = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        w = (C.c_uint64 * COMPONENT_WORDS)()
+        self._chk(self._L.kmc_unitig_components(self._h, lo, hi, lim, None, None, 0, None, 0, None, None, None, 0, C.byref(nc), C.byref(nu),
+                                                C.byref(nk), w))
+        khi, klo, cnt = (np.zeros(nk.value, np.uint64) for _ in range(3))
+        comp_of, verdict = np.zeros(nu.value, np.uint32), np.zeros(nu.value, np.uint8)
+        stats = np.zeros((nc.value, COMPONENT_STAT_WORDS), np.uint64)
+        ptr = lambda a: a.ctypes.data if a.size else None
+        self._chk(self._L.kmc_unitig_components(self._h, lo, hi, lim, ptr(comp_of), ptr(verdict), nu.value, ptr(stats), nc.value, ptr(khi), ptr(klo),
+                                                ptr(cnt), nk.value, C.byref(nc), C.byref(nu), C.byref(nk), w))
+        return Components(comp_of, stats, verdict, Table(khi, klo, cnt, self.k), ComponentSummary.from_words(list(w)))
+
+    def components_device(self, min_count: int = 1, max_count: int = 0, max_component_keys: int = 0):
+        """(d_comp_of, d_comp_stats, d_verdict, d_key_hi or 0, d_key_lo, d_count, n_comps, n_unitigs, n_kept, ComponentSummary)
+        of kmc_unitig_components_device: ctx-owned device arrays; the three of the kept table can be handed to another
+        counter's merge_pairs_device."""
+        p = [C.c_void_p() for _ in range(6)]
+        nc, nu, nk = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        w = (C.c_uint64 * COMPONENT_WORDS)()
+        self._chk(self._L.kmc_unitig_components_device(self._h, int(min_count), int(max_count), int(max_component_keys), *[C.byref(x) for x in p],
+                                                       C.byref(nc), C.byref(nu), C.byref(nk), w))
+        return tuple(x.value or 0 for x in p) + (nc.value, nu.value, nk.value, ComponentSummary.from_words(list(w)))
+
+    def components_into(self, dst: "KmerCounter", min_count: int = 1, max_count: int = 0, max_component_keys: int = 0) -> "ComponentSummary":
+        """kmc_unitig_components_into: the keys of self outside small components merged into dst's table (dst is not finalized)."""
+        w = (C.c_uint64 * COMPONENT_WORDS)()
+        self._chk(self._L.kmc_unitig_components_into(self._h, dst._h, int(min_count), int(max_count), int(max_component_keys), w))
+        return ComponentSummary.from_words(list(w))
 
     # -- and simple bubbles popped: the arm of a fork-and-rejoin that loses against its parallel arm --
     def _simplify_limits(self, max_tip_keys, max_island_keys, max_bubble_keys) -> Tuple[int, int, int]:

@@ -7,7 +7,8 @@
 //   k-mer-count [FASTA] [-k K] [--forward] [--expand] [--device N | --gpus N] [--algo auto|stream|walk|sort] [--stats]
 //               [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE | --map FILE | --correct FILE]
 //               [--with FASTA2 (--compare | --setop intersect|union|subtract [--counts left|right|min|max|sum|diff])]
-//               [--graph | --graph-stats | --unitigs | --gfa] [--clean ROUNDS [--tip-keys N] [--island-keys N] [--bubble-keys N]]
+//               [--graph | --graph-stats | --unitigs | --gfa | --components]
+//               [--clean ROUNDS [--tip-keys N] [--island-keys N] [--bubble-keys N]] [--component-keys N]
 //
 //   --gpus N  the file's chunks go round-robin to GPUs 0..N-1 of this process, tables reduced on GPU 0
 //             (there is no CPU backend: SURVEY.md's "--backend cpu" is deliberately absent)
@@ -70,6 +71,13 @@
 //               Without the option nothing is popped.  The per-round --stats line gains "bubbles B bubble_keys K
 //               bubble_candidates C"; a round that removes nothing, bubbles included, is the last.
 //
+//   --components         (with -k K) instead of the table: the connected components of the unitig graph (kmc_unitig_components), one
+//               line per component in order "COMPONENT<TAB>ROOT<TAB>UNITIGS<TAB>KEYS<TAB>ABUND": its number, its smallest unitig, how many
+//               unitigs and keys it has and the summed count of its keys.  Same solidity range.
+//   --component-keys N   (with -k K) after any --clean rounds and before whichever output was asked for, the connected components
+//               of at most N keys are taken out of the table (kmc_unitig_components_into, one step; 0: none).  It needs no
+//               --clean.  With --stats one line on stderr.
+//
 // Errors: message on stderr, exit code 101 (what a Rust panic exits with), never partial stdout.
 #include <errno.h>
 #include <limits.h>
@@ -124,6 +132,8 @@ int main(int argc, char** argv) {
     int clean = 0;
     long long tip_keys = -1, island_keys = -1;   // (-1: K)
     long long bubble_keys = -1;                  // (-1: no bubble is popped, the rounds are kmc_unitig_clean_into's)
+    int components = 0;
+    long long component_keys = -1;               // (-1: no component step)
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         if (a == "-k" && i + 1 < argc) { if (!parse_int("-k", argv[++i], 1, 63, &k)) return 2; }
@@ -145,6 +155,8 @@ int main(int argc, char** argv) {
         else if (a == "--graph-stats") graph_stats = 1;
         else if (a == "--unitigs") unitigs = 1;
         else if (a == "--gfa") gfa = 1;
+        else if (a == "--components") components = 1;
+        else if (a == "--component-keys" && i + 1 < argc) { if (!parse_count("--component-keys", argv[++i], 0, LLONG_MAX, &component_keys)) return 2; }
         else if (a == "--clean" && i + 1 < argc) { if (!parse_int("--clean", argv[++i], 1, 1000, &clean)) return 2; }
         else if (a == "--tip-keys" && i + 1 < argc) { if (!parse_count("--tip-keys", argv[++i], 0, LLONG_MAX, &tip_keys)) return 2; }
         else if (a == "--island-keys" && i + 1 < argc) { if (!parse_count("--island-keys", argv[++i], 0, LLONG_MAX, &island_keys)) return 2; }
@@ -165,11 +177,12 @@ int main(int argc, char** argv) {
             fprintf(stderr, "usage: k-mer-count [FASTA] [-k K] [--forward] [--expand] [--device N | --gpus N] [--algo auto|stream|walk|sort] [--stats]\n"
                             "                   [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE | --map FILE | --correct FILE]\n"
                             "                   [--with FASTA2 (--compare | --setop intersect|union|subtract [--counts left|right|min|max|sum|diff])]\n"
-                            "                   [--graph | --graph-stats | --unitigs | --gfa] [--clean ROUNDS [--tip-keys N] [--island-keys N] [--bubble-keys N]]\n");
+                            "                   [--graph | --graph-stats | --unitigs | --gfa | --components]\n"
+                            "                   [--clean ROUNDS [--tip-keys N] [--island-keys N] [--bubble-keys N]] [--component-keys N]\n");
             return 0;
         } else if (a == "-k" || a == "--device" || a == "--gpus" || a == "--algo" || a == "--min-count" || a == "--max-count" || a == "--histo" ||
                    a == "--query-kmers" || a == "--profile" || a == "--map" || a == "--correct" || a == "--with" || a == "--setop" || a == "--counts" ||
-                   a == "--clean" || a == "--tip-keys" || a == "--island-keys" || a == "--bubble-keys") {
+                   a == "--clean" || a == "--tip-keys" || a == "--island-keys" || a == "--bubble-keys" || a == "--component-keys") {
             fprintf(stderr, "k-mer-count: %s needs a value\n", a.c_str());
             return 2;
         } else if (!a.empty() && a[0] != '-') path = argv[i];
@@ -279,6 +292,23 @@ int main(int argc, char** argv) {
         else if (with_path || compare || setop >= 0) bad = "--clean and --with / --compare / --setop exclude each other";
         if (bad) { fprintf(stderr, "k-mer-count: %s\n", bad); return 2; }
     }
+    // --components / --component-keys: the same
+    if (components) {
+        const char* bad = nullptr;
+        if (!k) bad = "needs -k K";
+        else if (graph || graph_stats || unitigs || gfa) bad = "--graph / --graph-stats / --unitigs / --gfa exclude each other";
+        else if (histo) bad = "--histo exclude each other";
+        else if (query_path || profile_path || map_path || correct_path) bad = "--query-kmers / --profile / --map / --correct exclude each other";
+        else if (with_path || compare || setop >= 0) bad = "--with / --compare / --setop exclude each other";
+        else if (expand) bad = "--expand exclude each other";
+        if (bad) { fprintf(stderr, "k-mer-count: --components %s%s\n", strncmp(bad, "needs", 5) ? "and " : "", bad); return 2; }
+    }
+    if (component_keys >= 0) {
+        const char* bad = nullptr;
+        if (!k) bad = "--component-keys needs -k K";
+        else if (with_path || compare || setop >= 0) bad = "--component-keys and --with / --compare / --setop exclude each other";
+        if (bad) { fprintf(stderr, "k-mer-count: %s\n", bad); return 2; }
+    }
     const bool filtered = min_count > 1 || max_count != 0;
     kmc_config cfg;
     memset(&cfg, 0, sizeof(cfg));
@@ -340,6 +370,28 @@ int main(int argc, char** argv) {
         }
         ctx = next;
         if (w[1] + w[2] + w[8] == 0) break;
+    }
+    // --component-keys: one more step of the same kind, the table without its small components
+    if (component_keys >= 0) {
+        cfg.device = gpus == 1 ? device : (share ? atoi(share) : 0);
+        kmc_ctx* next = nullptr;
+        rc = kmc_create(&next, &cfg);
+        if (rc) { int r = die("kmc_create", kmc_last_error(nullptr)); destroy_all(); return r; }
+        ctxs.push_back(next);
+        uint64_t w[KMC_COMPONENT_WORDS] = {0};
+        rc = kmc_unitig_components_into(ctx, next, (uint64_t)min_count, (uint64_t)max_count, (uint64_t)component_keys, w);
+        if (rc) { int r = die("kmc_unitig_components_into", kmc_last_error(ctx)); destroy_all(); return r; }
+        rc = kmc_finalize(next, &nd, &nt);
+        if (rc) { int r = die("kmc_finalize", kmc_last_error(next)); destroy_all(); return r; }
+        if (stats)
+            fprintf(stderr, "component step unitigs %llu components %llu single_unitig %llu max_keys %llu max_unitigs %llu small %llu kept_keys %llu kept_count %llu\n",
+                    (unsigned long long)w[0], (unsigned long long)w[1], (unsigned long long)w[2], (unsigned long long)w[3], (unsigned long long)w[4],
+                    (unsigned long long)w[5], (unsigned long long)w[6], (unsigned long long)w[7]);
+        if (ctx != counted) {
+            kmc_destroy(ctx);
+            ctxs.erase(std::find(ctxs.begin(), ctxs.end(), ctx));
+        }
+        ctx = next;
     }
     std::vector<char> obuf(1 << 22);
     if (with_path) {
@@ -507,6 +559,24 @@ int main(int argc, char** argv) {
                    (unsigned long long)ua[u], (unsigned)(uf[u] & KMC_UNITIG_CIRCULAR));
             fwrite(ub.data() + uo[u], 1, (size_t)(uo[u + 1] - uo[u]), stdout);
             fputc('\n', stdout);
+        }
+        fflush(stdout);
+        destroy_all();
+        return 0;
+    }
+    if (components) {   // size, then copy: the ctx computes once
+        uint64_t nc = 0, nu = 0, nk = 0;
+        const uint64_t lo_c = (uint64_t)min_count, hi_c = (uint64_t)max_count;
+        rc = kmc_unitig_components(ctx, lo_c, hi_c, 0, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, &nc, &nu, &nk, nullptr);
+        if (rc) { int r = die("kmc_unitig_components", kmc_last_error(ctx)); destroy_all(); return r; }
+        std::vector<uint64_t> cs((size_t)(nc ? nc : 1) * KMC_COMPONENT_STAT_WORDS);
+        rc = kmc_unitig_components(ctx, lo_c, hi_c, 0, nullptr, nullptr, 0, cs.data(), nc, nullptr, nullptr, nullptr, 0, &nc, &nu, &nk, nullptr);
+        if (rc) { int r = die("kmc_unitig_components", kmc_last_error(ctx)); destroy_all(); return r; }
+        setvbuf(stdout, obuf.data(), _IOFBF, obuf.size());
+        for (uint64_t c = 0; c < nc; ++c) {
+            const uint64_t* w = &cs[(size_t)c * KMC_COMPONENT_STAT_WORDS];
+            printf("%llu\t%llu\t%llu\t%llu\t%llu\n", (unsigned long long)c, (unsigned long long)w[0], (unsigned long long)w[1],
+                   (unsigned long long)w[2], (unsigned long long)w[3]);
         }
         fflush(stdout);
         destroy_all();

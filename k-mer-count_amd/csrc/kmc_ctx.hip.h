@@ -235,6 +235,15 @@ struct kmc_ctx : CtxStream {
     DevBuf cl_verdict, cl_row, cl_part;
     ResultKey cl_key;
     u64 cl_tip = 0, cl_isl = 0, cl_bub = 0, cl_kept = 0, cl_words[12] = {};
+    // kmc_unitig_components* (kmc_components.hip.h) read the unitigs and the links.  Their result, in buffers of their own
+    // (a clean / simplify result stays as it is): the component per unitig, four words per component, the verdict per
+    // unitig and the kept table, with cc_key plus its limit cc_limit and cc_words as above, cc_comps components and
+    // cc_kept keys.  Whatever drops l_key drops cc_key.  Work arrays: the parents of the label rounds, the root flags and
+    // their scan, the totals per workgroup of the summary pass, the control words and round counters.
+    KeyBufs cc;
+    DevBuf cc_comp, cc_stats, cc_verdict, cc_parent, cc_flag, cc_rank, cc_part, cc_ctl;
+    ResultKey cc_key;
+    u64 cc_limit = 0, cc_kept = 0, cc_comps = 0, cc_words[8] = {};
 };
 
 #pragma GCC visibility push(hidden)   // what follows is shared between the translation units, never exported

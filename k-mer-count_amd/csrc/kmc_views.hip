@@ -14,6 +14,7 @@
 #include "kmc_unitig.hip.h"
 #include "kmc_links.hip.h"
 #include "kmc_clean.hip.h"
+#include "kmc_components.hip.h"
 #include "kmc_map.hip.h"
 #include "kmc_correct.hip.h"
 
@@ -717,7 +718,7 @@ static int unitig_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count
     memset(h, 0, KMC_UNITIG_WORDS * sizeof(u64));
     const u64 n = c->n_sorted, n2 = 2 * n;
     int rc;
-    c->u_key.drop(); c->l_key.drop();   // the result arrays are rewritten from here on (and the links of the old ones go with them)
+    c->u_key.drop(); c->l_key.drop(); c->cc_key.drop();   // the result arrays are rewritten from here on (and the links of the old ones, and their components, go with them)
     if ((rc = ensure(c, c->u_offs, sizeof(u64))) || (rc = ensure(c, c->u_bases, 64)) || (rc = ensure(c, c->u_abund, sizeof(u64))) ||
         (rc = ensure(c, c->u_flags, 8)))
         return rc;
@@ -900,7 +901,7 @@ static int links_run(kmc_ctx* c, const char* what, u64* h) {
     memset(h, 0, KMC_LINK_WORDS * sizeof(u64));
     const u64 n = c->n_sorted, nu = c->u_words[0], ne = 2 * nu;
     int rc;
-    c->l_key.drop();
+    c->l_key.drop(); c->cc_key.drop();
     if ((rc = ensure(c, c->l_offs, (size_t)(ne + 1) * sizeof(u64))) || (rc = ensure(c, c->l_to, sizeof(u32)))) return rc;
     if (!nu) {   // an empty view, or one without a solid key
         HIPCHK(c, hipMemsetAsync(c->l_offs.p, 0, sizeof(u64), c->stream));
@@ -1465,6 +1466,228 @@ static int kmc_unitig_clean_into_impl(kmc_ctx* src, kmc_ctx* dst, uint64_t min_c
     return KMC_OK;
 }
 
+// ---- the connected components of the compacted graph: a number per unitig, four words per component, the small ones
+// dropped from the kept table (kmc_components.hip.h) ----
+static bool components_kept(const kmc_ctx* c, u64 min_count, u64 max_count, u64 limit) {
+    return c->cc_key.holds(c->view_gen, min_count, max_count) && c->cc_limit == limit;
+}
+
+// The label rounds on cc_parent (kmc_components.hip.h): batches of KMC_CC_ROUND_BATCH hook + shortcut rounds, their counters
+// read in one copy, until a hook pass that hooked nothing.  A hook pass that hooks leaves a root fewer, so nu passes are the
+// most there can be; beyond that the call fails.  *rounds: the passes up to and including the quiet one.
+static int components_label(kmc_ctx* c, const char* what, u64 nu, u64 nl, u32* rounds) {
+    u32* parent = (u32*)c->cc_parent.p;
+    kmc_ull* ctl = (kmc_ull*)c->cc_ctl.p;
+    kmc_ull* cnt = ctl + KMC_CC_ROUNDS_AT;
+    const u32 grid_u = (u32)((nu + KMC_CC_THREADS - 1) / KMC_CC_THREADS);
+    const u32 grid_e = (u32)std::min<u64>((2 * nu + KMC_CC_THREADS - 1) / KMC_CC_THREADS, (u64)c->n_cu * 4);
+    hipLaunchKernelGGL(kmc_cc_init_kernel, dim3(grid_u), dim3(KMC_CC_THREADS), 0, c->stream, parent, nu);
+    const u64 max_rounds = nu;
+    u64 t = 0;
+    bool done = false;
+    while (!done && t < max_rounds) {
+        const int batch = (int)std::min<u64>(KMC_CC_ROUND_BATCH, max_rounds - t);
+        u64 h[KMC_CC_ROUND_BATCH] = {0};
+        HIPCHK(c, hipMemsetAsync(cnt, 0, KMC_CC_ROUND_BATCH * sizeof(u64), c->stream));
+        for (int i = 0; i < batch; ++i) {
+            hipLaunchKernelGGL(kmc_cc_hook_kernel, dim3(grid_e), dim3(KMC_CC_THREADS), 0, c->stream, (const u64*)c->l_offs.p, (const u32*)c->l_to.p,
+                               nu, nl, parent, cnt + i, ctl);
+            hipLaunchKernelGGL(kmc_cc_shortcut_kernel, dim3(grid_u), dim3(KMC_CC_THREADS), 0, c->stream, parent, nu, ctl);
+        }
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (int i = 0; i < batch && !done; ++i) { ++t; done = h[i] == 0; }
+    }
+    *rounds = (u32)std::min<u64>(t, 0xFFFFFFFFull);
+    if (!done) return fail(c, KMC_ERR_HIP, "internal error: %s still hooked after %llu rounds over %llu unitigs", what, (unsigned long long)t, (unsigned long long)nu);
+    return KMC_OK;
+}
+
+// The components pass behind the unitigs and links of this view and range -- those the ctx holds under clean_run's
+// condition, otherwise computed and kept -- into the cc_* buffers, the summary into cc_words; finished when it returns.
+// It shares the scratch of a compaction and the class bytes per row (cl_row) with the clean pass and writes nothing else of it.
+static int components_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count, u64 limit) {
+    int rc;
+    u64 lw[KMC_LINK_WORDS];
+    const bool held = c->u_live && c->u_key.holds(c->view_gen, min_count, max_count);
+    if ((rc = links_result(c, what, min_count, max_count, held, lw))) return rc;
+    c->cc_key.drop();
+    const u64 n = c->n_sorted, nu = lw[0], nl = lw[1];
+    u64 w[KMC_CC_ROUNDS_AT] = {0}, h[KMC_C_CTL_WORDS] = {0}, nc = 0;
+    u32 rounds = 0;
+    if ((rc = ensure(c, c->cc_comp, (size_t)std::max<u64>(nu, 2) * sizeof(u32))) || (rc = ensure(c, c->cc_verdict, (size_t)std::max<u64>(nu, 8))) ||
+        (rc = ensure(c, c->cc_stats, KMC_COMPONENT_STAT_WORDS * sizeof(u64))) || (rc = ensure(c, c->cl_row, (size_t)std::max<u64>(n, 8))))
+        return rc;
+    UnitigTrace tr;
+    tr.mark(c->stream);
+    if (nu) {
+        if (nu > n || c->u_words[0] != nu) return fail(c, KMC_ERR_HIP, "internal error: %s holds %llu unitigs, its links %llu", what, (unsigned long long)c->u_words[0], (unsigned long long)nu);
+        const size_t ub = (size_t)nu * sizeof(u32);
+        if ((rc = ensure(c, c->cc_parent, ub)) || (rc = ensure(c, c->cc_flag, ub)) || (rc = ensure(c, c->cc_rank, ub)) ||
+            (rc = ensure(c, c->cc_ctl, KMC_CC_CTL_BYTES)) ||
+            (rc = ensure(c, c->c_bsum, (size_t)((nu + KMC_SCAN_PER_BLOCK - 1) / KMC_SCAN_PER_BLOCK + 2) * sizeof(u32))))
+            return rc;
+        kmc_ull* ctl = (kmc_ull*)c->cc_ctl.p;
+        HIPCHK(c, hipMemsetAsync(ctl, 0, KMC_CC_CTL_BYTES, c->stream));
+        if ((rc = components_label(c, what, nu, nl, &rounds))) return rc;
+        tr.mark(c->stream);
+        // number
+        const u32 grid_u = (u32)((nu + KMC_CC_THREADS - 1) / KMC_CC_THREADS);
+        hipLaunchKernelGGL(kmc_cc_flag_kernel, dim3(grid_u), dim3(KMC_CC_THREADS), 0, c->stream, (const u32*)c->cc_parent.p, nu, (u32*)c->cc_flag.p, ctl);
+        launch_exclusive_scan<0>(c->stream, c->cc_flag.p, (u32)nu, (u32*)c->c_bsum.p, (u32*)c->cc_rank.p, (u32*)ctl);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(w, ctl, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        nc = w[0] & 0xFFFFFFFFull;
+        if (w[KMC_CC_BAD] || !nc || nc > nu)
+            return fail(c, KMC_ERR_HIP, "internal error: %s met %llu indices outside their arrays (%llu components of %llu unitigs)", what,
+                        (unsigned long long)w[KMC_CC_BAD], (unsigned long long)nc, (unsigned long long)nu);
+        const size_t stb = (size_t)nc * KMC_COMPONENT_STAT_WORDS * sizeof(u64);
+        const u32 grid_c = (u32)std::min<u64>((nc + KMC_CC_THREADS - 1) / KMC_CC_THREADS, (u64)c->n_cu * 8);
+        if ((rc = ensure(c, c->cc_stats, stb)) || (rc = ensure(c, c->cc_part, (size_t)grid_c * KMC_CC_PART * sizeof(u64)))) return rc;
+        kmc_ull* stats = (kmc_ull*)c->cc_stats.p;
+        HIPCHK(c, hipMemsetAsync(stats, 0, stb, c->stream));
+        hipLaunchKernelGGL(kmc_cc_number_kernel, dim3(grid_u), dim3(KMC_CC_THREADS), 0, c->stream, (const u32*)c->cc_parent.p, (const u32*)c->cc_rank.p,
+                           nu, nc, (u32*)c->cc_comp.p, stats, ctl);
+        HIPCHK(c, hipGetLastError());
+        tr.mark(c->stream);
+        // the words of every component, the verdicts, the summary
+        hipLaunchKernelGGL(kmc_cc_stats_kernel, dim3(grid_u), dim3(KMC_CC_THREADS), 0, c->stream, (const u64*)c->u_offs.p, (const u64*)c->u_abund.p,
+                           (u64)(c->klen - 1), (const u32*)c->cc_comp.p, nu, nc, stats, ctl);
+        hipLaunchKernelGGL(kmc_cc_verdict_kernel, dim3(grid_u), dim3(KMC_CC_THREADS), 0, c->stream, (const u32*)c->cc_comp.p, (const kmc_ull*)stats, nu,
+                           nc, limit, (uint8_t*)c->cc_verdict.p, ctl);
+        hipLaunchKernelGGL(kmc_cc_summary_kernel, dim3(grid_c), dim3(KMC_CC_THREADS), 0, c->stream, (const kmc_ull*)stats, nc, limit, (kmc_ull*)c->cc_part.p);
+        hipLaunchKernelGGL(kmc_cc_reduce_kernel, dim3(1), dim3(KMC_CC_THREADS), 0, c->stream, (const kmc_ull*)c->cc_part.p, grid_c, ctl);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(w, ctl, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        tr.mark(c->stream);
+        if (w[KMC_CC_BAD] || w[KMC_CC_SMALLKEYS] > c->u_words[2])
+            return fail(c, KMC_ERR_HIP, "internal error: %s met %llu indices outside their arrays (%llu keys in small components of %llu)", what,
+                        (unsigned long long)w[KMC_CC_BAD], (unsigned long long)w[KMC_CC_SMALLKEYS], (unsigned long long)c->u_words[2]);
+        // the kept table: the mark and scatter passes of the clean pass with this verdict array (any byte that is not KEEP
+        // removes a row; their tip and island totals stay 0)
+        const u64 n_tiles = (n + KMC_C_TILE - 1) / KMC_C_TILE;
+        if ((rc = compact_plan(c, n_tiles, KMC_C_CTL_WORDS))) return rc;
+        const u32 grid = (u32)std::min<u64>(n_tiles, (u64)c->n_cu * 8);
+        hipLaunchKernelGGL(kmc_clean_mark_kernel<false>, dim3(grid), dim3(KMC_C_THREADS), 0, c->stream, c->v_cnt, n, n_tiles,
+                           (const uint16_t*)c->g_adj.p, (const u32*)c->u_ptr[c->u_cur].p, (const u32*)c->u_join.p, c->cfg.canonical ? 1 : 0,
+                           (const uint8_t*)c->cc_verdict.p, nu, (uint8_t*)c->cl_row.p, (u32*)c->c_tile.p, (kmc_ull*)c->c_ctl.p, (kmc_ull*)nullptr);
+        if ((rc = compact_scan_and_read(c, n_tiles, h, KMC_C_CTL_WORDS))) return rc;
+        if (h[KMC_C_BAD] || h[0] != h[KMC_C_SUM + 3] || h[KMC_C_SUM + 4] || h[KMC_C_SUM + 5] || h[KMC_C_SUM + 3] + w[KMC_CC_SMALLKEYS] != c->u_words[2])
+            return fail(c, KMC_ERR_HIP, "internal error: %s met %llu indices outside their arrays (%llu kept + %llu small of %llu keys, %llu scanned)",
+                        what, (unsigned long long)h[KMC_C_BAD], (unsigned long long)h[KMC_C_SUM + 3], (unsigned long long)w[KMC_CC_SMALLKEYS],
+                        (unsigned long long)c->u_words[2], (unsigned long long)h[0]);
+    }
+    const u64 n_kept = h[0];
+    if ((rc = ensure_keys(c, c->cc, n_kept))) return rc;
+    if (n_kept) {
+        const KView v = view_of(c);
+        const u64 n_tiles = (n + KMC_C_TILE - 1) / KMC_C_TILE;
+        kmc_ull* ctl = (kmc_ull*)c->c_ctl.p;
+        with_kw(c, [&](auto KW) {
+            hipLaunchKernelGGL(kmc_clean_scatter_kernel<KW()>, dim3((u32)n_tiles), dim3(KMC_C_THREADS), 0, c->stream, v.hi, v.lo, v.cnt, v.n,
+                               (const uint8_t*)c->cl_row.p, (const u32*)c->c_tpos.p, n_kept, (u64*)c->cc.hi.p, (u64*)c->cc.lo.p, (u64*)c->cc.cnt.p, ctl);
+        });
+        HIPCHK(c, hipGetLastError());
+        u64 bad = 0;
+        HIPCHK(c, hipMemcpyAsync(&bad, ctl + KMC_C_BAD, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (bad) return fail(c, KMC_ERR_HIP, "internal error: %s could not place %llu kept keys", what, (unsigned long long)bad);
+    }
+    tr.mark(c->stream);
+    if (tr.on && nu && tr.n_ev == 5) {
+        float ms[4] = {0, 0, 0, 0};
+        bool ok = hipEventSynchronize(tr.ev[4]) == hipSuccess;
+        for (int i = 0; ok && i < 4; ++i) ok = hipEventElapsedTime(&ms[i], tr.ev[i], tr.ev[i + 1]) == hipSuccess;
+        if (ok)
+            fprintf(stderr, "kmc_unitig_components: keys %llu unitigs %llu records %llu components %llu small %llu kept %llu rounds %u "
+                    "label_ms %.4f number_ms %.4f stats_ms %.4f keep_ms %.4f\n", (unsigned long long)n, (unsigned long long)nu, (unsigned long long)nl,
+                    (unsigned long long)nc, (unsigned long long)w[KMC_CC_SMALL], (unsigned long long)n_kept, rounds, ms[0], ms[1], ms[2], ms[3]);
+    }
+    u64* s = c->cc_words;
+    s[0] = nu; s[1] = nc; s[2] = w[KMC_CC_SINGLE]; s[3] = w[KMC_CC_MAXKEYS]; s[4] = w[KMC_CC_MAXUNI]; s[5] = w[KMC_CC_SMALL];
+    s[6] = n_kept; s[7] = h[KMC_C_SUM + 7];
+    c->cc_kept = n_kept; c->cc_comps = nc;
+    c->cc_key.keep(c->view_gen, min_count, max_count); c->cc_limit = limit;
+    return KMC_OK;
+}
+
+static int kmc_unitig_components_device_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t max_component_keys,
+                                             const void** d_comp_of, const void** d_comp_stats, const void** d_verdict, const void** d_key_hi,
+                                             const void** d_key_lo, const void** d_count, uint64_t* n_comps, uint64_t* n_unitigs, uint64_t* n_kept,
+                                             uint64_t* summary, const char* what = "kmc_unitig_components_device") {
+    if (!c) return KMC_ERR_ARG;
+    int rc;
+    if ((rc = unitig_begin(c, what, min_count, max_count)) || (rc = components_run(c, what, min_count, max_count, clean_limit(max_component_keys))))
+        return rc;
+    publish_keys(c, c->cc, d_key_hi, d_key_lo, d_count);
+    if (d_comp_of) *d_comp_of = c->cc_comp.p;
+    if (d_comp_stats) *d_comp_stats = c->cc_stats.p;
+    if (d_verdict) *d_verdict = c->cc_verdict.p;
+    if (n_comps) *n_comps = c->cc_comps;
+    if (n_unitigs) *n_unitigs = c->cc_words[0];
+    if (n_kept) *n_kept = c->cc_kept;
+    if (summary) memcpy(summary, c->cc_words, sizeof(c->cc_words));
+    return KMC_OK;
+}
+
+static int kmc_unitig_components_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t max_component_keys, uint32_t* comp_of,
+                                      uint8_t* verdict, uint64_t cap_unitigs, uint64_t* comp_stats, uint64_t cap_comps, uint64_t* key_hi,
+                                      uint64_t* key_lo, uint64_t* count, uint64_t cap_keys, uint64_t* n_comps, uint64_t* n_unitigs, uint64_t* n_kept,
+                                      uint64_t* summary) {
+    if (n_comps) *n_comps = 0;
+    if (n_unitigs) *n_unitigs = 0;
+    if (n_kept) *n_kept = 0;
+    if (!c) return KMC_ERR_ARG;
+    int rc;
+    const char* what = "kmc_unitig_components";
+    if ((rc = unitig_begin(c, what, min_count, max_count))) return rc;
+    const u64 limit = clean_limit(max_component_keys);
+    if (!components_kept(c, min_count, max_count, limit) && (rc = components_run(c, what, min_count, max_count, limit))) return rc;
+    const u64 nk = c->cc_kept, nu = c->cc_words[0], nc = c->cc_comps;
+    if (n_comps) *n_comps = nc;
+    if (n_unitigs) *n_unitigs = nu;
+    if (n_kept) *n_kept = nk;
+    if ((key_hi || key_lo || count) && cap_keys < nk)
+        return fail(c, KMC_ERR_ARG, "%s: capacity %llu < %llu kept keys", what, (unsigned long long)cap_keys, (unsigned long long)nk);
+    if ((comp_of || verdict) && cap_unitigs < nu)
+        return fail(c, KMC_ERR_ARG, "%s: capacity %llu < %llu unitigs", what, (unsigned long long)cap_unitigs, (unsigned long long)nu);
+    if (comp_stats && cap_comps < nc)
+        return fail(c, KMC_ERR_ARG, "%s: capacity %llu < %llu components", what, (unsigned long long)cap_comps, (unsigned long long)nc);
+    if (nk && (rc = queue_to_host(c, c->cc.hi.p, c->cc.lo.p, c->cc.cnt.p, nk, key_hi, key_lo, count))) return rc;
+    if (comp_of && nu) HIPCHK(c, hipMemcpyAsync(comp_of, c->cc_comp.p, (size_t)nu * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+    if (verdict && nu) HIPCHK(c, hipMemcpyAsync(verdict, c->cc_verdict.p, (size_t)nu, hipMemcpyDeviceToHost, c->stream));
+    if (comp_stats && nc)
+        HIPCHK(c, hipMemcpyAsync(comp_stats, c->cc_stats.p, (size_t)nc * KMC_COMPONENT_STAT_WORDS * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (summary) memcpy(summary, c->cc_words, sizeof(c->cc_words));
+    return KMC_OK;
+}
+
+// One step of a round that drops small components: the kept pairs of src merged into dst's table, as kmc_unitig_clean_into.
+static int kmc_unitig_components_into_impl(kmc_ctx* src, kmc_ctx* dst, uint64_t min_count, uint64_t max_count, uint64_t max_component_keys,
+                                           uint64_t* summary) {
+    const char* what = "kmc_unitig_components_into";
+    if (!src || !dst) return src ? fail(src, KMC_ERR_ARG, "%s: null context", what) : KMC_ERR_ARG;
+    if (dst == src) return fail(src, KMC_ERR_ARG, "%s: dst is src", what);
+    int rc;
+    if ((rc = same_kind(src, dst, what))) return rc;
+    const void *hi = nullptr, *lo = nullptr, *cnt = nullptr;
+    uint64_t nk = 0;
+    u64 h[KMC_COMPONENT_WORDS];
+    if ((rc = kmc_unitig_components_device_impl(src, min_count, max_count, max_component_keys, nullptr, nullptr, nullptr, &hi, &lo, &cnt, nullptr,
+                                                nullptr, &nk, h, what)))
+        return rc;
+    if (nk) {
+        if ((rc = kmc_merge_pairs_device(dst, hi, lo, cnt, nk)) || (rc = kmc_sync(dst)))
+            return fail(src, rc, "%s: merging into dst failed: %s", what, kmc_last_error(dst));
+    }
+    if (summary) memcpy(summary, h, sizeof(h));
+    return KMC_OK;
+}
+
 // ---- the ABI proper (guarded: no C++ exception leaves the library) ----
 extern "C" int kmc_export(kmc_ctx* c, uint64_t* key_hi, uint64_t* key_lo, uint64_t* count, uint64_t cap) {
     return guarded(c, [&]() -> int { return kmc_export_impl(c, key_hi, key_lo, count, cap); });
@@ -1618,6 +1841,28 @@ extern "C" int kmc_unitig_simplify_into(kmc_ctx* src, kmc_ctx* dst, uint64_t min
         return kmc_unitig_clean_into_impl(src, dst, min_count, max_count, max_tip_keys, max_island_keys, summary,
                                           {max_bubble_keys, KMC_SIMPLIFY_WORDS, true, "kmc_unitig_simplify_into"});
     });
+}
+extern "C" int kmc_unitig_components_device(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t max_component_keys,
+                                            const void** d_comp_of, const void** d_comp_stats, const void** d_verdict, const void** d_key_hi,
+                                            const void** d_key_lo, const void** d_count, uint64_t* n_comps, uint64_t* n_unitigs, uint64_t* n_kept,
+                                            uint64_t* summary) {
+    return guarded(c, [&]() -> int {
+        return kmc_unitig_components_device_impl(c, min_count, max_count, max_component_keys, d_comp_of, d_comp_stats, d_verdict, d_key_hi, d_key_lo,
+                                                 d_count, n_comps, n_unitigs, n_kept, summary);
+    });
+}
+extern "C" int kmc_unitig_components(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t max_component_keys, uint32_t* comp_of,
+                                     uint8_t* verdict, uint64_t cap_unitigs, uint64_t* comp_stats, uint64_t cap_comps, uint64_t* key_hi,
+                                     uint64_t* key_lo, uint64_t* count, uint64_t cap_keys, uint64_t* n_comps, uint64_t* n_unitigs, uint64_t* n_kept,
+                                     uint64_t* summary) {
+    return guarded(c, [&]() -> int {
+        return kmc_unitig_components_impl(c, min_count, max_count, max_component_keys, comp_of, verdict, cap_unitigs, comp_stats, cap_comps, key_hi,
+                                          key_lo, count, cap_keys, n_comps, n_unitigs, n_kept, summary);
+    });
+}
+extern "C" int kmc_unitig_components_into(kmc_ctx* src, kmc_ctx* dst, uint64_t min_count, uint64_t max_count, uint64_t max_component_keys,
+                                          uint64_t* summary) {
+    return guarded(src, [&]() -> int { return kmc_unitig_components_into_impl(src, dst, min_count, max_count, max_component_keys, summary); });
 }
 extern "C" int kmc_partition_device(kmc_ctx* c, uint32_t n_parts, uint64_t* part_begin, const void** d_key_hi,
                                     const void** d_key_lo, const void** d_count) {

@@ -53,6 +53,10 @@ pub const KMC_CLEAN_ISLAND: u8 = 2;
 pub const KMC_CLEAN_BUBBLE: u8 = 3;
 /// summary words of `kmc_unitig_simplify`
 pub const KMC_SIMPLIFY_WORDS: usize = 12;
+/// summary words of `kmc_unitig_components`, words per component of its `comp_stats`, the verdict of a small component's unitigs
+pub const KMC_COMPONENT_WORDS: usize = 8;
+pub const KMC_COMPONENT_STAT_WORDS: usize = 4;
+pub const KMC_CLEAN_COMPONENT: u8 = 4;
 
 // The structs and the extern block below are checked against include/kmc.h by
 // tests/test_abi_host.py::test_rust_binding_matches_the_header (names, arity, argument types, field
@@ -175,6 +179,9 @@ extern "C" {
     pub fn kmc_unitig_simplify_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, max_tip_keys: u64, max_island_keys: u64, max_bubble_keys: u64, d_key_hi: *mut *const c_void, d_key_lo: *mut *const c_void, d_count: *mut *const c_void, d_verdict: *mut *const c_void, n_kept: *mut u64, n_unitigs: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_simplify(ctx: *mut KmcCtx, min_count: u64, max_count: u64, max_tip_keys: u64, max_island_keys: u64, max_bubble_keys: u64, key_hi: *mut u64, key_lo: *mut u64, count: *mut u64, cap_keys: u64, verdict: *mut u8, cap_unitigs: u64, n_kept: *mut u64, n_unitigs: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_simplify_into(src: *mut KmcCtx, dst: *mut KmcCtx, min_count: u64, max_count: u64, max_tip_keys: u64, max_island_keys: u64, max_bubble_keys: u64, summary: *mut u64) -> c_int;
+    pub fn kmc_unitig_components_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, max_component_keys: u64, d_comp_of: *mut *const c_void, d_comp_stats: *mut *const c_void, d_verdict: *mut *const c_void, d_key_hi: *mut *const c_void, d_key_lo: *mut *const c_void, d_count: *mut *const c_void, n_comps: *mut u64, n_unitigs: *mut u64, n_kept: *mut u64, summary: *mut u64) -> c_int;
+    pub fn kmc_unitig_components(ctx: *mut KmcCtx, min_count: u64, max_count: u64, max_component_keys: u64, comp_of: *mut u32, verdict: *mut u8, cap_unitigs: u64, comp_stats: *mut u64, cap_comps: u64, key_hi: *mut u64, key_lo: *mut u64, count: *mut u64, cap_keys: u64, n_comps: *mut u64, n_unitigs: *mut u64, n_kept: *mut u64, summary: *mut u64) -> c_int;
+    pub fn kmc_unitig_components_into(src: *mut KmcCtx, dst: *mut KmcCtx, min_count: u64, max_count: u64, max_component_keys: u64, summary: *mut u64) -> c_int;
     // multi-GPU reduce (one process per GPU; the collective itself is the host program's, e.g. RCCL)
     pub fn kmc_slab_words(ctx: *const KmcCtx, slab_entries: u64) -> u64;
     pub fn kmc_pack_slab_device(ctx: *mut KmcCtx, d_slab: *mut c_void, slab_entries: u64) -> c_int;
@@ -600,6 +607,52 @@ impl Counter {
         self.check(unsafe {
             kmc_unitig_simplify_into(self.ctx, dst.ctx, min_count, max_count, max_tip_keys, max_island_keys, max_bubble_keys, w.as_mut_ptr())
         })?;
+        Ok(w)
+    }
+
+    /// The connected components of the unitig graph (`kmc_unitig_components`): the component of every unitig (numbered by
+    /// their smallest unitig), `[root, unitigs, keys, abundance]` per component, the verdict per unitig (`KMC_CLEAN_KEEP`, or
+    /// `KMC_CLEAN_COMPONENT` in a component of at most `max_component_keys` keys; 0 drops none), the kept table and the
+    /// eight summary words.
+    #[allow(clippy::type_complexity)]
+    pub fn components(&mut self, min_count: u64, max_count: u64, max_component_keys: u64)
+                      -> Result<(Vec<u32>, Vec<[u64; KMC_COMPONENT_STAT_WORDS]>, Vec<u8>, Vec<(String, u64)>, [u64; KMC_COMPONENT_WORDS]), KmcError> {
+        let (mut nd, mut nt) = (0u64, 0u64);
+        self.check(unsafe { kmc_finalize(self.ctx, &mut nd, &mut nt) })?;
+        let (mut nc, mut nu, mut nk) = (0u64, 0u64, 0u64);
+        let mut w = [0u64; KMC_COMPONENT_WORDS];
+        let null64 = std::ptr::null_mut::<u64>();
+        self.check(unsafe {
+            kmc_unitig_components(self.ctx, min_count, max_count, max_component_keys, std::ptr::null_mut::<u32>(), std::ptr::null_mut::<u8>(), 0,
+                                  null64, 0, null64, null64, null64, 0, &mut nc, &mut nu, &mut nk, w.as_mut_ptr())
+        })?;
+        let k = nk as usize;
+        let (mut hi, mut lo, mut cnt) = (vec![0u64; k], vec![0u64; k], vec![0u64; k]);
+        let mut comp_of = vec![0u32; nu as usize];
+        let mut verdict = vec![0u8; nu as usize];
+        let mut stats = vec![[0u64; KMC_COMPONENT_STAT_WORDS]; nc as usize];
+        self.check(unsafe {
+            kmc_unitig_components(self.ctx, min_count, max_count, max_component_keys, comp_of.as_mut_ptr(), verdict.as_mut_ptr(), nu,
+                                  stats.as_mut_ptr() as *mut u64, nc, hi.as_mut_ptr(), lo.as_mut_ptr(), cnt.as_mut_ptr(), nk, &mut nc, &mut nu,
+                                  &mut nk, w.as_mut_ptr())
+        })?;
+        let mut buf = vec![0u8; self.klen as usize];
+        let mut out = Vec::with_capacity(k);
+        for i in 0..k {
+            unsafe { kmc_decode_key(hi[i], lo[i], self.klen, buf.as_mut_ptr() as *mut c_char) };
+            out.push((String::from_utf8_lossy(&buf).into_owned(), cnt[i]));
+        }
+        Ok((comp_of, stats, verdict, out, w))
+    }
+
+    /// One step that drops small components (`kmc_unitig_components_into`): as `clean_into`, with the eight words of
+    /// `components`.
+    pub fn components_into(&mut self, dst: &mut Counter, min_count: u64, max_count: u64, max_component_keys: u64)
+                           -> Result<[u64; KMC_COMPONENT_WORDS], KmcError> {
+        let (mut nd, mut nt) = (0u64, 0u64);
+        self.check(unsafe { kmc_finalize(self.ctx, &mut nd, &mut nt) })?;
+        let mut w = [0u64; KMC_COMPONENT_WORDS];
+        self.check(unsafe { kmc_unitig_components_into(self.ctx, dst.ctx, min_count, max_count, max_component_keys, w.as_mut_ptr()) })?;
         Ok(w)
     }
 }
