@@ -135,6 +135,9 @@ typedef struct kmc_stats {
                                      counters older than the last queued unfold / merge (must stay 0) */
     uint64_t walk_uniform_launches; /* walk-kernel launches since kmc_create (kmc_reset does not clear it) that ran the
                                        uniform-length variant: all reads of the batch equally long, no offsets read */
+    uint64_t walk_plan_finalizes;   /* finalizes since kmc_create (kmc_reset does not clear them) whose view the walk path's plan
+                                       launch wrote: a repeat batch gathered from its rank plan, no table, no sort */
+    uint64_t walk_plan_builds;      /* rank plans built (queued) since kmc_create */
 } kmc_stats;
 
 const char* kmc_version(void);

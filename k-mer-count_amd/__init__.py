@@ -54,7 +54,8 @@ class Stats(C.Structure):
                 ("launches_last", C.c_int32), ("n_slabs_skipped", C.c_uint64), ("n_direct", C.c_uint64),
                 ("kernel_ms_lifetime", C.c_double), ("launches_lifetime", C.c_uint64),
                 ("n_async_ok", C.c_uint64), ("n_async_slabs_skipped", C.c_uint64), ("n_planner_stale", C.c_uint64),
-                ("walk_uniform_launches", C.c_uint64)]
+                ("walk_uniform_launches", C.c_uint64), ("walk_plan_finalizes", C.c_uint64),
+                ("walk_plan_builds", C.c_uint64)]
 
 
 class _Reads(C.Structure):

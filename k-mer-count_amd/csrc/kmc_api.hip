@@ -20,6 +20,7 @@
 #include "kmc_synth.hip.h"
 #include "kmc_table.hip.h"
 #include "kmc_walk.hip.h"
+#include "kmc_walk_plan.hip.h"
 #include "kmc_sklog.hip.h"
 #include "kmc_lr.hip.h"
 #include "kmc_msd.hip.h"
@@ -233,6 +234,7 @@ void launch_merge_pairs(kmc_ctx* c, const u64* hi, const u64* lo, const u64* cnt
 
 // what a poll learns from fresh h_counters
 int poll_book(kmc_ctx* c);
+void plan_book(kmc_ctx* c, bool delivered);
 // read the device counters (synchronises the stream)
 int resolve_async(kmc_ctx* c);
 int poll(kmc_ctx* c) {
@@ -264,6 +266,7 @@ int poll_fin(kmc_ctx* c) {
     std::atomic_thread_fence(std::memory_order_acquire);
     if (!seen) HIPCHK(c, hipStreamSynchronize(c->stream));
     c->view_unsynced = seen;   // (the kernel may still be running: kmc_export_device waits for its end before it hands out pointers)
+    plan_book(c, c->h_pub[KMC_CTR_FASTFIN] == 1 && c->h_pub[KMC_CTR_FINSEQ] == c->fin_seq);
     c->st.n_async_ok = c->h_pub[KMC_CTR_FINOK];
     c->st.n_async_slabs_skipped = c->h_pub[KMC_CTR_FINSKIP];
     if (c->h_pub[KMC_CTR_FASTFIN] != 1 || c->h_pub[KMC_CTR_FINSEQ] != c->fin_seq) {   // it gave up: read the counters the usual way
@@ -380,6 +383,52 @@ int poll_and_settle(kmc_ctx* c) {
     return settle(c);
 }
 
+// ---- the rank plan of the walk path (kmc_walk_plan.hip.h) ----
+// Whatever is queued on the ctx that is not the finalize a plan launch was armed for takes the request away from it: the
+// launch must never deliver a finalize that is meant to see more, or less, than its own batch.
+void plan_disarm(kmc_ctx* c) {
+    c->plan_req_seq = 0;
+    c->plan_src_ok = false;
+}
+// the memo is gone (kmc_forget_source, a restart after an overflow, a fresh allocation): so is the plan
+void plan_forget(kmc_ctx* c) {
+    plan_disarm(c);
+    c->plan_valid = c->plan_stale = false;
+    c->plan_budget = KMC_WALK_PLAN_BUILDS;
+}
+// What the plan launch numbered plan_seq said (behind a poll that saw the finalize of that number, or the end of the stream)
+void plan_book(kmc_ctx* c, bool delivered) {
+    const u64 s = __atomic_load_n(&c->h_plan[KMC_PLAN_W_STATUS], __ATOMIC_ACQUIRE);
+    if (!c->plan_seq || (s >> 2) != c->plan_seq) return;
+    if ((s & 3) == KMC_PLAN_STALE) c->plan_stale = true;
+    if ((s & 3) == KMC_PLAN_DONE && delivered && c->fin_seq == c->plan_seq) c->st.walk_plan_finalizes++;
+    c->plan_seq = 0;   // (booked once)
+}
+// Behind a finalize whose view is the small-table kernel's: build the plan from it when the table was one walk launch on an
+// empty table and the ctx has no plan, or one that its last launch found stale.  Queued on the ctx stream; nothing waits.
+int plan_maybe_build(kmc_ctx* c) {
+    const bool src = c->plan_src_ok;
+    c->plan_src_ok = false;
+    if (!src || c->walk_no_plan || !c->walk_memo.p || (c->plan_valid && !c->plan_stale)) return KMC_OK;
+    if (c->n_sorted < 1 || c->n_sorted > KMC_WALK_PLAN_MAX || c->plan_budget <= 0) return KMC_OK;
+    if (!c->plan_rank) {
+        HIPCHK(c, c->plan_rank.alloc((size_t)KMC_WALK_ITEMS * sizeof(unsigned short)));
+        HIPCHK(c, c->plan_lo.alloc((size_t)KMC_WALK_PLAN_MAX * sizeof(u64)));
+        if (c->KW == 2) HIPCHK(c, c->plan_hi.alloc((size_t)KMC_WALK_PLAN_MAX * sizeof(u64)));
+    }
+    c->plan_n = (u32)c->n_sorted;
+    const WalkPlan pl{c->plan_rank, c->plan_lo, c->plan_hi, c->plan_n};
+    // the snapshot the launch WROTE: the one the next launch reads
+    const void* slot = (const char*)c->walk_memo.p + (size_t)c->memo_parity * kmc_walk_slot_bytes(c->KW);
+    const int rc = kmc_walk_plan_build_launch(c->stream, c->KW, c->cfg.k, c->cfg.canonical != 0, slot, c->v_hi, c->v_lo, pl);
+    if (rc) return fail(c, rc, "walk plan build launch failed");
+    c->plan_valid = true;
+    c->plan_stale = false;
+    c->plan_budget--;
+    c->st.walk_plan_builds++;
+    return KMC_OK;
+}
+
 // one workgroup per KMC_FIN_CHUNK keys; the grid follows the size of the last table seen (+ 25 %), at least 64
 // workgroups.  (Workgroups past the table leave at once, but hundreds of them still cost microseconds.)  A table that
 // outgrew the grid is noticed by kmc_finalize and finalized again with the full grid.
@@ -393,6 +442,10 @@ int launch_small_finalize(kmc_ctx* c, int grid) {
     // when it carries this launch's number (earlier launches may still be in flight: kmc_finalize_async)
     const u64 seq = ++c->fin_seq;
     const u64* skc = c->d_counters + KMC_CTR_N;
+    // the late request of the walk path's plan launch (kmc_walk_plan.hip.h): this finalize is the one it was armed for, and
+    // nothing else has been queued on the ctx since.  The launch may be running already; it reads the word once.
+    __atomic_store_n(&c->h_plan[KMC_PLAN_W_REQ], c->plan_req_seq == seq ? seq : 0ull, __ATOMIC_RELEASE);
+    c->plan_req_seq = 0;
     if (c->KW == 1) hipLaunchKernelGGL(kmc_small_finalize_kernel<1>, dim3(grid), dim3(1024), 0, c->stream, g, skc, c->fin_rank, c->d_mirror, seq, (u64*)nullptr, (u64*)c->o.lo.p, (u64*)c->o.cnt.p);
     else hipLaunchKernelGGL(kmc_small_finalize_kernel<2>, dim3(grid), dim3(1024), 0, c->stream, g, skc, c->fin_rank, c->d_mirror, seq, (u64*)c->o.hi.p, (u64*)c->o.lo.p, (u64*)c->o.cnt.p);
     HIPCHK(c, hipGetLastError());
@@ -435,8 +488,9 @@ int resolve_async(kmc_ctx* c) {
         c->fin_hint = n;
         c->st.n_distinct = n;
         c->st.n_kmers = n ? c->h_counters[KMC_CTR_SUM2] : 0;
-        return KMC_OK;
+        return plan_maybe_build(c);
     }
+    c->plan_src_ok = false;
     return settle(c);
 }
 
@@ -1097,6 +1151,7 @@ struct BatchPlan {
 // What a batch settles first: a queued finalize, a drained table, the previous batch's counters and (k+16)-mer counts
 int begin_batch(kmc_ctx* c) {
     { int rc = resolve_async(c); if (rc) return rc; }
+    plan_disarm(c);
     { int rc = undrain(c); if (rc) return rc; }
     if (c->pending) { int rc = poll_and_settle(c); if (rc) return rc; }
     // the previous batch's (k+16)-mer counts, if it left any: the counters are as of a poll that came after
@@ -1248,6 +1303,7 @@ int count_walk(kmc_ctx* c, BatchPlan& bp, const uint8_t* d_bases, const u64* d_o
         HIPCHK(c, hipMemsetAsync(c->walk_memo.p, 0, kmc_walk_memo_bytes(c->n_cu, c->KW), c->stream));
         c->memo_parity = 0;
         c->walk_overflowed = false;
+        plan_forget(c);
     }
     // the reads the kernel walks: the batch's own, or pieces of <= KMC_WALK_MAX_READ bases
     const u64 *d_vs = d_offsets, *d_ve = d_offsets + 1;
@@ -1320,6 +1376,23 @@ int count_walk(kmc_ctx* c, BatchPlan& bp, const uint8_t* d_bases, const u64* d_o
         if (uni_len) c->st.walk_uniform_launches++;
         c->batch_pending = true;
         if (skt.key_lo) c->sk_dirty = true;
+        // the whole batch in one launch on a table the host knows empty, no log: what a plan is built from, and -- with a plan
+        // -- what the plan launch may finalize, if kmc_finalize is what the host calls next (kmc_walk_plan.hip.h)
+        // (A launch sized by a prediction -- risky.armed, every large batch -- is no obstacle: the plan launch finalizes only a
+        // table that is EMPTY behind the walk kernel, nothing spilled, no error bit, so there is nothing a recovery would undo.)
+        const bool plain = done == 0 && take == n_tiles && bp.on_empty_table && !lg.rec && c->runs.empty() && !c->acc_n;
+        c->plan_src_ok = plain;
+        if (plain && !c->walk_no_plan && c->plan_valid && !c->plan_stale) {
+            rc = ensure_keys(c, c->o, KMC_FIN_KERNEL_MAX);   // (the small finalize's view buffers: they do not move before the finalize)
+            if (rc) return rc;
+            if (c->fin_seq < c->plan_seq_max) c->fin_seq = c->plan_seq_max;   // (a number an earlier plan launch carries is never used again)
+            c->plan_seq = c->plan_req_seq = c->plan_seq_max = c->fin_seq + 1;
+            const WalkPlan pl{c->plan_rank, c->plan_lo, c->plan_hi, c->plan_n};
+            rc = kmc_walk_plan_finalize_launch(c->stream, c->KW, c->cfg.k, c->walk_ws.p, c->walk_memo.p, c->memo_parity, pl, gtable_of(c, c->tab),
+                                               c->d_counters + KMC_CTR_N, c->fin_rank, c->d_mirror, c->d_plan, c->plan_seq,
+                                               (u64*)c->o.hi.p, (u64*)c->o.lo.p, (u64*)c->o.cnt.p);
+            if (rc) return fail(c, rc, "walk plan launch failed: %s", hipGetErrorString(hipGetLastError()));
+        }
         rc = kmc_walk_launch(c->stream, c->n_cu, c->KW, c->cfg.k, c->cfg.canonical != 0, d_bases, d_vs, d_ve, n_v, n_bases,
                              done, done + take, c->walk_ws.p, c->walk_memo.p, c->memo_parity, gtable_of(c, c->tab), skt, lg, 1, nullptr, nullptr, uni_len);
         if (rc) return fail(c, rc, "scalar/unfold kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
@@ -1541,6 +1614,8 @@ static int kmc_create_impl(kmc_ctx** out, const kmc_config* cfg) {
     c->sort_sub_chunks = seam("KMC_SORT_SUB_CHUNKS", KMC_MSD_RANGE / KMC_CHUNK, c->sort_sub_chunks);
     c->lr_sub_starts = seam("KMC_LR_SUB_STARTS", KMC_LRX_POS, c->lr_sub_starts);
     if (const char* e = getenv("KMC_WALK_NO_UNIFORM")) c->walk_no_uniform = e[0] != 0 && e[0] != '0';   // (A/B runs on one build, tests)
+    if (const char* e = getenv("KMC_WALK_NO_PLAN")) c->walk_no_plan = e[0] != 0 && e[0] != '0';   // (A/B runs on one build, tests)
+    c->plan_budget = KMC_WALK_PLAN_BUILDS;
     int rc = KMC_OK;
     auto body = [&]() -> int {
         HIPCHK(c, hipSetDevice(cfg->device));
@@ -1557,6 +1632,9 @@ static int kmc_create_impl(kmc_ctx** out, const kmc_config* cfg) {
         memset(c->h_pub, 0, 2 * KMC_CTR_N * sizeof(u64));
         HIPCHK(c, hipHostGetDevicePointer((void**)&c->d_mirror, c->h_pub, 0));
         HIPCHK(c, c->h_restore.alloc(KMC_CTR_N * sizeof(u64)));
+        HIPCHK(c, c->h_plan.alloc(KMC_PLAN_W_N * sizeof(u64)));
+        memset(c->h_plan, 0, KMC_PLAN_W_N * sizeof(u64));
+        HIPCHK(c, hipHostGetDevicePointer((void**)&c->d_plan, c->h_plan, 0));
         u64 cap = next_pow2(std::max<u64>(cfg->capacity_hint * 2, 1ull << 20));
         c->spill_cap = std::max<u64>(cap / 4, 1ull << 18);
         HIPCHK(c, c->occ_list.alloc(KMC_OCC_LIST_CAP * sizeof(u64)));
@@ -1586,6 +1664,7 @@ static int kmc_create_impl(kmc_ctx** out, const kmc_config* cfg) {
 static int kmc_reset_impl(kmc_ctx* c) {
     if (!c) return KMC_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->cfg.device));
+    plan_disarm(c);
     if (c->drained && !c->async_fin) {
         // the last kmc_finalize emptied the table into its sorted view (kmc_small_finalize_kernel): table and device
         // counters are already what the reset kernel would leave -- nothing to launch
@@ -1622,6 +1701,8 @@ static int kmc_reset_impl(kmc_ctx* c) {
     c->st.launches_lifetime = keep.launches_lifetime;
     c->st.n_planner_stale = keep.n_planner_stale;
     c->st.walk_uniform_launches = keep.walk_uniform_launches;
+    c->st.walk_plan_finalizes = keep.walk_plan_finalizes;
+    c->st.walk_plan_builds = keep.walk_plan_builds;
     c->st.n_async_ok = keep.n_async_ok;
     c->st.n_async_slabs_skipped = keep.n_async_slabs_skipped;
     return KMC_OK;
@@ -1669,6 +1750,7 @@ static int kmc_add_batch_impl(kmc_ctx* c, const uint8_t* bases, const uint64_t* 
 // bound, so a series of merges (one per peer in the multi-GPU reduce) needs no host synchronisation in between.
 static int merge_begin(kmc_ctx* c, u64 n) {
     { int rc = resolve_async(c); if (rc) return rc; }
+    plan_disarm(c);
     { int rc = undrain(c); if (rc) return rc; }
     if (c->batch_pending || (c->h_counters[KMC_CTR_OCCUPIED] + c->unpolled_adds + n) * 2 > c->tab.cap) {
         if (c->pending) { int rc = poll_and_settle(c); if (rc) return rc; }
@@ -1843,6 +1925,8 @@ static int kmc_finalize_impl(kmc_ctx* c, uint64_t* n_distinct, uint64_t* n_total
     c->view_gen += 1;
     c->st.n_distinct = n;
     c->st.n_kmers = n ? n_kmers : 0;
+    if (fast_done) { rc = plan_maybe_build(c); if (rc) return rc; }
+    c->plan_src_ok = false;
     if (!fast_done && c->tb.size() >= 4) harvest_timing(c);
     if (n_distinct) *n_distinct = n;
     if (n_total) *n_total = c->st.n_kmers;
@@ -1881,6 +1965,7 @@ static int kmc_pack_slab_device_impl(kmc_ctx* c, void* d_slab, uint64_t slab_ent
     if (((uintptr_t)d_slab & 7) != 0) return fail(c, KMC_ERR_ARG, "d_slab must be 8-byte aligned");
     HIPCHK(c, hipSetDevice(c->cfg.device));
     { int rc = resolve_async(c); if (rc) return rc; }
+    plan_disarm(c);   // (the pack below reads the live table)
     if (c->sk_dirty && (c->sklog_on || c->sorted_valid)) { int r = flush_sk(c); if (r) return r; }   // (else: none expected -- the pack kernel checks)
     if (!c->sorted_valid) {
         // not finalized: pack the live table (unsorted) -- the device decides whether it fits
@@ -1949,6 +2034,7 @@ static int kmc_forget_source_impl(kmc_ctx* c, int what) {
     if (!c) return KMC_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->cfg.device));
     { int rc = resolve_async(c); if (rc) return rc; }
+    if (what & KMC_FORGET_MEMO) plan_forget(c); else plan_disarm(c);
     if ((what & KMC_FORGET_MEMO) && c->walk_memo.p) {
         HIPCHK(c, hipMemsetAsync(c->walk_memo.p, 0, kmc_walk_memo_bytes(c->n_cu, c->KW), c->stream));  // tag 0 = no snapshot
         c->memo_parity = 0;

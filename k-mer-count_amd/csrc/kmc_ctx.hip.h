@@ -93,6 +93,23 @@ struct kmc_ctx : CtxStream {
     int memo_parity = 0;  // snapshot slot the next walk launch reads
     bool walk_no_uniform = false;  // KMC_WALK_NO_UNIFORM=1 at kmc_create: uniform-length batches take the ragged kernels too
     bool walk_ws_clean = false;  // workspace header + dense counters are zero (left so by kmc_walk_tail_kernel)
+    // The rank plan of the walk path (kmc_walk_plan.hip.h), kept next to the memo and forgotten with it: item -> view row, the
+    // rows' keys.  plan_valid: built (queued) for the memo as it stands; plan_stale: its last launch met a counter without a
+    // row -- the next suitable finalize rebuilds it, while plan_budget lasts.  plan_src_ok: the table the next finalize will
+    // see is exactly one walk launch on an empty table, no log -- what a plan can be built from.
+    Dev<unsigned short> plan_rank;
+    Dev<u64> plan_lo, plan_hi;
+    u32 plan_n = 0;
+    bool plan_valid = false, plan_stale = false, plan_src_ok = false;
+    int plan_budget = 0;
+    bool walk_no_plan = false;   // KMC_WALK_NO_PLAN=1 at kmc_create: no plan is built, no plan launch queued
+    // The plan launch is armed for ONE finalize: the one numbered plan_seq, and only while that finalize would be the next
+    // thing queued on this ctx (plan_req_seq == plan_seq; anything else that is queued first clears it).  No two plan launches
+    // ever carry the same number: arming skips the numbers handed out before.
+    u64 plan_seq = 0, plan_req_seq = 0;   // (plan_seq: the last plan launch's number until its status has been booked)
+    u64 plan_seq_max = 0;                 // the largest number a plan launch has carried
+    Pin<u64> h_plan;             // pinned: the request and status words (KMC_PLAN_W_*): words of their own, nothing copies over them
+    u64* d_plan = nullptr;       // h_plan as the device sees it (an alias, not an owner)
     // KMC_ALGO_SORT: scratch for one sub-batch and the sorted (key,count) runs produced so far
     DevBuf s_lo[2], s_hi[2];
     // the walk kernel's log of steps that fell off its LDS memo (kmc_walk.hip.h SkLog, kmc_sklog.hip.h): per-workgroup spans,

@@ -297,6 +297,9 @@ __device__ __forceinline__ void kmc_fin_publish_and_drain(GTable g, const u64* _
 // ticket[0]: the ticket counter; ticket[1], ticket[2]: launches that produced a view / oversize slabs they saw, since
 // kmc_create (a caller that queues several finalizes without waiting -- kmc_finalize_async -- checks afterwards that
 // every one of them delivered); seq: this launch's number, published with everything else.
+// ticket[3]: kmc_reset_kernel's ticket; the u64 at ticket + KMC_FIN_TICKET_PLAN: the number of the last finalize that the
+// walk path's plan launch delivered (numbers start at 1).
+#define KMC_FIN_TICKET_PLAN 4
 template <int KW>
 __global__ __launch_bounds__(1024)
 void kmc_small_finalize_kernel(GTable g, const u64* __restrict__ sk_counters, u32* __restrict__ ticket, u64* __restrict__ host_mirror, u64 seq,
@@ -308,6 +311,10 @@ void kmc_small_finalize_kernel(GTable g, const u64* __restrict__ sk_counters, u3
     __shared__ u32 s_last;
     __shared__ u64 s_sum[16];
     const u32 tid = threadIdx.x;
+    // The walk path's plan launch (kmc_walk_plan.hip.h) has delivered this very finalize -- view written, counters published
+    // under this number, table empty: nothing is left to do.  The word was written by an earlier kernel in stream order, so
+    // every workgroup decides alike.
+    if (*reinterpret_cast<const u64*>(ticket + KMC_FIN_TICKET_PLAN) == seq) return;
     const u64 n = g.counters[KMC_CTR_OCCUPIED];
     const bool ok = n > 0 && n <= KMC_FIN_KERNEL_MAX && n <= g.occ_list_cap && n <= (u64)gridDim.x * KMC_FIN_CHUNK &&
                     g.counters[KMC_CTR_SPILL] == 0 && g.counters[KMC_CTR_ERR] == 0 &&

@@ -159,14 +159,20 @@ __device__ __forceinline__ WCtx node_key_load(WalkLds<KW>& L, u32 id) {
 }
 
 // canonical (or forward) key of a k-mer context -> global table
-template <int KW, bool CANON>
-__device__ __forceinline__ void walk_gadd(const GTable& g, WCtx kmer, int k, u64 cnt) {
-    u64 khi = kmer.hi, klo = kmer.lo;
+template <bool CANON>
+__device__ __forceinline__ void walk_key(WCtx kmer, int k, u64& khi, u64& klo) {
+    khi = kmer.hi;
+    klo = kmer.lo;
     if (CANON) {
         u64 rhi, rlo;
         revcomp_key(kmer.hi, kmer.lo, k, rhi, rlo);
         if (key_less(rhi, rlo, khi, klo)) { khi = rhi; klo = rlo; }
     }
+}
+template <int KW, bool CANON>
+__device__ __forceinline__ void walk_gadd(const GTable& g, WCtx kmer, int k, u64 cnt) {
+    u64 khi, klo;
+    walk_key<CANON>(kmer, k, khi, klo);
     gtable_add<KW>(g, khi, klo, cnt);
 }
 
@@ -883,6 +889,29 @@ void kmc_walk_kernel(const uint8_t* __restrict__ bases, u64 n_bases, const u64* 
     if (tid == 0) WALK_STAMP(20);
 }
 
+// Item (i, step) of a snapshot: the k-mer that base `step` of entry i's label completes -- i < NCAP: the primary edge of
+// node i, else hashed edge i - NCAP.  False when the item stands for no k-mer: the label is shorter, or the context is
+// not k bases deep yet.  (The entry itself must exist: the caller knows from its counter, or looks -- kmc_walk_plan.hip.h.)
+#define KMC_WALK_ITEMS ((KMC_WALK_NCAP + KMC_WALK_ECAP) * KMC_WALK_STRIDE)
+template <int KW>
+__device__ __forceinline__ bool walk_item_kmer(const WalkMemoSlot<KW>* memo, u32 i, u32 step, int k, u64 mask_hi, u64 mask_lo, WCtx& ctx) {
+    u32 label, len, id;
+    if (i < KMC_WALK_NCAP) {
+        id = i; label = (u32)memo->prim[i]; len = KMC_WALK_STRIDE;
+    } else {
+        const u64 kv = memo->ekv[i - KMC_WALK_NCAP];
+        label = (u32)kv; len = ((u32)(kv >> 32) & 15u) + 1; id = (u32)(kv >> 36) & (KMC_WALK_NCAP - 1);
+    }
+    if (step >= len) return false;
+    WCtx nk;
+    nk.lo = memo->nkeys[id];
+    nk.hi = KW == 2 ? memo->nkeys_hi[id] : 0ull;
+    u32 depth;
+    node_decode<KW>(nk, k, ctx, depth);
+    (void)walk_roll<KW, false, false>(GTable{}, ctx, depth, label, (int)step + 1, k, mask_hi, mask_lo, 0);   // context after base `step`
+    return depth >= (u32)k;
+}
+
 // Turns the traversal counters that all workgroups reduced into gcnt (one per snapshot slot) into
 // k-mer counts, once per launch (gcnt is cleared by kmc_walk_prepare before the next launch).
 template <int KW, bool CANON>
@@ -892,26 +921,12 @@ __device__ __forceinline__ void walk_unfold_part(const WalkMemoSlot<KW>* memo, u
     const int kb = 2 * k;
     const u64 mask_lo = kb >= 64 ? ~0ull : ((1ull << kb) - 1);
     const u64 mask_hi = kb <= 64 ? 0ull : ((1ull << (kb - 64)) - 1);
-    for (u32 w = tid; w < (KMC_WALK_NCAP + KMC_WALK_ECAP) * KMC_WALK_STRIDE; w += nthreads) {
+    for (u32 w = tid; w < KMC_WALK_ITEMS; w += nthreads) {
         const u32 i = w / KMC_WALK_STRIDE, step = w % KMC_WALK_STRIDE;
         const u64 cnt = gcnt[i];
         if (!cnt) continue;
-        u32 label, len, id;
-        if (i < KMC_WALK_NCAP) {
-            id = i; label = (u32)memo->prim[i]; len = KMC_WALK_STRIDE;
-        } else {
-            const u64 kv = memo->ekv[i - KMC_WALK_NCAP];
-            label = (u32)kv; len = ((u32)(kv >> 32) & 15u) + 1; id = (u32)(kv >> 36) & (KMC_WALK_NCAP - 1);
-        }
-        if (step < len) {
-            WCtx nk, ctx;
-            nk.lo = memo->nkeys[id];
-            nk.hi = KW == 2 ? memo->nkeys_hi[id] : 0ull;
-            u32 depth;
-            node_decode<KW>(nk, k, ctx, depth);
-            (void)walk_roll<KW, CANON, false>(g, ctx, depth, label, (int)step + 1, k, mask_hi, mask_lo, 0);
-            if (depth >= (u32)k) walk_gadd<KW, CANON>(g, ctx, k, cnt);
-        }
+        WCtx ctx;
+        if (walk_item_kmer<KW>(memo, i, step, k, mask_hi, mask_lo, ctx)) walk_gadd<KW, CANON>(g, ctx, k, cnt);
     }
     // every entry is read by 16 consecutive threads of ONE block (the grid covers the item space exactly
     // once): after the block's reads, clear its entries for the next launch

@@ -94,6 +94,8 @@ pub struct KmcStats {
     pub n_async_slabs_skipped: u64,
     pub n_planner_stale: u64,
     pub walk_uniform_launches: u64,
+    pub walk_plan_finalizes: u64,
+    pub walk_plan_builds: u64,
 }
 
 #[repr(C)]

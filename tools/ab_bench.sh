@@ -14,7 +14,10 @@ for r in $(seq 1 $rounds); do
   for v in "${vars[@]}"; do
     lib=$root/k-mer-count_amd/libkmc_$v.so
     [ "$v" == "main" ] && lib=$root/k-mer-count_amd/libkmc.so
-    log=$(KMC_LIB_PATH=$lib timeout -k 10 ${AB_STEP_LIMIT:-300} python3 bench.py --no-cpu-baseline --steps 20 --warmup 8 "$@" 2>&1)
+    # "noplan": this build with the walk path's rank plan switched off (KMC_WALK_NO_PLAN, read by kmc_create)
+    noplan=
+    [ "$v" == "noplan" ] && { lib=$root/k-mer-count_amd/libkmc.so; noplan=1; }
+    log=$(KMC_WALK_NO_PLAN=$noplan KMC_LIB_PATH=$lib timeout -k 10 ${AB_STEP_LIMIT:-300} python3 bench.py --no-cpu-baseline --steps 20 --warmup 8 "$@" 2>&1)
     rc=$?
     line=$(echo "$log" | tail -1)
     echo "$v $line" | python3 -c "

@@ -2,7 +2,7 @@
 # Profiles `bench.py` on the GPU box: kernel trace + stats, then PMC passes (each in its own run;
 # --pmc is never combined with other trace domains).  Output under gpurun_out/prof_<tag>/.
 # Every run has its own time limit (PROF_STEP_LIMIT seconds, default 300) and the first one that fails or times out
-# ends the script.  KMC_LIB_PATH selects the library (a variant of tools/build_variant.sh).
+# ends the script.  KMC_LIB_PATH selects the library (a variant of tools/build_variant.sh).  PROF_TRACE_ONLY=1: no PMC passes.
 # usage: tools/profile_bench.sh <tag> [bench args...]
 set -u
 tag=$1; shift
@@ -17,6 +17,7 @@ timeout -k 10 $limit rocprofv3 --kernel-trace --stats --output-format csv -d $ou
 rc=$?
 echo "trace rc=$rc"
 [ $rc -ne 0 ] && exit $rc
+[ -n "${PROF_TRACE_ONLY:-}" ] && exit 0   # (a step timeline needs the kernel trace alone: tools/step_timeline.py)
 i=0
 for ctrs in "FETCH_SIZE" "WRITE_SIZE" \
   "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT" \
