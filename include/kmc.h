@@ -32,6 +32,7 @@
  *   (addition: no equivalent in the reference)             kmc_unitig_components_into (the table without small components, into another ctx)
  *   (addition: no equivalent in the reference)             kmc_unitig_map / kmc_unitig_map_device (reads threaded through the unitigs)
  *   (addition: no equivalent in the reference)             kmc_correct / kmc_correct_device (substitution errors of reads repaired from the table)
+ *   (addition: no equivalent in the reference)             kmc_trim / kmc_trim_device (reads trimmed and filtered by their solid k-mers)
  *
  * Conventions
  *   - Every function returns 0 (KMC_OK) or a negative kmc_status; no exception or abort crosses
@@ -585,6 +586,85 @@ int kmc_correct_device(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, con
 int kmc_correct(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, const uint8_t* bases, const uint64_t* offsets,
                 uint64_t n_reads, uint8_t* out_bases, uint32_t* read_stats, uint64_t* cand_offsets, uint32_t* cands,
                 uint64_t cap_cands, uint64_t* n_cands, uint64_t* summary);
+
+/* ---- reads trimmed and filtered by their solid k-mers (additions, as above): which reads, and which part of each, the
+ * table supports -- quality trimming behind kmc_correct, decontamination (INVERT against a contaminant's table), baiting.
+ * KMC_MODE_CONTIG only; every k, in a canonical or a forward ctx.  Reads the sorted view of the last kmc_finalize (a view
+ * queued by kmc_finalize_async counts as one).  The batch is NOT counted.  The formula is the definition.
+ * WINDOW, VALID, STRONG, WEAK.  Exactly as in the kmc_correct block: window j of a read R of L bases is R[j : j+k], 0 <= j <=
+ *   L - k; valid iff it holds only upper-case ACGT; strong iff valid and canon(f) is solid by the range rule of kmc_graph
+ *   (min_count, max_count, 0 = no upper bound); weak iff valid and not strong.  V = valid windows of the read, S = strong
+ *   windows.
+ * STRONG RUN.  A maximal set of consecutive window indices of one read that are all strong; an invalid or weak window, or
+ *   the read's end, ends it.  F / E = index of the first / last strong window of the read.  (B, N) = start and length in
+ *   windows of the longest strong run; of several longest runs, the one with the smallest start.
+ * SPAN, by mode, as (start, len) in bases relative to the read:
+ *     KMC_TRIM_NONE (0):    (0, L).
+ *     KMC_TRIM_ENDS (1):    (F, E - F + k) if S > 0, else (0, 0).  Weak and invalid windows inside stay.
+ *     KMC_TRIM_LONGEST (2): (B, N + k - 1) if S > 0, else (0, 0).  Every window of the span is strong.
+ * PASS.  A read passes iff all of: S >= min_strong; S * 1000 >= (uint64_t)min_permille * V, as plain 64-bit products;
+ *   len >= min_len; mode == KMC_TRIM_NONE || S > 0.  A read with no valid window passes only if min_strong == 0, min_len <= L
+ *   and the mode is NONE: no special case is made.
+ * PAIRS.  flags & KMC_TRIM_PAIR_BOTH or flags & KMC_TRIM_PAIR_EITHER: reads 2i and 2i + 1 are mates.  Giving both flags, or
+ *   an odd n_reads, is KMC_ERR_ARG.  The pair's verdict is the AND (BOTH) or the OR (EITHER) of its mates' PASS, and both
+ *   mates get it.  Without a pair flag a read's verdict is its own PASS.
+ * INVERT.  flags & KMC_TRIM_INVERT: a read is emitted iff its verdict is false.  This requires mode == KMC_TRIM_NONE,
+ *   otherwise KMC_ERR_ARG.  Without the flag a read is emitted iff its verdict is true.
+ * Outputs.  out_bases: the spans of the emitted reads, concatenated in read order, bytes copied as given (lower case and N
+ *   inside an ENDS span included).  out_offsets[n_out + 1], uint64_t, [0] == 0.  origin[n_out], uint64_t: the source read
+ *   of each emitted read.  read_stats[n_reads * KMC_TRIM_READ_WORDS], uint32_t, for EVERY read, emitted or not: [0] V,
+ *   [1] S, [2] span start, [3] span len.  verdict[n_reads], uint8_t: bit 0 (KMC_TRIM_PASS) = the read's own PASS, bit 1
+ *   (KMC_TRIM_EMITTED) = emitted.  summary[KMC_TRIM_WORDS]: [0] reads, [1] valid windows, [2] strong windows, [3] reads whose
+ *   own PASS is true, [4] reads emitted (= n_out), [5] bases emitted (= out_offsets[n_out]), [6] emitted reads whose span is
+ *   shorter than the read, [7] the bases of the emitted reads before trimming.  Bases cut off the emitted reads: [7] - [5].
+ * Identities.  Mode NONE with min_strong = min_permille = min_len = 0 and no flags returns the batch as it came: same bytes,
+ *   same offsets, origin[i] == i.  The same arguments with INVERT emit nothing.  A second call with the same arguments on the
+ *   output of a LONGEST or ENDS call (min_len 0) returns that output unchanged; after LONGEST its summary has [1] == [2].
+ *   For every read, words [0], [1] equal words [0] and [0] - [1] of kmc_correct's read_stats for the same range.  With
+ *   max_count == 0, words [0], [1] equal words [0], [1] of kmc_profile's read_stats with the same min_count.
+ * Rules: NULL ctx, KMC_MODE_LR, a non-zero max_count below min_count, an unknown mode or flag bit, min_permille > 1000, the
+ * flag combinations above, a read of 2^32 bases or more: KMC_ERR_ARG; no view: KMC_ERR_STATE (where kmc_export says so); a
+ * view of 2^32 keys or more: KMC_ERR_CAPACITY (the index's rule); a batch of 2^31 reads or 2^32 bases or more in one call:
+ * KMC_ERR_CAPACITY (the positions among the emitted reads and bases are scanned as 32-bit words; split the batch).
+ * n_reads == 0 gives zeros and out_offsets[0] == 0.  An empty view makes nothing strong.
+ * What the call changes: it builds or reuses the query index.  It rewrites none of: the view, a partition, a filter or
+ * set-operation result, adj, the unitigs, links, a clean / simplify / components result, a map result, and the arrays a
+ * kmc_correct* call handed out.
+ * Diagnostic: with KMC_UNITIG_TRACE set, a call prints "kmc_trim: keys N reads R windows W strong S passed P emitted E bases
+ * B mark_ms .. reduce_ms .. layout_ms .. gather_ms .." to stderr (tools/measure_trim.py reads it). ---- */
+#define KMC_TRIM_WORDS 8
+#define KMC_TRIM_READ_WORDS 4
+#define KMC_TRIM_NONE 0
+#define KMC_TRIM_ENDS 1
+#define KMC_TRIM_LONGEST 2
+#define KMC_TRIM_INVERT 1u
+#define KMC_TRIM_PAIR_BOTH 2u
+#define KMC_TRIM_PAIR_EITHER 4u
+#define KMC_TRIM_PASS 1u      /* verdict bit 0 */
+#define KMC_TRIM_EMITTED 2u   /* verdict bit 1 */
+/* The batch in device memory, by the layout and alignment rules of kmc_profile_device.  The results in ctx-owned device
+ * arrays -- uint8_t out_bases[n_out_bases], uint64_t out_offsets[n_out + 1], uint64_t origin[n_out], uint32_t read_stats[n_reads
+ * * 4], uint8_t verdict[n_reads] -- valid until the next kmc_trim* call / finalize / reset / destroy (the contract of
+ * kmc_correct_device: the call has finished when it returns).  d_out_bases is 16-byte aligned and readable to the next 16-byte
+ * boundary past the last base (those bytes are zero): with d_out_offsets it goes straight into kmc_add_batch_device,
+ * kmc_profile_device, kmc_unitig_map_device, kmc_correct_device and back into kmc_trim_device, of this or another ctx on the
+ * device.  A caller may hand the last call's own d_out_bases / d_out_offsets back in: the ctx double-buffers the two arrays
+ * (a call writes the pair the call before it did not), so the result of the call BEFORE the last one is gone.  Every output
+ * pointer may be NULL. */
+int kmc_trim_device(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, int mode, uint32_t flags, uint64_t min_strong,
+                    uint32_t min_permille, uint64_t min_len, const void* d_bases, const void* d_offsets, uint64_t n_reads,
+                    uint64_t n_bases, const void** d_out_bases, const void** d_out_offsets, const void** d_origin,
+                    const void** d_read_stats, const void** d_verdict, uint64_t* n_out, uint64_t* n_out_bases,
+                    uint64_t* summary);
+/* The same on host buffers (the batch as kmc_profile takes it).  The caller supplies out_bases with room for cap_bases
+ * bytes, out_offsets with room for cap_reads + 1 entries, origin for cap_reads, read_stats[n_reads * 4] and verdict[n_reads].
+ * *n_out and *n_out_bases are always set; a cap too small for an array that was given -> KMC_ERR_ARG and nothing is copied;
+ * an array that is NULL is not copied and its cap not looked at.  All arrays NULL is the sizing call.  The host form computes
+ * on EVERY call. */
+int kmc_trim(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, int mode, uint32_t flags, uint64_t min_strong,
+             uint32_t min_permille, uint64_t min_len, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads,
+             uint8_t* out_bases, uint64_t cap_bases, uint64_t* out_offsets, uint64_t* origin, uint64_t cap_reads,
+             uint32_t* read_stats, uint8_t* verdict, uint64_t* n_out, uint64_t* n_out_bases, uint64_t* summary);
 
 /* ---- the compacted graph cleaned: tips clipped, islands dropped (additions, as above).  Everything refers to the unitigs
  * and the link records of kmc_unitigs / kmc_unitig_links for the same view and range min_count..max_count.  For unitig u:

@@ -97,6 +97,7 @@ ABI_SYMBOLS = [
     "kmc_unitig_components", "kmc_unitig_components_device", "kmc_unitig_components_into",
     "kmc_unitig_map", "kmc_unitig_map_device",
     "kmc_correct", "kmc_correct_device",
+    "kmc_trim", "kmc_trim_device",
 ]
 
 PROFILE_WORDS = 5  # KMC_PROFILE_WORDS: valid windows, present windows, min, max, sum
@@ -119,6 +120,12 @@ MAP_NONE = 0xFFFFFFFF  # KMC_MAP_NONE: the low half of the place word of a windo
 CORRECT_WORDS = 8       # KMC_CORRECT_WORDS: reads, valid windows, weak windows, weak runs, candidates, corrected, ambiguous, weak windows left
 CORRECT_READ_WORDS = 4  # KMC_CORRECT_READ_WORDS: a read's valid windows, weak windows, candidates, corrected
 CORRECT_INTERIOR, CORRECT_HEAD, CORRECT_TAIL = 0, 1, 2   # KMC_CORRECT_*: a candidate's kind
+TRIM_WORDS = 8       # KMC_TRIM_WORDS: reads, valid windows, strong windows, reads passing, reads emitted, bases emitted, emitted reads cut, their bases before
+TRIM_READ_WORDS = 4  # KMC_TRIM_READ_WORDS: a read's valid windows, strong windows, span start, span length
+TRIM_NONE, TRIM_ENDS, TRIM_LONGEST = 0, 1, 2   # KMC_TRIM_*: the mode
+TRIM_INVERT, TRIM_PAIR_BOTH, TRIM_PAIR_EITHER = 1, 2, 4   # KMC_TRIM_*: the flag bits
+TRIM_PASS, TRIM_EMITTED = 1, 2   # KMC_TRIM_*: the bits of a read's verdict byte
+TRIM_MODE_NAMES = {"none": TRIM_NONE, "ends": TRIM_ENDS, "longest": TRIM_LONGEST}
 SETOP_INTERSECT, SETOP_UNION, SETOP_SUBTRACT = 0, 1, 2
 COUNT_LEFT, COUNT_RIGHT, COUNT_MIN, COUNT_MAX, COUNT_SUM, COUNT_DIFF = 0, 1, 2, 3, 4, 5
 SETOP_NAMES = {"intersect": SETOP_INTERSECT, "union": SETOP_UNION, "subtract": SETOP_SUBTRACT}
@@ -203,6 +210,8 @@ def lib() -> C.CDLL:
     L.kmc_unitig_map.argtypes = [vp, u64, u64, vp, vp, u64, vp, vp, vp, vp, u64, vp, u64, pu64, pu64, vp]
     L.kmc_correct_device.argtypes = [vp, u64, u64, vp, vp, u64, u64] + [C.POINTER(vp)] * 4 + [pu64, vp]
     L.kmc_correct.argtypes = [vp, u64, u64, vp, vp, u64, vp, vp, vp, vp, u64, pu64, vp]
+    L.kmc_trim_device.argtypes = [vp, u64, u64, i32, u32, u64, u32, u64, vp, vp, u64, u64] + [C.POINTER(vp)] * 5 + [pu64, pu64, vp]
+    L.kmc_trim.argtypes = [vp, u64, u64, i32, u32, u64, u32, u64, vp, vp, u64, vp, u64, vp, vp, u64, vp, vp, pu64, pu64, vp]
     L.kmc_owner_of.argtypes = [u64, u64, u32]
     L.kmc_owner_of.restype = u32
     L.kmc_get_stats.argtypes = [vp, C.POINTER(Stats)]
@@ -651,6 +660,61 @@ class CorrectedReads:
     def to_fasta(self) -> str:
         """What ``k-mer-count --correct`` prints: ``>INDEX WINDOWS WEAK CANDIDATES FIXED`` and the corrected read."""
         return "".join(">%d %d %d %d %d\n%s\n" % (i, s[0], s[1], s[2], s[3], r) for i, (s, r) in enumerate(zip(self.stats.tolist(), self.strings())))
+
+
+_TRIM_FIELDS = ("reads", "valid_windows", "strong_windows", "passed", "emitted", "bases", "cut_reads", "bases_before")
+
+
+@dataclass
+class TrimSummary:
+    """The eight words of kmc_trim: reads, valid windows, strong windows, reads whose own PASS is true, reads emitted, bases
+    emitted, emitted reads whose span is shorter than the read, the bases of the emitted reads before trimming."""
+    reads: int
+    valid_windows: int
+    strong_windows: int
+    passed: int
+    emitted: int
+    bases: int
+    cut_reads: int
+    bases_before: int
+
+    @classmethod
+    def from_words(cls, words) -> "TrimSummary":
+        return cls(*[int(w) for w in words])
+
+    def words(self) -> list:
+        return [getattr(self, f) for f in _TRIM_FIELDS]
+
+    def to_text(self) -> str:
+        """``NAME\tVALUE`` lines."""
+        return "\n".join("%s\t%d" % (f, getattr(self, f)) for f in _TRIM_FIELDS) + "\n"
+
+
+@dataclass
+class TrimmedReads:
+    """What KmerCounter.trim_reads returns: the emitted spans as a batch -- ``bases`` uint8[n_out_bases], ``offsets``
+    uint64[n_out + 1] -- with ``origin`` uint64[n_out] (the source read of each), and for every read of the input ``stats``
+    uint32[n_reads, 4] (valid windows, strong windows, span start, span length) and ``verdict`` uint8[n_reads] (TRIM_PASS |
+    TRIM_EMITTED); ``summary``."""
+    bases: np.ndarray
+    offsets: np.ndarray
+    origin: np.ndarray
+    stats: np.ndarray
+    verdict: np.ndarray
+    summary: TrimSummary
+
+    def __len__(self) -> int:
+        return len(self.offsets) - 1
+
+    def strings(self) -> list:
+        """The emitted spans as str."""
+        o, b = self.offsets, self.bases.tobytes()
+        return [b[int(o[i]):int(o[i + 1])].decode("latin-1") for i in range(len(self))]
+
+    def to_fasta(self) -> str:
+        """What ``k-mer-count --trim`` prints, emitted reads only: ``>INDEX WINDOWS STRONG START LEN`` and the span."""
+        st = self.stats.tolist()
+        return "".join(">%d %d %d %d %d\n%s\n" % ((r,) + tuple(st[r]) + (s,)) for r, s in zip(self.origin.tolist(), self.strings()))
 
 
 _CLEAN_FIELDS = ("unitigs", "tips", "islands", "kept_keys", "tip_keys", "island_keys", "tip_candidates", "kept_count")
@@ -1177,6 +1241,50 @@ class KmerCounter:
         out = words(db, n_bases) if n_reads else bases.copy()
         return CorrectedReads(out, offsets.copy() if n_reads else np.zeros(1, np.uint64), words(ds, 16 * n_reads).view(np.uint32).reshape(n_reads, CORRECT_READ_WORDS),
                               words(do, 8 * (n_reads + 1)).view(np.uint64), words(dc, 16 * nc).view(np.uint32).reshape(nc, 4), summary)
+
+    # -- reads trimmed and filtered by their strong windows (of the sorted view; finalize() first) --
+    def trim_reads_device(self, d_bases: int, d_offsets: int, n_reads: int, n_bases: int, min_count: int = 1, max_count: int = 0,
+                          mode: int = TRIM_LONGEST, flags: int = 0, min_strong: int = 0, min_permille: int = 0, min_len: int = 0):
+        """(d_out_bases, d_out_offsets, d_origin, d_read_stats, d_verdict, n_out, n_out_bases, TrimSummary) of kmc_trim_device
+        for a batch in device memory (raw addresses, laid out as for profile_device): ctx-owned device arrays of n_out_bases
+        uint8 (padded as add_batch_device asks), n_out + 1 uint64, n_out uint64, n_reads * 4 uint32 and n_reads uint8."""
+        p = [C.c_void_p() for _ in range(5)]
+        no, nb = C.c_uint64(), C.c_uint64()
+        w = (C.c_uint64 * TRIM_WORDS)()
+        self._chk(self._L.kmc_trim_device(self._h, int(min_count), int(max_count), int(mode), int(flags), int(min_strong), int(min_permille),
+                                          int(min_len), d_bases or None, d_offsets or None, int(n_reads), int(n_bases),
+                                          *[C.byref(x) for x in p], C.byref(no), C.byref(nb), w))
+        return tuple(x.value or 0 for x in p) + (no.value, nb.value, TrimSummary.from_words(list(w)))
+
+    def trim_reads_tensors(self, bases, offsets, min_count: int = 1, max_count: int = 0, mode: int = TRIM_LONGEST, flags: int = 0,
+                           min_strong: int = 0, min_permille: int = 0, min_len: int = 0):
+        """trim_reads_device for torch tensors on this ctx's GPU (bases uint8[n_bases], padded as for add_batch_tensors;
+        offsets int64[n_reads + 1])."""
+        assert bases.is_cuda and offsets.is_cuda and bases.is_contiguous() and offsets.is_contiguous()
+        return self.trim_reads_device(bases.data_ptr(), offsets.data_ptr(), max(offsets.numel() - 1, 0), bases.numel(), min_count, max_count,
+                                      mode, flags, min_strong, min_permille, min_len)
+
+    def trim_reads(self, bases: np.ndarray, offsets: np.ndarray, min_count: int = 1, max_count: int = 0, mode: int = TRIM_LONGEST,
+                   flags: int = 0, min_strong: int = 0, min_permille: int = 0, min_len: int = 0) -> "TrimmedReads":
+        """kmc_trim for a host batch (the batch is not counted): per read the span the table supports (mode: the whole read,
+        from the first to the last strong window, or the longest run of strong windows; strong = count in
+        min_count..max_count), the reads that pass min_strong / min_permille / min_len (flags: pairs, inverted) and their
+        spans as a new batch."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n_reads = max(int(offsets.shape[0]) - 1, 0)
+        if n_reads and int(offsets[-1]) != int(bases.shape[0]):
+            raise ValueError("offsets must end at len(bases)")
+        args = (int(min_count), int(max_count), int(mode), int(flags), int(min_strong), int(min_permille), int(min_len),
+                bases.ctypes.data if n_reads else None, offsets.ctypes.data if n_reads else None, n_reads)
+        no, nb = C.c_uint64(), C.c_uint64()
+        w = (C.c_uint64 * TRIM_WORDS)()
+        self._chk(self._L.kmc_trim(self._h, *args, None, 0, None, None, 0, None, None, C.byref(no), C.byref(nb), None))
+        out, oo, org = np.zeros(nb.value, np.uint8), np.zeros(no.value + 1, np.uint64), np.zeros(no.value, np.uint64)
+        stats, verdict = np.zeros((n_reads, TRIM_READ_WORDS), np.uint32), np.zeros(n_reads, np.uint8)
+        self._chk(self._L.kmc_trim(self._h, *args, out.ctypes.data, nb.value, oo.ctypes.data, org.ctypes.data, no.value, stats.ctypes.data,
+                                   verdict.ctypes.data, C.byref(no), C.byref(nb), w))
+        return TrimmedReads(out, oo, org, stats, verdict, TrimSummary.from_words(list(w)))
 
     # -- that graph cleaned: tips clipped, islands dropped (of the sorted view; finalize() first) --
     def _clean_limits(self, max_tip_keys, max_island_keys) -> Tuple[int, int]:

@@ -6,6 +6,8 @@
 //
 //   k-mer-count [FASTA] [-k K] [--forward] [--expand] [--device N | --gpus N] [--algo auto|stream|walk|sort] [--stats]
 //               [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE | --map FILE | --correct FILE]
+//               [--trim FILE [--trim-mode none|ends|longest] [--min-strong N] [--strong-permille N] [--min-len N] [--invert]
+//                [--paired both|either]]
 //               [--with FASTA2 (--compare | --setop intersect|union|subtract [--counts left|right|min|max|sum|diff])]
 //               [--graph | --graph-stats | --unitigs | --gfa | --components]
 //               [--clean ROUNDS [--tip-keys N] [--island-keys N] [--bubble-keys N]] [--component-keys N]
@@ -39,6 +41,17 @@
 //               ">INDEX WINDOWS WEAK CANDIDATES FIXED" -- its valid K-mer windows, how many of them are not solid, the weak
 //               runs that qualify as one substitution, how many of those were repaired -- then the corrected read on one
 //               line.  With --clean the reads are corrected against the cleaned table.
+//   --trim FILE          (with -k K) instead of the table: every read of FILE (FASTA / FASTQ) judged by its strong windows -- those
+//               whose key the counted input holds within --min-count / --max-count -- and cut down to the span the table
+//               supports (kmc_trim).  --trim-mode: none keeps a read whole, ends cuts it from its first to its last strong
+//               window, longest (the default) to its longest run of strong windows.  A read passes with --min-strong N
+//               strong windows or more, --strong-permille N thousandths or more of its valid windows strong, and a span of
+//               --min-len N bases or more (default 0 each; a trimming mode also asks for one strong window).  --paired
+//               both|either: reads 2i and 2i + 1 are mates and stay or go together, if both / either of them pass.
+//               --invert (with --trim-mode none) prints the reads that fail instead.  Output: FASTA in file order, the
+//               emitted reads only: ">INDEX WINDOWS STRONG START LEN" -- the read's number in FILE, its valid and its strong
+//               windows, the span's start and length in bases -- then the span on one line.  It excludes --query-kmers /
+//               --profile / --map / --correct; with --clean the reads are judged against the cleaned table.
 //
 //   --with FASTA2        (with -k K) a second file, counted into a second table on the same device; one of:
 //     --compare          instead of the table: "NAME<TAB>VALUE" lines -- the eight words of kmc_compare (n_a, n_b, n_both, sum_a,
@@ -128,6 +141,9 @@ int main(int argc, char** argv) {
     int k = 0, canonical = 1, expand = 0, device = 0, algo = KMC_ALGO_AUTO, stats = 0, gpus = 1, histo = 0;
     long long min_count = 1, max_count = 0;   // (max_count 0: no upper bound)
     const char *query_path = nullptr, *profile_path = nullptr, *with_path = nullptr, *map_path = nullptr, *correct_path = nullptr;
+    const char* trim_path = nullptr;
+    int trim_mode = -1, trim_invert = 0, trim_pair = 0;   // (-1: the default mode, longest)
+    long long min_strong = -1, strong_permille = -1, min_len = -1;   // (-1: not given)
     int compare = 0, setop = -1, count_mode = -1, graph = 0, graph_stats = 0, unitigs = 0, gfa = 0;
     int clean = 0;
     long long tip_keys = -1, island_keys = -1;   // (-1: K)
@@ -149,6 +165,22 @@ int main(int argc, char** argv) {
         else if (a == "--profile" && i + 1 < argc) profile_path = argv[++i];
         else if (a == "--map" && i + 1 < argc) map_path = argv[++i];
         else if (a == "--correct" && i + 1 < argc) correct_path = argv[++i];
+        else if (a == "--trim" && i + 1 < argc) trim_path = argv[++i];
+        else if (a == "--trim-mode" && i + 1 < argc) {
+            std::string v = argv[++i];
+            trim_mode = v == "none" ? KMC_TRIM_NONE : v == "ends" ? KMC_TRIM_ENDS : v == "longest" ? KMC_TRIM_LONGEST : -1;
+            if (trim_mode < 0) { fprintf(stderr, "k-mer-count: --trim-mode needs none, ends or longest (got '%s')\n", v.c_str()); return 2; }
+        } else if (a == "--min-strong" && i + 1 < argc) { if (!parse_count("--min-strong", argv[++i], 0, LLONG_MAX, &min_strong)) return 2; }
+        else if (a == "--strong-permille" && i + 1 < argc) { if (!parse_count("--strong-permille", argv[++i], 0, 1000, &strong_permille)) return 2; }
+        else if (a == "--min-len" && i + 1 < argc) { if (!parse_count("--min-len", argv[++i], 0, LLONG_MAX, &min_len)) return 2; }
+        else if (a == "--invert") trim_invert = 1;
+        else if (a == "--paired" && i + 1 < argc) {
+            std::string v = argv[++i];
+            const int p = v == "both" ? (int)KMC_TRIM_PAIR_BOTH : v == "either" ? (int)KMC_TRIM_PAIR_EITHER : 0;
+            if (!p) { fprintf(stderr, "k-mer-count: --paired needs both or either (got '%s')\n", v.c_str()); return 2; }
+            if (trim_pair && trim_pair != p) { fprintf(stderr, "k-mer-count: --paired both and --paired either exclude each other\n"); return 2; }
+            trim_pair = p;
+        }
         else if (a == "--with" && i + 1 < argc) with_path = argv[++i];
         else if (a == "--compare") compare = 1;
         else if (a == "--graph") graph = 1;
@@ -176,13 +208,16 @@ int main(int argc, char** argv) {
         } else if (a == "-h" || a == "--help") {
             fprintf(stderr, "usage: k-mer-count [FASTA] [-k K] [--forward] [--expand] [--device N | --gpus N] [--algo auto|stream|walk|sort] [--stats]\n"
                             "                   [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE | --map FILE | --correct FILE]\n"
+                            "                   [--trim FILE [--trim-mode none|ends|longest] [--min-strong N] [--strong-permille N] [--min-len N] [--invert]\n"
+                            "                    [--paired both|either]]\n"
                             "                   [--with FASTA2 (--compare | --setop intersect|union|subtract [--counts left|right|min|max|sum|diff])]\n"
                             "                   [--graph | --graph-stats | --unitigs | --gfa | --components]\n"
                             "                   [--clean ROUNDS [--tip-keys N] [--island-keys N] [--bubble-keys N]] [--component-keys N]\n");
             return 0;
         } else if (a == "-k" || a == "--device" || a == "--gpus" || a == "--algo" || a == "--min-count" || a == "--max-count" || a == "--histo" ||
                    a == "--query-kmers" || a == "--profile" || a == "--map" || a == "--correct" || a == "--with" || a == "--setop" || a == "--counts" ||
-                   a == "--clean" || a == "--tip-keys" || a == "--island-keys" || a == "--bubble-keys" || a == "--component-keys") {
+                   a == "--clean" || a == "--tip-keys" || a == "--island-keys" || a == "--bubble-keys" || a == "--component-keys" || a == "--trim" ||
+                   a == "--trim-mode" || a == "--min-strong" || a == "--strong-permille" || a == "--min-len" || a == "--paired") {
             fprintf(stderr, "k-mer-count: %s needs a value\n", a.c_str());
             return 2;
         } else if (!a.empty() && a[0] != '-') path = argv[i];
@@ -226,6 +261,23 @@ int main(int argc, char** argv) {
         else if (expand) bad = "--expand exclude each other";
         if (bad) { fprintf(stderr, "k-mer-count: --correct %s%s\n", strncmp(bad, "needs", 5) ? "and " : "", bad); return 2; }
     }
+    // --trim and its options: the same again
+    if (trim_path) {
+        const char* bad = nullptr;
+        if (!k) bad = "needs -k K";
+        else if (map_path || correct_path) bad = "--map / --correct exclude each other";
+        else if (query_path || profile_path) bad = "--query-kmers / --profile exclude each other";
+        else if (histo) bad = "--histo exclude each other";
+        else if (with_path || compare || setop >= 0) bad = "--with / --compare / --setop exclude each other";
+        else if (graph || graph_stats || unitigs || gfa) bad = "--graph / --graph-stats / --unitigs / --gfa exclude each other";
+        else if (expand) bad = "--expand exclude each other";
+        if (bad) { fprintf(stderr, "k-mer-count: --trim %s%s\n", strncmp(bad, "needs", 5) ? "and " : "", bad); return 2; }
+        if (trim_mode < 0) trim_mode = KMC_TRIM_LONGEST;
+        if (trim_invert && trim_mode != KMC_TRIM_NONE) { fprintf(stderr, "k-mer-count: --invert needs --trim-mode none\n"); return 2; }
+    } else if (trim_mode >= 0 || trim_invert || trim_pair || min_strong >= 0 || strong_permille >= 0 || min_len >= 0) {
+        fprintf(stderr, "k-mer-count: --trim-mode / --min-strong / --strong-permille / --min-len / --invert / --paired need --trim FILE\n");
+        return 2;
+    }
     if (query_path) {
         FILE* f = fopen(query_path, "r");
         if (!f) return die(query_path, strerror(errno));
@@ -250,8 +302,8 @@ int main(int argc, char** argv) {
         }
         fclose(f);
     }
-    if (profile_path || map_path || correct_path) {
-        const char* reads_path = profile_path ? profile_path : map_path ? map_path : correct_path;
+    if (profile_path || map_path || correct_path || trim_path) {
+        const char* reads_path = profile_path ? profile_path : map_path ? map_path : correct_path ? correct_path : trim_path;
         char eb[256] = {0};
         const int prc = kmc_parse_fasta(reads_path, &prof, eb, sizeof(eb));
         if (prc) return die(reads_path, eb[0] ? eb : kmc_status_string(prc));
@@ -267,6 +319,7 @@ int main(int argc, char** argv) {
         else if (with_path && !k) bad = "--with needs -k K";
         else if (with_path && (histo || query_path || profile_path)) bad = "--with and --histo / --query-kmers / --profile exclude each other";
         else if (with_path && map_path) bad = "--with and --map exclude each other";
+        else if (with_path && trim_path) bad = "--with and --trim exclude each other";
         else if (with_path && gpus != 1) bad = "--with and --gpus exclude each other";
         if (bad) { fprintf(stderr, "k-mer-count: %s\n", bad); return 2; }
     }
@@ -298,7 +351,7 @@ int main(int argc, char** argv) {
         if (!k) bad = "needs -k K";
         else if (graph || graph_stats || unitigs || gfa) bad = "--graph / --graph-stats / --unitigs / --gfa exclude each other";
         else if (histo) bad = "--histo exclude each other";
-        else if (query_path || profile_path || map_path || correct_path) bad = "--query-kmers / --profile / --map / --correct exclude each other";
+        else if (query_path || profile_path || map_path || correct_path || trim_path) bad = "--query-kmers / --profile / --map / --correct / --trim exclude each other";
         else if (with_path || compare || setop >= 0) bad = "--with / --compare / --setop exclude each other";
         else if (expand) bad = "--expand exclude each other";
         if (bad) { fprintf(stderr, "k-mer-count: --components %s%s\n", strncmp(bad, "needs", 5) ? "and " : "", bad); return 2; }
@@ -515,6 +568,40 @@ int main(int argc, char** argv) {
         }
         fflush(stdout);
         kmc_free_reads(&prof);
+        destroy_all();
+        return 0;
+    }
+    if (trim_path) {
+        // the host form computes on every call: the first call sizes the emitted batch (and fills the per-read rows), the second
+        // copies it
+        const uint64_t n_trim = prof.n_reads, lo_c = (uint64_t)min_count, hi_c = (uint64_t)max_count;
+        const uint32_t flags = (trim_invert ? KMC_TRIM_INVERT : 0u) | (uint32_t)trim_pair;
+        const uint64_t ms = min_strong < 0 ? 0 : (uint64_t)min_strong, ml = min_len < 0 ? 0 : (uint64_t)min_len;
+        const uint32_t mp = strong_permille < 0 ? 0u : (uint32_t)strong_permille;
+        if (trim_pair && (n_trim & 1)) {
+            kmc_free_reads(&prof);
+            fprintf(stderr, "k-mer-count: --paired needs an even number of reads (%s has %llu)\n", trim_path, (unsigned long long)n_trim);
+            destroy_all();
+            return 2;
+        }
+        std::vector<uint32_t> rs((size_t)n_trim * KMC_TRIM_READ_WORDS + 1);
+        uint64_t no = 0, nb = 0;
+        rc = kmc_trim(ctx, lo_c, hi_c, trim_mode, flags, ms, mp, ml, prof.bases, prof.offsets, n_trim, nullptr, 0, nullptr, nullptr, 0, rs.data(), nullptr,
+                      &no, &nb, nullptr);
+        std::vector<uint8_t> ob((size_t)nb + 1);
+        std::vector<uint64_t> oo((size_t)no + 1), og((size_t)no + 1);
+        if (!rc) rc = kmc_trim(ctx, lo_c, hi_c, trim_mode, flags, ms, mp, ml, prof.bases, prof.offsets, n_trim, ob.data(), nb, oo.data(), og.data(), no,
+                               nullptr, nullptr, &no, &nb, nullptr);
+        kmc_free_reads(&prof);
+        if (rc) { int r = die("kmc_trim", kmc_last_error(ctx)); destroy_all(); return r; }
+        setvbuf(stdout, obuf.data(), _IOFBF, obuf.size());
+        for (uint64_t i = 0; i < no; ++i) {
+            const uint32_t* w = &rs[(size_t)og[i] * KMC_TRIM_READ_WORDS];
+            printf(">%llu %u %u %u %u\n", (unsigned long long)og[i], w[0], w[1], w[2], w[3]);
+            fwrite(ob.data() + oo[i], 1, (size_t)(oo[i + 1] - oo[i]), stdout);
+            fputc('\n', stdout);
+        }
+        fflush(stdout);
         destroy_all();
         return 0;
     }

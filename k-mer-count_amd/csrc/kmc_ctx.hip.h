@@ -243,6 +243,14 @@ struct kmc_ctx : CtxStream {
     // call: the corrected copy of the batch, per-read rows, candidate offsets and records; between the passes the
     // read-start, valid-window and weak-window bits of the batch and, per candidate, its batch position and read.
     DevBuf cr_out, cr_stats, cr_coffs, cr_cands, cr_where, cr_sbits, cr_vbits, cr_wbits;
+    // kmc_trim / kmc_trim_device (kmc_trim.hip.h) read the view and the query index alone.  The result of the last call: the
+    // emitted spans as a batch (bases and offsets in two buffers each, written in turn: tr_cur is the pair of the last call,
+    // so a caller may hand that result back in), the source read of each, per-read rows and verdicts.  Between the passes:
+    // the bit arrays of the mark pass (its own, a correct result stays as it is), six words of runs per read, the list of
+    // the reads a wave or a workgroup reduces, the emitted flags and span lengths with their scans, each span's batch position.
+    DevBuf tr_out[2], tr_ooffs[2], tr_origin, tr_stats, tr_verdict;
+    DevBuf tr_sbits, tr_vbits, tr_wbits, tr_runs, tr_list, tr_emit, tr_elen, tr_epos, tr_lpos, tr_src;
+    int tr_cur = 0;
     // kmc_unitig_clean* and kmc_unitig_simplify* (kmc_clean.hip.h) read the unitigs, the links and what the links pass
     // reads.  Their result: the verdict per unitig and the kept table, with cl_key plus its three limits cl_tip / cl_isl /
     // cl_bub (0 for a clean call) and cl_words as above (nothing but the clean pass writes them; a clean call hands out the

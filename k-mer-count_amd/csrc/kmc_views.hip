@@ -17,6 +17,7 @@
 #include "kmc_components.hip.h"
 #include "kmc_map.hip.h"
 #include "kmc_correct.hip.h"
+#include "kmc_trim.hip.h"
 
 namespace {
 
@@ -1310,6 +1311,170 @@ static int kmc_correct_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, 
     return KMC_OK;
 }
 
+// ---- reads trimmed and filtered by their strong windows: runs per read, verdicts, the emitted spans as a batch (kmc_trim.hip.h) ----
+// the rule arguments of both calls (kmc.h: SPAN, PASS, PAIRS, INVERT)
+static int trim_rule(kmc_ctx* c, const char* what, int mode, uint32_t flags, uint64_t min_strong, uint32_t min_permille, uint64_t min_len,
+                     uint64_t n_reads, TrimRule* R) {
+    if (mode != KMC_TRIM_NONE && mode != KMC_TRIM_ENDS && mode != KMC_TRIM_LONGEST) return fail(c, KMC_ERR_ARG, "%s: unknown mode %d", what, mode);
+    if (flags & ~(KMC_TRIM_INVERT | KMC_TRIM_PAIR_BOTH | KMC_TRIM_PAIR_EITHER)) return fail(c, KMC_ERR_ARG, "%s: unknown flag bits 0x%x", what, flags);
+    if ((flags & KMC_TRIM_PAIR_BOTH) && (flags & KMC_TRIM_PAIR_EITHER)) return fail(c, KMC_ERR_ARG, "%s: KMC_TRIM_PAIR_BOTH and KMC_TRIM_PAIR_EITHER exclude each other", what);
+    if ((flags & (KMC_TRIM_PAIR_BOTH | KMC_TRIM_PAIR_EITHER)) && (n_reads & 1))
+        return fail(c, KMC_ERR_ARG, "%s: %llu reads cannot be pairs", what, (unsigned long long)n_reads);
+    if ((flags & KMC_TRIM_INVERT) && mode != KMC_TRIM_NONE) return fail(c, KMC_ERR_ARG, "%s: KMC_TRIM_INVERT needs KMC_TRIM_NONE", what);
+    if (min_permille > 1000) return fail(c, KMC_ERR_ARG, "%s: min_permille %u > 1000", what, min_permille);
+    R->mode = mode; R->k = c->klen; R->flags = flags; R->min_permille = min_permille; R->min_strong = min_strong; R->min_len = min_len;
+    return KMC_OK;
+}
+
+// The batch (device arrays) judged against the keys of this view inside the range, into the tr_* buffers; h[KMC_TRIM_WORDS]
+// the summary.  Finished when it returns.
+static int trim_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count, const TrimRule& R, const uint8_t* d_bases, const u64* d_offsets,
+                    u64 n_reads, u64 n_bases, u64* h) {
+    memset(h, 0, KMC_TRIM_WORDS * sizeof(u64));
+    int rc;
+    const u64 n = c->n_sorted;
+    const int k = c->klen;
+    // the scans of kmc_scan.hip.h work on u32: positions among the reads and among the emitted bases
+    if (n_reads >= (1ull << 31) || n_bases >= (1ull << 32)) return fail(c, KMC_ERR_CAPACITY, "%s: a batch of 2^31 reads or 2^32 bases or more", what);
+    ChunkGrid g;
+    if ((rc = chunk_grid(c, what, n_bases, k, &g))) return rc;
+    const int cur = c->tr_cur ^ 1;   // the last call's result stays readable while this one is written
+    const u64 nr1 = std::max<u64>(n_reads, 1);
+    const size_t bitb = (size_t)std::max<u64>(g.n_chunks, 1) * 64 * sizeof(uint16_t), w32 = (size_t)nr1 * sizeof(u32);
+    const size_t scan_blocks = (size_t)((n_reads + KMC_SCAN_PER_BLOCK - 1) / KMC_SCAN_PER_BLOCK);
+    if ((rc = ensure(c, c->tr_out[cur], (size_t)n_bases + 64)) || (rc = ensure(c, c->tr_ooffs[cur], (size_t)(n_reads + 1) * sizeof(u64))) ||
+        (rc = ensure(c, c->tr_origin, (size_t)nr1 * sizeof(u64))) || (rc = ensure(c, c->tr_stats, (size_t)nr1 * KMC_TRIM_READ_WORDS * sizeof(u32))) ||
+        (rc = ensure(c, c->tr_verdict, (size_t)nr1)) || (rc = ensure(c, c->tr_sbits, bitb)) || (rc = ensure(c, c->tr_vbits, bitb)) ||
+        (rc = ensure(c, c->tr_wbits, bitb)) || (rc = ensure(c, c->tr_runs, (size_t)nr1 * 2 * sizeof(uint4))) || (rc = ensure(c, c->tr_list, w32)) ||
+        (rc = ensure(c, c->tr_emit, w32)) || (rc = ensure(c, c->tr_elen, w32)) || (rc = ensure(c, c->tr_epos, w32)) || (rc = ensure(c, c->tr_lpos, w32)) ||
+        (rc = ensure(c, c->tr_src, (size_t)nr1 * sizeof(u64))) || (rc = ensure(c, c->c_bsum, (scan_blocks + 2) * sizeof(u32))) ||
+        (rc = ensure(c, c->c_ctl, KMC_TR_CTL_WORDS * sizeof(u64))))
+        return rc;
+    c->tr_cur = cur;
+    if (!n_reads) {
+        HIPCHK(c, hipMemsetAsync(c->tr_ooffs[cur].p, 0, sizeof(u64), c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return KMC_OK;
+    }
+    QView v;
+    if ((rc = query_view(c, what, &v))) return rc;
+    kmc_ull* ctl = (kmc_ull*)c->c_ctl.p;
+    HIPCHK(c, hipMemsetAsync(ctl, 0, KMC_TR_CTL_WORDS * sizeof(u64), c->stream));
+    const u64 lo_c = std::max<u64>(min_count, 1), hi_c = count_hi(max_count);
+    UnitigTrace tr;
+    tr.mark(c->stream);
+    if (g.n_chunks) with_kw_canon(c, [&](auto KW, auto CANON) {
+        hipLaunchKernelGGL((kmc_correct_mark_kernel<KW(), CANON()>), dim3((u32)g.grid), dim3(KMC_Q_THREADS), 0, c->stream, d_bases, n_bases, d_offsets,
+                           n_reads, k, g.n_chunks, g.cpw, v, lo_c, hi_c, (uint16_t*)c->tr_sbits.p, (uint16_t*)c->tr_vbits.p, (uint16_t*)c->tr_wbits.p);
+    });
+    HIPCHK(c, hipGetLastError());
+    tr.mark(c->stream);
+    TrimBits B;
+    B.valid = (const u64*)c->tr_vbits.p; B.weak = (const u64*)c->tr_wbits.p; B.n_words = g.n_chunks * 16;
+    const u32 rgrid = (u32)grid_for(c, n_reads, KMC_TR_THREADS), ggrid = (u32)std::min<u64>(n_reads, (u64)c->n_cu * 8);
+    uint4* runs = (uint4*)c->tr_runs.p;
+    hipLaunchKernelGGL(kmc_trim_reduce_kernel, dim3(rgrid), dim3(KMC_TR_THREADS), 0, c->stream, B, d_offsets, n_reads, n_bases, k, runs, (u32*)c->tr_list.p, ctl);
+    hipLaunchKernelGGL(kmc_trim_reduce_group_kernel<64>, dim3(ggrid), dim3(KMC_TR_THREADS), 0, c->stream, B, d_offsets, n_reads, n_bases, k, runs,
+                       (const u32*)c->tr_list.p, ctl);
+    hipLaunchKernelGGL(kmc_trim_reduce_group_kernel<KMC_TR_THREADS>, dim3(ggrid), dim3(KMC_TR_THREADS), 0, c->stream, B, d_offsets, n_reads, n_bases, k,
+                       runs, (const u32*)c->tr_list.p, ctl);
+    HIPCHK(c, hipGetLastError());
+    tr.mark(c->stream);
+    hipLaunchKernelGGL(kmc_trim_verdict_kernel, dim3(rgrid), dim3(KMC_TR_THREADS), 0, c->stream, R, (const uint4*)runs, d_offsets, n_reads, n_bases,
+                       (uint4*)c->tr_stats.p, (uint8_t*)c->tr_verdict.p, (u32*)c->tr_emit.p, (u32*)c->tr_elen.p, ctl);
+    launch_exclusive_scan<0>(c->stream, c->tr_emit.p, (u32)n_reads, (u32*)c->c_bsum.p, (u32*)c->tr_epos.p, (u32*)(ctl + KMC_TR_N_OUT));
+    launch_exclusive_scan<0>(c->stream, c->tr_elen.p, (u32)n_reads, (u32*)c->c_bsum.p, (u32*)c->tr_lpos.p, (u32*)(ctl + KMC_TR_N_BASES));
+    hipLaunchKernelGGL(kmc_trim_layout_kernel, dim3(rgrid), dim3(KMC_TR_THREADS), 0, c->stream, (const uint4*)c->tr_stats.p, d_offsets, n_reads,
+                       (const u32*)c->tr_emit.p, (const u32*)c->tr_elen.p, (const u32*)c->tr_epos.p, (const u32*)c->tr_lpos.p, (u64*)c->tr_ooffs[cur].p,
+                       (u64*)c->tr_origin.p, (u64*)c->tr_src.p, ctl);
+    HIPCHK(c, hipGetLastError());
+    tr.mark(c->stream);
+    if (n_bases) {
+        // the emitted bases are at most the batch's: a lane per 16 of those, the ones past the scan's total leave at once
+        const u64 blocks = ((n_bases + 15) / 16 + KMC_TR_THREADS - 1) / KMC_TR_THREADS;
+        hipLaunchKernelGGL(kmc_trim_gather_kernel, dim3((u32)blocks), dim3(KMC_TR_THREADS), 0, c->stream, d_bases, n_bases, n_reads,
+                           (const u64*)c->tr_ooffs[cur].p, (const u64*)c->tr_src.p, (uint8_t*)c->tr_out[cur].p, ctl);
+        HIPCHK(c, hipGetLastError());
+    }
+    tr.mark(c->stream);
+    u64 w[KMC_TR_CTL_WORDS];
+    HIPCHK(c, hipMemcpyAsync(w, ctl, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (w[KMC_TR_LONG]) return fail(c, KMC_ERR_ARG, "%s: %llu reads of 2^32 bases or more", what, (unsigned long long)w[KMC_TR_LONG]);
+    if (w[KMC_TR_BAD]) return fail(c, KMC_ERR_HIP, "internal error: %s met %llu indices outside their arrays", what, (unsigned long long)w[KMC_TR_BAD]);
+    if (w[KMC_TR_N_OUT] != w[KMC_TR_EMITTED] || w[KMC_TR_N_BASES] != w[KMC_TR_BASES])
+        return fail(c, KMC_ERR_HIP, "internal error: %s scanned %llu reads and %llu bases of %llu and %llu", what, (unsigned long long)w[KMC_TR_N_OUT],
+                    (unsigned long long)w[KMC_TR_N_BASES], (unsigned long long)w[KMC_TR_EMITTED], (unsigned long long)w[KMC_TR_BASES]);
+    h[0] = n_reads; h[1] = w[KMC_TR_VALID]; h[2] = w[KMC_TR_STRONG]; h[3] = w[KMC_TR_PASSED]; h[4] = w[KMC_TR_EMITTED]; h[5] = w[KMC_TR_BASES];
+    h[6] = w[KMC_TR_CUT]; h[7] = w[KMC_TR_BEFORE];
+    if (tr.on && tr.n_ev == 5) {
+        float ms[4] = {0, 0, 0, 0};
+        bool ok = hipEventSynchronize(tr.ev[4]) == hipSuccess;
+        for (int i = 0; ok && i < 4; ++i) ok = hipEventElapsedTime(&ms[i], tr.ev[i], tr.ev[i + 1]) == hipSuccess;
+        if (ok)
+            fprintf(stderr, "kmc_trim: keys %llu reads %llu windows %llu strong %llu passed %llu emitted %llu bases %llu mark_ms %.4f reduce_ms %.4f "
+                    "layout_ms %.4f gather_ms %.4f\n", (unsigned long long)n, (unsigned long long)n_reads, (unsigned long long)h[1], (unsigned long long)h[2],
+                    (unsigned long long)h[3], (unsigned long long)h[4], (unsigned long long)h[5], ms[0], ms[1], ms[2], ms[3]);
+    }
+    return KMC_OK;
+}
+
+static int kmc_trim_device_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, int mode, uint32_t flags, uint64_t min_strong,
+                                uint32_t min_permille, uint64_t min_len, const void* d_bases, const void* d_offsets, uint64_t n_reads,
+                                uint64_t n_bases, const void** d_out_bases, const void** d_out_offsets, const void** d_origin,
+                                const void** d_read_stats, const void** d_verdict, uint64_t* n_out, uint64_t* n_out_bases, uint64_t* summary) {
+    if (n_out) *n_out = 0;
+    if (n_out_bases) *n_out_bases = 0;
+    if (!c) return KMC_ERR_ARG;
+    const char* what = "kmc_trim_device";
+    int rc;
+    TrimRule R;
+    if ((rc = graph_begin(c, what, min_count, max_count)) || (rc = trim_rule(c, what, mode, flags, min_strong, min_permille, min_len, n_reads, &R))) return rc;
+    if (n_reads && (rc = check_device_batch(c, what, d_bases, d_offsets))) return rc;
+    u64 h[KMC_TRIM_WORDS];
+    if ((rc = trim_run(c, what, min_count, max_count, R, (const uint8_t*)d_bases, (const u64*)d_offsets, n_reads, n_reads ? n_bases : 0, h))) return rc;
+    if (d_out_bases) *d_out_bases = c->tr_out[c->tr_cur].p;
+    if (d_out_offsets) *d_out_offsets = c->tr_ooffs[c->tr_cur].p;
+    if (d_origin) *d_origin = c->tr_origin.p;
+    if (d_read_stats) *d_read_stats = c->tr_stats.p;
+    if (d_verdict) *d_verdict = c->tr_verdict.p;
+    if (n_out) *n_out = h[4];
+    if (n_out_bases) *n_out_bases = h[5];
+    if (summary) memcpy(summary, h, sizeof(h));
+    return KMC_OK;
+}
+
+static int kmc_trim_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, int mode, uint32_t flags, uint64_t min_strong, uint32_t min_permille,
+                         uint64_t min_len, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads, uint8_t* out_bases, uint64_t cap_bases,
+                         uint64_t* out_offsets, uint64_t* origin, uint64_t cap_reads, uint32_t* read_stats, uint8_t* verdict, uint64_t* n_out,
+                         uint64_t* n_out_bases, uint64_t* summary) {
+    if (n_out) *n_out = 0;
+    if (n_out_bases) *n_out_bases = 0;
+    if (!c) return KMC_ERR_ARG;
+    const char* what = "kmc_trim";
+    int rc;
+    TrimRule R;
+    if ((rc = graph_begin(c, what, min_count, max_count)) || (rc = trim_rule(c, what, mode, flags, min_strong, min_permille, min_len, n_reads, &R))) return rc;
+    u64 n_bases = 0;
+    if (n_reads && (rc = stage_batch(c, what, bases, offsets, n_reads, true, &n_bases))) return rc;
+    u64 h[KMC_TRIM_WORDS];
+    if ((rc = trim_run(c, what, min_count, max_count, R, (const uint8_t*)c->q_bases.p, (const u64*)c->q_offs.p, n_reads, n_bases, h))) return rc;
+    const u64 no = h[4], nb = h[5];
+    if (n_out) *n_out = no;
+    if (n_out_bases) *n_out_bases = nb;
+    if (out_bases && cap_bases < nb) return fail(c, KMC_ERR_ARG, "%s: capacity %llu < %llu bases", what, (unsigned long long)cap_bases, (unsigned long long)nb);
+    if ((out_offsets || origin) && cap_reads < no) return fail(c, KMC_ERR_ARG, "%s: capacity %llu < %llu reads", what, (unsigned long long)cap_reads, (unsigned long long)no);
+    const int cur = c->tr_cur;
+    if (out_bases && nb) HIPCHK(c, hipMemcpyAsync(out_bases, c->tr_out[cur].p, (size_t)nb, hipMemcpyDeviceToHost, c->stream));
+    if (out_offsets) HIPCHK(c, hipMemcpyAsync(out_offsets, c->tr_ooffs[cur].p, (size_t)(no + 1) * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    if (origin && no) HIPCHK(c, hipMemcpyAsync(origin, c->tr_origin.p, (size_t)no * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    if (read_stats && n_reads) HIPCHK(c, hipMemcpyAsync(read_stats, c->tr_stats.p, (size_t)n_reads * KMC_TRIM_READ_WORDS * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+    if (verdict && n_reads) HIPCHK(c, hipMemcpyAsync(verdict, c->tr_verdict.p, (size_t)n_reads, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (summary) memcpy(summary, h, sizeof(h));
+    return KMC_OK;
+}
+
 // ---- the compacted graph cleaned: a verdict per unitig, the table of the kept keys (kmc_clean.hip.h) ----
 static u64 clean_limit(uint64_t keys) { return keys >= (1ull << 31) ? ~0ull : (u64)keys; }   // 2^31 or more: unlimited
 
@@ -1797,7 +1962,25 @@ extern "C" int kmc_correct(kmc_ctx* c, uint64_t min_count, uint64_t max_count, c
         return kmc_correct_impl(c, min_count, max_count, bases, offsets, n_reads, out_bases, read_stats, cand_offsets, cands, cap_cands, n_cands, summary);
     });
 }
-extern "C" int kmc_unitig_clean_device(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t max_tip_keys, uint64_t max_island_keys,
+extern "C" int kmc_trim_device(kmc_ctx* c, uint64_t min_count, uint64_t max_count, int mode, uint32_t flags, uint64_t min_strong, uint32_t min_permille,
+                               uint64_t min_len, const void* d_bases, const void* d_offsets, uint64_t n_reads, uint64_t n_bases,
+                               const void** d_out_bases, const void** d_out_offsets, const void** d_origin, const void** d_read_stats,
+                               const void** d_verdict, uint64_t* n_out, uint64_t* n_out_bases, uint64_t* summary) {
+    return guarded(c, [&]() -> int {
+        return kmc_trim_device_impl(c, min_count, max_count, mode, flags, min_strong, min_permille, min_len, d_bases, d_offsets, n_reads, n_bases,
+                                    d_out_bases, d_out_offsets, d_origin, d_read_stats, d_verdict, n_out, n_out_bases, summary);
+    });
+}
+extern "C" int kmc_trim(kmc_ctx* c, uint64_t min_count, uint64_t max_count, int mode, uint32_t flags, uint64_t min_strong, uint32_t min_permille,
+                        uint64_t min_len, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads, uint8_t* out_bases, uint64_t cap_bases,
+                        uint64_t* out_offsets, uint64_t* origin, uint64_t cap_reads, uint32_t* read_stats, uint8_t* verdict, uint64_t* n_out,
+                        uint64_t* n_out_bases, uint64_t* summary) {
+    return guarded(c, [&]() -> int {
+        return kmc_trim_impl(c, min_count, max_count, mode, flags, min_strong, min_permille, min_len, bases, offsets, n_reads, out_bases, cap_bases,
+                             out_offsets, origin, cap_reads, read_stats, verdict, n_out, n_out_bases, summary);
+    });
+}
+extern "C" int kmc_unitig_clean_device(kmc_ctx* c,uint64_t min_count, uint64_t max_count, uint64_t max_tip_keys, uint64_t max_island_keys,
                                        const void** d_key_hi, const void** d_key_lo, const void** d_count, const void** d_verdict,
                                        uint64_t* n_kept, uint64_t* n_unitigs, uint64_t* summary) {
     return guarded(c, [&]() -> int {

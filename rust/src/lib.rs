@@ -43,6 +43,17 @@ pub const KMC_CORRECT_READ_WORDS: usize = 4;
 pub const KMC_CORRECT_INTERIOR: u32 = 0;
 pub const KMC_CORRECT_HEAD: u32 = 1;
 pub const KMC_CORRECT_TAIL: u32 = 2;
+/// summary words of `kmc_trim`, words per read of its `read_stats`, its modes, flag bits and verdict bits
+pub const KMC_TRIM_WORDS: usize = 8;
+pub const KMC_TRIM_READ_WORDS: usize = 4;
+pub const KMC_TRIM_NONE: c_int = 0;
+pub const KMC_TRIM_ENDS: c_int = 1;
+pub const KMC_TRIM_LONGEST: c_int = 2;
+pub const KMC_TRIM_INVERT: u32 = 1;
+pub const KMC_TRIM_PAIR_BOTH: u32 = 2;
+pub const KMC_TRIM_PAIR_EITHER: u32 = 4;
+pub const KMC_TRIM_PASS: u8 = 1;
+pub const KMC_TRIM_EMITTED: u8 = 2;
 /// summary words of `kmc_unitig_clean`
 pub const KMC_CLEAN_WORDS: usize = 8;
 /// a unitig's verdict byte
@@ -175,6 +186,8 @@ extern "C" {
     pub fn kmc_unitig_map(ctx: *mut KmcCtx, min_count: u64, max_count: u64, bases: *const u8, offsets: *const u64, n_reads: u64, place: *mut u64, read_stats: *mut u32, seg_offsets: *mut u64, segs: *mut u32, cap_segs: u64, support: *mut u64, cap_unitigs: u64, n_segs: *mut u64, n_unitigs: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_correct_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, d_bases: *const c_void, d_offsets: *const c_void, n_reads: u64, n_bases: u64, d_corrected: *mut *const c_void, d_read_stats: *mut *const c_void, d_cand_offsets: *mut *const c_void, d_cands: *mut *const c_void, n_cands: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_correct(ctx: *mut KmcCtx, min_count: u64, max_count: u64, bases: *const u8, offsets: *const u64, n_reads: u64, out_bases: *mut u8, read_stats: *mut u32, cand_offsets: *mut u64, cands: *mut u32, cap_cands: u64, n_cands: *mut u64, summary: *mut u64) -> c_int;
+    pub fn kmc_trim_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, mode: c_int, flags: u32, min_strong: u64, min_permille: u32, min_len: u64, d_bases: *const c_void, d_offsets: *const c_void, n_reads: u64, n_bases: u64, d_out_bases: *mut *const c_void, d_out_offsets: *mut *const c_void, d_origin: *mut *const c_void, d_read_stats: *mut *const c_void, d_verdict: *mut *const c_void, n_out: *mut u64, n_out_bases: *mut u64, summary: *mut u64) -> c_int;
+    pub fn kmc_trim(ctx: *mut KmcCtx, min_count: u64, max_count: u64, mode: c_int, flags: u32, min_strong: u64, min_permille: u32, min_len: u64, bases: *const u8, offsets: *const u64, n_reads: u64, out_bases: *mut u8, cap_bases: u64, out_offsets: *mut u64, origin: *mut u64, cap_reads: u64, read_stats: *mut u32, verdict: *mut u8, n_out: *mut u64, n_out_bases: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_clean_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, max_tip_keys: u64, max_island_keys: u64, d_key_hi: *mut *const c_void, d_key_lo: *mut *const c_void, d_count: *mut *const c_void, d_verdict: *mut *const c_void, n_kept: *mut u64, n_unitigs: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_clean(ctx: *mut KmcCtx, min_count: u64, max_count: u64, max_tip_keys: u64, max_island_keys: u64, key_hi: *mut u64, key_lo: *mut u64, count: *mut u64, cap_keys: u64, verdict: *mut u8, cap_unitigs: u64, n_kept: *mut u64, n_unitigs: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_clean_into(src: *mut KmcCtx, dst: *mut KmcCtx, min_count: u64, max_count: u64, max_tip_keys: u64, max_island_keys: u64, summary: *mut u64) -> c_int;
@@ -522,6 +535,43 @@ impl Counter {
             })?;
         }
         Ok((out, stats, cand_offsets, cands, w))
+    }
+
+    /// A batch of reads trimmed and filtered by their strong windows (`kmc_trim`; the batch is not counted).  `mode`: the
+    /// span of a read (`KMC_TRIM_NONE` the whole read, `KMC_TRIM_ENDS` from its first to its last strong window,
+    /// `KMC_TRIM_LONGEST` its longest run of strong windows); a read passes with `min_strong` strong windows,
+    /// `min_permille` thousandths of its valid windows strong and a span of `min_len` bases; `flags`: `KMC_TRIM_INVERT`,
+    /// `KMC_TRIM_PAIR_BOTH`, `KMC_TRIM_PAIR_EITHER`.  Returns the emitted spans as a batch (bases, offsets), the source read
+    /// of each, per read of the input [valid windows, strong windows, span start, span length] and the verdict byte, and
+    /// the eight summary words.  The host form computes on every call, so the sizing call below judges the batch once more.
+    #[allow(clippy::type_complexity, clippy::too_many_arguments)]
+    pub fn trim_reads(&mut self, bases: &[u8], offsets: &[u64], min_count: u64, max_count: u64, mode: c_int, flags: u32, min_strong: u64,
+                      min_permille: u32, min_len: u64)
+                      -> Result<(Vec<u8>, Vec<u64>, Vec<u64>, Vec<[u32; KMC_TRIM_READ_WORDS]>, Vec<u8>, [u64; KMC_TRIM_WORDS]), KmcError> {
+        let (mut nd, mut nt) = (0u64, 0u64);
+        self.check(unsafe { kmc_finalize(self.ctx, &mut nd, &mut nt) })?;
+        let n_reads = offsets.len().saturating_sub(1);
+        if n_reads > 0 && offsets[n_reads] as usize != bases.len() {
+            return Err(KmcError(-1, "offsets do not end at the number of bases".into()));
+        }
+        let (mut no, mut nb) = (0u64, 0u64);
+        let mut w = [0u64; KMC_TRIM_WORDS];
+        let mut stats = vec![[0u32; KMC_TRIM_READ_WORDS]; n_reads];
+        let mut verdict = vec![0u8; n_reads];
+        self.check(unsafe {
+            kmc_trim(self.ctx, min_count, max_count, mode, flags, min_strong, min_permille, min_len, bases.as_ptr(), offsets.as_ptr(),
+                     n_reads as u64, std::ptr::null_mut::<u8>(), 0, std::ptr::null_mut::<u64>(), std::ptr::null_mut::<u64>(), 0,
+                     stats.as_mut_ptr() as *mut u32, verdict.as_mut_ptr(), &mut no, &mut nb, w.as_mut_ptr())
+        })?;
+        let mut out = vec![0u8; nb as usize];
+        let mut out_offsets = vec![0u64; no as usize + 1];
+        let mut origin = vec![0u64; no as usize];
+        self.check(unsafe {
+            kmc_trim(self.ctx, min_count, max_count, mode, flags, min_strong, min_permille, min_len, bases.as_ptr(), offsets.as_ptr(),
+                     n_reads as u64, out.as_mut_ptr(), nb, out_offsets.as_mut_ptr(), origin.as_mut_ptr(), no, std::ptr::null_mut::<u32>(),
+                     std::ptr::null_mut::<u8>(), &mut no, &mut nb, w.as_mut_ptr())
+        })?;
+        Ok((out, out_offsets, origin, stats, verdict, w))
     }
 
     /// That graph cleaned (`kmc_unitig_clean`): the keys of the kept unitigs with their counts, in the order of `table()`,
