@@ -30,6 +30,7 @@
  *   (addition: no equivalent in the reference)             kmc_unitig_components (connected components of the unitig graph, the small ones dropped)
  *   (addition: no equivalent in the reference)             kmc_unitig_components_device (the same in ctx-owned device memory)
  *   (addition: no equivalent in the reference)             kmc_unitig_components_into (the table without small components, into another ctx)
+ *   (addition: no equivalent in the reference)             kmc_unitig_bubbles / kmc_unitig_bubbles_device (its bubbles reported as variant records)
  *   (addition: no equivalent in the reference)             kmc_unitig_map / kmc_unitig_map_device (reads threaded through the unitigs)
  *   (addition: no equivalent in the reference)             kmc_correct / kmc_correct_device (substitution errors of reads repaired from the table)
  *   (addition: no equivalent in the reference)             kmc_trim / kmc_trim_device (reads trimmed and filtered by their solid k-mers)
@@ -843,6 +844,63 @@ int kmc_unitig_components(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, 
  * summary may be NULL. */
 int kmc_unitig_components_into(kmc_ctx* src, kmc_ctx* dst, uint64_t min_count, uint64_t max_count,
                                uint64_t max_component_keys, uint64_t* summary);
+
+/* ---- the bubbles of the compacted graph reported, not popped: variant records (additions, as above).  Everything refers to
+ * the unitigs and the link records of kmc_unitigs / kmc_unitig_links for the same view and range min_count..max_count.  m_u,
+ * A_u and rec(e) are those of the clean block; BUBBLE CANDIDATE, ends(u) = {p, q}, PARALLEL and the order "w beats u" (128-bit
+ * products, then keys, then the smaller id) are exactly those of the simplify block, with max_bubble_keys as the candidate
+ * limit.
+ * MAJOR ARM.  For a candidate u, with p the one record of its START end, let P(u) be the unitigs w = s >> 1 of the records s
+ *   of rec(p) with w != u that are candidates parallel to u.  If P(u) is not empty, major(u) is its greatest element under
+ *   "beats" (the order is strict and total, so that is one unitig).  u is CALLED iff major(u) beats u.  So u is called exactly
+ *   when kmc_unitig_simplify with the same three arguments and tip and island limits 0 gives it KMC_CLEAN_BUBBLE, and the number
+ *   of records equals that call's summary[8].  Around palindromic keys the formula is the definition, as everywhere else.
+ * ORIENTED ARMS.  U = S_u.  With w = major(u): W = S_w if the one record of w's START end equals p; otherwise W is the reverse
+ *   complement of S_w and the record's flag bit KMC_BUBBLE_REVERSED is set.  By the overlap property of the links U and W
+ *   begin with the same k - 1 bases and end with the same k - 1 bases.
+ * DIFFERENCE.  lcp is the length of the longest common prefix of U and W.  lcs is the length of their longest common suffix,
+ *   capped at min(|U|, |W|) - lcp: prefix first, so the two never overlap in the shorter arm.  The alleles are
+ *   U[lcp : |U| - lcs] and W[lcp : |W| - lcs].  mism is the Hamming distance of U and W if |U| == |W|, else 0.
+ * KIND.  KMC_BUBBLE_SUBST: |U| == |W| and mism == 1.  KMC_BUBBLE_INDEL: exactly one allele is empty.  KMC_BUBBLE_COMPLEX:
+ *   everything else (two substitutions closer than k give mism == 2 and alleles of length 2).
+ * RECORD.  KMC_BUBBLE_RECORD_WORDS = 8 uint32_t words per called unitig, in ascending u: [0] u, [1] w = major(u), [2] p,
+ *   [3] q, [4] lcp, [5] lcs, [6] the kind in bits 0-1 (KMC_BUBBLE_KIND) and KMC_BUBBLE_REVERSED in bit 2, [7] mism.  Allele
+ *   lengths, arm lengths and abundances follow from the unitig arrays.
+ * summary[KMC_BUBBLE_WORDS]: [0] unitigs, [1] records, [2] bubble candidates (kmc_unitig_simplify's [10]), [3] substitutions,
+ *   [4] indels, [5] complex, [6] records with KMC_BUBBLE_REVERSED, [7] the sum of m_u over the called arms
+ *   (kmc_unitig_simplify's [9] with tip and island limits 0).  [3] + [4] + [5] == [1].
+ * LIMITS.  max_bubble_keys == 0 gives no records (and no candidates).  max_bubble_keys of 2^31 or more is KMC_ERR_ARG here --
+ *   not "unlimited" as for the clean calls -- because the positions in a record are uint32_t.
+ * Rules: otherwise those of kmc_unitig_links (NULL ctx, KMC_MODE_LR, a non-zero max_count below min_count: KMC_ERR_ARG; no
+ * view: KMC_ERR_STATE; the capacity rules of the links: KMC_ERR_CAPACITY; an empty view gives zeros).
+ * RELATION TO THE OTHER VIEW CALLS.  A bubbles call counts as a kmc_unitig_links* call: it reuses the unitigs and links the
+ *   ctx still holds for this view and range under the condition of a clean call, otherwise it computes them and keeps them.
+ *   It writes a result of its own and nothing else: the unitig arrays, the links, adj, the view, a partition, a filter or
+ *   set-operation result, the query index, a map or correct result and a clean / simplify / components result -- their
+ *   pointers included -- stay valid and unchanged.  Its own result is keyed by view, range and limit; whatever drops the links
+ *   (a kmc_unitigs* or kmc_unitig_links_device call, any call that computes them again) drops it.
+ * Diagnostic: with KMC_UNITIG_TRACE set, a bubbles pass that computes prints "kmc_unitig_bubbles: keys N unitigs U candidates C
+ * records R subst S indel I complex X reversed V pair_ms .. diff_ms .." to stderr, behind the lines of the unitigs and links it
+ * had to compute (tools/measure_bubbles.py reads it): pair_ms the pair pass and the scan, diff_ms the records. ---- */
+#define KMC_BUBBLE_WORDS 8
+#define KMC_BUBBLE_RECORD_WORDS 8
+#define KMC_BUBBLE_SUBST 0u
+#define KMC_BUBBLE_INDEL 1u
+#define KMC_BUBBLE_COMPLEX 2u
+#define KMC_BUBBLE_KIND(flags) ((flags) & 3u)
+#define KMC_BUBBLE_REVERSED 4u      /* bit 2 of word [6] */
+/* uint32_t records[n_records * KMC_BUBBLE_RECORD_WORDS] in ctx-owned device memory, valid until the next kmc_unitig_bubbles*,
+ * kmc_unitig_links*, kmc_unitigs* or kmc_graph* call / finalize / reset / destroy (same ordering contract as
+ * kmc_export_device).  Every output pointer may be NULL.  Always computes the bubbles pass. */
+int kmc_unitig_bubbles_device(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, uint64_t max_bubble_keys,
+                              const void** d_records, uint64_t* n_records, uint64_t* n_unitigs, uint64_t* summary);
+/* The same, copied to the caller's array of cap_records * KMC_BUBBLE_RECORD_WORDS words.  Every output pointer may be NULL
+ * (records NULL: nothing is copied and its cap not looked at).  *n_records and *n_unitigs are always set; a cap too small for
+ * an array that was given -> KMC_ERR_ARG and nothing is copied.  records NULL is the sizing / summary-only call.  A call
+ * whose ctx still holds the result for this very view, range and limit copies from it: the sizing call followed by the call
+ * that copies computes once. */
+int kmc_unitig_bubbles(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, uint64_t max_bubble_keys, uint32_t* records,
+                       uint64_t cap_records, uint64_t* n_records, uint64_t* n_unitigs, uint64_t* summary);
 
 /* Multi-GPU reduce for small tables: ONE fixed-size all-gather instead of size exchange +
  * all-to-all (the reduce of main.rs:87's grouping across GPUs; for the generator's input a table is

@@ -95,6 +95,7 @@ ABI_SYMBOLS = [
     "kmc_unitig_clean", "kmc_unitig_clean_device", "kmc_unitig_clean_into",
     "kmc_unitig_simplify", "kmc_unitig_simplify_device", "kmc_unitig_simplify_into",
     "kmc_unitig_components", "kmc_unitig_components_device", "kmc_unitig_components_into",
+    "kmc_unitig_bubbles", "kmc_unitig_bubbles_device",
     "kmc_unitig_map", "kmc_unitig_map_device",
     "kmc_correct", "kmc_correct_device",
     "kmc_trim", "kmc_trim_device",
@@ -114,6 +115,10 @@ CLEAN_BUBBLE = 3     # KMC_CLEAN_BUBBLE: the fourth verdict, of a simplify call
 COMPONENT_WORDS = 8       # KMC_COMPONENT_WORDS: unitigs, components, those of one unitig, most keys / unitigs in one, small ones, keys kept, their counts
 COMPONENT_STAT_WORDS = 4  # KMC_COMPONENT_STAT_WORDS: a component's root, unitigs, keys, abundance
 CLEAN_COMPONENT = 4       # KMC_CLEAN_COMPONENT: the verdict of a unitig in a small component, of a components call
+BUBBLE_WORDS = 8          # KMC_BUBBLE_WORDS: unitigs, records, bubble candidates, substitutions, indels, complex, reversed records, keys of the called arms
+BUBBLE_RECORD_WORDS = 8   # KMC_BUBBLE_RECORD_WORDS: u, w, p, q, lcp, lcs, kind and flag, mism
+BUBBLE_SUBST, BUBBLE_INDEL, BUBBLE_COMPLEX = 0, 1, 2   # KMC_BUBBLE_*: a record's kind, bits 0-1 of word 6
+BUBBLE_REVERSED = 4       # KMC_BUBBLE_REVERSED: bit 2 of word 6, the major arm is spelled the other way round
 MAP_WORDS = 8        # KMC_MAP_WORDS: reads, valid windows, placed windows, segments, crossings, fully placed reads, unplaced reads, most segments
 MAP_READ_WORDS = 4   # KMC_MAP_READ_WORDS: a read's valid windows, placed windows, segments, crossings
 MAP_NONE = 0xFFFFFFFF  # KMC_MAP_NONE: the low half of the place word of a window that is not placed
@@ -206,6 +211,10 @@ def lib() -> C.CDLL:
     L.kmc_unitig_components_device.argtypes = [vp, u64, u64, u64] + [C.POINTER(vp)] * 6 + [pu64, pu64, pu64, vp]
     L.kmc_unitig_components.argtypes = [vp, u64, u64, u64, vp, vp, u64, vp, u64, vp, vp, vp, u64, pu64, pu64, pu64, vp]
     L.kmc_unitig_components_into.argtypes = [vp, vp, u64, u64, u64, vp]
+    # (an A/B library named by KMC_LIB_PATH may be a build from before these two: they stay unbound there and a call raises)
+    if "KMC_LIB_PATH" not in os.environ or hasattr(L, "kmc_unitig_bubbles"):
+        L.kmc_unitig_bubbles_device.argtypes = [vp, u64, u64, u64, C.POINTER(vp), pu64, pu64, vp]
+        L.kmc_unitig_bubbles.argtypes = [vp, u64, u64, u64, vp, u64, pu64, pu64, vp]
     L.kmc_unitig_map_device.argtypes = [vp, u64, u64, vp, vp, u64, u64] + [C.POINTER(vp)] * 5 + [pu64, pu64, vp]
     L.kmc_unitig_map.argtypes = [vp, u64, u64, vp, vp, u64, vp, vp, vp, vp, u64, vp, u64, pu64, pu64, vp]
     L.kmc_correct_device.argtypes = [vp, u64, u64, vp, vp, u64, u64] + [C.POINTER(vp)] * 4 + [pu64, vp]
@@ -860,6 +869,73 @@ class Components:
         return "".join("%d\t%d\t%d\t%d\t%d\n" % ((i,) + tuple(r)) for i, r in enumerate(self.stats.tolist()))
 
 
+_BUBBLE_FIELDS = ("unitigs", "records", "candidates", "substitutions", "indels", "complex", "reversed", "called_keys")
+_RC = bytes.maketrans(b"ACGT", b"TGCA")
+
+
+@dataclass
+class BubbleSummary:
+    """The eight words of kmc_unitig_bubbles: unitigs, records (= called arms), bubble candidates, records that are a
+    substitution / an indel / complex, records whose major arm is spelled the other way round, the keys of the called arms."""
+    unitigs: int
+    records: int
+    candidates: int
+    substitutions: int
+    indels: int
+    complex: int
+    reversed: int
+    called_keys: int
+
+    @classmethod
+    def from_words(cls, words) -> "BubbleSummary":
+        return cls(*[int(w) for w in words])
+
+    def words(self) -> list:
+        return [getattr(self, f) for f in _BUBBLE_FIELDS]
+
+    def to_text(self) -> str:
+        """``NAME\tVALUE`` lines."""
+        return "\n".join("%s\t%d" % (f, getattr(self, f)) for f in _BUBBLE_FIELDS) + "\n"
+
+
+@dataclass
+class Bubbles:
+    """What KmerCounter.bubbles returns: ``records`` uint32[n, 8] -- per called arm, ascending: u, its major arm w, the ends p
+    and q the pair sits between, lcp, lcs, kind (BUBBLE_SUBST / BUBBLE_INDEL / BUBBLE_COMPLEX, bits 0-1) with BUBBLE_REVERSED
+    (bit 2), mism -- ``summary``, and the ``unitigs`` of the same range the ids and positions refer to."""
+    records: np.ndarray
+    summary: BubbleSummary
+    unitigs: "Unitigs"
+    k: int
+
+    def __len__(self) -> int:
+        return len(self.records)
+
+    def arms(self) -> list:
+        """(U, W) per record: the called arm as spelled and its major arm oriented like it."""
+        s = self.unitigs.strings()
+        out = []
+        for r in self.records.tolist():
+            w = s[r[1]]
+            if r[6] & BUBBLE_REVERSED:
+                w = w.encode("ascii").translate(_RC)[::-1].decode("ascii")
+            out.append((s[r[0]], w))
+        return out
+
+    def alleles(self) -> list:
+        """(alt, major) per record: what is left of the two oriented arms between their common prefix and suffix."""
+        return [(u[r[4]:len(u) - r[5]], w[r[4]:len(w) - r[5]]) for r, (u, w) in zip(self.records.tolist(), self.arms())]
+
+    def to_text(self) -> str:
+        """What ``k-mer-count --variants`` prints: ``INDEX\tKIND\tU\tW\tPOS\tALT\tMAJOR\tA_U/M_U\tA_W/M_W`` lines, KIND one of
+        S, I, C, POS the common prefix, ``-`` for an empty allele, then abundance / keys of the two arms."""
+        o, a = self.unitigs.offsets, self.unitigs.abund
+        m = lambda u: int(o[u + 1]) - int(o[u]) - (self.k - 1)
+        return "".join("%d\t%s\t%d\t%d\t%d\t%s\t%s\t%d/%d\t%d/%d\n" % (i, "SIC"[r[6] & 3], r[0], r[1], r[4], alt or "-", maj or "-",
+                                                                     int(a[r[0]]), m(r[0]), int(a[r[1]]), m(r[1]))
+                       for i, (r, (alt, maj)) in enumerate(zip(self.records.tolist(), self.alleles())))
+
+
 def parse_fasta(path: str) -> Tuple[np.ndarray, np.ndarray]:
     """Host FASTA reader of libkmc (the reader the reference uses, main.rs:45-46,59-62).
     Returns (bases uint8[n_bases], offsets uint64[n_reads+1])."""
@@ -1385,6 +1461,32 @@ class KmerCounter:
         w = (C.c_uint64 * COMPONENT_WORDS)()
         self._chk(self._L.kmc_unitig_components_into(self._h, dst._h, int(min_count), int(max_count), int(max_component_keys), w))
         return ComponentSummary.from_words(list(w))
+
+    # -- its bubbles reported as variants: which arm lost against which, between which ends, and how the two differ --
+    def bubbles(self, min_count: int = 1, max_count: int = 0, max_bubble_keys: Optional[int] = None) -> "Bubbles":
+        """kmc_unitig_bubbles: one record per unitig that simplify_unitigs with the same range and bubble limit (None: k; 0:
+        none) would pop -- the arm it lost against, the two ends between which the pair sits, and the difference of the two
+        spellings as common prefix, common suffix, kind and mismatches.  Two calls, one computation; the unitigs of the range
+        come along (they are held by the ctx: nothing is computed again for them)."""
+        lo, hi = int(min_count), int(max_count)
+        lim = self.k if max_bubble_keys is None else int(max_bubble_keys)
+        nr, nu = C.c_uint64(), C.c_uint64()
+        w = (C.c_uint64 * BUBBLE_WORDS)()
+        self._chk(self._L.kmc_unitig_bubbles(self._h, lo, hi, lim, None, 0, C.byref(nr), C.byref(nu), w))
+        unitigs = self.unitigs(lo, hi)
+        rec = np.zeros((nr.value, BUBBLE_RECORD_WORDS), np.uint32)
+        self._chk(self._L.kmc_unitig_bubbles(self._h, lo, hi, lim, rec.ctypes.data if nr.value else None, nr.value, C.byref(nr), C.byref(nu), w))
+        return Bubbles(rec, BubbleSummary.from_words(list(w)), unitigs, self.k)
+
+    def bubbles_device(self, min_count: int = 1, max_count: int = 0, max_bubble_keys: Optional[int] = None):
+        """(d_records, n_records, n_unitigs, BubbleSummary) of kmc_unitig_bubbles_device: a ctx-owned device array of
+        n_records * 8 uint32."""
+        lim = self.k if max_bubble_keys is None else int(max_bubble_keys)
+        p = C.c_void_p()
+        nr, nu = C.c_uint64(), C.c_uint64()
+        w = (C.c_uint64 * BUBBLE_WORDS)()
+        self._chk(self._L.kmc_unitig_bubbles_device(self._h, int(min_count), int(max_count), lim, C.byref(p), C.byref(nr), C.byref(nu), w))
+        return p.value or 0, nr.value, nu.value, BubbleSummary.from_words(list(w))
 
     # -- and simple bubbles popped: the arm of a fork-and-rejoin that loses against its parallel arm --
     def _simplify_limits(self, max_tip_keys, max_island_keys, max_bubble_keys) -> Tuple[int, int, int]:

@@ -9,7 +9,7 @@
 //               [--trim FILE [--trim-mode none|ends|longest] [--min-strong N] [--strong-permille N] [--min-len N] [--invert]
 //                [--paired both|either]]
 //               [--with FASTA2 (--compare | --setop intersect|union|subtract [--counts left|right|min|max|sum|diff])]
-//               [--graph | --graph-stats | --unitigs | --gfa | --components]
+//               [--graph | --graph-stats | --unitigs | --gfa | --components | --variants [--bubble-keys N]]
 //               [--clean ROUNDS [--tip-keys N] [--island-keys N] [--bubble-keys N]] [--component-keys N]
 //
 //   --gpus N  the file's chunks go round-robin to GPUs 0..N-1 of this process, tables reduced on GPU 0
@@ -90,6 +90,14 @@
 //   --component-keys N   (with -k K) after any --clean rounds and before whichever output was asked for, the connected components
 //               of at most N keys are taken out of the table (kmc_unitig_components_into, one step; 0: none).  It needs no
 //               --clean.  With --stats one line on stderr.
+//   --variants           (with -k K) instead of the table: the bubbles of the unitig graph as variant calls (kmc_unitig_bubbles), one line
+//               per unitig that loses against a parallel unitig between the same two ends, in unitig order
+//               "INDEX<TAB>KIND<TAB>U<TAB>W<TAB>POS<TAB>ALT<TAB>MAJOR<TAB>A_U/M_U<TAB>A_W/M_W": the record's number, S (one substitution), I (an
+//               insertion or deletion: one allele empty) or C (anything else), the losing unitig U and the one it lost against W,
+//               the length POS of the common prefix of the two arms (W read in U's direction), what is left of U and of W between
+//               common prefix and common suffix ("-" for nothing), and the abundance / keys of the two arms.  --bubble-keys N is
+//               here the most keys an arm may have (default K; it needs no --clean, and with --variants the --clean rounds pop no
+//               bubbles: they would remove what is to be reported).  --min-count / --max-count are the solidity range.
 //
 // Errors: message on stderr, exit code 101 (what a Rust panic exits with), never partial stdout.
 #include <errno.h>
@@ -148,7 +156,7 @@ int main(int argc, char** argv) {
     int clean = 0;
     long long tip_keys = -1, island_keys = -1;   // (-1: K)
     long long bubble_keys = -1;                  // (-1: no bubble is popped, the rounds are kmc_unitig_clean_into's)
-    int components = 0;
+    int components = 0, variants = 0;
     long long component_keys = -1;               // (-1: no component step)
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -188,6 +196,7 @@ int main(int argc, char** argv) {
         else if (a == "--unitigs") unitigs = 1;
         else if (a == "--gfa") gfa = 1;
         else if (a == "--components") components = 1;
+        else if (a == "--variants") variants = 1;
         else if (a == "--component-keys" && i + 1 < argc) { if (!parse_count("--component-keys", argv[++i], 0, LLONG_MAX, &component_keys)) return 2; }
         else if (a == "--clean" && i + 1 < argc) { if (!parse_int("--clean", argv[++i], 1, 1000, &clean)) return 2; }
         else if (a == "--tip-keys" && i + 1 < argc) { if (!parse_count("--tip-keys", argv[++i], 0, LLONG_MAX, &tip_keys)) return 2; }
@@ -211,7 +220,7 @@ int main(int argc, char** argv) {
                             "                   [--trim FILE [--trim-mode none|ends|longest] [--min-strong N] [--strong-permille N] [--min-len N] [--invert]\n"
                             "                    [--paired both|either]]\n"
                             "                   [--with FASTA2 (--compare | --setop intersect|union|subtract [--counts left|right|min|max|sum|diff])]\n"
-                            "                   [--graph | --graph-stats | --unitigs | --gfa | --components]\n"
+                            "                   [--graph | --graph-stats | --unitigs | --gfa | --components | --variants [--bubble-keys N]]\n"
                             "                   [--clean ROUNDS [--tip-keys N] [--island-keys N] [--bubble-keys N]] [--component-keys N]\n");
             return 0;
         } else if (a == "-k" || a == "--device" || a == "--gpus" || a == "--algo" || a == "--min-count" || a == "--max-count" || a == "--histo" ||
@@ -340,7 +349,7 @@ int main(int argc, char** argv) {
     // --clean / --tip-keys / --island-keys / --bubble-keys: the same
     if (clean || tip_keys >= 0 || island_keys >= 0 || bubble_keys >= 0) {
         const char* bad = nullptr;
-        if (!clean) bad = "--tip-keys / --island-keys / --bubble-keys need --clean ROUNDS";
+        if (!clean && !(variants && tip_keys < 0 && island_keys < 0)) bad = "--tip-keys / --island-keys / --bubble-keys need --clean ROUNDS";
         else if (!k) bad = "--clean needs -k K";
         else if (with_path || compare || setop >= 0) bad = "--clean and --with / --compare / --setop exclude each other";
         if (bad) { fprintf(stderr, "k-mer-count: %s\n", bad); return 2; }
@@ -355,6 +364,18 @@ int main(int argc, char** argv) {
         else if (with_path || compare || setop >= 0) bad = "--with / --compare / --setop exclude each other";
         else if (expand) bad = "--expand exclude each other";
         if (bad) { fprintf(stderr, "k-mer-count: --components %s%s\n", strncmp(bad, "needs", 5) ? "and " : "", bad); return 2; }
+    }
+    // --variants: the same
+    if (variants) {
+        const char* bad = nullptr;
+        if (!k) bad = "needs -k K";
+        else if (graph || graph_stats || unitigs || gfa || components) bad = "--graph / --graph-stats / --unitigs / --gfa / --components exclude each other";
+        else if (histo) bad = "--histo exclude each other";
+        else if (query_path || profile_path || map_path || correct_path || trim_path) bad = "--query-kmers / --profile / --map / --correct / --trim exclude each other";
+        else if (with_path || compare || setop >= 0) bad = "--with / --compare / --setop exclude each other";
+        else if (expand) bad = "--expand exclude each other";
+        if (bad) { fprintf(stderr, "k-mer-count: --variants %s%s\n", strncmp(bad, "needs", 5) ? "and " : "", bad); return 2; }
+        if (bubble_keys >= (1ll << 31)) { fprintf(stderr, "k-mer-count: --variants needs --bubble-keys below 2^31 (got %lld)\n", bubble_keys); return 2; }
     }
     if (component_keys >= 0) {
         const char* bad = nullptr;
@@ -399,7 +420,7 @@ int main(int argc, char** argv) {
         ctxs.push_back(next);
         uint64_t w[KMC_SIMPLIFY_WORDS] = {0};
         const uint64_t tip = tip_keys < 0 ? (uint64_t)k : (uint64_t)tip_keys, isl = island_keys < 0 ? (uint64_t)k : (uint64_t)island_keys;
-        if (bubble_keys < 0) {
+        if (bubble_keys < 0 || variants) {   // (with --variants the limit is the report's: the rounds pop nothing)
             rc = kmc_unitig_clean_into(ctx, next, (uint64_t)min_count, (uint64_t)max_count, tip, isl, w);
             if (rc) { int r = die("kmc_unitig_clean_into", kmc_last_error(ctx)); destroy_all(); return r; }
         } else {
@@ -412,7 +433,7 @@ int main(int argc, char** argv) {
             fprintf(stderr, "clean round %d unitigs %llu tips %llu islands %llu kept_keys %llu tip_keys %llu island_keys %llu tip_candidates %llu kept_count %llu",
                     round, (unsigned long long)w[0], (unsigned long long)w[1], (unsigned long long)w[2], (unsigned long long)w[3],
                     (unsigned long long)w[4], (unsigned long long)w[5], (unsigned long long)w[6], (unsigned long long)w[7]);
-            if (bubble_keys >= 0)
+            if (bubble_keys >= 0 && !variants)
                 fprintf(stderr, " bubbles %llu bubble_keys %llu bubble_candidates %llu", (unsigned long long)w[8], (unsigned long long)w[9],
                         (unsigned long long)w[10]);
             fprintf(stderr, "\n");
@@ -664,6 +685,42 @@ int main(int argc, char** argv) {
             const uint64_t* w = &cs[(size_t)c * KMC_COMPONENT_STAT_WORDS];
             printf("%llu\t%llu\t%llu\t%llu\t%llu\n", (unsigned long long)c, (unsigned long long)w[0], (unsigned long long)w[1],
                    (unsigned long long)w[2], (unsigned long long)w[3]);
+        }
+        fflush(stdout);
+        destroy_all();
+        return 0;
+    }
+    if (variants) {   // size, the unitigs the records refer to (held by the ctx: copied, not computed again), then copy
+        const uint64_t lo_c = (uint64_t)min_count, hi_c = (uint64_t)max_count, lim = bubble_keys < 0 ? (uint64_t)k : (uint64_t)bubble_keys;
+        uint64_t nr = 0, nu = 0, nb = 0;
+        rc = kmc_unitig_bubbles(ctx, lo_c, hi_c, lim, nullptr, 0, &nr, &nu, nullptr);
+        if (rc) { int r = die("kmc_unitig_bubbles", kmc_last_error(ctx)); destroy_all(); return r; }
+        rc = kmc_unitigs(ctx, lo_c, hi_c, nullptr, 0, nullptr, nullptr, nullptr, 0, &nu, &nb, nullptr);
+        if (rc) { int r = die("kmc_unitigs", kmc_last_error(ctx)); destroy_all(); return r; }
+        std::vector<uint8_t> ub(nb ? nb : 1);
+        std::vector<uint64_t> uo(nu + 1), ua(nu ? nu : 1);
+        rc = kmc_unitigs(ctx, lo_c, hi_c, ub.data(), nb, uo.data(), ua.data(), nullptr, nu, &nu, &nb, nullptr);
+        if (rc) { int r = die("kmc_unitigs", kmc_last_error(ctx)); destroy_all(); return r; }
+        std::vector<uint32_t> rec((size_t)(nr ? nr : 1) * KMC_BUBBLE_RECORD_WORDS);
+        rc = kmc_unitig_bubbles(ctx, lo_c, hi_c, lim, rec.data(), nr, &nr, &nu, nullptr);
+        if (rc) { int r = die("kmc_unitig_bubbles", kmc_last_error(ctx)); destroy_all(); return r; }
+        setvbuf(stdout, obuf.data(), _IOFBF, obuf.size());
+        std::string arm;
+        for (uint64_t i = 0; i < nr; ++i) {
+            const uint32_t* w = &rec[(size_t)i * KMC_BUBBLE_RECORD_WORDS];
+            const uint64_t u = w[0], v = w[1], lu = uo[u + 1] - uo[u], lv = uo[v + 1] - uo[v];
+            arm.assign((const char*)ub.data() + uo[v], (size_t)lv);
+            if (w[6] & KMC_BUBBLE_REVERSED) {   // W in U's direction
+                std::reverse(arm.begin(), arm.end());
+                for (char& ch : arm) ch = ch == 'A' ? 'T' : ch == 'C' ? 'G' : ch == 'G' ? 'C' : 'A';
+            }
+            printf("%llu\t%c\t%u\t%u\t%u\t", (unsigned long long)i, "SIC?"[KMC_BUBBLE_KIND(w[6])], w[0], w[1], w[4]);
+            const uint64_t au = lu - w[4] - w[5], av = lv - w[4] - w[5];
+            if (au) fwrite(ub.data() + uo[u] + w[4], 1, (size_t)au, stdout); else fputc('-', stdout);
+            fputc('\t', stdout);
+            if (av) fwrite(arm.data() + w[4], 1, (size_t)av, stdout); else fputc('-', stdout);
+            printf("\t%llu/%llu\t%llu/%llu\n", (unsigned long long)ua[u], (unsigned long long)(lu - (uint64_t)(k - 1)), (unsigned long long)ua[v],
+                   (unsigned long long)(lv - (uint64_t)(k - 1)));
         }
         fflush(stdout);
         destroy_all();

@@ -269,6 +269,13 @@ struct kmc_ctx : CtxStream {
     DevBuf cc_comp, cc_stats, cc_verdict, cc_parent, cc_flag, cc_rank, cc_part, cc_ctl;
     ResultKey cc_key;
     u64 cc_limit = 0, cc_kept = 0, cc_comps = 0, cc_words[8] = {};
+    // kmc_unitig_bubbles* (kmc_bubbles.hip.h) read the unitigs and the links.  Their result, in a buffer of its own (a clean /
+    // simplify / components result stays as it is): eight words per called unitig, with bb_key plus its limit bb_limit and
+    // bb_words as above, bb_records records.  Whatever drops l_key drops bb_key.  Work arrays: the called flag per unitig,
+    // its scan, major(u), the control words.
+    DevBuf bb_rec, bb_flag, bb_pos, bb_major, bb_ctl;
+    ResultKey bb_key;
+    u64 bb_limit = 0, bb_records = 0, bb_words[8] = {};
 };
 
 #pragma GCC visibility push(hidden)   // what follows is shared between the translation units, never exported

@@ -15,6 +15,7 @@
 #include "kmc_links.hip.h"
 #include "kmc_clean.hip.h"
 #include "kmc_components.hip.h"
+#include "kmc_bubbles.hip.h"
 #include "kmc_map.hip.h"
 #include "kmc_correct.hip.h"
 #include "kmc_trim.hip.h"
@@ -719,7 +720,7 @@ static int unitig_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count
     memset(h, 0, KMC_UNITIG_WORDS * sizeof(u64));
     const u64 n = c->n_sorted, n2 = 2 * n;
     int rc;
-    c->u_key.drop(); c->l_key.drop(); c->cc_key.drop();   // the result arrays are rewritten from here on (and the links of the old ones, and their components, go with them)
+    c->u_key.drop(); c->l_key.drop(); c->cc_key.drop(); c->bb_key.drop();   // the result arrays are rewritten from here on (and the links of the old ones, their components and their bubbles go with them)
     if ((rc = ensure(c, c->u_offs, sizeof(u64))) || (rc = ensure(c, c->u_bases, 64)) || (rc = ensure(c, c->u_abund, sizeof(u64))) ||
         (rc = ensure(c, c->u_flags, 8)))
         return rc;
@@ -902,7 +903,7 @@ static int links_run(kmc_ctx* c, const char* what, u64* h) {
     memset(h, 0, KMC_LINK_WORDS * sizeof(u64));
     const u64 n = c->n_sorted, nu = c->u_words[0], ne = 2 * nu;
     int rc;
-    c->l_key.drop(); c->cc_key.drop();
+    c->l_key.drop(); c->cc_key.drop(); c->bb_key.drop();
     if ((rc = ensure(c, c->l_offs, (size_t)(ne + 1) * sizeof(u64))) || (rc = ensure(c, c->l_to, sizeof(u32)))) return rc;
     if (!nu) {   // an empty view, or one without a solid key
         HIPCHK(c, hipMemsetAsync(c->l_offs.p, 0, sizeof(u64), c->stream));
@@ -1853,6 +1854,128 @@ static int kmc_unitig_components_into_impl(kmc_ctx* src, kmc_ctx* dst, uint64_t 
     return KMC_OK;
 }
 
+// ---- the bubbles of the compacted graph as variant records: eight words per called arm (kmc_bubbles.hip.h) ----
+static bool bubbles_kept(const kmc_ctx* c, u64 min_count, u64 max_count, u64 limit) {
+    return c->bb_key.holds(c->view_gen, min_count, max_count) && c->bb_limit == limit;
+}
+
+// the limit of a bubbles call: unlike a clean limit it has no "unlimited" (a record's positions are u32)
+static int bubbles_limit(kmc_ctx* c, const char* what, uint64_t max_bubble_keys) {
+    if (max_bubble_keys >= (1ull << 31))
+        return fail(c, KMC_ERR_ARG, "%s: max_bubble_keys %llu is 2^31 or more (a record's positions are 32-bit)", what, (unsigned long long)max_bubble_keys);
+    return KMC_OK;
+}
+
+// The bubbles pass behind the unitigs and links of this view and range -- those the ctx holds under clean_run's condition,
+// otherwise computed and kept -- into bb_rec, the summary into bb_words; finished when it returns.  It shares the block sums
+// of a scan (c_bsum) with the other passes and writes nothing else of theirs.
+static int bubbles_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count, u64 limit) {
+    int rc;
+    u64 lw[KMC_LINK_WORDS];
+    const bool held = c->u_live && c->u_key.holds(c->view_gen, min_count, max_count);
+    if ((rc = links_result(c, what, min_count, max_count, held, lw))) return rc;
+    c->bb_key.drop();
+    const u64 n = c->n_sorted, nu = lw[0], nl = lw[1];
+    u64 w[KMC_B_CTL_WORDS] = {0}, nr = 0;
+    if ((rc = ensure(c, c->bb_rec, KMC_B_REC * sizeof(u32)))) return rc;
+    CleanGraph g;   // (read once the links stand: the unitig and link arrays, the candidate limit)
+    g.offsets = (const u64*)c->u_offs.p; g.abund = (const u64*)c->u_abund.p; g.flags = (const uint8_t*)c->u_flags.p;
+    g.link_offsets = (const u64*)c->l_offs.p; g.link_to = (const u32*)c->l_to.p;
+    g.n_unitigs = nu; g.n_links = nl; g.km1 = (u64)(c->klen - 1); g.max_tip = 0; g.max_island = 0; g.max_bubble = limit;
+    const u32 grid_u = (u32)((nu + KMC_B_THREADS - 1) / KMC_B_THREADS);
+    UnitigTrace tr;
+    tr.mark(c->stream);
+    if (nu && limit) {
+        if (nu > n || c->u_words[0] != nu) return fail(c, KMC_ERR_HIP, "internal error: %s holds %llu unitigs, its links %llu", what, (unsigned long long)c->u_words[0], (unsigned long long)nu);
+        const size_t ub = (size_t)nu * sizeof(u32);
+        if ((rc = ensure(c, c->bb_flag, ub)) || (rc = ensure(c, c->bb_pos, ub)) || (rc = ensure(c, c->bb_major, ub)) ||
+            (rc = ensure(c, c->bb_ctl, KMC_B_CTL_WORDS * sizeof(u64))) ||
+            (rc = ensure(c, c->c_bsum, (size_t)((nu + KMC_SCAN_PER_BLOCK - 1) / KMC_SCAN_PER_BLOCK + 2) * sizeof(u32))))
+            return rc;
+        kmc_ull* ctl = (kmc_ull*)c->bb_ctl.p;
+        HIPCHK(c, hipMemsetAsync(ctl, 0, KMC_B_CTL_WORDS * sizeof(u64), c->stream));
+        hipLaunchKernelGGL(kmc_bubble_pair_kernel, dim3(grid_u), dim3(KMC_B_THREADS), 0, c->stream, g, (u32*)c->bb_flag.p, (u32*)c->bb_major.p, ctl);
+        launch_exclusive_scan<0>(c->stream, c->bb_flag.p, (u32)nu, (u32*)c->c_bsum.p, (u32*)c->bb_pos.p, (u32*)ctl);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(w, ctl, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        nr = w[0] & 0xFFFFFFFFull;
+        if (w[KMC_B_BAD] || nr != w[KMC_B_CALLED] || nr > w[KMC_B_CAND] || w[KMC_B_CAND] > nu)
+            return fail(c, KMC_ERR_HIP, "internal error: %s met %llu indices outside their arrays (%llu called, %llu scanned, %llu candidates of %llu unitigs)",
+                        what, (unsigned long long)w[KMC_B_BAD], (unsigned long long)w[KMC_B_CALLED], (unsigned long long)nr,
+                        (unsigned long long)w[KMC_B_CAND], (unsigned long long)nu);
+    }
+    tr.mark(c->stream);
+    if (nr) {
+        if ((rc = ensure(c, c->bb_rec, (size_t)nr * KMC_B_REC * sizeof(u32)))) return rc;
+        kmc_ull* ctl = (kmc_ull*)c->bb_ctl.p;
+        const u32 grid_r = (u32)std::min<u64>((nr + KMC_B_WAVES - 1) / KMC_B_WAVES, (u64)c->n_cu * 8);
+        hipLaunchKernelGGL(kmc_bubble_place_kernel, dim3(grid_u), dim3(KMC_B_THREADS), 0, c->stream, g, (const u32*)c->bb_flag.p, (const u32*)c->bb_pos.p,
+                           (const u32*)c->bb_major.p, nr, (u32*)c->bb_rec.p, ctl);
+        hipLaunchKernelGGL(kmc_bubble_diff_kernel, dim3(grid_r), dim3(KMC_B_THREADS), 0, c->stream, g, (const uint8_t*)c->u_bases.p, c->u_words[1], nr,
+                           (u32*)c->bb_rec.p, ctl);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(w, ctl, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (w[KMC_B_BAD] || w[KMC_B_SUBST] + w[KMC_B_INDEL] + w[KMC_B_COMPLEX] != nr)
+            return fail(c, KMC_ERR_HIP, "internal error: %s met %llu indices outside their arrays (%llu + %llu + %llu of %llu records)", what,
+                        (unsigned long long)w[KMC_B_BAD], (unsigned long long)w[KMC_B_SUBST], (unsigned long long)w[KMC_B_INDEL],
+                        (unsigned long long)w[KMC_B_COMPLEX], (unsigned long long)nr);
+    }
+    tr.mark(c->stream);
+    if (tr.on && tr.n_ev == 3) {
+        float ms[2] = {0, 0};
+        bool ok = hipEventSynchronize(tr.ev[2]) == hipSuccess;
+        for (int i = 0; ok && i < 2; ++i) ok = hipEventElapsedTime(&ms[i], tr.ev[i], tr.ev[i + 1]) == hipSuccess;
+        if (ok)
+            fprintf(stderr, "kmc_unitig_bubbles: keys %llu unitigs %llu candidates %llu records %llu subst %llu indel %llu complex %llu reversed %llu "
+                    "pair_ms %.4f diff_ms %.4f\n", (unsigned long long)n, (unsigned long long)nu, (unsigned long long)w[KMC_B_CAND], (unsigned long long)nr,
+                    (unsigned long long)w[KMC_B_SUBST], (unsigned long long)w[KMC_B_INDEL], (unsigned long long)w[KMC_B_COMPLEX],
+                    (unsigned long long)w[KMC_B_REVERSED], ms[0], ms[1]);
+    }
+    u64* s = c->bb_words;
+    s[0] = nu; s[1] = nr; s[2] = w[KMC_B_CAND]; s[3] = w[KMC_B_SUBST]; s[4] = w[KMC_B_INDEL]; s[5] = w[KMC_B_COMPLEX]; s[6] = w[KMC_B_REVERSED];
+    s[7] = w[KMC_B_KEYS];
+    c->bb_records = nr;
+    c->bb_key.keep(c->view_gen, min_count, max_count); c->bb_limit = limit;
+    return KMC_OK;
+}
+
+static int kmc_unitig_bubbles_device_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t max_bubble_keys, const void** d_records,
+                                          uint64_t* n_records, uint64_t* n_unitigs, uint64_t* summary) {
+    if (!c) return KMC_ERR_ARG;
+    int rc;
+    const char* what = "kmc_unitig_bubbles_device";
+    if ((rc = unitig_begin(c, what, min_count, max_count)) || (rc = bubbles_limit(c, what, max_bubble_keys)) ||
+        (rc = bubbles_run(c, what, min_count, max_count, (u64)max_bubble_keys))) return rc;
+    if (d_records) *d_records = c->bb_rec.p;
+    if (n_records) *n_records = c->bb_records;
+    if (n_unitigs) *n_unitigs = c->bb_words[0];
+    if (summary) memcpy(summary, c->bb_words, sizeof(c->bb_words));
+    return KMC_OK;
+}
+
+static int kmc_unitig_bubbles_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t max_bubble_keys, uint32_t* records,
+                                   uint64_t cap_records, uint64_t* n_records, uint64_t* n_unitigs, uint64_t* summary) {
+    if (n_records) *n_records = 0;
+    if (n_unitigs) *n_unitigs = 0;
+    if (!c) return KMC_ERR_ARG;
+    int rc;
+    const char* what = "kmc_unitig_bubbles";
+    if ((rc = unitig_begin(c, what, min_count, max_count)) || (rc = bubbles_limit(c, what, max_bubble_keys))) return rc;
+    const u64 limit = (u64)max_bubble_keys;
+    if (!bubbles_kept(c, min_count, max_count, limit) && (rc = bubbles_run(c, what, min_count, max_count, limit))) return rc;
+    const u64 nr = c->bb_records;
+    if (n_records) *n_records = nr;
+    if (n_unitigs) *n_unitigs = c->bb_words[0];
+    if (records && cap_records < nr)
+        return fail(c, KMC_ERR_ARG, "%s: capacity %llu < %llu records", what, (unsigned long long)cap_records, (unsigned long long)nr);
+    if (records && nr) HIPCHK(c, hipMemcpyAsync(records, c->bb_rec.p, (size_t)nr * KMC_B_REC * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (summary) memcpy(summary, c->bb_words, sizeof(c->bb_words));
+    return KMC_OK;
+}
+
 // ---- the ABI proper (guarded: no C++ exception leaves the library) ----
 extern "C" int kmc_export(kmc_ctx* c, uint64_t* key_hi, uint64_t* key_lo, uint64_t* count, uint64_t cap) {
     return guarded(c, [&]() -> int { return kmc_export_impl(c, key_hi, key_lo, count, cap); });
@@ -2046,6 +2169,18 @@ extern "C" int kmc_unitig_components(kmc_ctx* c, uint64_t min_count, uint64_t ma
 extern "C" int kmc_unitig_components_into(kmc_ctx* src, kmc_ctx* dst, uint64_t min_count, uint64_t max_count, uint64_t max_component_keys,
                                           uint64_t* summary) {
     return guarded(src, [&]() -> int { return kmc_unitig_components_into_impl(src, dst, min_count, max_count, max_component_keys, summary); });
+}
+extern "C" int kmc_unitig_bubbles_device(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t max_bubble_keys, const void** d_records,
+                                         uint64_t* n_records, uint64_t* n_unitigs, uint64_t* summary) {
+    return guarded(c, [&]() -> int {
+        return kmc_unitig_bubbles_device_impl(c, min_count, max_count, max_bubble_keys, d_records, n_records, n_unitigs, summary);
+    });
+}
+extern "C" int kmc_unitig_bubbles(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t max_bubble_keys, uint32_t* records,
+                                  uint64_t cap_records, uint64_t* n_records, uint64_t* n_unitigs, uint64_t* summary) {
+    return guarded(c, [&]() -> int {
+        return kmc_unitig_bubbles_impl(c, min_count, max_count, max_bubble_keys, records, cap_records, n_records, n_unitigs, summary);
+    });
 }
 extern "C" int kmc_partition_device(kmc_ctx* c, uint32_t n_parts, uint64_t* part_begin, const void** d_key_hi,
                                     const void** d_key_lo, const void** d_count) {

@@ -68,6 +68,13 @@ pub const KMC_SIMPLIFY_WORDS: usize = 12;
 pub const KMC_COMPONENT_WORDS: usize = 8;
 pub const KMC_COMPONENT_STAT_WORDS: usize = 4;
 pub const KMC_CLEAN_COMPONENT: u8 = 4;
+/// summary words of `kmc_unitig_bubbles`, words per record, a record's kind (bits 0-1 of word 6) and its flag bit
+pub const KMC_BUBBLE_WORDS: usize = 8;
+pub const KMC_BUBBLE_RECORD_WORDS: usize = 8;
+pub const KMC_BUBBLE_SUBST: u32 = 0;
+pub const KMC_BUBBLE_INDEL: u32 = 1;
+pub const KMC_BUBBLE_COMPLEX: u32 = 2;
+pub const KMC_BUBBLE_REVERSED: u32 = 4;
 
 // The structs and the extern block below are checked against include/kmc.h by
 // tests/test_abi_host.py::test_rust_binding_matches_the_header (names, arity, argument types, field
@@ -197,6 +204,8 @@ extern "C" {
     pub fn kmc_unitig_components_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, max_component_keys: u64, d_comp_of: *mut *const c_void, d_comp_stats: *mut *const c_void, d_verdict: *mut *const c_void, d_key_hi: *mut *const c_void, d_key_lo: *mut *const c_void, d_count: *mut *const c_void, n_comps: *mut u64, n_unitigs: *mut u64, n_kept: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_components(ctx: *mut KmcCtx, min_count: u64, max_count: u64, max_component_keys: u64, comp_of: *mut u32, verdict: *mut u8, cap_unitigs: u64, comp_stats: *mut u64, cap_comps: u64, key_hi: *mut u64, key_lo: *mut u64, count: *mut u64, cap_keys: u64, n_comps: *mut u64, n_unitigs: *mut u64, n_kept: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_components_into(src: *mut KmcCtx, dst: *mut KmcCtx, min_count: u64, max_count: u64, max_component_keys: u64, summary: *mut u64) -> c_int;
+    pub fn kmc_unitig_bubbles_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, max_bubble_keys: u64, d_records: *mut *const c_void, n_records: *mut u64, n_unitigs: *mut u64, summary: *mut u64) -> c_int;
+    pub fn kmc_unitig_bubbles(ctx: *mut KmcCtx, min_count: u64, max_count: u64, max_bubble_keys: u64, records: *mut u32, cap_records: u64, n_records: *mut u64, n_unitigs: *mut u64, summary: *mut u64) -> c_int;
     // multi-GPU reduce (one process per GPU; the collective itself is the host program's, e.g. RCCL)
     pub fn kmc_slab_words(ctx: *const KmcCtx, slab_entries: u64) -> u64;
     pub fn kmc_pack_slab_device(ctx: *mut KmcCtx, d_slab: *mut c_void, slab_entries: u64) -> c_int;
@@ -706,6 +715,25 @@ impl Counter {
         let mut w = [0u64; KMC_COMPONENT_WORDS];
         self.check(unsafe { kmc_unitig_components_into(self.ctx, dst.ctx, min_count, max_count, max_component_keys, w.as_mut_ptr()) })?;
         Ok(w)
+    }
+
+    /// The bubbles of the unitig graph as variant records (`kmc_unitig_bubbles`): per unitig that loses against a parallel
+    /// one, ascending, `[u, w, p, q, lcp, lcs, kind | KMC_BUBBLE_REVERSED, mism]`, and the eight summary words.
+    /// `max_bubble_keys` is the most keys an arm may have (0: none; 2^31 or more is an argument error).
+    pub fn bubbles(&mut self, min_count: u64, max_count: u64, max_bubble_keys: u64)
+                   -> Result<(Vec<[u32; KMC_BUBBLE_RECORD_WORDS]>, [u64; KMC_BUBBLE_WORDS]), KmcError> {
+        let (mut nd, mut nt) = (0u64, 0u64);
+        self.check(unsafe { kmc_finalize(self.ctx, &mut nd, &mut nt) })?;
+        let (mut nr, mut nu) = (0u64, 0u64);
+        let mut w = [0u64; KMC_BUBBLE_WORDS];
+        self.check(unsafe {
+            kmc_unitig_bubbles(self.ctx, min_count, max_count, max_bubble_keys, std::ptr::null_mut::<u32>(), 0, &mut nr, &mut nu, w.as_mut_ptr())
+        })?;
+        let mut rec = vec![[0u32; KMC_BUBBLE_RECORD_WORDS]; nr as usize];
+        self.check(unsafe {
+            kmc_unitig_bubbles(self.ctx, min_count, max_count, max_bubble_keys, rec.as_mut_ptr() as *mut u32, nr, &mut nr, &mut nu, w.as_mut_ptr())
+        })?;
+        Ok((rec, w))
     }
 }
 
