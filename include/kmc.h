@@ -34,6 +34,7 @@
  *   (addition: no equivalent in the reference)             kmc_unitig_map / kmc_unitig_map_device (reads threaded through the unitigs)
  *   (addition: no equivalent in the reference)             kmc_correct / kmc_correct_device (substitution errors of reads repaired from the table)
  *   (addition: no equivalent in the reference)             kmc_trim / kmc_trim_device (reads trimmed and filtered by their solid k-mers)
+ *   (addition: no equivalent in the reference)             kmc_normalize / kmc_normalize_device (read depth normalised: a per-read k-mer depth, deep reads sampled down)
  *
  * Conventions
  *   - Every function returns 0 (KMC_OK) or a negative kmc_status; no exception or abort crosses
@@ -666,6 +667,77 @@ int kmc_trim(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, int mode, uin
              uint32_t min_permille, uint64_t min_len, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads,
              uint8_t* out_bases, uint64_t cap_bases, uint64_t* out_offsets, uint64_t* origin, uint64_t cap_reads,
              uint32_t* read_stats, uint8_t* verdict, uint64_t* n_out, uint64_t* n_out_bases, uint64_t* summary);
+
+/* ---- read depth normalised (additions, as above): every read gets a depth, a percentile of the counts of its k-mers; reads
+ * of over-covered regions are sampled down to a target depth and reads below a floor depth are dropped (digital
+ * normalisation in its static, two-pass form: the table is given and each read is judged on its own, so the result does not
+ * depend on the order of the reads).  KMC_MODE_CONTIG only; every k, in a canonical or a forward ctx.  Reads the sorted view
+ * of the last kmc_finalize (a view queued by kmc_finalize_async counts as one).  The batch is NOT counted.  The formula is
+ * the definition.
+ * WINDOW, VALID.  Exactly kmc_profile's: window j of a read R of L bases is R[j : j+k], 0 <= j <= L - k; valid iff it holds
+ *   only upper-case ACGT.  c(j) is the entry window_count of kmc_profile: the view's count of canon(f) (of f in a forward
+ *   ctx), 0 if absent, saturated at 0xFFFFFFFF.  There is no count range.  V = valid windows of the read.
+ * DEPTH.  The counts of the V valid windows sorted ascending, c_(0) <= ... <= c_(V-1); q = ((V - 1) * permille) / 1000 by
+ *   64-bit integer division, permille in 0..1000; the read's own depth is d_r = c_(q), and d_r = 0 if V == 0.  permille 0 is
+ *   the minimum, 1000 the maximum, 500 the lower median.
+ * UNIT.  Without KMC_NORM_PAIRED the unit of read r is g = r and D = d_r.  With it reads 2i and 2i + 1 are mates, g = r >> 1
+ *   and D = min(d_2i, d_2i+1); an odd n_reads is KMC_ERR_ARG.
+ * DRAW.  All arithmetic mod 2^64: x = seed + (g + 1) * 0x9E3779B97F4A7C15; x ^= x >> 30; x *= 0xBF58476D1CE4E5B9;
+ *   x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31; u = ((x >> 32) * D) >> 32 -- 0 when D == 0, else in 0..D-1.
+ * LOW, DEEP.  LOW iff D < min_depth.  DEEP iff not LOW, target != 0 and D > target.
+ * KEEP, EMITTED.  KEEP iff not LOW and (not DEEP or u < target): a DEEP unit survives with probability target / D.  Both
+ *   mates of a pair get their unit's verdict.  EMITTED is KEEP; with KMC_NORM_INVERT it is not KEEP.  target == 0 samples
+ *   nothing down, min_depth == 0 drops nothing.
+ * Outputs.  out_bases: the emitted reads whole, concatenated in read order, bytes as given.  out_offsets[n_out + 1],
+ *   uint64_t, [0] == 0.  origin[n_out], uint64_t: the source read of each emitted read.  read_stats[n_reads *
+ *   KMC_NORMALIZE_READ_WORDS], uint32_t, for EVERY read, emitted or not: [0] V, [1] d_r, [2] D, [3] u.  verdict[n_reads],
+ *   uint8_t: bit 0 KMC_NORM_KEEP, bit 1 KMC_NORM_EMITTED, bit 2 KMC_NORM_LOW, bit 3 KMC_NORM_DEEP.
+ *   summary[KMC_NORMALIZE_WORDS]: [0] reads, [1] valid windows, [2] reads emitted (= n_out), [3] bases emitted (=
+ *   out_offsets[n_out]), [4] LOW reads, [5] DEEP reads, [6] DEEP reads that are kept, [7] the sum of d_r.  Without INVERT
+ *   [2] == [0] - [4] - [5] + [6].
+ * Identities.  For one seed, the units kept at target T1 are a subset of those kept at T2 > T1 (u does not depend on the
+ *   target).  permille 0 and 1000 give d_r = min(kmc_profile's read_stats [2] and [3], 0xFFFFFFFF), and word [0] equals
+ *   kmc_profile's [0].  target 0, min_depth 0 and no flags return the batch as it came: same bytes, same offsets, origin[i]
+ *   == i.  The same arguments with INVERT emit nothing.
+ * Rules: NULL ctx, KMC_MODE_LR, permille > 1000, an unknown flag bit, an odd n_reads with PAIRED, a read of 2^32 bases or
+ * more, the ctx's own last kmc_normalize* output arrays handed in as the input (the call would read what it writes; the
+ * outputs of kmc_trim* and kmc_correct* are fine as input, and this call's are fine as input to them): KMC_ERR_ARG; no view:
+ * KMC_ERR_STATE (where kmc_export says so); a view of 2^32 keys or more: KMC_ERR_CAPACITY (the index's rule); a batch of 2^31
+ * reads or 2^32 bases or more in one call: KMC_ERR_CAPACITY (kmc_trim's rule).  target or min_depth above 2^32 are plain
+ * 64-bit comparisons.  n_reads == 0 gives zeros and out_offsets[0] == 0.  An empty view makes every count 0.
+ * What the call changes: it builds or reuses the query index.  It rewrites none of: the view, a partition, a filter or
+ * set-operation result, adj, the unitigs, links, a clean / simplify / components / bubbles result, a map result, and the
+ * arrays a kmc_correct* or kmc_trim* call handed out.
+ * Diagnostic: with KMC_UNITIG_TRACE set, a call prints "kmc_normalize: keys N reads R windows W emitted E bases B low L deep
+ * D kept K profile_ms .. select_ms .. layout_ms .. gather_ms .." to stderr (tools/measure_normalize.py reads it). ---- */
+#define KMC_NORMALIZE_WORDS 8
+#define KMC_NORMALIZE_READ_WORDS 4
+#define KMC_NORM_PAIRED 1u
+#define KMC_NORM_INVERT 2u
+#define KMC_NORM_KEEP 1u      /* verdict bit 0 */
+#define KMC_NORM_EMITTED 2u   /* verdict bit 1 */
+#define KMC_NORM_LOW 4u       /* verdict bit 2 */
+#define KMC_NORM_DEEP 8u      /* verdict bit 3 */
+/* The batch in device memory, by the layout and alignment rules of kmc_profile_device.  The results in ctx-owned device
+ * arrays -- uint8_t out_bases[n_out_bases], uint64_t out_offsets[n_out + 1], uint64_t origin[n_out], uint32_t read_stats[n_reads
+ * * 4], uint8_t verdict[n_reads] -- valid until the next kmc_normalize* call / finalize / reset / destroy (the contract of
+ * kmc_trim_device: the call has finished when it returns).  d_out_bases is 16-byte aligned and readable to the next 16-byte
+ * boundary past the last base (those bytes are zero): with d_out_offsets it goes straight into kmc_add_batch_device,
+ * kmc_correct_device, kmc_trim_device and kmc_unitig_map_device, of this or another ctx on the device -- but not back into
+ * kmc_normalize* of this ctx (above).  Every output pointer may be NULL. */
+int kmc_normalize_device(kmc_ctx* ctx, uint32_t permille, uint64_t target, uint64_t min_depth, uint64_t seed, uint32_t flags,
+                         const void* d_bases, const void* d_offsets, uint64_t n_reads, uint64_t n_bases, const void** d_out_bases,
+                         const void** d_out_offsets, const void** d_origin, const void** d_read_stats, const void** d_verdict,
+                         uint64_t* n_out, uint64_t* n_out_bases, uint64_t* summary);
+/* The same on host buffers (the batch as kmc_profile takes it), by the cap conventions of kmc_trim: out_bases with room for
+ * cap_bases bytes, out_offsets for cap_reads + 1 entries, origin for cap_reads, read_stats[n_reads * 4] and verdict[n_reads].
+ * *n_out and *n_out_bases are always set; a cap too small for an array that was given -> KMC_ERR_ARG and nothing is copied;
+ * an array that is NULL is not copied and its cap not looked at.  All arrays NULL is the sizing call.  The host form computes
+ * on EVERY call. */
+int kmc_normalize(kmc_ctx* ctx, uint32_t permille, uint64_t target, uint64_t min_depth, uint64_t seed, uint32_t flags,
+                  const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads, uint8_t* out_bases, uint64_t cap_bases,
+                  uint64_t* out_offsets, uint64_t* origin, uint64_t cap_reads, uint32_t* read_stats, uint8_t* verdict,
+                  uint64_t* n_out, uint64_t* n_out_bases, uint64_t* summary);
 
 /* ---- the compacted graph cleaned: tips clipped, islands dropped (additions, as above).  Everything refers to the unitigs
  * and the link records of kmc_unitigs / kmc_unitig_links for the same view and range min_count..max_count.  For unitig u:

@@ -99,6 +99,7 @@ ABI_SYMBOLS = [
     "kmc_unitig_map", "kmc_unitig_map_device",
     "kmc_correct", "kmc_correct_device",
     "kmc_trim", "kmc_trim_device",
+    "kmc_normalize", "kmc_normalize_device",
 ]
 
 PROFILE_WORDS = 5  # KMC_PROFILE_WORDS: valid windows, present windows, min, max, sum
@@ -131,6 +132,10 @@ TRIM_NONE, TRIM_ENDS, TRIM_LONGEST = 0, 1, 2   # KMC_TRIM_*: the mode
 TRIM_INVERT, TRIM_PAIR_BOTH, TRIM_PAIR_EITHER = 1, 2, 4   # KMC_TRIM_*: the flag bits
 TRIM_PASS, TRIM_EMITTED = 1, 2   # KMC_TRIM_*: the bits of a read's verdict byte
 TRIM_MODE_NAMES = {"none": TRIM_NONE, "ends": TRIM_ENDS, "longest": TRIM_LONGEST}
+NORMALIZE_WORDS = 8       # KMC_NORMALIZE_WORDS: reads, valid windows, reads emitted, bases emitted, LOW reads, DEEP reads, DEEP reads kept, sum of the depths
+NORMALIZE_READ_WORDS = 4  # KMC_NORMALIZE_READ_WORDS: a read's valid windows, its own depth, its unit's depth, its unit's draw
+NORM_PAIRED, NORM_INVERT = 1, 2   # KMC_NORM_*: the flag bits
+NORM_KEEP, NORM_EMITTED, NORM_LOW, NORM_DEEP = 1, 2, 4, 8   # KMC_NORM_*: the bits of a read's verdict byte
 SETOP_INTERSECT, SETOP_UNION, SETOP_SUBTRACT = 0, 1, 2
 COUNT_LEFT, COUNT_RIGHT, COUNT_MIN, COUNT_MAX, COUNT_SUM, COUNT_DIFF = 0, 1, 2, 3, 4, 5
 SETOP_NAMES = {"intersect": SETOP_INTERSECT, "union": SETOP_UNION, "subtract": SETOP_SUBTRACT}
@@ -221,6 +226,9 @@ def lib() -> C.CDLL:
     L.kmc_correct.argtypes = [vp, u64, u64, vp, vp, u64, vp, vp, vp, vp, u64, pu64, vp]
     L.kmc_trim_device.argtypes = [vp, u64, u64, i32, u32, u64, u32, u64, vp, vp, u64, u64] + [C.POINTER(vp)] * 5 + [pu64, pu64, vp]
     L.kmc_trim.argtypes = [vp, u64, u64, i32, u32, u64, u32, u64, vp, vp, u64, vp, u64, vp, vp, u64, vp, vp, pu64, pu64, vp]
+    if "KMC_LIB_PATH" not in os.environ or hasattr(L, "kmc_normalize"):   # (as for the bubbles calls above)
+        L.kmc_normalize_device.argtypes = [vp, u32, u64, u64, u64, u32, vp, vp, u64, u64] + [C.POINTER(vp)] * 5 + [pu64, pu64, vp]
+        L.kmc_normalize.argtypes = [vp, u32, u64, u64, u64, u32, vp, vp, u64, vp, u64, vp, vp, u64, vp, vp, pu64, pu64, vp]
     L.kmc_owner_of.argtypes = [u64, u64, u32]
     L.kmc_owner_of.restype = u32
     L.kmc_get_stats.argtypes = [vp, C.POINTER(Stats)]
@@ -724,6 +732,61 @@ class TrimmedReads:
         """What ``k-mer-count --trim`` prints, emitted reads only: ``>INDEX WINDOWS STRONG START LEN`` and the span."""
         st = self.stats.tolist()
         return "".join(">%d %d %d %d %d\n%s\n" % ((r,) + tuple(st[r]) + (s,)) for r, s in zip(self.origin.tolist(), self.strings()))
+
+
+_NORMALIZE_FIELDS = ("reads", "valid_windows", "emitted", "bases", "low", "deep", "deep_kept", "depth_sum")
+
+
+@dataclass
+class NormalizeSummary:
+    """The eight words of kmc_normalize: reads, valid windows, reads emitted, bases emitted, LOW reads, DEEP reads, DEEP
+    reads that are kept, the sum of the reads' own depths."""
+    reads: int
+    valid_windows: int
+    emitted: int
+    bases: int
+    low: int
+    deep: int
+    deep_kept: int
+    depth_sum: int
+
+    @classmethod
+    def from_words(cls, words) -> "NormalizeSummary":
+        return cls(*[int(w) for w in words])
+
+    def words(self) -> list:
+        return [getattr(self, f) for f in _NORMALIZE_FIELDS]
+
+    def to_text(self) -> str:
+        """``NAME\tVALUE`` lines."""
+        return "\n".join("%s\t%d" % (f, getattr(self, f)) for f in _NORMALIZE_FIELDS) + "\n"
+
+
+@dataclass
+class NormalizedReads:
+    """What KmerCounter.normalize_reads returns: the emitted reads as a batch -- ``bases`` uint8[n_out_bases], ``offsets``
+    uint64[n_out + 1] -- with ``origin`` uint64[n_out] (the source read of each), and for every read of the input ``stats``
+    uint32[n_reads, 4] (valid windows, own depth, unit depth, draw) and ``verdict`` uint8[n_reads] (NORM_KEEP | NORM_EMITTED |
+    NORM_LOW | NORM_DEEP); ``summary``."""
+    bases: np.ndarray
+    offsets: np.ndarray
+    origin: np.ndarray
+    stats: np.ndarray
+    verdict: np.ndarray
+    summary: NormalizeSummary
+
+    def __len__(self) -> int:
+        return len(self.offsets) - 1
+
+    def strings(self) -> list:
+        """The emitted reads as str."""
+        o, b = self.offsets, self.bases.tobytes()
+        return [b[int(o[i]):int(o[i + 1])].decode("latin-1") for i in range(len(self))]
+
+    def to_fasta(self) -> str:
+        """What ``k-mer-count --normalize`` prints, emitted reads only: ``>INDEX WINDOWS DEPTH UNITDEPTH`` and the read."""
+        st = self.stats.tolist()
+        return "".join(">%d %d %d %d\n%s\n" % ((r,) + tuple(st[r][:3]) + (s,)) for r, s in zip(self.origin.tolist(), self.strings()))
 
 
 _CLEAN_FIELDS = ("unitigs", "tips", "islands", "kept_keys", "tip_keys", "island_keys", "tip_candidates", "kept_count")
@@ -1361,6 +1424,49 @@ class KmerCounter:
         self._chk(self._L.kmc_trim(self._h, *args, out.ctypes.data, nb.value, oo.ctypes.data, org.ctypes.data, no.value, stats.ctypes.data,
                                    verdict.ctypes.data, C.byref(no), C.byref(nb), w))
         return TrimmedReads(out, oo, org, stats, verdict, TrimSummary.from_words(list(w)))
+
+    # -- read depth normalised: a percentile depth per read, deep reads sampled down (of the sorted view; finalize() first) --
+    def normalize_reads_device(self, d_bases: int, d_offsets: int, n_reads: int, n_bases: int, target: int = 0, permille: int = 500,
+                               min_depth: int = 0, seed: int = 0, flags: int = 0):
+        """(d_out_bases, d_out_offsets, d_origin, d_read_stats, d_verdict, n_out, n_out_bases, NormalizeSummary) of
+        kmc_normalize_device for a batch in device memory (raw addresses, laid out as for profile_device): ctx-owned device
+        arrays of n_out_bases uint8 (padded as add_batch_device asks), n_out + 1 uint64, n_out uint64, n_reads * 4 uint32 and
+        n_reads uint8."""
+        p = [C.c_void_p() for _ in range(5)]
+        no, nb = C.c_uint64(), C.c_uint64()
+        w = (C.c_uint64 * NORMALIZE_WORDS)()
+        self._chk(self._L.kmc_normalize_device(self._h, int(permille), int(target), int(min_depth), int(seed), int(flags), d_bases or None,
+                                               d_offsets or None, int(n_reads), int(n_bases), *[C.byref(x) for x in p], C.byref(no), C.byref(nb), w))
+        return tuple(x.value or 0 for x in p) + (no.value, nb.value, NormalizeSummary.from_words(list(w)))
+
+    def normalize_reads_tensors(self, bases, offsets, target: int = 0, permille: int = 500, min_depth: int = 0, seed: int = 0, flags: int = 0):
+        """normalize_reads_device for torch tensors on this ctx's GPU (bases uint8[n_bases], padded as for add_batch_tensors;
+        offsets int64[n_reads + 1])."""
+        assert bases.is_cuda and offsets.is_cuda and bases.is_contiguous() and offsets.is_contiguous()
+        return self.normalize_reads_device(bases.data_ptr(), offsets.data_ptr(), max(offsets.numel() - 1, 0), bases.numel(), target, permille,
+                                           min_depth, seed, flags)
+
+    def normalize_reads(self, bases: np.ndarray, offsets: np.ndarray, target: int = 0, permille: int = 500, min_depth: int = 0, seed: int = 0,
+                        flags: int = 0) -> "NormalizedReads":
+        """kmc_normalize for a host batch (the batch is not counted): per read its depth, the permille-th thousandth of the
+        sorted counts of its valid windows (500: the lower median); units (reads, or pairs with NORM_PAIRED) below min_depth
+        are dropped, units above target are kept with probability target / depth (seed), and the emitted reads (NORM_INVERT:
+        the others) come back whole as a new batch."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n_reads = max(int(offsets.shape[0]) - 1, 0)
+        if n_reads and int(offsets[-1]) != int(bases.shape[0]):
+            raise ValueError("offsets must end at len(bases)")
+        args = (int(permille), int(target), int(min_depth), int(seed), int(flags), bases.ctypes.data if n_reads else None,
+                offsets.ctypes.data if n_reads else None, n_reads)
+        no, nb = C.c_uint64(), C.c_uint64()
+        w = (C.c_uint64 * NORMALIZE_WORDS)()
+        self._chk(self._L.kmc_normalize(self._h, *args, None, 0, None, None, 0, None, None, C.byref(no), C.byref(nb), None))
+        out, oo, org = np.zeros(nb.value, np.uint8), np.zeros(no.value + 1, np.uint64), np.zeros(no.value, np.uint64)
+        stats, verdict = np.zeros((n_reads, NORMALIZE_READ_WORDS), np.uint32), np.zeros(n_reads, np.uint8)
+        self._chk(self._L.kmc_normalize(self._h, *args, out.ctypes.data, nb.value, oo.ctypes.data, org.ctypes.data, no.value, stats.ctypes.data,
+                                        verdict.ctypes.data, C.byref(no), C.byref(nb), w))
+        return NormalizedReads(out, oo, org, stats, verdict, NormalizeSummary.from_words(list(w)))
 
     # -- that graph cleaned: tips clipped, islands dropped (of the sorted view; finalize() first) --
     def _clean_limits(self, max_tip_keys, max_island_keys) -> Tuple[int, int]:

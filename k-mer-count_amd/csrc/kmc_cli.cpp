@@ -8,6 +8,7 @@
 //               [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE | --map FILE | --correct FILE]
 //               [--trim FILE [--trim-mode none|ends|longest] [--min-strong N] [--strong-permille N] [--min-len N] [--invert]
 //                [--paired both|either]]
+//               [--normalize FILE --target N [--depth-permille P] [--min-depth N] [--seed S] [--norm-paired] [--norm-invert]]
 //               [--with FASTA2 (--compare | --setop intersect|union|subtract [--counts left|right|min|max|sum|diff])]
 //               [--graph | --graph-stats | --unitigs | --gfa | --components | --variants [--bubble-keys N]]
 //               [--clean ROUNDS [--tip-keys N] [--island-keys N] [--bubble-keys N]] [--component-keys N]
@@ -52,6 +53,16 @@
 //               emitted reads only: ">INDEX WINDOWS STRONG START LEN" -- the read's number in FILE, its valid and its strong
 //               windows, the span's start and length in bases -- then the span on one line.  It excludes --query-kmers /
 //               --profile / --map / --correct; with --clean the reads are judged against the cleaned table.
+//   --normalize FILE     (with -k K) instead of the table: every read of FILE (FASTA / FASTQ) gets a depth -- the count at
+//               --depth-permille P thousandths (default 500, the lower median) of the sorted counts of its valid windows in
+//               the counted input -- and the reads are normalised by it (kmc_normalize): a read shallower than --min-depth N
+//               (default 0) is dropped, a read deeper than --target N is kept with probability N / depth, decided by a draw
+//               from --seed S (default 0) and the read's number, so a run repeats exactly; --target 0 samples nothing down.
+//               --norm-paired: reads 2i and 2i + 1 are mates, judged together by the smaller depth.  --norm-invert prints the
+//               reads that go instead.  Output: FASTA in file order, the emitted reads only: ">INDEX WINDOWS DEPTH UNITDEPTH"
+//               -- the read's number in FILE, its valid windows, its own depth, the depth it was judged by -- then the read on
+//               one line.  It excludes --query-kmers / --profile / --map / --correct / --trim and --with; with --clean the
+//               reads are judged against the cleaned table.
 //
 //   --with FASTA2        (with -k K) a second file, counted into a second table on the same device; one of:
 //     --compare          instead of the table: "NAME<TAB>VALUE" lines -- the eight words of kmc_compare (n_a, n_b, n_both, sum_a,
@@ -152,6 +163,9 @@ int main(int argc, char** argv) {
     const char* trim_path = nullptr;
     int trim_mode = -1, trim_invert = 0, trim_pair = 0;   // (-1: the default mode, longest)
     long long min_strong = -1, strong_permille = -1, min_len = -1;   // (-1: not given)
+    const char* norm_path = nullptr;
+    int norm_paired = 0, norm_invert = 0;
+    long long norm_target = -1, depth_permille = -1, min_depth = -1, norm_seed = -1;   // (-1: not given)
     int compare = 0, setop = -1, count_mode = -1, graph = 0, graph_stats = 0, unitigs = 0, gfa = 0;
     int clean = 0;
     long long tip_keys = -1, island_keys = -1;   // (-1: K)
@@ -189,6 +203,13 @@ int main(int argc, char** argv) {
             if (trim_pair && trim_pair != p) { fprintf(stderr, "k-mer-count: --paired both and --paired either exclude each other\n"); return 2; }
             trim_pair = p;
         }
+        else if (a == "--normalize" && i + 1 < argc) norm_path = argv[++i];
+        else if (a == "--target" && i + 1 < argc) { if (!parse_count("--target", argv[++i], 0, LLONG_MAX, &norm_target)) return 2; }
+        else if (a == "--depth-permille" && i + 1 < argc) { if (!parse_count("--depth-permille", argv[++i], 0, 1000, &depth_permille)) return 2; }
+        else if (a == "--min-depth" && i + 1 < argc) { if (!parse_count("--min-depth", argv[++i], 0, LLONG_MAX, &min_depth)) return 2; }
+        else if (a == "--seed" && i + 1 < argc) { if (!parse_count("--seed", argv[++i], 0, LLONG_MAX, &norm_seed)) return 2; }
+        else if (a == "--norm-paired") norm_paired = 1;
+        else if (a == "--norm-invert") norm_invert = 1;
         else if (a == "--with" && i + 1 < argc) with_path = argv[++i];
         else if (a == "--compare") compare = 1;
         else if (a == "--graph") graph = 1;
@@ -219,6 +240,7 @@ int main(int argc, char** argv) {
                             "                   [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE | --map FILE | --correct FILE]\n"
                             "                   [--trim FILE [--trim-mode none|ends|longest] [--min-strong N] [--strong-permille N] [--min-len N] [--invert]\n"
                             "                    [--paired both|either]]\n"
+                            "                   [--normalize FILE --target N [--depth-permille P] [--min-depth N] [--seed S] [--norm-paired] [--norm-invert]]\n"
                             "                   [--with FASTA2 (--compare | --setop intersect|union|subtract [--counts left|right|min|max|sum|diff])]\n"
                             "                   [--graph | --graph-stats | --unitigs | --gfa | --components | --variants [--bubble-keys N]]\n"
                             "                   [--clean ROUNDS [--tip-keys N] [--island-keys N] [--bubble-keys N]] [--component-keys N]\n");
@@ -226,7 +248,8 @@ int main(int argc, char** argv) {
         } else if (a == "-k" || a == "--device" || a == "--gpus" || a == "--algo" || a == "--min-count" || a == "--max-count" || a == "--histo" ||
                    a == "--query-kmers" || a == "--profile" || a == "--map" || a == "--correct" || a == "--with" || a == "--setop" || a == "--counts" ||
                    a == "--clean" || a == "--tip-keys" || a == "--island-keys" || a == "--bubble-keys" || a == "--component-keys" || a == "--trim" ||
-                   a == "--trim-mode" || a == "--min-strong" || a == "--strong-permille" || a == "--min-len" || a == "--paired") {
+                   a == "--trim-mode" || a == "--min-strong" || a == "--strong-permille" || a == "--min-len" || a == "--paired" ||
+                   a == "--normalize" || a == "--target" || a == "--depth-permille" || a == "--min-depth" || a == "--seed") {
             fprintf(stderr, "k-mer-count: %s needs a value\n", a.c_str());
             return 2;
         } else if (!a.empty() && a[0] != '-') path = argv[i];
@@ -287,6 +310,22 @@ int main(int argc, char** argv) {
         fprintf(stderr, "k-mer-count: --trim-mode / --min-strong / --strong-permille / --min-len / --invert / --paired need --trim FILE\n");
         return 2;
     }
+    // --normalize and its options: the same again
+    if (norm_path) {
+        const char* bad = nullptr;
+        if (!k) bad = "needs -k K";
+        else if (norm_target < 0) bad = "needs --target N";
+        else if (map_path || correct_path || trim_path) bad = "--map / --correct / --trim exclude each other";
+        else if (query_path || profile_path) bad = "--query-kmers / --profile exclude each other";
+        else if (histo) bad = "--histo exclude each other";
+        else if (with_path || compare || setop >= 0) bad = "--with / --compare / --setop exclude each other";
+        else if (graph || graph_stats || unitigs || gfa) bad = "--graph / --graph-stats / --unitigs / --gfa exclude each other";
+        else if (expand) bad = "--expand exclude each other";
+        if (bad) { fprintf(stderr, "k-mer-count: --normalize %s%s\n", strncmp(bad, "needs", 5) ? "and " : "", bad); return 2; }
+    } else if (norm_target >= 0 || depth_permille >= 0 || min_depth >= 0 || norm_seed >= 0 || norm_paired || norm_invert) {
+        fprintf(stderr, "k-mer-count: --target / --depth-permille / --min-depth / --seed / --norm-paired / --norm-invert need --normalize FILE\n");
+        return 2;
+    }
     if (query_path) {
         FILE* f = fopen(query_path, "r");
         if (!f) return die(query_path, strerror(errno));
@@ -311,8 +350,8 @@ int main(int argc, char** argv) {
         }
         fclose(f);
     }
-    if (profile_path || map_path || correct_path || trim_path) {
-        const char* reads_path = profile_path ? profile_path : map_path ? map_path : correct_path ? correct_path : trim_path;
+    if (profile_path || map_path || correct_path || trim_path || norm_path) {
+        const char* reads_path = profile_path ? profile_path : map_path ? map_path : correct_path ? correct_path : trim_path ? trim_path : norm_path;
         char eb[256] = {0};
         const int prc = kmc_parse_fasta(reads_path, &prof, eb, sizeof(eb));
         if (prc) return die(reads_path, eb[0] ? eb : kmc_status_string(prc));
@@ -360,7 +399,8 @@ int main(int argc, char** argv) {
         if (!k) bad = "needs -k K";
         else if (graph || graph_stats || unitigs || gfa) bad = "--graph / --graph-stats / --unitigs / --gfa exclude each other";
         else if (histo) bad = "--histo exclude each other";
-        else if (query_path || profile_path || map_path || correct_path || trim_path) bad = "--query-kmers / --profile / --map / --correct / --trim exclude each other";
+        else if (query_path || profile_path || map_path || correct_path || trim_path || norm_path)
+            bad = "--query-kmers / --profile / --map / --correct / --trim / --normalize exclude each other";
         else if (with_path || compare || setop >= 0) bad = "--with / --compare / --setop exclude each other";
         else if (expand) bad = "--expand exclude each other";
         if (bad) { fprintf(stderr, "k-mer-count: --components %s%s\n", strncmp(bad, "needs", 5) ? "and " : "", bad); return 2; }
@@ -371,7 +411,8 @@ int main(int argc, char** argv) {
         if (!k) bad = "needs -k K";
         else if (graph || graph_stats || unitigs || gfa || components) bad = "--graph / --graph-stats / --unitigs / --gfa / --components exclude each other";
         else if (histo) bad = "--histo exclude each other";
-        else if (query_path || profile_path || map_path || correct_path || trim_path) bad = "--query-kmers / --profile / --map / --correct / --trim exclude each other";
+        else if (query_path || profile_path || map_path || correct_path || trim_path || norm_path)
+            bad = "--query-kmers / --profile / --map / --correct / --trim / --normalize exclude each other";
         else if (with_path || compare || setop >= 0) bad = "--with / --compare / --setop exclude each other";
         else if (expand) bad = "--expand exclude each other";
         if (bad) { fprintf(stderr, "k-mer-count: --variants %s%s\n", strncmp(bad, "needs", 5) ? "and " : "", bad); return 2; }
@@ -619,6 +660,40 @@ int main(int argc, char** argv) {
         for (uint64_t i = 0; i < no; ++i) {
             const uint32_t* w = &rs[(size_t)og[i] * KMC_TRIM_READ_WORDS];
             printf(">%llu %u %u %u %u\n", (unsigned long long)og[i], w[0], w[1], w[2], w[3]);
+            fwrite(ob.data() + oo[i], 1, (size_t)(oo[i + 1] - oo[i]), stdout);
+            fputc('\n', stdout);
+        }
+        fflush(stdout);
+        destroy_all();
+        return 0;
+    }
+    if (norm_path) {
+        // the host form computes on every call: the first call sizes the emitted batch (and fills the per-read rows), the second
+        // copies it
+        const uint64_t n_norm = prof.n_reads, tg = (uint64_t)norm_target, md = min_depth < 0 ? 0 : (uint64_t)min_depth;
+        const uint64_t sd = norm_seed < 0 ? 0 : (uint64_t)norm_seed;
+        const uint32_t pm = depth_permille < 0 ? 500u : (uint32_t)depth_permille;
+        const uint32_t flags = (norm_paired ? KMC_NORM_PAIRED : 0u) | (norm_invert ? KMC_NORM_INVERT : 0u);
+        if (norm_paired && (n_norm & 1)) {
+            kmc_free_reads(&prof);
+            fprintf(stderr, "k-mer-count: --norm-paired needs an even number of reads (%s has %llu)\n", norm_path, (unsigned long long)n_norm);
+            destroy_all();
+            return 2;
+        }
+        std::vector<uint32_t> rs((size_t)n_norm * KMC_NORMALIZE_READ_WORDS + 1);
+        uint64_t no = 0, nb = 0;
+        rc = kmc_normalize(ctx, pm, tg, md, sd, flags, prof.bases, prof.offsets, n_norm, nullptr, 0, nullptr, nullptr, 0, rs.data(), nullptr, &no, &nb,
+                           nullptr);
+        std::vector<uint8_t> ob((size_t)nb + 1);
+        std::vector<uint64_t> oo((size_t)no + 1), og((size_t)no + 1);
+        if (!rc) rc = kmc_normalize(ctx, pm, tg, md, sd, flags, prof.bases, prof.offsets, n_norm, ob.data(), nb, oo.data(), og.data(), no, nullptr,
+                                    nullptr, &no, &nb, nullptr);
+        kmc_free_reads(&prof);
+        if (rc) { int r = die("kmc_normalize", kmc_last_error(ctx)); destroy_all(); return r; }
+        setvbuf(stdout, obuf.data(), _IOFBF, obuf.size());
+        for (uint64_t i = 0; i < no; ++i) {
+            const uint32_t* w = &rs[(size_t)og[i] * KMC_NORMALIZE_READ_WORDS];
+            printf(">%llu %u %u %u\n", (unsigned long long)og[i], w[0], w[1], w[2]);
             fwrite(ob.data() + oo[i], 1, (size_t)(oo[i + 1] - oo[i]), stdout);
             fputc('\n', stdout);
         }

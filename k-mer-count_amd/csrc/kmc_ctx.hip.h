@@ -251,6 +251,13 @@ struct kmc_ctx : CtxStream {
     DevBuf tr_out[2], tr_ooffs[2], tr_origin, tr_stats, tr_verdict;
     DevBuf tr_sbits, tr_vbits, tr_wbits, tr_runs, tr_list, tr_emit, tr_elen, tr_epos, tr_lpos, tr_src;
     int tr_cur = 0;
+    // kmc_normalize / kmc_normalize_device (kmc_normalize.hip.h) read the view and the query index alone.  The result of the
+    // last call: the emitted reads as a batch, the source read of each, per-read rows and verdicts (one buffer each: the call
+    // refuses its own result as input).  Between the passes: the profile pass's window counts and per-read rows (its own, no
+    // call hands them out), a depth per read, the list of the reads a workgroup selects, the emitted flags and lengths with
+    // their scans, each emitted read's batch position.
+    DevBuf nm_out, nm_ooffs, nm_origin, nm_stats, nm_verdict;
+    DevBuf nm_win, nm_pstats, nm_depth, nm_list, nm_emit, nm_elen, nm_epos, nm_lpos, nm_src;
     // kmc_unitig_clean* and kmc_unitig_simplify* (kmc_clean.hip.h) read the unitigs, the links and what the links pass
     // reads.  Their result: the verdict per unitig and the kept table, with cl_key plus its three limits cl_tip / cl_isl /
     // cl_bub (0 for a clean call) and cl_words as above (nothing but the clean pass writes them; a clean call hands out the

@@ -313,7 +313,9 @@ void kmc_trim_verdict_kernel(TrimRule R, const uint4* __restrict__ runs, const u
 }
 
 // Behind the scans of emit (epos) and elen (lpos): out_offsets[n_out + 1], origin[n_out] and src[n_out], the batch position
-// of each emitted span.  The arrays hold n_reads (+ 1) entries.
+// of each emitted span.  The arrays hold n_reads (+ 1) entries.  WHOLE: the spans are the reads themselves (src = offsets[r];
+// kmc_normalize.hip.h, whose read_stats hold no span), else a span starts read_stats[r].z bases into its read.
+template <bool WHOLE>
 __global__ __launch_bounds__(KMC_TR_THREADS)
 void kmc_trim_layout_kernel(const uint4* __restrict__ read_stats, const u64* __restrict__ offsets, u64 n_reads, const u32* __restrict__ emit,
                             const u32* __restrict__ elen, const u32* __restrict__ epos, const u32* __restrict__ lpos,
@@ -325,7 +327,7 @@ void kmc_trim_layout_kernel(const uint4* __restrict__ read_stats, const u64* __r
         if (emit[r]) {
             out_offsets[i] = lpos[r];
             origin[i] = r;
-            src[i] = offsets[r] + read_stats[r].z;
+            src[i] = WHOLE ? offsets[r] : offsets[r] + read_stats[r].z;
         }
         if (r == n_reads - 1) out_offsets[i + emit[r]] = (u64)lpos[r] + elen[r];
     }

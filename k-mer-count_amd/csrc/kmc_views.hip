@@ -19,6 +19,7 @@
 #include "kmc_map.hip.h"
 #include "kmc_correct.hip.h"
 #include "kmc_trim.hip.h"
+#include "kmc_normalize.hip.h"
 
 namespace {
 
@@ -1385,7 +1386,7 @@ static int trim_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count, 
                        (uint4*)c->tr_stats.p, (uint8_t*)c->tr_verdict.p, (u32*)c->tr_emit.p, (u32*)c->tr_elen.p, ctl);
     launch_exclusive_scan<0>(c->stream, c->tr_emit.p, (u32)n_reads, (u32*)c->c_bsum.p, (u32*)c->tr_epos.p, (u32*)(ctl + KMC_TR_N_OUT));
     launch_exclusive_scan<0>(c->stream, c->tr_elen.p, (u32)n_reads, (u32*)c->c_bsum.p, (u32*)c->tr_lpos.p, (u32*)(ctl + KMC_TR_N_BASES));
-    hipLaunchKernelGGL(kmc_trim_layout_kernel, dim3(rgrid), dim3(KMC_TR_THREADS), 0, c->stream, (const uint4*)c->tr_stats.p, d_offsets, n_reads,
+    hipLaunchKernelGGL(kmc_trim_layout_kernel<false>, dim3(rgrid), dim3(KMC_TR_THREADS), 0, c->stream, (const uint4*)c->tr_stats.p, d_offsets, n_reads,
                        (const u32*)c->tr_emit.p, (const u32*)c->tr_elen.p, (const u32*)c->tr_epos.p, (const u32*)c->tr_lpos.p, (u64*)c->tr_ooffs[cur].p,
                        (u64*)c->tr_origin.p, (u64*)c->tr_src.p, ctl);
     HIPCHK(c, hipGetLastError());
@@ -1471,6 +1472,164 @@ static int kmc_trim_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, int
     if (origin && no) HIPCHK(c, hipMemcpyAsync(origin, c->tr_origin.p, (size_t)no * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     if (read_stats && n_reads) HIPCHK(c, hipMemcpyAsync(read_stats, c->tr_stats.p, (size_t)n_reads * KMC_TRIM_READ_WORDS * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
     if (verdict && n_reads) HIPCHK(c, hipMemcpyAsync(verdict, c->tr_verdict.p, (size_t)n_reads, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (summary) memcpy(summary, h, sizeof(h));
+    return KMC_OK;
+}
+
+// ---- read depth normalised: a depth per read, verdicts, the emitted reads as a batch (kmc_normalize.hip.h) ----
+// the rule arguments of both calls (kmc.h: DEPTH, UNIT, LOW, DEEP, KEEP)
+static int normalize_rule(kmc_ctx* c, const char* what, uint32_t permille, uint64_t target, uint64_t min_depth, uint64_t seed, uint32_t flags,
+                          uint64_t n_reads, NormRule* R) {
+    if (permille > 1000) return fail(c, KMC_ERR_ARG, "%s: permille %u > 1000", what, permille);
+    if (flags & ~(KMC_NORM_PAIRED | KMC_NORM_INVERT)) return fail(c, KMC_ERR_ARG, "%s: unknown flag bits 0x%x", what, flags);
+    if ((flags & KMC_NORM_PAIRED) && (n_reads & 1)) return fail(c, KMC_ERR_ARG, "%s: %llu reads cannot be pairs", what, (unsigned long long)n_reads);
+    R->permille = permille; R->flags = flags; R->target = target; R->min_depth = min_depth; R->seed = seed;
+    return KMC_OK;
+}
+
+// does the array that begins at p lie in b?
+static bool inside(const DevBuf& b, const void* p) {
+    return b.p && p && (uintptr_t)p >= (uintptr_t)b.p && (uintptr_t)p < (uintptr_t)b.p + b.bytes;
+}
+
+// The batch (device arrays) judged against this view, into the nm_* buffers; h[KMC_NORMALIZE_WORDS] the summary.  Finished
+// when it returns.
+static int normalize_run(kmc_ctx* c, const char* what, const NormRule& R, const uint8_t* d_bases, const u64* d_offsets, u64 n_reads, u64 n_bases,
+                         u64* h) {
+    memset(h, 0, KMC_NORMALIZE_WORDS * sizeof(u64));
+    int rc;
+    const u64 n = c->n_sorted;
+    const int k = c->klen;
+    // the scans of kmc_scan.hip.h work on u32: positions among the reads and among the emitted bases
+    if (n_reads >= (1ull << 31) || n_bases >= (1ull << 32)) return fail(c, KMC_ERR_CAPACITY, "%s: a batch of 2^31 reads or 2^32 bases or more", what);
+    // the call writes these while it still reads the batch
+    if (n_reads && (inside(c->nm_out, d_bases) || inside(c->nm_ooffs, d_offsets)))
+        return fail(c, KMC_ERR_ARG, "%s: the input is this ctx's own kmc_normalize result", what);
+    const u64 nr1 = std::max<u64>(n_reads, 1);
+    const size_t w32 = (size_t)nr1 * sizeof(u32);
+    const size_t scan_blocks = (size_t)((n_reads + KMC_SCAN_PER_BLOCK - 1) / KMC_SCAN_PER_BLOCK);
+    if ((rc = ensure(c, c->nm_out, (size_t)n_bases + 64)) || (rc = ensure(c, c->nm_ooffs, (size_t)(n_reads + 1) * sizeof(u64))) ||
+        (rc = ensure(c, c->nm_origin, (size_t)nr1 * sizeof(u64))) || (rc = ensure(c, c->nm_stats, (size_t)nr1 * KMC_NORMALIZE_READ_WORDS * sizeof(u32))) ||
+        (rc = ensure(c, c->nm_verdict, (size_t)nr1)) || (rc = ensure(c, c->nm_win, (size_t)std::max<u64>(n_bases, 1) * sizeof(u32))) ||
+        (rc = ensure(c, c->nm_pstats, (size_t)nr1 * KMC_PROFILE_WORDS * sizeof(u64))) || (rc = ensure(c, c->nm_depth, w32)) ||
+        (rc = ensure(c, c->nm_list, w32)) || (rc = ensure(c, c->nm_emit, w32)) || (rc = ensure(c, c->nm_elen, w32)) || (rc = ensure(c, c->nm_epos, w32)) ||
+        (rc = ensure(c, c->nm_lpos, w32)) || (rc = ensure(c, c->nm_src, (size_t)nr1 * sizeof(u64))) ||
+        (rc = ensure(c, c->c_bsum, (scan_blocks + 2) * sizeof(u32))) || (rc = ensure(c, c->c_ctl, KMC_NM_CTL_WORDS * sizeof(u64))))
+        return rc;
+    if (!n_reads) {
+        HIPCHK(c, hipMemsetAsync(c->nm_ooffs.p, 0, sizeof(u64), c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return KMC_OK;
+    }
+    kmc_ull* ctl = (kmc_ull*)c->c_ctl.p;
+    HIPCHK(c, hipMemsetAsync(ctl, 0, KMC_NM_CTL_WORDS * sizeof(u64), c->stream));
+    UnitigTrace tr;
+    tr.mark(c->stream);
+    const u32* win = (const u32*)c->nm_win.p;
+    const kmc_ull* pstats = (const kmc_ull*)c->nm_pstats.p;
+    if ((rc = profile_launch(c, d_bases, d_offsets, n_reads, n_bases, 1, (u32*)c->nm_win.p, (u64*)c->nm_pstats.p))) return rc;
+    tr.mark(c->stream);
+    const u32 rgrid = (u32)grid_for(c, n_reads, KMC_NM_THREADS), ggrid = (u32)std::min<u64>(n_reads, (u64)c->n_cu * 8);
+    // a wave takes KMC_NM_TRIP reads per trip and selects them one after the other: a workgroup per trip, up to 16 per CU
+    const u64 per_wg = (u64)KMC_NM_WAVES * KMC_NM_TRIP;
+    const u32 sgrid = (u32)std::min<u64>((n_reads + per_wg - 1) / per_wg, (u64)c->n_cu * 16);
+    hipLaunchKernelGGL(kmc_normalize_select_kernel, dim3(sgrid), dim3(KMC_NM_THREADS), 0, c->stream, win, pstats, d_offsets, n_reads, n_bases, k,
+                       R.permille, (u32*)c->nm_depth.p, (u32*)c->nm_list.p, ctl);
+    hipLaunchKernelGGL(kmc_normalize_select_group_kernel, dim3(ggrid), dim3(KMC_NM_THREADS), 0, c->stream, win, pstats, d_offsets, n_reads, n_bases, k,
+                       R.permille, (u32*)c->nm_depth.p, (const u32*)c->nm_list.p, ctl);
+    HIPCHK(c, hipGetLastError());
+    tr.mark(c->stream);
+    hipLaunchKernelGGL(kmc_normalize_verdict_kernel, dim3(rgrid), dim3(KMC_NM_THREADS), 0, c->stream, R, (const u32*)c->nm_depth.p, pstats, d_offsets,
+                       n_reads, (uint4*)c->nm_stats.p, (uint8_t*)c->nm_verdict.p, (u32*)c->nm_emit.p, (u32*)c->nm_elen.p, ctl);
+    launch_exclusive_scan<0>(c->stream, c->nm_emit.p, (u32)n_reads, (u32*)c->c_bsum.p, (u32*)c->nm_epos.p, (u32*)(ctl + KMC_NM_N_OUT));
+    launch_exclusive_scan<0>(c->stream, c->nm_elen.p, (u32)n_reads, (u32*)c->c_bsum.p, (u32*)c->nm_lpos.p, (u32*)(ctl + KMC_NM_N_BASES));
+    hipLaunchKernelGGL(kmc_trim_layout_kernel<true>, dim3(rgrid), dim3(KMC_NM_THREADS), 0, c->stream, (const uint4*)c->nm_stats.p, d_offsets, n_reads,
+                       (const u32*)c->nm_emit.p, (const u32*)c->nm_elen.p, (const u32*)c->nm_epos.p, (const u32*)c->nm_lpos.p, (u64*)c->nm_ooffs.p,
+                       (u64*)c->nm_origin.p, (u64*)c->nm_src.p, ctl);
+    HIPCHK(c, hipGetLastError());
+    tr.mark(c->stream);
+    if (n_bases) {
+        // the emitted bases are at most the batch's: a lane per 16 of those, the ones past the scan's total leave at once
+        const u64 blocks = ((n_bases + 15) / 16 + KMC_NM_THREADS - 1) / KMC_NM_THREADS;
+        hipLaunchKernelGGL(kmc_trim_gather_kernel, dim3((u32)blocks), dim3(KMC_NM_THREADS), 0, c->stream, d_bases, n_bases, n_reads,
+                           (const u64*)c->nm_ooffs.p, (const u64*)c->nm_src.p, (uint8_t*)c->nm_out.p, ctl);
+        HIPCHK(c, hipGetLastError());
+    }
+    tr.mark(c->stream);
+    u64 w[KMC_NM_CTL_WORDS];
+    HIPCHK(c, hipMemcpyAsync(w, ctl, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (w[KMC_NM_LONG]) return fail(c, KMC_ERR_ARG, "%s: %llu reads of 2^32 bases or more", what, (unsigned long long)w[KMC_NM_LONG]);
+    if (w[KMC_NM_BAD]) return fail(c, KMC_ERR_HIP, "internal error: %s met %llu indices outside their arrays", what, (unsigned long long)w[KMC_NM_BAD]);
+    if (w[KMC_NM_N_OUT] != w[KMC_NM_EMITTED] || w[KMC_NM_N_BASES] != w[KMC_NM_BASES])
+        return fail(c, KMC_ERR_HIP, "internal error: %s scanned %llu reads and %llu bases of %llu and %llu", what, (unsigned long long)w[KMC_NM_N_OUT],
+                    (unsigned long long)w[KMC_NM_N_BASES], (unsigned long long)w[KMC_NM_EMITTED], (unsigned long long)w[KMC_NM_BASES]);
+    h[0] = n_reads; h[1] = w[KMC_NM_VALID]; h[2] = w[KMC_NM_EMITTED]; h[3] = w[KMC_NM_BASES]; h[4] = w[KMC_NM_LOW]; h[5] = w[KMC_NM_DEEP];
+    h[6] = w[KMC_NM_DEEP_KEPT]; h[7] = w[KMC_NM_DSUM];
+    if (tr.on && tr.n_ev == 5) {
+        float ms[4] = {0, 0, 0, 0};
+        bool ok = hipEventSynchronize(tr.ev[4]) == hipSuccess;
+        for (int i = 0; ok && i < 4; ++i) ok = hipEventElapsedTime(&ms[i], tr.ev[i], tr.ev[i + 1]) == hipSuccess;
+        if (ok)
+            fprintf(stderr, "kmc_normalize: keys %llu reads %llu windows %llu emitted %llu bases %llu low %llu deep %llu kept %llu profile_ms %.4f "
+                    "select_ms %.4f layout_ms %.4f gather_ms %.4f\n", (unsigned long long)n, (unsigned long long)n_reads, (unsigned long long)h[1],
+                    (unsigned long long)h[2], (unsigned long long)h[3], (unsigned long long)h[4], (unsigned long long)h[5], (unsigned long long)h[6],
+                    ms[0], ms[1], ms[2], ms[3]);
+    }
+    return KMC_OK;
+}
+
+static int kmc_normalize_device_impl(kmc_ctx* c, uint32_t permille, uint64_t target, uint64_t min_depth, uint64_t seed, uint32_t flags,
+                                     const void* d_bases, const void* d_offsets, uint64_t n_reads, uint64_t n_bases, const void** d_out_bases,
+                                     const void** d_out_offsets, const void** d_origin, const void** d_read_stats, const void** d_verdict,
+                                     uint64_t* n_out, uint64_t* n_out_bases, uint64_t* summary) {
+    if (n_out) *n_out = 0;
+    if (n_out_bases) *n_out_bases = 0;
+    if (!c) return KMC_ERR_ARG;
+    const char* what = "kmc_normalize_device";
+    int rc;
+    NormRule R;
+    if ((rc = graph_begin(c, what, 0, 0)) || (rc = normalize_rule(c, what, permille, target, min_depth, seed, flags, n_reads, &R))) return rc;
+    if (n_reads && (rc = check_device_batch(c, what, d_bases, d_offsets))) return rc;
+    u64 h[KMC_NORMALIZE_WORDS];
+    if ((rc = normalize_run(c, what, R, (const uint8_t*)d_bases, (const u64*)d_offsets, n_reads, n_reads ? n_bases : 0, h))) return rc;
+    if (d_out_bases) *d_out_bases = c->nm_out.p;
+    if (d_out_offsets) *d_out_offsets = c->nm_ooffs.p;
+    if (d_origin) *d_origin = c->nm_origin.p;
+    if (d_read_stats) *d_read_stats = c->nm_stats.p;
+    if (d_verdict) *d_verdict = c->nm_verdict.p;
+    if (n_out) *n_out = h[2];
+    if (n_out_bases) *n_out_bases = h[3];
+    if (summary) memcpy(summary, h, sizeof(h));
+    return KMC_OK;
+}
+
+static int kmc_normalize_impl(kmc_ctx* c, uint32_t permille, uint64_t target, uint64_t min_depth, uint64_t seed, uint32_t flags,
+                              const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads, uint8_t* out_bases, uint64_t cap_bases,
+                              uint64_t* out_offsets, uint64_t* origin, uint64_t cap_reads, uint32_t* read_stats, uint8_t* verdict, uint64_t* n_out,
+                              uint64_t* n_out_bases, uint64_t* summary) {
+    if (n_out) *n_out = 0;
+    if (n_out_bases) *n_out_bases = 0;
+    if (!c) return KMC_ERR_ARG;
+    const char* what = "kmc_normalize";
+    int rc;
+    NormRule R;
+    if ((rc = graph_begin(c, what, 0, 0)) || (rc = normalize_rule(c, what, permille, target, min_depth, seed, flags, n_reads, &R))) return rc;
+    u64 n_bases = 0;
+    if (n_reads && (rc = stage_batch(c, what, bases, offsets, n_reads, true, &n_bases))) return rc;
+    u64 h[KMC_NORMALIZE_WORDS];
+    if ((rc = normalize_run(c, what, R, (const uint8_t*)c->q_bases.p, (const u64*)c->q_offs.p, n_reads, n_bases, h))) return rc;
+    const u64 no = h[2], nb = h[3];
+    if (n_out) *n_out = no;
+    if (n_out_bases) *n_out_bases = nb;
+    if (out_bases && cap_bases < nb) return fail(c, KMC_ERR_ARG, "%s: capacity %llu < %llu bases", what, (unsigned long long)cap_bases, (unsigned long long)nb);
+    if ((out_offsets || origin) && cap_reads < no) return fail(c, KMC_ERR_ARG, "%s: capacity %llu < %llu reads", what, (unsigned long long)cap_reads, (unsigned long long)no);
+    if (out_bases && nb) HIPCHK(c, hipMemcpyAsync(out_bases, c->nm_out.p, (size_t)nb, hipMemcpyDeviceToHost, c->stream));
+    if (out_offsets) HIPCHK(c, hipMemcpyAsync(out_offsets, c->nm_ooffs.p, (size_t)(no + 1) * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    if (origin && no) HIPCHK(c, hipMemcpyAsync(origin, c->nm_origin.p, (size_t)no * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    if (read_stats && n_reads) HIPCHK(c, hipMemcpyAsync(read_stats, c->nm_stats.p, (size_t)n_reads * KMC_NORMALIZE_READ_WORDS * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+    if (verdict && n_reads) HIPCHK(c, hipMemcpyAsync(verdict, c->nm_verdict.p, (size_t)n_reads, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (summary) memcpy(summary, h, sizeof(h));
     return KMC_OK;
@@ -2101,6 +2260,24 @@ extern "C" int kmc_trim(kmc_ctx* c, uint64_t min_count, uint64_t max_count, int 
     return guarded(c, [&]() -> int {
         return kmc_trim_impl(c, min_count, max_count, mode, flags, min_strong, min_permille, min_len, bases, offsets, n_reads, out_bases, cap_bases,
                              out_offsets, origin, cap_reads, read_stats, verdict, n_out, n_out_bases, summary);
+    });
+}
+extern "C" int kmc_normalize_device(kmc_ctx* c, uint32_t permille, uint64_t target, uint64_t min_depth, uint64_t seed, uint32_t flags,
+                                    const void* d_bases, const void* d_offsets, uint64_t n_reads, uint64_t n_bases, const void** d_out_bases,
+                                    const void** d_out_offsets, const void** d_origin, const void** d_read_stats, const void** d_verdict,
+                                    uint64_t* n_out, uint64_t* n_out_bases, uint64_t* summary) {
+    return guarded(c, [&]() -> int {
+        return kmc_normalize_device_impl(c, permille, target, min_depth, seed, flags, d_bases, d_offsets, n_reads, n_bases, d_out_bases, d_out_offsets,
+                                         d_origin, d_read_stats, d_verdict, n_out, n_out_bases, summary);
+    });
+}
+extern "C" int kmc_normalize(kmc_ctx* c, uint32_t permille, uint64_t target, uint64_t min_depth, uint64_t seed, uint32_t flags, const uint8_t* bases,
+                             const uint64_t* offsets, uint64_t n_reads, uint8_t* out_bases, uint64_t cap_bases, uint64_t* out_offsets,
+                             uint64_t* origin, uint64_t cap_reads, uint32_t* read_stats, uint8_t* verdict, uint64_t* n_out, uint64_t* n_out_bases,
+                             uint64_t* summary) {
+    return guarded(c, [&]() -> int {
+        return kmc_normalize_impl(c, permille, target, min_depth, seed, flags, bases, offsets, n_reads, out_bases, cap_bases, out_offsets, origin,
+                                  cap_reads, read_stats, verdict, n_out, n_out_bases, summary);
     });
 }
 extern "C" int kmc_unitig_clean_device(kmc_ctx* c,uint64_t min_count, uint64_t max_count, uint64_t max_tip_keys, uint64_t max_island_keys,

@@ -54,6 +54,15 @@ pub const KMC_TRIM_PAIR_BOTH: u32 = 2;
 pub const KMC_TRIM_PAIR_EITHER: u32 = 4;
 pub const KMC_TRIM_PASS: u8 = 1;
 pub const KMC_TRIM_EMITTED: u8 = 2;
+/// summary words of `kmc_normalize`, words per read of its `read_stats`, its flag bits and verdict bits
+pub const KMC_NORMALIZE_WORDS: usize = 8;
+pub const KMC_NORMALIZE_READ_WORDS: usize = 4;
+pub const KMC_NORM_PAIRED: u32 = 1;
+pub const KMC_NORM_INVERT: u32 = 2;
+pub const KMC_NORM_KEEP: u8 = 1;
+pub const KMC_NORM_EMITTED: u8 = 2;
+pub const KMC_NORM_LOW: u8 = 4;
+pub const KMC_NORM_DEEP: u8 = 8;
 /// summary words of `kmc_unitig_clean`
 pub const KMC_CLEAN_WORDS: usize = 8;
 /// a unitig's verdict byte
@@ -195,6 +204,8 @@ extern "C" {
     pub fn kmc_correct(ctx: *mut KmcCtx, min_count: u64, max_count: u64, bases: *const u8, offsets: *const u64, n_reads: u64, out_bases: *mut u8, read_stats: *mut u32, cand_offsets: *mut u64, cands: *mut u32, cap_cands: u64, n_cands: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_trim_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, mode: c_int, flags: u32, min_strong: u64, min_permille: u32, min_len: u64, d_bases: *const c_void, d_offsets: *const c_void, n_reads: u64, n_bases: u64, d_out_bases: *mut *const c_void, d_out_offsets: *mut *const c_void, d_origin: *mut *const c_void, d_read_stats: *mut *const c_void, d_verdict: *mut *const c_void, n_out: *mut u64, n_out_bases: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_trim(ctx: *mut KmcCtx, min_count: u64, max_count: u64, mode: c_int, flags: u32, min_strong: u64, min_permille: u32, min_len: u64, bases: *const u8, offsets: *const u64, n_reads: u64, out_bases: *mut u8, cap_bases: u64, out_offsets: *mut u64, origin: *mut u64, cap_reads: u64, read_stats: *mut u32, verdict: *mut u8, n_out: *mut u64, n_out_bases: *mut u64, summary: *mut u64) -> c_int;
+    pub fn kmc_normalize_device(ctx: *mut KmcCtx, permille: u32, target: u64, min_depth: u64, seed: u64, flags: u32, d_bases: *const c_void, d_offsets: *const c_void, n_reads: u64, n_bases: u64, d_out_bases: *mut *const c_void, d_out_offsets: *mut *const c_void, d_origin: *mut *const c_void, d_read_stats: *mut *const c_void, d_verdict: *mut *const c_void, n_out: *mut u64, n_out_bases: *mut u64, summary: *mut u64) -> c_int;
+    pub fn kmc_normalize(ctx: *mut KmcCtx, permille: u32, target: u64, min_depth: u64, seed: u64, flags: u32, bases: *const u8, offsets: *const u64, n_reads: u64, out_bases: *mut u8, cap_bases: u64, out_offsets: *mut u64, origin: *mut u64, cap_reads: u64, read_stats: *mut u32, verdict: *mut u8, n_out: *mut u64, n_out_bases: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_clean_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, max_tip_keys: u64, max_island_keys: u64, d_key_hi: *mut *const c_void, d_key_lo: *mut *const c_void, d_count: *mut *const c_void, d_verdict: *mut *const c_void, n_kept: *mut u64, n_unitigs: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_clean(ctx: *mut KmcCtx, min_count: u64, max_count: u64, max_tip_keys: u64, max_island_keys: u64, key_hi: *mut u64, key_lo: *mut u64, count: *mut u64, cap_keys: u64, verdict: *mut u8, cap_unitigs: u64, n_kept: *mut u64, n_unitigs: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_clean_into(src: *mut KmcCtx, dst: *mut KmcCtx, min_count: u64, max_count: u64, max_tip_keys: u64, max_island_keys: u64, summary: *mut u64) -> c_int;
@@ -579,6 +590,43 @@ impl Counter {
             kmc_trim(self.ctx, min_count, max_count, mode, flags, min_strong, min_permille, min_len, bases.as_ptr(), offsets.as_ptr(),
                      n_reads as u64, out.as_mut_ptr(), nb, out_offsets.as_mut_ptr(), origin.as_mut_ptr(), no, std::ptr::null_mut::<u32>(),
                      std::ptr::null_mut::<u8>(), &mut no, &mut nb, w.as_mut_ptr())
+        })?;
+        Ok((out, out_offsets, origin, stats, verdict, w))
+    }
+
+    /// A batch of reads normalised by depth (`kmc_normalize`; the batch is not counted).  A read's depth is the count at
+    /// `permille` thousandths (500: the lower median) of the sorted counts of its valid windows; a unit -- a read, or with
+    /// `KMC_NORM_PAIRED` a pair judged by its smaller depth -- below `min_depth` is dropped, one above `target` is kept with
+    /// probability `target / depth` by a draw from `seed` and the unit's number (`target` 0: nothing is sampled down);
+    /// `KMC_NORM_INVERT` emits the others.  Returns the emitted reads whole as a batch (bases, offsets), the source read of
+    /// each, per read of the input [valid windows, own depth, unit depth, draw] and the verdict byte (`KMC_NORM_KEEP`,
+    /// `KMC_NORM_EMITTED`, `KMC_NORM_LOW`, `KMC_NORM_DEEP`), and the eight summary words.  The host form computes on every
+    /// call, so the sizing call below judges the batch once more.
+    #[allow(clippy::type_complexity, clippy::too_many_arguments)]
+    pub fn normalize_reads(&mut self, bases: &[u8], offsets: &[u64], permille: u32, target: u64, min_depth: u64, seed: u64, flags: u32)
+                           -> Result<(Vec<u8>, Vec<u64>, Vec<u64>, Vec<[u32; KMC_NORMALIZE_READ_WORDS]>, Vec<u8>, [u64; KMC_NORMALIZE_WORDS]), KmcError> {
+        let (mut nd, mut nt) = (0u64, 0u64);
+        self.check(unsafe { kmc_finalize(self.ctx, &mut nd, &mut nt) })?;
+        let n_reads = offsets.len().saturating_sub(1);
+        if n_reads > 0 && offsets[n_reads] as usize != bases.len() {
+            return Err(KmcError(-1, "offsets do not end at the number of bases".into()));
+        }
+        let (mut no, mut nb) = (0u64, 0u64);
+        let mut w = [0u64; KMC_NORMALIZE_WORDS];
+        let mut stats = vec![[0u32; KMC_NORMALIZE_READ_WORDS]; n_reads];
+        let mut verdict = vec![0u8; n_reads];
+        self.check(unsafe {
+            kmc_normalize(self.ctx, permille, target, min_depth, seed, flags, bases.as_ptr(), offsets.as_ptr(), n_reads as u64,
+                          std::ptr::null_mut::<u8>(), 0, std::ptr::null_mut::<u64>(), std::ptr::null_mut::<u64>(), 0,
+                          stats.as_mut_ptr() as *mut u32, verdict.as_mut_ptr(), &mut no, &mut nb, w.as_mut_ptr())
+        })?;
+        let mut out = vec![0u8; nb as usize];
+        let mut out_offsets = vec![0u64; no as usize + 1];
+        let mut origin = vec![0u64; no as usize];
+        self.check(unsafe {
+            kmc_normalize(self.ctx, permille, target, min_depth, seed, flags, bases.as_ptr(), offsets.as_ptr(), n_reads as u64,
+                          out.as_mut_ptr(), nb, out_offsets.as_mut_ptr(), origin.as_mut_ptr(), no, std::ptr::null_mut::<u32>(),
+                          std::ptr::null_mut::<u8>(), &mut no, &mut nb, w.as_mut_ptr())
         })?;
         Ok((out, out_offsets, origin, stats, verdict, w))
     }
