@@ -32,6 +32,7 @@
  *   (addition: no equivalent in the reference)             kmc_unitig_components_into (the table without small components, into another ctx)
  *   (addition: no equivalent in the reference)             kmc_unitig_bubbles / kmc_unitig_bubbles_device (its bubbles reported as variant records)
  *   (addition: no equivalent in the reference)             kmc_unitig_map / kmc_unitig_map_device (reads threaded through the unitigs)
+ *   (addition: no equivalent in the reference)             kmc_unitig_transits / kmc_unitig_transits_device (read walks counted per link and per unitig)
  *   (addition: no equivalent in the reference)             kmc_correct / kmc_correct_device (substitution errors of reads repaired from the table)
  *   (addition: no equivalent in the reference)             kmc_trim / kmc_trim_device (reads trimmed and filtered by their solid k-mers)
  *   (addition: no equivalent in the reference)             kmc_normalize / kmc_normalize_device (read depth normalised: a per-read k-mer depth, deep reads sampled down)
@@ -523,6 +524,89 @@ int kmc_unitig_map(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, const u
                    uint64_t n_reads, uint64_t* place, uint32_t* read_stats, uint64_t* seg_offsets, uint32_t* segs,
                    uint64_t cap_segs, uint64_t* support, uint64_t cap_unitigs, uint64_t* n_segs, uint64_t* n_unitigs,
                    uint64_t* summary);
+
+/* ---- read walks counted per graph element: link support, transits through unitigs, repeat verdicts (additions, as above).
+ * Everything refers to the unitigs, the link records and the map result of one view and one range min_count..max_count; a
+ * call takes that range and a batch laid out as kmc_unitig_map takes it.  KMC_MODE_CONTIG only; every k, in a canonical or a
+ * forward ctx.
+ * CROSSING.  kmc_unitig_map's: segment i of read r with i > seg_offsets[r] is a crossing iff segs[i].start ==
+ *   segs[i-1].start + segs[i-1].len.  start is relative to the read, so the test alone is not enough across a read boundary:
+ *   the first segment of a read is never a crossing.  With uni_a = 2u + o_a of segment i-1 and uni_b = 2v + o_b of segment i,
+ *   the read leaves end a = 2u + 1 - o_a and enters end b = 2v + o_b.
+ * LINK SUPPORT.  link_support[n_links], uint64_t, indexed like link_to.  For record j of end e with target t = link_to[j] it
+ *   holds the number of crossings of the batch with (a, b) == (e, t), plus, if t != e, the number with (a, b) == (t, e): the
+ *   same link read on the other strand.  One end never has two records with the same target (distinct extension bases reach
+ *   distinct keys, hence distinct ends), so "the record e -> t" is well defined.  A crossing for which neither a -> b nor
+ *   b -> a is a record is counted in the summary and nowhere else; that happens only around palindromic keys (even k,
+ *   canonical).
+ * TRANSIT.  A segment i such that i and i + 1 are both crossings of the same read: the read entered unitig v from somewhere,
+ *   ran through it and left it.  o is the orientation bit of segment i; e_in = 2v + o, e_out = 2v + 1 - o; a is the end the
+ *   read came from (as above, for crossing i) and b' the end it enters next (for crossing i + 1).  p is the rank (0..3) of
+ *   the record e_in -> a among the records of e_in, q the rank of e_out -> b' among those of e_out.  If either record does not
+ *   exist the transit is dropped and counted in the summary.  Stored orientation-free: P is the rank at the START end 2v, Q
+ *   the rank at the END end 2v + 1: (P, Q) = (p, q) if o == 0, else (q, p).
+ * TRANSIT MATRIX.  dS(v) and dE(v) are the record counts of ends 2v and 2v + 1.  transit_offsets[n_unitigs + 1], uint64_t:
+ *   transit_offsets[0] == 0 and transit_offsets[v+1] - transit_offsets[v] == dS(v) * dE(v).  transit_count[n_slots], uint64_t:
+ *   slot transit_offsets[v] + P * dE(v) + Q holds the number of transits of the batch through v by that pair.  The layout is
+ *   dense per unitig, at most 16 slots, and zeros are stored; unitigs with a bare end have no slots.
+ * VERDICT.  verdict[n_unitigs], uint8_t, under the parameter min_reads (0 is taken as 1).  KMC_TRANSIT_PLAIN: dS < 2 or
+ *   dE < 2.  Every other unitig is a REPEAT, and a slot is supported iff its count is at least min_reads.
+ *   KMC_TRANSIT_UNSPANNED: no slot is supported.  KMC_TRANSIT_RESOLVED: every row and every column of the dS x dE matrix has
+ *   exactly one supported slot (so dS == dE and the supported slots are a perfect matching; slots below min_reads are noise
+ *   and are ignored).  KMC_TRANSIT_AMBIGUOUS: every other repeat.
+ * summary[KMC_TRANSIT_WORDS]: [0] crossings, [1] crossings with no record in either direction, [2] records with support 0,
+ *   [3] transits stored, [4] transits dropped for a missing record, [5] repeat unitigs, [6] RESOLVED, [7] AMBIGUOUS.  The
+ *   formulas are the definition.  [0] equals kmc_unitig_map's summary[4] for the same batch; the sum of transit_count equals
+ *   [3].  Where the record set is symmetric -- t -> e is a record whenever e -> t is: every forward ctx and every canonical
+ *   ctx of odd k; for even k a canonical set can be asymmetric even when the links summary[5] is 0, because a palindromic key
+ *   that is a unitig of its own lists a neighbour at both of its ends and is entered by it through one -- [1] == 0 and
+ *   [4] == 0, and the sum of link_support equals 2 * [0] - (crossings with a == b).
+ * KMC_TRANSIT_ACCUMULATE (flags bit 0).  Real inputs arrive in many batches.  With the flag the call adds onto the arrays the
+ *   ctx still holds from the last transits call of this very view and range: [0], [1], [3], [4] are totals, verdict and [2],
+ *   [5]..[7] are recomputed from the totals with this call's min_reads.  No such result held: KMC_ERR_STATE (the first batch
+ *   goes without the flag).  The held result is dropped by finalize, reset, destroy and by any call that recomputes the
+ *   unitigs or the links -- a kmc_graph* call in between makes the next transits call one of those.  A map, correct, trim,
+ *   normalize or profile call in between leaves it alone.
+ * RELATION TO THE OTHER VIEW CALLS.  A transits call counts as a kmc_unitig_links call: it reuses the unitigs and links the ctx
+ *   still holds for this view and range under the condition of a bubbles call, otherwise it computes them and keeps them.
+ *   After that it counts as a kmc_unitig_map_device call on the batch (map arrays handed out earlier are invalid); with no
+ *   read or no unitig there is nothing to map and it leaves them alone.  Links first, then map, then the transit passes.  It
+ *   rewrites none of: the unitig arrays, link_offsets / link_to, a clean, simplify, components or bubbles result, the view, a
+ *   partition, a filter or set-operation result, the query index.
+ * Rules: the argument and state errors of kmc_unitig_map (NULL ctx, KMC_MODE_LR, a non-zero max_count below min_count, a bad
+ *   batch: KMC_ERR_ARG; no view: KMC_ERR_STATE); unknown flag bits: KMC_ERR_ARG; the capacity rules of the map and links calls,
+ *   and 2^32 slots or more: KMC_ERR_CAPACITY.  An empty view gives transit_offsets[0] == 0 and zeros.  n_reads == 0 is legal:
+ *   it gives the sizes and the held (ACCUMULATE) or zeroed arrays and adds nothing.
+ * Diagnostic: with KMC_UNITIG_TRACE set, a call prints "kmc_unitig_transits: unitigs U records R reads N segments S crossings C
+ *   transits T links_reused 0|1 map_ms .. transit_ms .. verdict_ms .." to stderr, behind the lines of what it had to compute
+ *   (tools/measure_transits.py reads it).  KMC_TRANSITS_PLAIN in the environment makes every lane add its own 1 instead of
+ *   combining equal targets per wave -- a diagnostic for that tool, the result is the same. ---- */
+#define KMC_TRANSIT_WORDS 8
+#define KMC_TRANSIT_PLAIN 0
+#define KMC_TRANSIT_UNSPANNED 1
+#define KMC_TRANSIT_RESOLVED 2
+#define KMC_TRANSIT_AMBIGUOUS 3
+#define KMC_TRANSIT_ACCUMULATE 1u   /* flags bit 0 */
+/* The batch in device memory by the rules of kmc_unitig_map_device.  The results in ctx-owned device arrays -- uint64_t
+ * link_support[n_links], uint64_t transit_offsets[n_unitigs + 1], uint64_t transit_count[n_slots], uint8_t verdict[n_unitigs]
+ * -- valid until the next kmc_unitig_transits*, kmc_unitigs*, kmc_unitig_links* or kmc_graph* call that computes / finalize /
+ * reset / destroy (same ordering contract as kmc_export_device).  Every output pointer may be NULL. */
+int kmc_unitig_transits_device(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, uint64_t min_reads, uint32_t flags,
+                               const void* d_bases, const void* d_offsets, uint64_t n_reads, uint64_t n_bases,
+                               const void** d_link_support, const void** d_transit_offsets, const void** d_transit_count,
+                               const void** d_verdict, uint64_t* n_unitigs, uint64_t* n_links, uint64_t* n_slots,
+                               uint64_t* summary);
+/* The same on host buffers (the batch as kmc_unitig_map takes it).  link_support has cap_links entries, transit_offsets room
+ * for cap_unitigs + 1, transit_count cap_slots, and verdict shares cap_unitigs.  *n_unitigs, *n_links and *n_slots are always
+ * set; a cap too small for an array that was given -> KMC_ERR_ARG and nothing is copied; an array that is NULL is not copied
+ * and its cap not looked at.  All arrays NULL is the sizing call (kmc_unitig_links plus that call's *n_slots size them as
+ * well).  Like kmc_unitig_map's host form it computes on EVERY call: with KMC_TRANSIT_ACCUMULATE size with n_reads == 0, or the
+ * batch is added twice. */
+int kmc_unitig_transits(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, uint64_t min_reads, uint32_t flags,
+                        const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads, uint64_t* link_support,
+                        uint64_t cap_links, uint64_t* transit_offsets, uint64_t cap_unitigs, uint64_t* transit_count,
+                        uint64_t cap_slots, uint8_t* verdict, uint64_t* n_unitigs, uint64_t* n_links, uint64_t* n_slots,
+                        uint64_t* summary);
 
 /* ---- reads corrected against the table: substitution errors repaired from the solid keys (additions, as above).
  * KMC_MODE_CONTIG only; every k, in a canonical or a forward ctx.  Reads the sorted view of the last kmc_finalize (a view

@@ -97,6 +97,7 @@ ABI_SYMBOLS = [
     "kmc_unitig_components", "kmc_unitig_components_device", "kmc_unitig_components_into",
     "kmc_unitig_bubbles", "kmc_unitig_bubbles_device",
     "kmc_unitig_map", "kmc_unitig_map_device",
+    "kmc_unitig_transits", "kmc_unitig_transits_device",
     "kmc_correct", "kmc_correct_device",
     "kmc_trim", "kmc_trim_device",
     "kmc_normalize", "kmc_normalize_device",
@@ -123,6 +124,10 @@ BUBBLE_REVERSED = 4       # KMC_BUBBLE_REVERSED: bit 2 of word 6, the major arm 
 MAP_WORDS = 8        # KMC_MAP_WORDS: reads, valid windows, placed windows, segments, crossings, fully placed reads, unplaced reads, most segments
 MAP_READ_WORDS = 4   # KMC_MAP_READ_WORDS: a read's valid windows, placed windows, segments, crossings
 MAP_NONE = 0xFFFFFFFF  # KMC_MAP_NONE: the low half of the place word of a window that is not placed
+TRANSIT_WORDS = 8       # KMC_TRANSIT_WORDS: crossings, those without a record, unsupported records, transits stored / dropped, repeats, resolved, ambiguous
+TRANSIT_PLAIN, TRANSIT_UNSPANNED, TRANSIT_RESOLVED, TRANSIT_AMBIGUOUS = 0, 1, 2, 3   # KMC_TRANSIT_*: a unitig's verdict
+TRANSIT_VERDICT_NAMES = ("plain", "unspanned", "resolved", "ambiguous")
+TRANSIT_ACCUMULATE = 1  # KMC_TRANSIT_ACCUMULATE: flags bit 0, add onto the result the ctx holds
 CORRECT_WORDS = 8       # KMC_CORRECT_WORDS: reads, valid windows, weak windows, weak runs, candidates, corrected, ambiguous, weak windows left
 CORRECT_READ_WORDS = 4  # KMC_CORRECT_READ_WORDS: a read's valid windows, weak windows, candidates, corrected
 CORRECT_INTERIOR, CORRECT_HEAD, CORRECT_TAIL = 0, 1, 2   # KMC_CORRECT_*: a candidate's kind
@@ -222,6 +227,9 @@ def lib() -> C.CDLL:
         L.kmc_unitig_bubbles.argtypes = [vp, u64, u64, u64, vp, u64, pu64, pu64, vp]
     L.kmc_unitig_map_device.argtypes = [vp, u64, u64, vp, vp, u64, u64] + [C.POINTER(vp)] * 5 + [pu64, pu64, vp]
     L.kmc_unitig_map.argtypes = [vp, u64, u64, vp, vp, u64, vp, vp, vp, vp, u64, vp, u64, pu64, pu64, vp]
+    if "KMC_LIB_PATH" not in os.environ or hasattr(L, "kmc_unitig_transits"):   # (as for the bubbles calls above)
+        L.kmc_unitig_transits_device.argtypes = [vp, u64, u64, u64, u32, vp, vp, u64, u64] + [C.POINTER(vp)] * 4 + [pu64, pu64, pu64, vp]
+        L.kmc_unitig_transits.argtypes = [vp, u64, u64, u64, u32, vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, pu64, pu64, pu64, vp]
     L.kmc_correct_device.argtypes = [vp, u64, u64, vp, vp, u64, u64] + [C.POINTER(vp)] * 4 + [pu64, vp]
     L.kmc_correct.argtypes = [vp, u64, u64, vp, vp, u64, vp, vp, vp, vp, u64, pu64, vp]
     L.kmc_trim_device.argtypes = [vp, u64, u64, i32, u32, u64, u32, u64, vp, vp, u64, u64] + [C.POINTER(vp)] * 5 + [pu64, pu64, vp]
@@ -483,15 +491,23 @@ class Unitigs:
         return "".join(">%d LN:i:%d KC:i:%d CL:i:%d\n%s\n" % (i, len(s), int(self.abund[i]), int(self.flags[i]) & UNITIG_CIRCULAR, s)
                        for i, s in enumerate(self.strings()))
 
-    def to_gfa(self, links: "UnitigLinks", k: int) -> str:
+    def to_gfa(self, links: "UnitigLinks", k: int, transits: Optional["Transits"] = None) -> str:
         """GFA 1.0 as the CLI's --gfa prints it: ``H VN:Z:1.0``, one ``S INDEX SEQ LN:i:BASES KC:i:ABUND CL:i:0|1`` per
-        unitig, one ``L U +|- V +|- (k-1)M`` per record of ``links`` (KmerCounter.unitig_links of the same range), tab-separated."""
+        unitig, one ``L U +|- V +|- (k-1)M`` per record of ``links`` (KmerCounter.unitig_links of the same range), tab-separated.
+        With ``transits`` (KmerCounter.transits of the same range) every ``L`` line ends in ``RC:i:SUPPORT``, the reads that
+        walked the link."""
         if len(links.offsets) != 2 * len(self) + 1:
             raise ValueError("the links are not those of these unitigs")
+        if transits is not None and len(transits.link_support) != len(links):
+            raise ValueError("the transits are not those of these links")
         out = ["H\tVN:Z:1.0\n"]
         out += ["S\t%d\t%s\tLN:i:%d\tKC:i:%d\tCL:i:%d\n" % (i, s, len(s), int(self.abund[i]), int(self.flags[i]) & UNITIG_CIRCULAR)
                 for i, s in enumerate(self.strings())]
-        out += ["L\t%d\t%s\t%d\t%s\t%dM\n" % (u, o1, v, o2, k - 1) for u, o1, v, o2 in links.records()]
+        if transits is None:
+            out += ["L\t%d\t%s\t%d\t%s\t%dM\n" % (u, o1, v, o2, k - 1) for u, o1, v, o2 in links.records()]
+        else:
+            out += ["L\t%d\t%s\t%d\t%s\t%dM\tRC:i:%d\n" % (u, o1, v, o2, k - 1, int(n))
+                    for (u, o1, v, o2), n in zip(links.records(), transits.link_support)]
         return "".join(out)
 
 
@@ -615,6 +631,82 @@ class ReadMap:
             parts.append("%s%d:%d:%d" % ("<" if uni & 1 else ">", uni >> 1, pos, ln))
             end = start + ln
         return "".join(parts) or "*"
+
+
+_TRANSIT_FIELDS = ("crossings", "crossings_without_record", "records_unsupported", "transits", "transits_dropped", "repeats", "resolved", "ambiguous")
+
+
+@dataclass
+class TransitSummary:
+    """The eight words of kmc_unitig_transits: crossings, crossings with no link record in either direction, records with
+    support 0, transits stored, transits dropped for a missing record, repeat unitigs, RESOLVED ones, AMBIGUOUS ones."""
+    crossings: int
+    crossings_without_record: int
+    records_unsupported: int
+    transits: int
+    transits_dropped: int
+    repeats: int
+    resolved: int
+    ambiguous: int
+
+    @classmethod
+    def from_words(cls, words) -> "TransitSummary":
+        return cls(*[int(w) for w in words])
+
+    def words(self) -> list:
+        return [getattr(self, f) for f in _TRANSIT_FIELDS]
+
+    @property
+    def unspanned(self) -> int:
+        return self.repeats - self.resolved - self.ambiguous
+
+    def to_text(self) -> str:
+        """``NAME\tVALUE`` lines."""
+        return "\n".join("%s\t%d" % (f, getattr(self, f)) for f in _TRANSIT_FIELDS) + "\n"
+
+
+@dataclass
+class Transits:
+    """What KmerCounter.transits returns: ``link_support`` uint64[records] indexed like ``links.to``, ``transit_offsets``
+    uint64[n_unitigs + 1], ``transit_count`` uint64[slots] (unitig u: a dS x dE matrix, row P a record rank at its START
+    end, column Q one at its END end), ``verdict`` uint8[n_unitigs] (TRANSIT_PLAIN / UNSPANNED / RESOLVED / AMBIGUOUS),
+    ``summary``, and ``links``, the UnitigLinks they are indexed by."""
+    link_support: np.ndarray
+    transit_offsets: np.ndarray
+    transit_count: np.ndarray
+    verdict: np.ndarray
+    summary: TransitSummary
+    links: UnitigLinks
+
+    def __len__(self) -> int:
+        return len(self.verdict)
+
+    def degrees(self, u: int) -> Tuple[int, int]:
+        """(dS, dE): the records at the START and at the END end of unitig u"""
+        o = self.links.offsets
+        return int(o[2 * u + 1]) - int(o[2 * u]), int(o[2 * u + 2]) - int(o[2 * u + 1])
+
+    def matrix(self, u: int) -> np.ndarray:
+        """The dS x dE transit counts of unitig u (an array without entries if one of its ends is bare)."""
+        ds, de = self.degrees(u)
+        return self.transit_count[int(self.transit_offsets[u]):int(self.transit_offsets[u + 1])].reshape(ds, de)
+
+    def records(self):
+        """(end, to, support) per link record, in array order."""
+        o = self.links.offsets
+        for e in range(len(o) - 1):
+            for j in range(int(o[e]), int(o[e + 1])):
+                yield e, int(self.links.to[j]), int(self.link_support[j])
+
+    def to_text(self) -> str:
+        """What ``k-mer-count --transits`` prints: ``L END TO SUPPORT`` per record with support, then per repeat unitig
+        ``U UNITIG VERDICT DS DE`` and its non-zero slots ``T UNITIG P Q COUNT``, tab-separated, in array order."""
+        out = ["L\t%d\t%d\t%d\n" % r for r in self.records() if r[2]]
+        for u in np.flatnonzero(self.verdict != TRANSIT_PLAIN).tolist():
+            m = self.matrix(u)
+            out.append("U\t%d\t%s\t%d\t%d\n" % (u, TRANSIT_VERDICT_NAMES[int(self.verdict[u])], m.shape[0], m.shape[1]))
+            out += ["T\t%d\t%d\t%d\t%d\n" % (u, p, q, int(m[p, q])) for p in range(m.shape[0]) for q in range(m.shape[1]) if m[p, q]]
+        return "".join(out)
 
 
 _CORRECT_FIELDS = ("reads", "valid_windows", "weak_windows", "weak_runs", "candidates", "corrected", "ambiguous", "weak_windows_left")
@@ -1336,6 +1428,56 @@ class KmerCounter:
         return ReadMap(words(dp, 8 * n_bases).view(np.uint64), words(ds, 16 * n_reads).view(np.uint32).reshape(n_reads, MAP_READ_WORDS),
                        words(do, 8 * (n_reads + 1)).view(np.uint64), words(dg, 16 * ns).view(np.uint32).reshape(ns, 4),
                        words(du, 8 * nu).view(np.uint64), summary)
+
+    # -- read walks counted per link record and per unitig (of the sorted view; finalize() first) --
+    def transits_device(self, d_bases: int, d_offsets: int, n_reads: int, n_bases: int, min_count: int = 1, max_count: int = 0,
+                        min_reads: int = 1, accumulate: bool = False):
+        """(d_link_support, d_transit_offsets, d_transit_count, d_verdict, n_unitigs, n_links, n_slots, TransitSummary) of
+        kmc_unitig_transits_device for a batch in device memory (raw addresses, laid out as for map_reads_device): ctx-owned
+        device arrays of n_links uint64, n_unitigs + 1 uint64, n_slots uint64 and n_unitigs uint8.  ``accumulate`` adds onto
+        the result the ctx holds from the last transits call of this view and range."""
+        p = [C.c_void_p() for _ in range(4)]
+        nu, nl, nsl = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        w = (C.c_uint64 * TRANSIT_WORDS)()
+        self._chk(self._L.kmc_unitig_transits_device(self._h, int(min_count), int(max_count), int(min_reads), TRANSIT_ACCUMULATE if accumulate else 0,
+                                                     d_bases or None, d_offsets or None, int(n_reads), int(n_bases), *[C.byref(x) for x in p],
+                                                     C.byref(nu), C.byref(nl), C.byref(nsl), w))
+        return tuple(x.value or 0 for x in p) + (nu.value, nl.value, nsl.value, TransitSummary.from_words(list(w)))
+
+    def transits_tensors(self, bases, offsets, min_count: int = 1, max_count: int = 0, min_reads: int = 1, accumulate: bool = False):
+        """transits_device for torch tensors on this ctx's GPU (bases uint8[n_bases], padded as for add_batch_tensors;
+        offsets int64[n_reads + 1])."""
+        assert bases.is_cuda and offsets.is_cuda and bases.is_contiguous() and offsets.is_contiguous()
+        return self.transits_device(bases.data_ptr(), offsets.data_ptr(), max(offsets.numel() - 1, 0), bases.numel(), min_count, max_count,
+                                    min_reads, accumulate)
+
+    def transits(self, bases: np.ndarray, offsets: np.ndarray, min_count: int = 1, max_count: int = 0, min_reads: int = 1,
+                 accumulate: bool = False) -> "Transits":
+        """kmc_unitig_transits_device for a host batch (the batch is not counted): how many of its reads walk every link
+        record of unitig_links() with the same range, which way into a unitig goes with which way out, and a verdict per
+        repeat.  The batch goes to the device as tensors and the result arrays are read back from the ctx, so the library
+        computes once; the links it returns with them are the ones it counted on."""
+        import torch
+        from .distributed import device_view
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n_reads, n_bases = max(int(offsets.shape[0]) - 1, 0), int(bases.shape[0])
+        if n_reads and (int(offsets[0]) != 0 or int(offsets[-1]) != n_bases or (np.diff(offsets.astype(np.int64)) < 0).any()):
+            raise ValueError("offsets must start at 0, not decrease, and end at len(bases)")
+        if n_reads and int(np.diff(offsets.astype(np.int64)).max()) >= 1 << 32:
+            raise KmcError(ERR_ARG, "a read of 2^32 bases or more")
+        dev = torch.device("cuda", self.device)
+        d_bases = torch.zeros(n_bases + 64, dtype=torch.uint8, device=dev)   # (readable past the end, 16-byte aligned)
+        d_bases[:n_bases] = torch.from_numpy(bases.copy())
+        d_offs = torch.from_numpy(offsets.view(np.int64).copy()).to(dev)
+        torch.cuda.synchronize(dev)
+        ds, do, dc, dv, nu, nl, nsl, summary = self.transits_device(d_bases.data_ptr(), d_offs.data_ptr(), n_reads, n_bases, min_count, max_count,
+                                                                    min_reads, accumulate)
+
+        def words(ptr, n_bytes):
+            return device_view(ptr, (n_bytes + 7) // 8, dev).cpu().numpy().view(np.uint8)[:n_bytes].copy()
+        got = (words(ds, 8 * nl).view(np.uint64), words(do, 8 * (nu + 1)).view(np.uint64), words(dc, 8 * nsl).view(np.uint64), words(dv, nu))
+        return Transits(*got, summary, self.unitig_links(min_count, max_count))   # (the held links: copied, not computed)
 
     # -- reads corrected against the solid keys of the table (of the sorted view; finalize() first) --
     def correct_reads_device(self, d_bases: int, d_offsets: int, n_reads: int, n_bases: int, min_count: int = 2, max_count: int = 0):

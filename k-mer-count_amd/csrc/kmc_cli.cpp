@@ -6,6 +6,7 @@
 //
 //   k-mer-count [FASTA] [-k K] [--forward] [--expand] [--device N | --gpus N] [--algo auto|stream|walk|sort] [--stats]
 //               [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE | --map FILE | --correct FILE]
+//               [--transits FILE [--min-reads N]]
 //               [--trim FILE [--trim-mode none|ends|longest] [--min-strong N] [--strong-permille N] [--min-len N] [--invert]
 //                [--paired both|either]]
 //               [--normalize FILE --target N [--depth-permille P] [--min-depth N] [--seed S] [--norm-paired] [--norm-invert]]
@@ -37,6 +38,15 @@
 //               "<U:POS:LEN" (against it).  A segment that starts at the window right behind its predecessor -- the read crossed
 //               from one unitig end to another -- is written directly behind it, one behind a gap after a ","; "*" for a read
 //               with no segment.  With --clean the reads are laid on the cleaned graph.
+//   --transits FILE      (with -k K) instead of the table: the walks of the reads of FILE (FASTA / FASTQ) through the unitig graph of
+//               the counted input, counted per graph element (kmc_unitig_transits; --min-count / --max-count are the solidity
+//               range).  First "L<TAB>END<TAB>TO<TAB>SUPPORT" per link record that a read walked, in array order: the unitig end
+//               2 * U + (0 START | 1 END) it leaves, the end it reaches, the reads that stepped across in either direction.
+//               Then per unitig with two or more links at both ends "U<TAB>UNITIG<TAB>VERDICT<TAB>DS<TAB>DE" -- unspanned, resolved
+//               or ambiguous under --min-reads N (default 1: the reads a way through must have to count), the links at its START
+//               and END end -- followed by "T<TAB>UNITIG<TAB>P<TAB>Q<TAB>COUNT" per pair of the P-th START link and the Q-th END
+//               link that COUNT reads took through it.  It excludes what --map excludes, and --map; with --clean the reads
+//               walk the cleaned graph.
 //   --correct FILE       (with -k K) instead of the table: every read of FILE (FASTA / FASTQ) corrected against the solid keys of
 //               the counted input (kmc_correct; --min-count / --max-count are the solidity range), as FASTA in file order:
 //               ">INDEX WINDOWS WEAK CANDIDATES FIXED" -- its valid K-mer windows, how many of them are not solid, the weak
@@ -161,6 +171,8 @@ int main(int argc, char** argv) {
     long long min_count = 1, max_count = 0;   // (max_count 0: no upper bound)
     const char *query_path = nullptr, *profile_path = nullptr, *with_path = nullptr, *map_path = nullptr, *correct_path = nullptr;
     const char* trim_path = nullptr;
+    const char* transits_path = nullptr;
+    long long min_reads = -1;   // (-1: not given)
     int trim_mode = -1, trim_invert = 0, trim_pair = 0;   // (-1: the default mode, longest)
     long long min_strong = -1, strong_permille = -1, min_len = -1;   // (-1: not given)
     const char* norm_path = nullptr;
@@ -187,6 +199,8 @@ int main(int argc, char** argv) {
         else if (a == "--profile" && i + 1 < argc) profile_path = argv[++i];
         else if (a == "--map" && i + 1 < argc) map_path = argv[++i];
         else if (a == "--correct" && i + 1 < argc) correct_path = argv[++i];
+        else if (a == "--transits" && i + 1 < argc) transits_path = argv[++i];
+        else if (a == "--min-reads" && i + 1 < argc) { if (!parse_count("--min-reads", argv[++i], 0, LLONG_MAX, &min_reads)) return 2; }
         else if (a == "--trim" && i + 1 < argc) trim_path = argv[++i];
         else if (a == "--trim-mode" && i + 1 < argc) {
             std::string v = argv[++i];
@@ -238,6 +252,7 @@ int main(int argc, char** argv) {
         } else if (a == "-h" || a == "--help") {
             fprintf(stderr, "usage: k-mer-count [FASTA] [-k K] [--forward] [--expand] [--device N | --gpus N] [--algo auto|stream|walk|sort] [--stats]\n"
                             "                   [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE | --map FILE | --correct FILE]\n"
+                            "                   [--transits FILE [--min-reads N]]\n"
                             "                   [--trim FILE [--trim-mode none|ends|longest] [--min-strong N] [--strong-permille N] [--min-len N] [--invert]\n"
                             "                    [--paired both|either]]\n"
                             "                   [--normalize FILE --target N [--depth-permille P] [--min-depth N] [--seed S] [--norm-paired] [--norm-invert]]\n"
@@ -249,7 +264,8 @@ int main(int argc, char** argv) {
                    a == "--query-kmers" || a == "--profile" || a == "--map" || a == "--correct" || a == "--with" || a == "--setop" || a == "--counts" ||
                    a == "--clean" || a == "--tip-keys" || a == "--island-keys" || a == "--bubble-keys" || a == "--component-keys" || a == "--trim" ||
                    a == "--trim-mode" || a == "--min-strong" || a == "--strong-permille" || a == "--min-len" || a == "--paired" ||
-                   a == "--normalize" || a == "--target" || a == "--depth-permille" || a == "--min-depth" || a == "--seed") {
+                   a == "--normalize" || a == "--target" || a == "--depth-permille" || a == "--min-depth" || a == "--seed" || a == "--transits" ||
+                   a == "--min-reads") {
             fprintf(stderr, "k-mer-count: %s needs a value\n", a.c_str());
             return 2;
         } else if (!a.empty() && a[0] != '-') path = argv[i];
@@ -280,6 +296,22 @@ int main(int argc, char** argv) {
         else if (graph || graph_stats || unitigs || gfa) bad = "--graph / --graph-stats / --unitigs / --gfa exclude each other";
         else if (expand) bad = "--expand exclude each other";
         if (bad) { fprintf(stderr, "k-mer-count: --map %s%s\n", strncmp(bad, "needs", 5) ? "and " : "", bad); return 2; }
+    }
+    // --transits and its option: the same again
+    if (transits_path) {
+        const char* bad = nullptr;
+        if (!k) bad = "needs -k K";
+        else if (map_path || correct_path || trim_path || norm_path) bad = "--map / --correct / --trim / --normalize exclude each other";
+        else if (query_path || profile_path) bad = "--query-kmers / --profile exclude each other";
+        else if (histo) bad = "--histo exclude each other";
+        else if (with_path || compare || setop >= 0) bad = "--with / --compare / --setop exclude each other";
+        else if (graph || graph_stats || unitigs || gfa || components || variants)
+            bad = "--graph / --graph-stats / --unitigs / --gfa / --components / --variants exclude each other";
+        else if (expand) bad = "--expand exclude each other";
+        if (bad) { fprintf(stderr, "k-mer-count: --transits %s%s\n", strncmp(bad, "needs", 5) ? "and " : "", bad); return 2; }
+    } else if (min_reads >= 0) {
+        fprintf(stderr, "k-mer-count: --min-reads needs --transits FILE\n");
+        return 2;
     }
     // --correct: the same again
     if (correct_path) {
@@ -350,8 +382,8 @@ int main(int argc, char** argv) {
         }
         fclose(f);
     }
-    if (profile_path || map_path || correct_path || trim_path || norm_path) {
-        const char* reads_path = profile_path ? profile_path : map_path ? map_path : correct_path ? correct_path : trim_path ? trim_path : norm_path;
+    if (profile_path || map_path || correct_path || trim_path || norm_path || transits_path) {
+        const char* reads_path = profile_path ? profile_path : map_path ? map_path : correct_path ? correct_path : trim_path ? trim_path : norm_path ? norm_path : transits_path;
         char eb[256] = {0};
         const int prc = kmc_parse_fasta(reads_path, &prof, eb, sizeof(eb));
         if (prc) return die(reads_path, eb[0] ? eb : kmc_status_string(prc));
@@ -399,8 +431,8 @@ int main(int argc, char** argv) {
         if (!k) bad = "needs -k K";
         else if (graph || graph_stats || unitigs || gfa) bad = "--graph / --graph-stats / --unitigs / --gfa exclude each other";
         else if (histo) bad = "--histo exclude each other";
-        else if (query_path || profile_path || map_path || correct_path || trim_path || norm_path)
-            bad = "--query-kmers / --profile / --map / --correct / --trim / --normalize exclude each other";
+        else if (query_path || profile_path || map_path || correct_path || trim_path || norm_path || transits_path)
+            bad = "--query-kmers / --profile / --map / --correct / --trim / --normalize / --transits exclude each other";
         else if (with_path || compare || setop >= 0) bad = "--with / --compare / --setop exclude each other";
         else if (expand) bad = "--expand exclude each other";
         if (bad) { fprintf(stderr, "k-mer-count: --components %s%s\n", strncmp(bad, "needs", 5) ? "and " : "", bad); return 2; }
@@ -411,8 +443,8 @@ int main(int argc, char** argv) {
         if (!k) bad = "needs -k K";
         else if (graph || graph_stats || unitigs || gfa || components) bad = "--graph / --graph-stats / --unitigs / --gfa / --components exclude each other";
         else if (histo) bad = "--histo exclude each other";
-        else if (query_path || profile_path || map_path || correct_path || trim_path || norm_path)
-            bad = "--query-kmers / --profile / --map / --correct / --trim / --normalize exclude each other";
+        else if (query_path || profile_path || map_path || correct_path || trim_path || norm_path || transits_path)
+            bad = "--query-kmers / --profile / --map / --correct / --trim / --normalize / --transits exclude each other";
         else if (with_path || compare || setop >= 0) bad = "--with / --compare / --setop exclude each other";
         else if (expand) bad = "--expand exclude each other";
         if (bad) { fprintf(stderr, "k-mer-count: --variants %s%s\n", strncmp(bad, "needs", 5) ? "and " : "", bad); return 2; }
@@ -608,6 +640,39 @@ int main(int argc, char** argv) {
             }
             if (so[r] == so[r + 1]) fputc('*', stdout);
             fputc('\n', stdout);
+        }
+        fflush(stdout);
+        destroy_all();
+        return 0;
+    }
+    if (transits_path) {
+        // sized from the links (a unitig's slots are at most four times the records of one of its ends): the batch is walked once
+        const uint64_t n_tr = prof.n_reads, lo_c = (uint64_t)min_count, hi_c = (uint64_t)max_count;
+        uint64_t nu = 0, nl = 0, nsl = 0;
+        rc = kmc_unitig_links(ctx, lo_c, hi_c, nullptr, 0, nullptr, 0, &nu, &nl, nullptr);
+        std::vector<uint64_t> lo_((size_t)2 * nu + 1), sup((size_t)nl + 1), to_((size_t)nu + 1), cnt((size_t)std::min<uint64_t>(16 * nu, 4 * nl) + 1);
+        std::vector<uint32_t> lt((size_t)nl + 1);
+        std::vector<uint8_t> vd((size_t)nu + 1);
+        if (!rc) rc = kmc_unitig_links(ctx, lo_c, hi_c, lo_.data(), 2 * nu, lt.data(), nl, &nu, &nl, nullptr);
+        if (rc) { kmc_free_reads(&prof); int r = die("kmc_unitig_links", kmc_last_error(ctx)); destroy_all(); return r; }
+        rc = kmc_unitig_transits(ctx, lo_c, hi_c, min_reads < 0 ? 1 : (uint64_t)min_reads, 0, prof.bases, prof.offsets, n_tr, sup.data(), nl, to_.data(), nu,
+                                 cnt.data(), cnt.size() - 1, vd.data(), &nu, &nl, &nsl, nullptr);
+        kmc_free_reads(&prof);
+        if (rc) { int r = die("kmc_unitig_transits", kmc_last_error(ctx)); destroy_all(); return r; }
+        static const char* const verdict_name[4] = {"plain", "unspanned", "resolved", "ambiguous"};
+        setvbuf(stdout, obuf.data(), _IOFBF, obuf.size());
+        for (uint64_t e = 0; e < 2 * nu; ++e)
+            for (uint64_t j = lo_[e]; j < lo_[e + 1] && j < nl; ++j)
+                if (sup[j]) printf("L\t%llu\t%u\t%llu\n", (unsigned long long)e, lt[j], (unsigned long long)sup[j]);
+        for (uint64_t u = 0; u < nu; ++u) {
+            if (vd[u] == KMC_TRANSIT_PLAIN) continue;
+            const uint64_t ds = lo_[2 * u + 1] - lo_[2 * u], de = lo_[2 * u + 2] - lo_[2 * u + 1];
+            printf("U\t%llu\t%s\t%llu\t%llu\n", (unsigned long long)u, verdict_name[vd[u] & 3], (unsigned long long)ds, (unsigned long long)de);
+            for (uint64_t p = 0; p < ds; ++p)
+                for (uint64_t q = 0; q < de; ++q) {
+                    const uint64_t at = to_[u] + p * de + q;
+                    if (at < nsl && cnt[at]) printf("T\t%llu\t%llu\t%llu\t%llu\n", (unsigned long long)u, (unsigned long long)p, (unsigned long long)q, (unsigned long long)cnt[at]);
+                }
         }
         fflush(stdout);
         destroy_all();

@@ -283,6 +283,14 @@ struct kmc_ctx : CtxStream {
     DevBuf bb_rec, bb_flag, bb_pos, bb_major, bb_ctl;
     ResultKey bb_key;
     u64 bb_limit = 0, bb_records = 0, bb_words[8] = {};
+    // kmc_unitig_transits* (kmc_transits.hip.h) read the links and the segments of a map call.  Their result, in buffers of
+    // their own (a map, correct, trim, normalize or profile call leaves them alone, and KMC_TRANSIT_ACCUMULATE adds onto
+    // them): support per link record, the slot offsets per unitig, the slots, the verdict per unitig, with tx_key and
+    // tx_words as above and tx_slots slots.  Whatever drops l_key drops tx_key.  Work arrays: the slots per unitig and
+    // their scan, the first-segment byte per segment of the batch, the control words.
+    DevBuf tx_sup, tx_offs, tx_count, tx_verdict, tx_cnt, tx_pos, tx_first, tx_ctl;
+    ResultKey tx_key;
+    u64 tx_slots = 0, tx_words[8] = {};
 };
 
 #pragma GCC visibility push(hidden)   // what follows is shared between the translation units, never exported

@@ -17,6 +17,7 @@
 #include "kmc_components.hip.h"
 #include "kmc_bubbles.hip.h"
 #include "kmc_map.hip.h"
+#include "kmc_transits.hip.h"
 #include "kmc_correct.hip.h"
 #include "kmc_trim.hip.h"
 #include "kmc_normalize.hip.h"
@@ -721,7 +722,7 @@ static int unitig_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count
     memset(h, 0, KMC_UNITIG_WORDS * sizeof(u64));
     const u64 n = c->n_sorted, n2 = 2 * n;
     int rc;
-    c->u_key.drop(); c->l_key.drop(); c->cc_key.drop(); c->bb_key.drop();   // the result arrays are rewritten from here on (and the links of the old ones, their components and their bubbles go with them)
+    c->u_key.drop(); c->l_key.drop(); c->cc_key.drop(); c->bb_key.drop(); c->tx_key.drop();   // the result arrays are rewritten from here on (and the links of the old ones, their components, their bubbles and their transit counts go with them)
     if ((rc = ensure(c, c->u_offs, sizeof(u64))) || (rc = ensure(c, c->u_bases, 64)) || (rc = ensure(c, c->u_abund, sizeof(u64))) ||
         (rc = ensure(c, c->u_flags, 8)))
         return rc;
@@ -904,7 +905,7 @@ static int links_run(kmc_ctx* c, const char* what, u64* h) {
     memset(h, 0, KMC_LINK_WORDS * sizeof(u64));
     const u64 n = c->n_sorted, nu = c->u_words[0], ne = 2 * nu;
     int rc;
-    c->l_key.drop(); c->cc_key.drop(); c->bb_key.drop();
+    c->l_key.drop(); c->cc_key.drop(); c->bb_key.drop(); c->tx_key.drop();
     if ((rc = ensure(c, c->l_offs, (size_t)(ne + 1) * sizeof(u64))) || (rc = ensure(c, c->l_to, sizeof(u32)))) return rc;
     if (!nu) {   // an empty view, or one without a solid key
         HIPCHK(c, hipMemsetAsync(c->l_offs.p, 0, sizeof(u64), c->stream));
@@ -1177,6 +1178,184 @@ static int kmc_unitig_map_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_coun
     if (support && nu) HIPCHK(c, hipMemcpyAsync(support, c->m_support.p, (size_t)nu * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (summary) memcpy(summary, h, sizeof(h));
+    return KMC_OK;
+}
+
+// ---- read walks counted per link record and per unitig: support, transit matrices, verdicts (kmc_transits.hip.h) ----
+// KMC_TRANSITS_PLAIN in the environment makes every lane of the transit kernel add its own 1 instead of combining equal
+// targets per wave -- a diagnostic for tools/measure_transits.py, the result is the same.
+static int transits_flags(kmc_ctx* c, const char* what, uint32_t flags) {
+    if (flags & ~(uint32_t)KMC_TRANSIT_ACCUMULATE) return fail(c, KMC_ERR_ARG, "%s: unknown flag bits 0x%x", what, flags & ~(uint32_t)KMC_TRANSIT_ACCUMULATE);
+    return KMC_OK;
+}
+
+// The batch (device arrays) walked through the unitigs and links of this view and range -- those the ctx holds under
+// bubbles_run's condition, otherwise computed and kept -- into the tx_* buffers, the summary into tx_words; finished when it
+// returns.  Links first, then the map passes, then the transit passes: a links call that computes may not run behind the map
+// passes whose ids it would renumber.  It shares the block sums of a scan (c_bsum) with the other passes and, through
+// map_run, the map buffers; it writes nothing else of theirs.
+static int transits_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count, u64 min_reads, bool accumulate, const uint8_t* d_bases,
+                        const u64* d_offsets, u64 n_reads, u64 n_bases) {
+    int rc;
+    u64 lw[KMC_LINK_WORDS];
+    const bool held = c->u_live && c->u_key.holds(c->view_gen, min_count, max_count);
+    const bool links_reused = held && c->l_key.holds(c->view_gen, min_count, max_count);
+    if (accumulate && !(links_reused && c->tx_key.holds(c->view_gen, min_count, max_count)))
+        return fail(c, KMC_ERR_STATE, "%s: KMC_TRANSIT_ACCUMULATE, and the ctx holds no transits of this view and range to add to", what);
+    if ((rc = links_result(c, what, min_count, max_count, held, lw))) return rc;
+    const u64 n = c->n_sorted, nu = lw[0], nl = lw[1];
+    if (nu > n || c->u_words[0] != nu)
+        return fail(c, KMC_ERR_HIP, "internal error: %s holds %llu unitigs, its links %llu", what, (unsigned long long)c->u_words[0], (unsigned long long)nu);
+    TransitGraph g;
+    g.link_offsets = (const u64*)c->l_offs.p; g.link_to = (const u32*)c->l_to.p; g.n_unitigs = nu; g.n_links = nl;
+    const u32 grid_u = (u32)((nu + KMC_T_THREADS - 1) / KMC_T_THREADS);
+    if ((rc = ensure(c, c->tx_ctl, KMC_T_CTL_WORDS * sizeof(u64)))) return rc;
+    kmc_ull* ctl = (kmc_ull*)c->tx_ctl.p;
+    u64 w[KMC_T_CTL_WORDS] = {0};
+    HIPCHK(c, hipMemsetAsync(ctl, 0, KMC_T_CTL_WORDS * sizeof(u64), c->stream));
+    if (!accumulate) {
+        // the layout: it depends on the links alone
+        c->tx_key.drop();
+        const size_t lb = (size_t)std::max<u64>(nl, 1) * sizeof(u64);
+        if ((rc = ensure(c, c->tx_sup, lb)) || (rc = ensure(c, c->tx_offs, (size_t)(nu + 1) * sizeof(u64))) ||
+            (rc = ensure(c, c->tx_verdict, (size_t)std::max<u64>(nu, 1))) || (rc = ensure(c, c->tx_count, sizeof(u64))))
+            return rc;
+        u64 n_slots = 0;
+        if (nu) {
+            const size_t ub = (size_t)nu * sizeof(u32);
+            if ((rc = ensure(c, c->tx_cnt, ub)) || (rc = ensure(c, c->tx_pos, ub)) ||
+                (rc = ensure(c, c->c_bsum, (size_t)((nu + KMC_SCAN_PER_BLOCK - 1) / KMC_SCAN_PER_BLOCK + 2) * sizeof(u32))))
+                return rc;
+            hipLaunchKernelGGL(kmc_transit_layout_kernel, dim3(grid_u), dim3(KMC_T_THREADS), 0, c->stream, g, (u32*)c->tx_cnt.p, ctl);
+            launch_exclusive_scan<0>(c->stream, c->tx_cnt.p, (u32)nu, (u32*)c->c_bsum.p, (u32*)c->tx_pos.p, (u32*)(ctl + KMC_T_SCAN));
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipMemcpyAsync(w, ctl, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (w[KMC_T_BAD]) return fail(c, KMC_ERR_HIP, "internal error: %s met %llu ends whose records lie outside their array", what, (unsigned long long)w[KMC_T_BAD]);
+            n_slots = w[KMC_T_SLOTS];
+            if (n_slots >= (1ull << 32)) return fail(c, KMC_ERR_CAPACITY, "%s: 2^32 transit slots or more", what);
+            if ((w[KMC_T_SCAN] & 0xFFFFFFFFull) != n_slots)
+                return fail(c, KMC_ERR_HIP, "internal error: %s scanned %llu of %llu slots", what, (unsigned long long)(w[KMC_T_SCAN] & 0xFFFFFFFFull), (unsigned long long)n_slots);
+            if ((rc = ensure(c, c->tx_count, (size_t)std::max<u64>(n_slots, 1) * sizeof(u64)))) return rc;
+            hipLaunchKernelGGL(kmc_transit_offsets_kernel, dim3(grid_u), dim3(KMC_T_THREADS), 0, c->stream, (const u32*)c->tx_pos.p, nu, n_slots, (u64*)c->tx_offs.p);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipMemsetAsync(ctl, 0, KMC_T_CTL_WORDS * sizeof(u64), c->stream));
+        } else {
+            HIPCHK(c, hipMemsetAsync(c->tx_offs.p, 0, sizeof(u64), c->stream));
+        }
+        HIPCHK(c, hipMemsetAsync(c->tx_sup.p, 0, lb, c->stream));
+        HIPCHK(c, hipMemsetAsync(c->tx_count.p, 0, (size_t)std::max<u64>(n_slots, 1) * sizeof(u64), c->stream));
+        c->tx_slots = n_slots;
+        memset(c->tx_words, 0, sizeof(c->tx_words));
+    }
+    const u64 n_slots = c->tx_slots;
+    UnitigTrace tr;
+    tr.mark(c->stream);
+    // the map passes: they find the unitigs held, so they renumber nothing (tx_ctl is not theirs)
+    u64 mh[KMC_MAP_WORDS] = {0}, ns = 0, mu = nu;
+    if (n_reads && nu) {
+        if ((rc = map_run(c, what, min_count, max_count, d_bases, d_offsets, n_reads, n_bases, mh, &ns, &mu))) return rc;
+        if (mu != nu || !c->l_key.holds(c->view_gen, min_count, max_count))
+            return fail(c, KMC_ERR_HIP, "internal error: %s mapped onto %llu unitigs, its links know %llu", what, (unsigned long long)mu, (unsigned long long)nu);
+    }
+    tr.mark(c->stream);
+    if (ns) {
+        if ((rc = ensure(c, c->tx_first, (size_t)ns))) return rc;
+        HIPCHK(c, hipMemsetAsync(c->tx_first.p, 0, (size_t)ns, c->stream));
+        hipLaunchKernelGGL(kmc_transit_first_kernel, dim3((u32)((n_reads + KMC_T_THREADS - 1) / KMC_T_THREADS)), dim3(KMC_T_THREADS), 0, c->stream,
+                           (const u64*)c->m_soffs.p, n_reads, ns, (uint8_t*)c->tx_first.p, ctl);
+        const u32 grid = (u32)grid_for(c, ns, KMC_T_THREADS);
+        auto go = [&](auto COMBINE) {
+            hipLaunchKernelGGL(kmc_transit_kernel<COMBINE()>, dim3(grid), dim3(KMC_T_THREADS), 0, c->stream, g, (const uint4*)c->m_segs.p,
+                               (const uint8_t*)c->tx_first.p, ns, (const u64*)c->tx_offs.p, n_slots, (kmc_ull*)c->tx_sup.p, (kmc_ull*)c->tx_count.p, ctl);
+        };
+        if (getenv("KMC_TRANSITS_PLAIN") == nullptr) go(std::true_type{}); else go(std::false_type{});
+        HIPCHK(c, hipGetLastError());
+    }
+    tr.mark(c->stream);
+    const u64 nx = std::max(nu, nl);
+    if (nx) {
+        hipLaunchKernelGGL(kmc_transit_verdict_kernel, dim3((u32)((nx + KMC_T_THREADS - 1) / KMC_T_THREADS)), dim3(KMC_T_THREADS), 0, c->stream, g,
+                           (const u64*)c->tx_offs.p, n_slots, (const kmc_ull*)c->tx_sup.p, (const kmc_ull*)c->tx_count.p, std::max<u64>(min_reads, 1),
+                           (uint8_t*)c->tx_verdict.p, ctl);
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipMemcpyAsync(w, ctl, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    tr.mark(c->stream);
+    if (w[KMC_T_BAD] || w[KMC_T_CROSS] != mh[4]) {
+        c->tx_key.drop();   // the arrays may hold a part of this batch
+        return fail(c, KMC_ERR_HIP, "internal error: %s met %llu indices outside their arrays (%llu crossings, the map pass %llu)", what,
+                    (unsigned long long)w[KMC_T_BAD], (unsigned long long)w[KMC_T_CROSS], (unsigned long long)mh[4]);
+    }
+    u64* s = c->tx_words;
+    s[0] += w[KMC_T_CROSS]; s[1] += w[KMC_T_ORPHAN]; s[3] += w[KMC_T_STORED]; s[4] += w[KMC_T_DROPPED];
+    s[2] = w[KMC_T_ZERO]; s[5] = w[KMC_T_REPEAT]; s[6] = w[KMC_T_RESOLVED]; s[7] = w[KMC_T_AMBIG];
+    c->tx_key.keep(c->view_gen, min_count, max_count);
+    if (tr.on && tr.n_ev == 4) {
+        float ms[3] = {0, 0, 0};
+        bool ok = hipEventSynchronize(tr.ev[3]) == hipSuccess;
+        for (int i = 0; ok && i < 3; ++i) ok = hipEventElapsedTime(&ms[i], tr.ev[i], tr.ev[i + 1]) == hipSuccess;
+        if (ok)
+            fprintf(stderr, "kmc_unitig_transits: unitigs %llu records %llu reads %llu segments %llu crossings %llu transits %llu links_reused %d "
+                    "map_ms %.4f transit_ms %.4f verdict_ms %.4f\n", (unsigned long long)nu, (unsigned long long)nl, (unsigned long long)n_reads,
+                    (unsigned long long)ns, (unsigned long long)w[KMC_T_CROSS], (unsigned long long)w[KMC_T_STORED], links_reused ? 1 : 0, ms[0], ms[1], ms[2]);
+    }
+    return KMC_OK;
+}
+
+static int kmc_unitig_transits_device_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t min_reads, uint32_t flags,
+                                           const void* d_bases, const void* d_offsets, uint64_t n_reads, uint64_t n_bases,
+                                           const void** d_link_support, const void** d_transit_offsets, const void** d_transit_count,
+                                           const void** d_verdict, uint64_t* n_unitigs, uint64_t* n_links, uint64_t* n_slots, uint64_t* summary) {
+    if (!c) return KMC_ERR_ARG;
+    const char* what = "kmc_unitig_transits_device";
+    int rc;
+    if ((rc = map_begin(c, what, min_count, max_count)) || (rc = transits_flags(c, what, flags))) return rc;
+    if (n_reads && (rc = check_device_batch(c, what, d_bases, d_offsets))) return rc;
+    if ((rc = transits_run(c, what, min_count, max_count, min_reads, (flags & KMC_TRANSIT_ACCUMULATE) != 0, (const uint8_t*)d_bases,
+                           (const u64*)d_offsets, n_reads, n_reads ? n_bases : 0)))
+        return rc;
+    if (d_link_support) *d_link_support = c->tx_sup.p;
+    if (d_transit_offsets) *d_transit_offsets = c->tx_offs.p;
+    if (d_transit_count) *d_transit_count = c->tx_count.p;
+    if (d_verdict) *d_verdict = c->tx_verdict.p;
+    if (n_unitigs) *n_unitigs = c->l_words[0];
+    if (n_links) *n_links = c->l_words[1];
+    if (n_slots) *n_slots = c->tx_slots;
+    if (summary) memcpy(summary, c->tx_words, sizeof(c->tx_words));
+    return KMC_OK;
+}
+
+static int kmc_unitig_transits_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t min_reads, uint32_t flags, const uint8_t* bases,
+                                    const uint64_t* offsets, uint64_t n_reads, uint64_t* link_support, uint64_t cap_links,
+                                    uint64_t* transit_offsets, uint64_t cap_unitigs, uint64_t* transit_count, uint64_t cap_slots, uint8_t* verdict,
+                                    uint64_t* n_unitigs, uint64_t* n_links, uint64_t* n_slots, uint64_t* summary) {
+    if (n_unitigs) *n_unitigs = 0;
+    if (n_links) *n_links = 0;
+    if (n_slots) *n_slots = 0;
+    if (!c) return KMC_ERR_ARG;
+    const char* what = "kmc_unitig_transits";
+    int rc;
+    if ((rc = map_begin(c, what, min_count, max_count)) || (rc = transits_flags(c, what, flags))) return rc;
+    u64 n_bases = 0;
+    if (n_reads && (rc = stage_batch(c, what, bases, offsets, n_reads, true, &n_bases))) return rc;
+    if ((rc = transits_run(c, what, min_count, max_count, min_reads, (flags & KMC_TRANSIT_ACCUMULATE) != 0, (const uint8_t*)c->q_bases.p,
+                           (const u64*)c->q_offs.p, n_reads, n_bases)))
+        return rc;
+    const u64 nu = c->l_words[0], nl = c->l_words[1], nsl = c->tx_slots;
+    if (n_unitigs) *n_unitigs = nu;
+    if (n_links) *n_links = nl;
+    if (n_slots) *n_slots = nsl;
+    if (link_support && cap_links < nl) return fail(c, KMC_ERR_ARG, "%s: capacity %llu < %llu records", what, (unsigned long long)cap_links, (unsigned long long)nl);
+    if ((transit_offsets || verdict) && cap_unitigs < nu) return fail(c, KMC_ERR_ARG, "%s: capacity %llu < %llu unitigs", what, (unsigned long long)cap_unitigs, (unsigned long long)nu);
+    if (transit_count && cap_slots < nsl) return fail(c, KMC_ERR_ARG, "%s: capacity %llu < %llu slots", what, (unsigned long long)cap_slots, (unsigned long long)nsl);
+    if (link_support && nl) HIPCHK(c, hipMemcpyAsync(link_support, c->tx_sup.p, (size_t)nl * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    if (transit_offsets) HIPCHK(c, hipMemcpyAsync(transit_offsets, c->tx_offs.p, (size_t)(nu + 1) * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    if (transit_count && nsl) HIPCHK(c, hipMemcpyAsync(transit_count, c->tx_count.p, (size_t)nsl * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    if (verdict && nu) HIPCHK(c, hipMemcpyAsync(verdict, c->tx_verdict.p, (size_t)nu, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (summary) memcpy(summary, c->tx_words, sizeof(c->tx_words));
     return KMC_OK;
 }
 
@@ -2227,6 +2406,24 @@ extern "C" int kmc_unitig_map(kmc_ctx* c, uint64_t min_count, uint64_t max_count
     return guarded(c, [&]() -> int {
         return kmc_unitig_map_impl(c, min_count, max_count, bases, offsets, n_reads, place, read_stats, seg_offsets, segs, cap_segs, support,
                                    cap_unitigs, n_segs, n_unitigs, summary);
+    });
+}
+extern "C" int kmc_unitig_transits_device(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t min_reads, uint32_t flags, const void* d_bases,
+                                          const void* d_offsets, uint64_t n_reads, uint64_t n_bases, const void** d_link_support,
+                                          const void** d_transit_offsets, const void** d_transit_count, const void** d_verdict, uint64_t* n_unitigs,
+                                          uint64_t* n_links, uint64_t* n_slots, uint64_t* summary) {
+    return guarded(c, [&]() -> int {
+        return kmc_unitig_transits_device_impl(c, min_count, max_count, min_reads, flags, d_bases, d_offsets, n_reads, n_bases, d_link_support,
+                                               d_transit_offsets, d_transit_count, d_verdict, n_unitigs, n_links, n_slots, summary);
+    });
+}
+extern "C" int kmc_unitig_transits(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t min_reads, uint32_t flags, const uint8_t* bases,
+                                   const uint64_t* offsets, uint64_t n_reads, uint64_t* link_support, uint64_t cap_links, uint64_t* transit_offsets,
+                                   uint64_t cap_unitigs, uint64_t* transit_count, uint64_t cap_slots, uint8_t* verdict, uint64_t* n_unitigs,
+                                   uint64_t* n_links, uint64_t* n_slots, uint64_t* summary) {
+    return guarded(c, [&]() -> int {
+        return kmc_unitig_transits_impl(c, min_count, max_count, min_reads, flags, bases, offsets, n_reads, link_support, cap_links, transit_offsets,
+                                        cap_unitigs, transit_count, cap_slots, verdict, n_unitigs, n_links, n_slots, summary);
     });
 }
 extern "C" int kmc_correct_device(kmc_ctx* c, uint64_t min_count, uint64_t max_count, const void* d_bases, const void* d_offsets, uint64_t n_reads,

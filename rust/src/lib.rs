@@ -37,6 +37,13 @@ pub const KMC_LINK_WORDS: usize = 8;
 pub const KMC_MAP_WORDS: usize = 8;
 pub const KMC_MAP_READ_WORDS: usize = 4;
 pub const KMC_MAP_NONE: u32 = 0xFFFF_FFFF;
+/// summary words of `kmc_unitig_transits`, a unitig's verdict, the flag that adds onto the held result
+pub const KMC_TRANSIT_WORDS: usize = 8;
+pub const KMC_TRANSIT_PLAIN: u8 = 0;
+pub const KMC_TRANSIT_UNSPANNED: u8 = 1;
+pub const KMC_TRANSIT_RESOLVED: u8 = 2;
+pub const KMC_TRANSIT_AMBIGUOUS: u8 = 3;
+pub const KMC_TRANSIT_ACCUMULATE: u32 = 1;
 /// summary words of `kmc_correct`, words per read of its `read_stats`, the kinds of a candidate
 pub const KMC_CORRECT_WORDS: usize = 8;
 pub const KMC_CORRECT_READ_WORDS: usize = 4;
@@ -200,6 +207,8 @@ extern "C" {
     pub fn kmc_unitig_links(ctx: *mut KmcCtx, min_count: u64, max_count: u64, link_offsets: *mut u64, cap_ends: u64, link_to: *mut u32, cap_links: u64, n_unitigs: *mut u64, n_links: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_map_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, d_bases: *const c_void, d_offsets: *const c_void, n_reads: u64, n_bases: u64, d_place: *mut *const c_void, d_read_stats: *mut *const c_void, d_seg_offsets: *mut *const c_void, d_segs: *mut *const c_void, d_support: *mut *const c_void, n_segs: *mut u64, n_unitigs: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_map(ctx: *mut KmcCtx, min_count: u64, max_count: u64, bases: *const u8, offsets: *const u64, n_reads: u64, place: *mut u64, read_stats: *mut u32, seg_offsets: *mut u64, segs: *mut u32, cap_segs: u64, support: *mut u64, cap_unitigs: u64, n_segs: *mut u64, n_unitigs: *mut u64, summary: *mut u64) -> c_int;
+    pub fn kmc_unitig_transits_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, min_reads: u64, flags: u32, d_bases: *const c_void, d_offsets: *const c_void, n_reads: u64, n_bases: u64, d_link_support: *mut *const c_void, d_transit_offsets: *mut *const c_void, d_transit_count: *mut *const c_void, d_verdict: *mut *const c_void, n_unitigs: *mut u64, n_links: *mut u64, n_slots: *mut u64, summary: *mut u64) -> c_int;
+    pub fn kmc_unitig_transits(ctx: *mut KmcCtx, min_count: u64, max_count: u64, min_reads: u64, flags: u32, bases: *const u8, offsets: *const u64, n_reads: u64, link_support: *mut u64, cap_links: u64, transit_offsets: *mut u64, cap_unitigs: u64, transit_count: *mut u64, cap_slots: u64, verdict: *mut u8, n_unitigs: *mut u64, n_links: *mut u64, n_slots: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_correct_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, d_bases: *const c_void, d_offsets: *const c_void, n_reads: u64, n_bases: u64, d_corrected: *mut *const c_void, d_read_stats: *mut *const c_void, d_cand_offsets: *mut *const c_void, d_cands: *mut *const c_void, n_cands: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_correct(ctx: *mut KmcCtx, min_count: u64, max_count: u64, bases: *const u8, offsets: *const u64, n_reads: u64, out_bases: *mut u8, read_stats: *mut u32, cand_offsets: *mut u64, cands: *mut u32, cap_cands: u64, n_cands: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_trim_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, mode: c_int, flags: u32, min_strong: u64, min_permille: u32, min_len: u64, d_bases: *const c_void, d_offsets: *const c_void, n_reads: u64, n_bases: u64, d_out_bases: *mut *const c_void, d_out_offsets: *mut *const c_void, d_origin: *mut *const c_void, d_read_stats: *mut *const c_void, d_verdict: *mut *const c_void, n_out: *mut u64, n_out_bases: *mut u64, summary: *mut u64) -> c_int;
@@ -520,6 +529,42 @@ impl Counter {
             })?;
         }
         Ok((place, stats, seg_offsets, segs, support, w))
+    }
+
+    /// The read walks of a batch counted per graph element (`kmc_unitig_transits`; the batch is not counted).  Returns the
+    /// support of every link record (indexed like the `to` of `unitig_links`), `transit_offsets[n_unitigs + 1]`, the transit
+    /// slots (unitig u: a dS x dE matrix at its offset, row = record rank at the START end, column = at the END end), the
+    /// verdict per unitig (`KMC_TRANSIT_*`) and the eight summary words [crossings, those without a record, records without
+    /// support, transits stored, dropped, repeats, resolved, ambiguous].  `accumulate` adds onto the result of the last call
+    /// for this range (the first batch goes without it).  The arrays are sized from `kmc_unitig_links` -- a unitig's slots
+    /// are at most four times the records of one of its ends -- so the batch is walked once.
+    #[allow(clippy::type_complexity)]
+    pub fn transits(&mut self, bases: &[u8], offsets: &[u64], min_count: u64, max_count: u64, min_reads: u64, accumulate: bool)
+                    -> Result<(Vec<u64>, Vec<u64>, Vec<u64>, Vec<u8>, [u64; KMC_TRANSIT_WORDS]), KmcError> {
+        let (mut nd, mut nt) = (0u64, 0u64);
+        self.check(unsafe { kmc_finalize(self.ctx, &mut nd, &mut nt) })?;
+        let n_reads = offsets.len().saturating_sub(1);
+        if n_reads > 0 && offsets[n_reads] as usize != bases.len() {
+            return Err(KmcError(-1, "offsets do not end at the number of bases".into()));
+        }
+        let (mut nu, mut nl, mut nsl) = (0u64, 0u64, 0u64);
+        let mut lw = [0u64; KMC_LINK_WORDS];
+        self.check(unsafe {
+            kmc_unitig_links(self.ctx, min_count, max_count, std::ptr::null_mut::<u64>(), 0, std::ptr::null_mut::<u32>(), 0, &mut nu, &mut nl, lw.as_mut_ptr())
+        })?;
+        let cap_slots = std::cmp::min(16 * nu, 4 * nl);
+        let mut support = vec![0u64; nl as usize];
+        let mut transit_offsets = vec![0u64; nu as usize + 1];
+        let mut count = vec![0u64; cap_slots as usize];
+        let mut verdict = vec![0u8; nu as usize];
+        let mut w = [0u64; KMC_TRANSIT_WORDS];
+        self.check(unsafe {
+            kmc_unitig_transits(self.ctx, min_count, max_count, min_reads, if accumulate { KMC_TRANSIT_ACCUMULATE } else { 0 }, bases.as_ptr(),
+                                offsets.as_ptr(), n_reads as u64, support.as_mut_ptr(), nl, transit_offsets.as_mut_ptr(), nu, count.as_mut_ptr(),
+                                cap_slots, verdict.as_mut_ptr(), &mut nu, &mut nl, &mut nsl, w.as_mut_ptr())
+        })?;
+        count.truncate(nsl as usize);
+        Ok((support, transit_offsets, count, verdict, w))
     }
 
     /// A batch of reads corrected against the solid keys of the table (`kmc_correct`; the batch is not counted): every
