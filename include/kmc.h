@@ -183,7 +183,13 @@ int kmc_merge_pairs_device(kmc_ctx* ctx, const void* d_key_hi, const void* d_key
                            const void* d_count, uint64_t n_pairs);
 
 /* Compact the table, sort by key on the device, report sizes.  May be called repeatedly;
- * more batches may be added afterwards (the sorted view is then stale until the next finalize). */
+ * more batches may be added afterwards (the sorted view is then stale until the next finalize).
+ * A call that finds nothing added, merged or reset since the last finalize makes NO new view when that finalize went the
+ * small-table way (it emptied the table into the view: tables up to some ten thousand keys, the empty one included, and
+ * every view kmc_finalize_async queued): it reports the sizes of the view in place and changes nothing.  Where this header
+ * says that "finalize" ends the validity of a device pointer, drops a result a ctx holds or makes a call compute again,
+ * such a call is not meant: the pointers stay valid, a host form still copies what is held and KMC_TRANSIT_ACCUMULATE still
+ * finds its result.  A larger table is compacted and sorted again: a new view, with everything that says. */
 int kmc_finalize(kmc_ctx* ctx, uint64_t* n_distinct, uint64_t* n_total);
 
 /* kmc_finalize for a pipeline that does not want to wait: the device work of a SMALL table's finalize (at most 131072

@@ -271,6 +271,24 @@ def test_accumulate(kmc, oracle):
         _equal(got, _want(whole), "after finalize")
 
 
+def test_a_finalize_with_nothing_added_makes_no_new_view(kmc, oracle):
+    """include/kmc.h, kmc_finalize: a call that finds nothing added since the last finalize of a small table reports the view
+    in place and drops nothing: the same device pointers, and the held transits are still there to add to (a finalize
+    behind an added batch drops them: test_accumulate)"""
+    k = 31
+    sample, reads = ti.repeat(k, 500 + k)
+    kc, table = _counter(kmc, oracle, sample, k, True)
+    bases, offs = mi.pack(reads)
+    twice = tm.transits(table, True, [reads, reads])
+    with kc:
+        _device(kc, 1, 0, bases, offs)
+        view = kc.export_device()
+        assert kc.finalize() == (len(table), sum(table.values())) and kc.export_device() == view
+        got, sizes, w = _device(kc, 1, 0, bases, offs, accumulate=True)
+        _equal(got, _want(twice), "behind a finalize with nothing added")
+        assert w == twice.summary and sizes == _sizes(twice)
+
+
 _CHILD = r"""
 import importlib, sys
 import numpy as np
