@@ -33,6 +33,7 @@
  *   (addition: no equivalent in the reference)             kmc_unitig_bubbles / kmc_unitig_bubbles_device (its bubbles reported as variant records)
  *   (addition: no equivalent in the reference)             kmc_unitig_map / kmc_unitig_map_device (reads threaded through the unitigs)
  *   (addition: no equivalent in the reference)             kmc_unitig_transits / kmc_unitig_transits_device (read walks counted per link and per unitig)
+ *   (addition: no equivalent in the reference)             kmc_unitig_contigs / kmc_unitig_contigs_device (resolved repeats duplicated, unsupported links cut, contigs spelled)
  *   (addition: no equivalent in the reference)             kmc_correct / kmc_correct_device (substitution errors of reads repaired from the table)
  *   (addition: no equivalent in the reference)             kmc_trim / kmc_trim_device (reads trimmed and filtered by their solid k-mers)
  *   (addition: no equivalent in the reference)             kmc_normalize / kmc_normalize_device (read depth normalised: a per-read k-mer depth, deep reads sampled down)
@@ -613,6 +614,74 @@ int kmc_unitig_transits(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, ui
                         uint64_t cap_links, uint64_t* transit_offsets, uint64_t cap_unitigs, uint64_t* transit_count,
                         uint64_t cap_slots, uint8_t* verdict, uint64_t* n_unitigs, uint64_t* n_links, uint64_t* n_slots,
                         uint64_t* summary);
+
+/* ---- the counted walks acted on: contigs (additions, as above).  Every read-resolved repeat gets one copy per matched way
+ * through it, links without support are ignored on request, and the chains of unitigs that remain are spelled out.
+ * Everything refers to three results of one view and one range min_count..max_count: the unitigs (S_u, m_u keys, abund), the
+ * link records (link_offsets, link_to) and the transits result the ctx holds (link_support, transit_offsets, transit_count).
+ * KMC_MODE_CONTIG only; every k, in a canonical or a forward ctx.  Parameters: min_reads (0 is taken as 1) and min_support
+ * (0: every record is live).
+ * RESOLVED under this call's min_reads: recomputed from transit_count by the VERDICT rule of the transits block; the held
+ *   verdict byte is not trusted, it was made with another call's min_reads.  For a resolved unitig v with dS = dE = d,
+ *   sigma_v(P) is the one Q whose slot (P, Q) is supported.
+ * NODE.  A resolved unitig has d nodes: copy p (0 <= p < d) owns record rank p at its START end 2v and record rank sigma_v(p)
+ *   at its END end 2v + 1.  Every other unitig has one node.  node_offsets[u] is the exclusive scan of the copies; the id of
+ *   copy p of u is node_offsets[u] + p.  Every node has a START end and an END end.
+ * CHOICE of a node end (n, e) with source end s = 2u + e.  The chosen record: for a copy of a resolved unitig the one record
+ *   the copy owns at that end, whatever its support; otherwise the live records of s are those with link_support >=
+ *   min_support, and if exactly one is live that one is chosen, if not there is no choice.  With t = 2w + f the target of that
+ *   record the chosen node end is: if w is not resolved, (its node, f); if w is resolved, let q be the rank of the record
+ *   t -> s among all records of t (if it does not exist there is no choice): copy q of w if f is START, copy sigma_w^-1(q) if
+ *   f is END, at end f.
+ * JOIN.  (n, e) and (n', e') are joined iff each is the other's choice and they are not the same node end -- the mutual rule
+ *   of the unitigs; a hairpin record is no join.  Joins are a symmetric matching on node ends, so the nodes fall into simple
+ *   paths and simple cycles.
+ * CONTIG.  A maximal path or a cycle.  A cycle is cut at the join of the START end of its smallest node, flagged circular,
+ *   read from that node in + orientation and spelled without wrap, like a circular unitig.  A path of one node is read +.
+ *   Any other path starts at the end node with the smaller id, read + if its unjoined end is START and - if it is END.
+ *   Contigs are numbered by their start node, ascending.  The rule does not look at the ctx: in a forward ctx a path that
+ *   starts at an END end is spelled on the other strand, and its k-mers are the reverse complements of the table's.
+ * Outputs.  path_offsets[n_contigs + 1], uint64_t; path[n_nodes], uint32_t: entries 2u + o, o = 1 where the unitig is read
+ *   reverse-complemented.  bases / offsets[n_contigs + 1] in the kmc_add_batch layout: the oriented first unitig, then of
+ *   every following one its oriented spelling from base k - 1 on, so a contig has (sum of m_u) + k - 1 bases.
+ *   abund[n_contigs], uint64_t: the sum of abund[u] over the path -- a duplicated repeat counts IN FULL in each copy, so the
+ *   sum of abund over the contigs exceeds the table's total where something was duplicated.  flags[n_contigs], uint8_t: bit
+ *   0 circular.
+ * summary[KMC_CONTIG_WORDS]: [0] contigs, [1] nodes, [2] unitigs duplicated, [3] records ignored for support (counted at
+ *   the ends of single-copy unitigs), [4] circular contigs, [5] contigs of one node, [6] the most nodes in one contig,
+ *   [7] bases.  [1] == path_offsets[n_contigs], [7] == offsets[n_contigs] == (sum over path of m_u) + [0] * (k - 1).
+ * With nothing resolved and min_support 0 the joins are those the unitigs already made or refused, and bases, offsets,
+ *   abund and flags are those of kmc_unitigs with path[c] == 2c.
+ * State.  The call computes nothing it was not given: the ctx must hold the unitigs, the links and a transits result of this
+ *   very view and range -- the results, not the work arrays, so a kmc_graph* call in between does not matter as long as the
+ *   three are still held -- otherwise KMC_ERR_STATE with a message that names the missing one.  It rewrites none of: the
+ *   unitig, link, map and transit arrays, a clean, simplify, components or bubbles result, the view, a partition, a filter
+ *   or set-operation result, the query index.  The held contig result is keyed by view, range, min_reads and min_support;
+ *   it is dropped by any transits call (the counts changed), by anything that drops the links, and by finalize, reset and
+ *   destroy.
+ * Rules: NULL ctx, KMC_MODE_LR, a non-zero max_count below min_count: KMC_ERR_ARG; no view: KMC_ERR_STATE; 2^31 nodes or
+ *   more, or 2^32 keys or more over the paths: KMC_ERR_CAPACITY.  An empty view gives zeros and offsets[0] ==
+ *   path_offsets[0] == 0.
+ * Diagnostic: with KMC_UNITIG_TRACE set, a call that computes prints "kmc_unitig_contigs: unitigs U nodes N contigs C bases B
+ *   rounds R choice_ms .. rank_ms .. layout_ms .. emit_ms .." to stderr (tools/measure_contigs.py reads it). ---- */
+#define KMC_CONTIG_WORDS 8
+/* The results in ctx-owned device arrays -- uint8_t bases[n_bases] (readable to the next 16-byte boundary, as
+ * kmc_add_batch_device asks), uint64_t offsets[n_contigs + 1], uint64_t path_offsets[n_contigs + 1], uint32_t path[n_nodes],
+ * uint64_t abund[n_contigs], uint8_t flags[n_contigs] -- valid until the next kmc_unitig_contigs* call that computes, a
+ * transits call, anything that drops the links / finalize / reset / destroy (same ordering contract as kmc_export_device).
+ * Computes on every call.  Every output pointer may be NULL. */
+int kmc_unitig_contigs_device(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, uint64_t min_reads, uint64_t min_support,
+                              const void** d_bases, const void** d_offsets, const void** d_path_offsets, const void** d_path,
+                              const void** d_abund, const void** d_flags, uint64_t* n_contigs, uint64_t* n_nodes,
+                              uint64_t* n_bases, uint64_t* summary);
+/* The same on host buffers.  bases has cap_bases entries; offsets and path_offsets have room for cap_contigs + 1, abund and
+ * flags for cap_contigs; path has cap_nodes.  *n_contigs, *n_nodes and *n_bases are always set; a cap too small for an array
+ * that was given -> KMC_ERR_ARG and nothing is copied; an array that is NULL is not copied and its cap not looked at.  All
+ * arrays NULL is the sizing call; a sizing call followed by the copy call computes once, as for kmc_unitig_links. */
+int kmc_unitig_contigs(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, uint64_t min_reads, uint64_t min_support,
+                       uint8_t* bases, uint64_t cap_bases, uint64_t* offsets, uint64_t* path_offsets, uint64_t* abund,
+                       uint8_t* flags, uint64_t cap_contigs, uint32_t* path, uint64_t cap_nodes, uint64_t* n_contigs,
+                       uint64_t* n_nodes, uint64_t* n_bases, uint64_t* summary);
 
 /* ---- reads corrected against the table: substitution errors repaired from the solid keys (additions, as above).
  * KMC_MODE_CONTIG only; every k, in a canonical or a forward ctx.  Reads the sorted view of the last kmc_finalize (a view

@@ -98,6 +98,7 @@ ABI_SYMBOLS = [
     "kmc_unitig_bubbles", "kmc_unitig_bubbles_device",
     "kmc_unitig_map", "kmc_unitig_map_device",
     "kmc_unitig_transits", "kmc_unitig_transits_device",
+    "kmc_unitig_contigs", "kmc_unitig_contigs_device",
     "kmc_correct", "kmc_correct_device",
     "kmc_trim", "kmc_trim_device",
     "kmc_normalize", "kmc_normalize_device",
@@ -128,6 +129,8 @@ TRANSIT_WORDS = 8       # KMC_TRANSIT_WORDS: crossings, those without a record, 
 TRANSIT_PLAIN, TRANSIT_UNSPANNED, TRANSIT_RESOLVED, TRANSIT_AMBIGUOUS = 0, 1, 2, 3   # KMC_TRANSIT_*: a unitig's verdict
 TRANSIT_VERDICT_NAMES = ("plain", "unspanned", "resolved", "ambiguous")
 TRANSIT_ACCUMULATE = 1  # KMC_TRANSIT_ACCUMULATE: flags bit 0, add onto the result the ctx holds
+CONTIG_WORDS = 8        # KMC_CONTIG_WORDS: contigs, nodes, unitigs duplicated, records ignored for support, circular, one-node, most nodes in one, bases
+CONTIG_CIRCULAR = 1     # bit 0 of a contig's flags byte
 CORRECT_WORDS = 8       # KMC_CORRECT_WORDS: reads, valid windows, weak windows, weak runs, candidates, corrected, ambiguous, weak windows left
 CORRECT_READ_WORDS = 4  # KMC_CORRECT_READ_WORDS: a read's valid windows, weak windows, candidates, corrected
 CORRECT_INTERIOR, CORRECT_HEAD, CORRECT_TAIL = 0, 1, 2   # KMC_CORRECT_*: a candidate's kind
@@ -230,6 +233,9 @@ def lib() -> C.CDLL:
     if "KMC_LIB_PATH" not in os.environ or hasattr(L, "kmc_unitig_transits"):   # (as for the bubbles calls above)
         L.kmc_unitig_transits_device.argtypes = [vp, u64, u64, u64, u32, vp, vp, u64, u64] + [C.POINTER(vp)] * 4 + [pu64, pu64, pu64, vp]
         L.kmc_unitig_transits.argtypes = [vp, u64, u64, u64, u32, vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, pu64, pu64, pu64, vp]
+    if "KMC_LIB_PATH" not in os.environ or hasattr(L, "kmc_unitig_contigs"):   # (as for the bubbles calls above)
+        L.kmc_unitig_contigs_device.argtypes = [vp, u64, u64, u64, u64] + [C.POINTER(vp)] * 6 + [pu64, pu64, pu64, vp]
+        L.kmc_unitig_contigs.argtypes = [vp, u64, u64, u64, u64, vp, u64, vp, vp, vp, vp, u64, vp, u64, pu64, pu64, pu64, vp]
     L.kmc_correct_device.argtypes = [vp, u64, u64, vp, vp, u64, u64] + [C.POINTER(vp)] * 4 + [pu64, vp]
     L.kmc_correct.argtypes = [vp, u64, u64, vp, vp, u64, vp, vp, vp, vp, u64, pu64, vp]
     L.kmc_trim_device.argtypes = [vp, u64, u64, i32, u32, u64, u32, u64, vp, vp, u64, u64] + [C.POINTER(vp)] * 5 + [pu64, pu64, vp]
@@ -491,11 +497,12 @@ class Unitigs:
         return "".join(">%d LN:i:%d KC:i:%d CL:i:%d\n%s\n" % (i, len(s), int(self.abund[i]), int(self.flags[i]) & UNITIG_CIRCULAR, s)
                        for i, s in enumerate(self.strings()))
 
-    def to_gfa(self, links: "UnitigLinks", k: int, transits: Optional["Transits"] = None) -> str:
+    def to_gfa(self, links: "UnitigLinks", k: int, transits: Optional["Transits"] = None, contigs: Optional["Contigs"] = None) -> str:
         """GFA 1.0 as the CLI's --gfa prints it: ``H VN:Z:1.0``, one ``S INDEX SEQ LN:i:BASES KC:i:ABUND CL:i:0|1`` per
         unitig, one ``L U +|- V +|- (k-1)M`` per record of ``links`` (KmerCounter.unitig_links of the same range), tab-separated.
         With ``transits`` (KmerCounter.transits of the same range) every ``L`` line ends in ``RC:i:SUPPORT``, the reads that
-        walked the link."""
+        walked the link.  With ``contigs`` (KmerCounter.contigs of the same range) one ``P INDEX U+,V-,... OVERLAPS`` line per
+        contig follows: its unitig path, ``(k-1)M`` between neighbours, and once more at the end of a circular one."""
         if len(links.offsets) != 2 * len(self) + 1:
             raise ValueError("the links are not those of these unitigs")
         if transits is not None and len(transits.link_support) != len(links):
@@ -508,6 +515,13 @@ class Unitigs:
         else:
             out += ["L\t%d\t%s\t%d\t%s\t%dM\tRC:i:%d\n" % (u, o1, v, o2, k - 1, int(n))
                     for (u, o1, v, o2), n in zip(links.records(), transits.link_support)]
+        if contigs is not None:
+            if len(contigs.path) and int(contigs.path.max()) >> 1 >= len(self):
+                raise ValueError("the contigs are not those of these unitigs")
+            for i, (p, f) in enumerate(zip(contigs.paths(), contigs.flags)):
+                n_overlaps = len(p) - 1 + (int(f) & CONTIG_CIRCULAR)
+                out.append("P\t%d\t%s\t%s\n" % (i, ",".join("%d%s" % (e >> 1, "-" if e & 1 else "+") for e in p),
+                                                 ",".join(["%dM" % (k - 1)] * n_overlaps) or "*"))
         return "".join(out)
 
 
@@ -707,6 +721,75 @@ class Transits:
             out.append("U\t%d\t%s\t%d\t%d\n" % (u, TRANSIT_VERDICT_NAMES[int(self.verdict[u])], m.shape[0], m.shape[1]))
             out += ["T\t%d\t%d\t%d\t%d\n" % (u, p, q, int(m[p, q])) for p in range(m.shape[0]) for q in range(m.shape[1]) if m[p, q]]
         return "".join(out)
+
+
+_CONTIG_FIELDS = ("contigs", "nodes", "unitigs_duplicated", "records_ignored", "circular", "one_node", "most_nodes", "bases")
+
+
+@dataclass
+class ContigSummary:
+    """The eight words of kmc_unitig_contigs: contigs, nodes (path entries), unitigs duplicated, link records ignored for
+    support at the ends of single-copy unitigs, circular contigs, contigs of one node, the most nodes in one contig, bases."""
+    contigs: int
+    nodes: int
+    unitigs_duplicated: int
+    records_ignored: int
+    circular: int
+    one_node: int
+    most_nodes: int
+    bases: int
+
+    @classmethod
+    def from_words(cls, words) -> "ContigSummary":
+        return cls(*[int(w) for w in words])
+
+    def words(self) -> list:
+        return [getattr(self, f) for f in _CONTIG_FIELDS]
+
+    def to_text(self) -> str:
+        """``NAME\tVALUE`` lines."""
+        return "\n".join("%s\t%d" % (f, getattr(self, f)) for f in _CONTIG_FIELDS) + "\n"
+
+
+@dataclass
+class Contigs:
+    """What KmerCounter.contigs returns: ``bases`` uint8[n_bases] (ASCII, concatenated), ``offsets`` uint64[n + 1],
+    ``path_offsets`` uint64[n + 1], ``path`` uint32[n_nodes] (entries 2 * unitig + o, o = 1: read reverse-complemented),
+    ``abund`` uint64[n] (the unitigs' abundances summed over the path; a duplicated repeat counts in full in each copy),
+    ``flags`` uint8[n] (CONTIG_CIRCULAR), ``summary``."""
+    bases: np.ndarray
+    offsets: np.ndarray
+    path_offsets: np.ndarray
+    path: np.ndarray
+    abund: np.ndarray
+    flags: np.ndarray
+    summary: ContigSummary
+
+    def __len__(self) -> int:
+        return len(self.abund)
+
+    def strings(self) -> list:
+        text = self.bases.tobytes().decode("ascii")
+        o = self.offsets
+        return [text[int(o[i]):int(o[i + 1])] for i in range(len(self))]
+
+    def paths(self) -> list:
+        """per contig the list of its path entries 2 * unitig + o"""
+        o = self.path_offsets
+        return [self.path[int(o[i]):int(o[i + 1])].tolist() for i in range(len(self))]
+
+    def walks(self) -> list:
+        """per contig its path as ReadMap.walks() writes one: ``>U`` / ``<U`` per unitig, concatenated"""
+        return ["".join("%s%d" % ("<" if e & 1 else ">", e >> 1) for e in p) for p in self.paths()]
+
+    def to_fasta(self) -> str:
+        """FASTA as the CLI's --contigs prints it: ``>INDEX LN:i:BASES KC:i:ABUND CL:i:0|1 WK:Z:WALK`` and the sequence on one line."""
+        return "".join(">%d LN:i:%d KC:i:%d CL:i:%d WK:Z:%s\n%s\n" % (i, len(s), int(self.abund[i]), int(self.flags[i]) & CONTIG_CIRCULAR, w, s)
+                       for i, (s, w) in enumerate(zip(self.strings(), self.walks())))
+
+    def to_text(self) -> str:
+        """What ``k-mer-count --contigs`` prints: to_fasta()."""
+        return self.to_fasta()
 
 
 _CORRECT_FIELDS = ("reads", "valid_windows", "weak_windows", "weak_runs", "candidates", "corrected", "ambiguous", "weak_windows_left")
@@ -1478,6 +1561,35 @@ class KmerCounter:
             return device_view(ptr, (n_bytes + 7) // 8, dev).cpu().numpy().view(np.uint8)[:n_bytes].copy()
         got = (words(ds, 8 * nl).view(np.uint64), words(do, 8 * (nu + 1)).view(np.uint64), words(dc, 8 * nsl).view(np.uint64), words(dv, nu))
         return Transits(*got, summary, self.unitig_links(min_count, max_count))   # (the held links: copied, not computed)
+
+    # -- the counted walks acted on: contigs (after unitigs / unitig_links / transits of the same range) --
+    def contigs(self, min_count: int = 1, max_count: int = 0, min_reads: int = 1, min_support: int = 0) -> "Contigs":
+        """kmc_unitig_contigs: the chains of unitigs that remain once every repeat the held transit counts resolve (under
+        ``min_reads``) has one copy per matched way through it and, with ``min_support``, every link record below that support
+        is ignored at the ends of single-copy unitigs.  The ctx must hold the unitigs, links and transits of this range
+        (transits() leaves all three).  Two calls of the library, one computation, as in unitigs()."""
+        n = [C.c_uint64() for _ in range(3)]
+        w = (C.c_uint64 * CONTIG_WORDS)()
+        a = (int(min_count), int(max_count), int(min_reads), int(min_support))
+        self._chk(self._L.kmc_unitig_contigs(self._h, *a, None, 0, None, None, None, None, 0, None, 0, *[C.byref(x) for x in n], w))
+        nc, nn, nb = (x.value for x in n)
+        bases, flags, path = np.zeros(nb, np.uint8), np.zeros(nc, np.uint8), np.zeros(nn, np.uint32)
+        offsets, path_offsets, abund = np.zeros(nc + 1, np.uint64), np.zeros(nc + 1, np.uint64), np.zeros(nc, np.uint64)
+        self._chk(self._L.kmc_unitig_contigs(self._h, *a, bases.ctypes.data if nb else None, nb, offsets.ctypes.data, path_offsets.ctypes.data,
+                                             abund.ctypes.data if nc else None, flags.ctypes.data if nc else None, nc,
+                                             path.ctypes.data if nn else None, nn, *[C.byref(x) for x in n], w))
+        return Contigs(bases, offsets, path_offsets, path, abund, flags, ContigSummary.from_words(list(w)))
+
+    def contigs_device(self, min_count: int = 1, max_count: int = 0, min_reads: int = 1, min_support: int = 0):
+        """(d_bases, d_offsets, d_path_offsets, d_path, d_abund, d_flags, n_contigs, n_nodes, n_bases, ContigSummary) of
+        kmc_unitig_contigs_device: ctx-owned device arrays; d_bases / d_offsets can be handed to another counter's
+        add_batch_device."""
+        p = [C.c_void_p() for _ in range(6)]
+        n = [C.c_uint64() for _ in range(3)]
+        w = (C.c_uint64 * CONTIG_WORDS)()
+        self._chk(self._L.kmc_unitig_contigs_device(self._h, int(min_count), int(max_count), int(min_reads), int(min_support),
+                                                    *[C.byref(x) for x in p], *[C.byref(x) for x in n], w))
+        return tuple(x.value or 0 for x in p) + tuple(x.value for x in n) + (ContigSummary.from_words(list(w)),)
 
     # -- reads corrected against the solid keys of the table (of the sorted view; finalize() first) --
     def correct_reads_device(self, d_bases: int, d_offsets: int, n_reads: int, n_bases: int, min_count: int = 2, max_count: int = 0):

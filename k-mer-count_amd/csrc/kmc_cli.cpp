@@ -6,7 +6,7 @@
 //
 //   k-mer-count [FASTA] [-k K] [--forward] [--expand] [--device N | --gpus N] [--algo auto|stream|walk|sort] [--stats]
 //               [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE | --map FILE | --correct FILE]
-//               [--transits FILE [--min-reads N]]
+//               [--transits FILE [--min-reads N]] [--contigs FILE [--min-reads N] [--min-support N]]
 //               [--trim FILE [--trim-mode none|ends|longest] [--min-strong N] [--strong-permille N] [--min-len N] [--invert]
 //                [--paired both|either]]
 //               [--normalize FILE --target N [--depth-permille P] [--min-depth N] [--seed S] [--norm-paired] [--norm-invert]]
@@ -47,6 +47,14 @@
 //               and END end -- followed by "T<TAB>UNITIG<TAB>P<TAB>Q<TAB>COUNT" per pair of the P-th START link and the Q-th END
 //               link that COUNT reads took through it.  It excludes what --map excludes, and --map; with --clean the reads
 //               walk the cleaned graph.
+//   --contigs FILE       (with -k K) instead of the table: the contigs the reads of FILE (FASTA / FASTQ) leave of the unitig graph of
+//               the counted input (kmc_unitig_contigs behind kmc_unitig_transits, which walks FILE in chunks that add up;
+//               --min-count / --max-count are the solidity range).  A repeat whose ways in pair up one to one with its ways out,
+//               each pair walked by --min-reads N reads or more (default 1), gets one copy per pair; with --min-support N
+//               (default 0) a link that fewer than N reads walked is ignored at the ends of the other unitigs.  Output: FASTA,
+//               ">INDEX LN:i:BASES KC:i:ABUND CL:i:0|1 WK:Z:WALK" -- the abundance summed over the path, the circular flag, the
+//               path as ">U" / "<U" per unitig -- then the contig on one line.  It excludes what --transits excludes, and
+//               --transits; with --clean the reads walk the cleaned graph.
 //   --correct FILE       (with -k K) instead of the table: every read of FILE (FASTA / FASTQ) corrected against the solid keys of
 //               the counted input (kmc_correct; --min-count / --max-count are the solidity range), as FASTA in file order:
 //               ">INDEX WINDOWS WEAK CANDIDATES FIXED" -- its valid K-mer windows, how many of them are not solid, the weak
@@ -173,6 +181,8 @@ int main(int argc, char** argv) {
     const char* trim_path = nullptr;
     const char* transits_path = nullptr;
     long long min_reads = -1;   // (-1: not given)
+    const char* contigs_path = nullptr;
+    long long min_support = -1;   // (-1: not given)
     int trim_mode = -1, trim_invert = 0, trim_pair = 0;   // (-1: the default mode, longest)
     long long min_strong = -1, strong_permille = -1, min_len = -1;   // (-1: not given)
     const char* norm_path = nullptr;
@@ -200,6 +210,8 @@ int main(int argc, char** argv) {
         else if (a == "--map" && i + 1 < argc) map_path = argv[++i];
         else if (a == "--correct" && i + 1 < argc) correct_path = argv[++i];
         else if (a == "--transits" && i + 1 < argc) transits_path = argv[++i];
+        else if (a == "--contigs" && i + 1 < argc) contigs_path = argv[++i];
+        else if (a == "--min-support" && i + 1 < argc) { if (!parse_count("--min-support", argv[++i], 0, LLONG_MAX, &min_support)) return 2; }
         else if (a == "--min-reads" && i + 1 < argc) { if (!parse_count("--min-reads", argv[++i], 0, LLONG_MAX, &min_reads)) return 2; }
         else if (a == "--trim" && i + 1 < argc) trim_path = argv[++i];
         else if (a == "--trim-mode" && i + 1 < argc) {
@@ -252,7 +264,7 @@ int main(int argc, char** argv) {
         } else if (a == "-h" || a == "--help") {
             fprintf(stderr, "usage: k-mer-count [FASTA] [-k K] [--forward] [--expand] [--device N | --gpus N] [--algo auto|stream|walk|sort] [--stats]\n"
                             "                   [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE | --map FILE | --correct FILE]\n"
-                            "                   [--transits FILE [--min-reads N]]\n"
+                            "                   [--transits FILE [--min-reads N]] [--contigs FILE [--min-reads N] [--min-support N]]\n"
                             "                   [--trim FILE [--trim-mode none|ends|longest] [--min-strong N] [--strong-permille N] [--min-len N] [--invert]\n"
                             "                    [--paired both|either]]\n"
                             "                   [--normalize FILE --target N [--depth-permille P] [--min-depth N] [--seed S] [--norm-paired] [--norm-invert]]\n"
@@ -265,7 +277,7 @@ int main(int argc, char** argv) {
                    a == "--clean" || a == "--tip-keys" || a == "--island-keys" || a == "--bubble-keys" || a == "--component-keys" || a == "--trim" ||
                    a == "--trim-mode" || a == "--min-strong" || a == "--strong-permille" || a == "--min-len" || a == "--paired" ||
                    a == "--normalize" || a == "--target" || a == "--depth-permille" || a == "--min-depth" || a == "--seed" || a == "--transits" ||
-                   a == "--min-reads") {
+                   a == "--min-reads" || a == "--contigs" || a == "--min-support") {
             fprintf(stderr, "k-mer-count: %s needs a value\n", a.c_str());
             return 2;
         } else if (!a.empty() && a[0] != '-') path = argv[i];
@@ -309,8 +321,24 @@ int main(int argc, char** argv) {
             bad = "--graph / --graph-stats / --unitigs / --gfa / --components / --variants exclude each other";
         else if (expand) bad = "--expand exclude each other";
         if (bad) { fprintf(stderr, "k-mer-count: --transits %s%s\n", strncmp(bad, "needs", 5) ? "and " : "", bad); return 2; }
-    } else if (min_reads >= 0) {
-        fprintf(stderr, "k-mer-count: --min-reads needs --transits FILE\n");
+    } else if (min_reads >= 0 && !contigs_path) {
+        fprintf(stderr, "k-mer-count: --min-reads needs --transits FILE or --contigs FILE\n");
+        return 2;
+    }
+    // --contigs and its options: the same again
+    if (contigs_path) {
+        const char* bad = nullptr;
+        if (!k) bad = "needs -k K";
+        else if (transits_path || map_path || correct_path || trim_path || norm_path) bad = "--transits / --map / --correct / --trim / --normalize exclude each other";
+        else if (query_path || profile_path) bad = "--query-kmers / --profile exclude each other";
+        else if (histo) bad = "--histo exclude each other";
+        else if (with_path || compare || setop >= 0) bad = "--with / --compare / --setop exclude each other";
+        else if (graph || graph_stats || unitigs || gfa || components || variants)
+            bad = "--graph / --graph-stats / --unitigs / --gfa / --components / --variants exclude each other";
+        else if (expand) bad = "--expand exclude each other";
+        if (bad) { fprintf(stderr, "k-mer-count: --contigs %s%s\n", strncmp(bad, "needs", 5) ? "and " : "", bad); return 2; }
+    } else if (min_support >= 0) {
+        fprintf(stderr, "k-mer-count: --min-support needs --contigs FILE\n");
         return 2;
     }
     // --correct: the same again
@@ -382,8 +410,9 @@ int main(int argc, char** argv) {
         }
         fclose(f);
     }
-    if (profile_path || map_path || correct_path || trim_path || norm_path || transits_path) {
-        const char* reads_path = profile_path ? profile_path : map_path ? map_path : correct_path ? correct_path : trim_path ? trim_path : norm_path ? norm_path : transits_path;
+    if (profile_path || map_path || correct_path || trim_path || norm_path || transits_path || contigs_path) {
+        const char* reads_path = profile_path ? profile_path : map_path ? map_path : correct_path ? correct_path : trim_path ? trim_path : norm_path ? norm_path
+                                 : transits_path ? transits_path : contigs_path;
         char eb[256] = {0};
         const int prc = kmc_parse_fasta(reads_path, &prof, eb, sizeof(eb));
         if (prc) return die(reads_path, eb[0] ? eb : kmc_status_string(prc));
@@ -431,8 +460,8 @@ int main(int argc, char** argv) {
         if (!k) bad = "needs -k K";
         else if (graph || graph_stats || unitigs || gfa) bad = "--graph / --graph-stats / --unitigs / --gfa exclude each other";
         else if (histo) bad = "--histo exclude each other";
-        else if (query_path || profile_path || map_path || correct_path || trim_path || norm_path || transits_path)
-            bad = "--query-kmers / --profile / --map / --correct / --trim / --normalize / --transits exclude each other";
+        else if (query_path || profile_path || map_path || correct_path || trim_path || norm_path || transits_path || contigs_path)
+            bad = "--query-kmers / --profile / --map / --correct / --trim / --normalize / --transits / --contigs exclude each other";
         else if (with_path || compare || setop >= 0) bad = "--with / --compare / --setop exclude each other";
         else if (expand) bad = "--expand exclude each other";
         if (bad) { fprintf(stderr, "k-mer-count: --components %s%s\n", strncmp(bad, "needs", 5) ? "and " : "", bad); return 2; }
@@ -443,8 +472,8 @@ int main(int argc, char** argv) {
         if (!k) bad = "needs -k K";
         else if (graph || graph_stats || unitigs || gfa || components) bad = "--graph / --graph-stats / --unitigs / --gfa / --components exclude each other";
         else if (histo) bad = "--histo exclude each other";
-        else if (query_path || profile_path || map_path || correct_path || trim_path || norm_path || transits_path)
-            bad = "--query-kmers / --profile / --map / --correct / --trim / --normalize / --transits exclude each other";
+        else if (query_path || profile_path || map_path || correct_path || trim_path || norm_path || transits_path || contigs_path)
+            bad = "--query-kmers / --profile / --map / --correct / --trim / --normalize / --transits / --contigs exclude each other";
         else if (with_path || compare || setop >= 0) bad = "--with / --compare / --setop exclude each other";
         else if (expand) bad = "--expand exclude each other";
         if (bad) { fprintf(stderr, "k-mer-count: --variants %s%s\n", strncmp(bad, "needs", 5) ? "and " : "", bad); return 2; }
@@ -673,6 +702,41 @@ int main(int argc, char** argv) {
                     const uint64_t at = to_[u] + p * de + q;
                     if (at < nsl && cnt[at]) printf("T\t%llu\t%llu\t%llu\t%llu\n", (unsigned long long)u, (unsigned long long)p, (unsigned long long)q, (unsigned long long)cnt[at]);
                 }
+        }
+        fflush(stdout);
+        destroy_all();
+        return 0;
+    }
+    if (contigs_path) {
+        // the reads in chunks that add up, then the contigs of the totals: a sizing call, then the copy call
+        const uint64_t n_rd = prof.n_reads, lo_c = (uint64_t)min_count, hi_c = (uint64_t)max_count, chunk = 1ull << 16;
+        const uint64_t mr = min_reads < 0 ? 1 : (uint64_t)min_reads, ms = min_support < 0 ? 0 : (uint64_t)min_support;
+        uint64_t nu = 0, nl = 0, nsl = 0, first = 0;
+        std::vector<uint64_t> offs;
+        do {
+            const uint64_t n = std::min<uint64_t>(chunk, n_rd - first), b0 = n_rd ? prof.offsets[first] : 0;
+            offs.assign((size_t)n + 1, 0);
+            for (uint64_t i = 0; i <= n && n_rd; ++i) offs[(size_t)i] = prof.offsets[first + i] - b0;
+            rc = kmc_unitig_transits(ctx, lo_c, hi_c, mr, first ? KMC_TRANSIT_ACCUMULATE : 0, n_rd ? prof.bases + b0 : nullptr, offs.data(), n, nullptr, 0,
+                                     nullptr, 0, nullptr, 0, nullptr, &nu, &nl, &nsl, nullptr);
+            first += n;
+        } while (!rc && first < n_rd);
+        kmc_free_reads(&prof);
+        if (rc) { int r = die("kmc_unitig_transits", kmc_last_error(ctx)); destroy_all(); return r; }
+        uint64_t nc = 0, nn = 0, nb = 0;
+        rc = kmc_unitig_contigs(ctx, lo_c, hi_c, mr, ms, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, &nc, &nn, &nb, nullptr);
+        std::vector<uint8_t> cb((size_t)nb + 1), fl((size_t)nc + 1);
+        std::vector<uint64_t> co((size_t)nc + 1), po((size_t)nc + 1), ab((size_t)nc + 1);
+        std::vector<uint32_t> pa((size_t)nn + 1);
+        if (!rc) rc = kmc_unitig_contigs(ctx, lo_c, hi_c, mr, ms, cb.data(), nb, co.data(), po.data(), ab.data(), fl.data(), nc, pa.data(), nn, &nc, &nn, &nb, nullptr);
+        if (rc) { int r = die("kmc_unitig_contigs", kmc_last_error(ctx)); destroy_all(); return r; }
+        setvbuf(stdout, obuf.data(), _IOFBF, obuf.size());
+        for (uint64_t c = 0; c < nc; ++c) {
+            printf(">%llu LN:i:%llu KC:i:%llu CL:i:%d WK:Z:", (unsigned long long)c, (unsigned long long)(co[c + 1] - co[c]), (unsigned long long)ab[c], fl[c] & 1);
+            for (uint64_t i = po[c]; i < po[c + 1] && i < nn; ++i) printf("%c%u", (pa[i] & 1) ? '<' : '>', pa[i] >> 1);
+            fputc('\n', stdout);
+            fwrite(cb.data() + co[c], 1, (size_t)(co[c + 1] - co[c]), stdout);
+            fputc('\n', stdout);
         }
         fflush(stdout);
         destroy_all();

@@ -291,6 +291,17 @@ struct kmc_ctx : CtxStream {
     DevBuf tx_sup, tx_offs, tx_count, tx_verdict, tx_cnt, tx_pos, tx_first, tx_ctl;
     ResultKey tx_key;
     u64 tx_slots = 0, tx_words[8] = {};
+    // kmc_unitig_contigs* (kmc_contigs.hip.h) read the unitig arrays, the links and the transit counts.  Their result, in
+    // buffers of their own: bases, offsets, path offsets, path, abundances, flags, with ct_key plus its two parameters
+    // ct_reads / ct_support and ct_words as above.  Whatever drops l_key or tx_key drops ct_key, and so does every transits
+    // call (the counts changed).  Work arrays: copies and sigma per unitig, node_offsets, the unitig of a node; over the
+    // 2 * n_nodes node ends what u_link .. u_circ are over the side states (the unitigs' own stay as they are: a links or
+    // map call may still read them); per path slot its contig, key count, their scan, start base and source base; the
+    // control words and round counts.
+    DevBuf ct_bases, ct_offs, ct_poffs, ct_path, ct_abund, ct_flags;
+    DevBuf ct_copies, ct_sigma, ct_pos, ct_owner, ct_link, ct_join, ct_ptr[2], ct_dist[2], ct_circ, ct_cid, ct_keys, ct_g, ct_start, ct_src, ct_ctl;
+    ResultKey ct_key;
+    u64 ct_reads = 0, ct_support = 0, ct_words[8] = {};
 };
 
 #pragma GCC visibility push(hidden)   // what follows is shared between the translation units, never exported

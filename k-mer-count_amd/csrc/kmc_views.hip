@@ -20,6 +20,7 @@
 #include "kmc_transits.hip.h"
 #include "kmc_correct.hip.h"
 #include "kmc_trim.hip.h"
+#include "kmc_contigs.hip.h"
 #include "kmc_normalize.hip.h"
 
 namespace {
@@ -682,13 +683,20 @@ struct UnitigTrace {
     ~UnitigTrace() { for (int i = 0; i < n_ev; ++i) (void)hipEventDestroy(ev[i]); }
 };
 
-// Ranks the n2 side states along joined (kmc_unitig.hip.h): on return u_ptr[*cur] / u_dist[*cur] hold every path state's end
+// The arrays of a ranking: the unitigs' over the side states of the view rows (u_*), the contigs' over the node ends (ct_*)
+struct RankBufs { u32* joined; u32* ptr[2]; u32* dist[2]; uint8_t* circ; u32* cnt; };   // (cnt: KMC_U_ROUND_SLOTS round counts)
+static RankBufs unitig_bufs(kmc_ctx* c) {
+    return RankBufs{(u32*)c->u_join.p, {(u32*)c->u_ptr[0].p, (u32*)c->u_ptr[1].p}, {(u32*)c->u_dist[0].p, (u32*)c->u_dist[1].p},
+                    (uint8_t*)c->u_circ.p, (u32*)((u64*)c->u_ctl.p + 10)};
+}
+
+// Ranks the n2 side states along B.joined (kmc_unitig.hip.h): on return B.ptr[*cur] / B.dist[*cur] hold every path state's end
 // and distance, *open the states on cycles, *rounds is raised by the rounds launched.  Waits for the result.
-static int unitig_rank(kmc_ctx* c, u64 n2, int* cur, u32* rounds, u32* open) {
-    const u32* joined = (const u32*)c->u_join.p;
-    u32* ptr[2] = {(u32*)c->u_ptr[0].p, (u32*)c->u_ptr[1].p};
-    u32* dist[2] = {(u32*)c->u_dist[0].p, (u32*)c->u_dist[1].p};
-    u32* cnt = (u32*)((u64*)c->u_ctl.p + 10);
+static int unitig_rank(kmc_ctx* c, const RankBufs& B, u64 n2, int* cur, u32* rounds, u32* open) {
+    const u32* joined = B.joined;
+    u32* const* ptr = B.ptr;
+    u32* const* dist = B.dist;
+    u32* cnt = B.cnt;
     const u32 grid = (u32)((n2 + KMC_U_THREADS - 1) / KMC_U_THREADS);
     HIPCHK(c, hipMemsetAsync(cnt, 0, KMC_U_ROUND_SLOTS * sizeof(u32), c->stream));
     hipLaunchKernelGGL(kmc_unitig_rank_init_kernel, dim3(grid), dim3(KMC_U_THREADS), 0, c->stream, joined, n2, ptr[0], dist[0], cnt);
@@ -716,13 +724,38 @@ static int unitig_rank(kmc_ctx* c, u64 n2, int* cur, u32* rounds, u32* open) {
     return KMC_OK;
 }
 
+// The states the ranking left open lie on cycles (kmc_unitig.hip.h): every cycle is cut at side L of its smallest row, the
+// row is marked in circ, and the ranking runs again.  Nothing to do when open is 0.
+static int unitig_cut_cycles(kmc_ctx* c, const char* what, const RankBufs& B, u64 n, int* cur, u32* rounds, u32 open) {
+    if (!open) return KMC_OK;
+    const u64 n2 = 2 * n;
+    const u32 grid_n = (u32)((n + KMC_U_THREADS - 1) / KMC_U_THREADS), grid_2n = (u32)((n2 + KMC_U_THREADS - 1) / KMC_U_THREADS);
+    u32* const* ptr = B.ptr;
+    u32* const* mrow = B.dist;
+    hipLaunchKernelGGL(kmc_unitig_cycle_mark_kernel, dim3(grid_n), dim3(KMC_U_THREADS), 0, c->stream, (const u32*)B.joined,
+                       (const u32*)ptr[*cur], n, B.circ);
+    hipLaunchKernelGGL(kmc_unitig_minrow_init_kernel, dim3(grid_2n), dim3(KMC_U_THREADS), 0, c->stream, (const u32*)B.joined, n2, ptr[0], mrow[0]);
+    int cover = 0, b = 0;   // 2^cover states of a cycle seen from every state: the longest cycle has at most `open`
+    while ((1ull << cover) < open) ++cover;
+    for (int i = 0; i < cover; ++i) {
+        hipLaunchKernelGGL(kmc_unitig_minrow_round_kernel, dim3(grid_2n), dim3(KMC_U_THREADS), 0, c->stream, n2, (const u32*)ptr[b],
+                           (const u32*)mrow[b], ptr[b ^ 1], mrow[b ^ 1]);
+        b ^= 1;
+    }
+    hipLaunchKernelGGL(kmc_unitig_cycle_cut_kernel, dim3(grid_n), dim3(KMC_U_THREADS), 0, c->stream, (const u32*)mrow[b], n, B.joined, B.circ);
+    HIPCHK(c, hipGetLastError());
+    if (int rc = unitig_rank(c, B, n2, cur, rounds, &open)) return rc;
+    if (open) return fail(c, KMC_ERR_HIP, "internal error: %s left %u side states on cycles after the cut", what, open);
+    return KMC_OK;
+}
+
 // Everything on the device: the four arrays into the ctx's u_* buffers, the summary into h[KMC_UNITIG_WORDS]; finished
 // when it returns (kmc_export_device's ordering contract).
 static int unitig_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count, u64* h) {
     memset(h, 0, KMC_UNITIG_WORDS * sizeof(u64));
     const u64 n = c->n_sorted, n2 = 2 * n;
     int rc;
-    c->u_key.drop(); c->l_key.drop(); c->cc_key.drop(); c->bb_key.drop(); c->tx_key.drop();   // the result arrays are rewritten from here on (and the links of the old ones, their components, their bubbles and their transit counts go with them)
+    c->u_key.drop(); c->l_key.drop(); c->cc_key.drop(); c->bb_key.drop(); c->tx_key.drop(); c->ct_key.drop();   // the result arrays are rewritten from here on (and the links of the old ones, their components, their bubbles and their transit counts go with them)
     if ((rc = ensure(c, c->u_offs, sizeof(u64))) || (rc = ensure(c, c->u_bases, 64)) || (rc = ensure(c, c->u_abund, sizeof(u64))) ||
         (rc = ensure(c, c->u_flags, 8)))
         return rc;
@@ -762,27 +795,11 @@ static int unitig_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count
     // ranking; cycles, if there are any, are cut and the ranking runs again
     int cur = 0;
     u32 rounds = 0, open = 0, cycle_states = 0;
-    if ((rc = unitig_rank(c, n2, &cur, &rounds, &open))) return rc;
+    const RankBufs B = unitig_bufs(c);
+    if ((rc = unitig_rank(c, B, n2, &cur, &rounds, &open))) return rc;
     tr.mark(c->stream);
-    if (open) {
-        cycle_states = open;
-        u32* ptr[2] = {(u32*)c->u_ptr[0].p, (u32*)c->u_ptr[1].p};
-        u32* mrow[2] = {(u32*)c->u_dist[0].p, (u32*)c->u_dist[1].p};
-        hipLaunchKernelGGL(kmc_unitig_cycle_mark_kernel, dim3(grid_n), dim3(KMC_U_THREADS), 0, c->stream, (const u32*)joined,
-                           (const u32*)ptr[cur], n, circ);
-        hipLaunchKernelGGL(kmc_unitig_minrow_init_kernel, dim3(grid_2n), dim3(KMC_U_THREADS), 0, c->stream, (const u32*)joined, n2, ptr[0], mrow[0]);
-        int cover = 0, b = 0;   // 2^cover states of a cycle seen from every state: the longest cycle has at most `open`
-        while ((1ull << cover) < open) ++cover;
-        for (int i = 0; i < cover; ++i) {
-            hipLaunchKernelGGL(kmc_unitig_minrow_round_kernel, dim3(grid_2n), dim3(KMC_U_THREADS), 0, c->stream, n2, (const u32*)ptr[b],
-                               (const u32*)mrow[b], ptr[b ^ 1], mrow[b ^ 1]);
-            b ^= 1;
-        }
-        hipLaunchKernelGGL(kmc_unitig_cycle_cut_kernel, dim3(grid_n), dim3(KMC_U_THREADS), 0, c->stream, (const u32*)mrow[b], n, joined, circ);
-        HIPCHK(c, hipGetLastError());
-        if ((rc = unitig_rank(c, n2, &cur, &rounds, &open))) return rc;
-        if (open) return fail(c, KMC_ERR_HIP, "internal error: %s left %u side states on cycles after the cut", what, open);
-    }
+    cycle_states = open;
+    if ((rc = unitig_cut_cycles(c, what, B, n, &cur, &rounds, open))) return rc;
     tr.mark(c->stream);
     // layout: first keys and their key counts (link is free now), their scans (joined is free now)
     const u32 *ptr = (const u32*)c->u_ptr[cur].p, *dist = (const u32*)c->u_dist[cur].p;
@@ -905,7 +922,7 @@ static int links_run(kmc_ctx* c, const char* what, u64* h) {
     memset(h, 0, KMC_LINK_WORDS * sizeof(u64));
     const u64 n = c->n_sorted, nu = c->u_words[0], ne = 2 * nu;
     int rc;
-    c->l_key.drop(); c->cc_key.drop(); c->bb_key.drop(); c->tx_key.drop();
+    c->l_key.drop(); c->cc_key.drop(); c->bb_key.drop(); c->tx_key.drop(); c->ct_key.drop();
     if ((rc = ensure(c, c->l_offs, (size_t)(ne + 1) * sizeof(u64))) || (rc = ensure(c, c->l_to, sizeof(u32)))) return rc;
     if (!nu) {   // an empty view, or one without a solid key
         HIPCHK(c, hipMemsetAsync(c->l_offs.p, 0, sizeof(u64), c->stream));
@@ -1202,6 +1219,7 @@ static int transits_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_cou
     const bool links_reused = held && c->l_key.holds(c->view_gen, min_count, max_count);
     if (accumulate && !(links_reused && c->tx_key.holds(c->view_gen, min_count, max_count)))
         return fail(c, KMC_ERR_STATE, "%s: KMC_TRANSIT_ACCUMULATE, and the ctx holds no transits of this view and range to add to", what);
+    c->ct_key.drop();   // the counts a held contig result was made from change
     if ((rc = links_result(c, what, min_count, max_count, held, lw))) return rc;
     const u64 n = c->n_sorted, nu = lw[0], nl = lw[1];
     if (nu > n || c->u_words[0] != nu)
@@ -1356,6 +1374,213 @@ static int kmc_unitig_transits_impl(kmc_ctx* c, uint64_t min_count, uint64_t max
     if (verdict && nu) HIPCHK(c, hipMemcpyAsync(verdict, c->tx_verdict.p, (size_t)nu, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (summary) memcpy(summary, c->tx_words, sizeof(c->tx_words));
+    return KMC_OK;
+}
+
+// ---- the counted walks acted on: resolved repeats duplicated, unsupported links ignored, contigs spelled (kmc_contigs.hip.h) ----
+// What both calls check first.  The call computes nothing it was not given: the unitigs, the links and a transits result of
+// this view and range must be held (the result keys, not the work arrays: a kmc_graph* call in between does not matter).
+static int contigs_begin(kmc_ctx* c, const char* what, uint64_t min_count, uint64_t max_count) {
+    if (int rc = unitig_begin(c, what, min_count, max_count)) return rc;
+    const char* missing = !c->u_key.holds(c->view_gen, min_count, max_count)    ? "unitigs (kmc_unitigs*)"
+                          : !c->l_key.holds(c->view_gen, min_count, max_count)  ? "links (kmc_unitig_links*)"
+                          : !c->tx_key.holds(c->view_gen, min_count, max_count) ? "transits (kmc_unitig_transits*)"
+                                                                                : nullptr;
+    if (missing) return fail(c, KMC_ERR_STATE, "%s: the ctx holds no %s of this view and range", what, missing);
+    return KMC_OK;
+}
+
+static bool contigs_kept(const kmc_ctx* c, u64 min_count, u64 max_count, u64 min_reads, u64 min_support) {
+    return c->ct_key.holds(c->view_gen, min_count, max_count) && c->ct_reads == min_reads && c->ct_support == min_support;
+}
+
+// The contigs of the held unitigs, links and transit counts into the ct_* buffers, the summary into h[KMC_CONTIG_WORDS];
+// finished when it returns.  It reads u_bases / u_offs / u_abund, l_offs / l_to, tx_sup / tx_offs / tx_count and writes
+// nothing but its own buffers and the block sums of a scan (c_bsum).
+static int contigs_run(kmc_ctx* c, const char* what, u64 min_reads, u64 min_support, u64* h) {
+    memset(h, 0, KMC_CONTIG_WORDS * sizeof(u64));
+    const u64 nu = c->u_words[0], u_nb = c->u_words[1], nl = c->l_words[1], n_slots = c->tx_slots;
+    const int k = c->klen;
+    int rc;
+    c->ct_key.drop();
+    if ((rc = ensure(c, c->ct_offs, sizeof(u64))) || (rc = ensure(c, c->ct_poffs, sizeof(u64))) || (rc = ensure(c, c->ct_bases, 64)) ||
+        (rc = ensure(c, c->ct_path, sizeof(u32))) || (rc = ensure(c, c->ct_abund, sizeof(u64))) || (rc = ensure(c, c->ct_flags, 8)))
+        return rc;
+    if (!nu) {   // an empty view, or one without a solid key
+        HIPCHK(c, hipMemsetAsync(c->ct_offs.p, 0, sizeof(u64), c->stream));
+        HIPCHK(c, hipMemsetAsync(c->ct_poffs.p, 0, sizeof(u64), c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return KMC_OK;
+    }
+    if (c->l_words[0] != nu) return fail(c, KMC_ERR_HIP, "internal error: %s holds %llu unitigs, its links %llu", what, (unsigned long long)nu, (unsigned long long)c->l_words[0]);
+    UnitigTrace tr;
+    tr.mark(c->stream);
+    TransitGraph g;
+    g.link_offsets = (const u64*)c->l_offs.p; g.link_to = (const u32*)c->l_to.p; g.n_unitigs = nu; g.n_links = nl;
+    const auto blocks = [](u64 n) { return dim3((u32)((n + KMC_CT_THREADS - 1) / KMC_CT_THREADS)); };
+    const auto bsum_bytes = [](u64 n) { return (size_t)((n + KMC_SCAN_PER_BLOCK - 1) / KMC_SCAN_PER_BLOCK + 2) * sizeof(u32); };
+    // nodes: copies and sigma per unitig, node_offsets
+    if ((rc = ensure(c, c->ct_copies, (size_t)nu * sizeof(u32))) || (rc = ensure(c, c->ct_sigma, (size_t)nu)) ||
+        (rc = ensure(c, c->ct_pos, (size_t)nu * sizeof(u32))) || (rc = ensure(c, c->ct_ctl, KMC_CT_CTL_BYTES)) || (rc = ensure(c, c->c_bsum, bsum_bytes(nu))))
+        return rc;
+    kmc_ull* ctl = (kmc_ull*)c->ct_ctl.p;
+    u64 w[KMC_CT_CTL_WORDS];
+    const auto read_ctl = [&]() -> int {
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(w, ctl, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (w[KMC_CT_BAD]) return fail(c, KMC_ERR_HIP, "internal error: %s met %llu indices outside their arrays", what, (unsigned long long)w[KMC_CT_BAD]);
+        return KMC_OK;
+    };
+    HIPCHK(c, hipMemsetAsync(ctl, 0, KMC_CT_CTL_BYTES, c->stream));
+    const u32* copies = (const u32*)c->ct_copies.p;
+    const uint8_t* sigma = (const uint8_t*)c->ct_sigma.p;
+    const u32* node_offsets = (const u32*)c->ct_pos.p;
+    hipLaunchKernelGGL(kmc_contig_nodes_kernel, blocks(nu), dim3(KMC_CT_THREADS), 0, c->stream, g, (const u64*)c->tx_offs.p, n_slots,
+                       (const kmc_ull*)c->tx_sup.p, (const kmc_ull*)c->tx_count.p, std::max<u64>(min_reads, 1), min_support, (u32*)c->ct_copies.p,
+                       (uint8_t*)c->ct_sigma.p, ctl);
+    launch_exclusive_scan<0>(c->stream, copies, (u32)nu, (u32*)c->c_bsum.p, (u32*)c->ct_pos.p, (u32*)(ctl + KMC_CT_SCAN_N));
+    if ((rc = read_ctl())) return rc;
+    const u64 nn = w[KMC_CT_NODES], n2 = 2 * nn;
+    if (nn >= (1ull << 31)) return fail(c, KMC_ERR_CAPACITY, "%s: 2^31 nodes or more have more ends than a u32 numbers", what);
+    if ((w[KMC_CT_SCAN_N] & 0xFFFFFFFFull) != nn || nn < nu)
+        return fail(c, KMC_ERR_HIP, "internal error: %s scanned %llu of %llu nodes", what, (unsigned long long)(w[KMC_CT_SCAN_N] & 0xFFFFFFFFull), (unsigned long long)nn);
+    // choice and join over the 2 * nn node ends
+    const size_t sb = (size_t)n2 * sizeof(u32);
+    if ((rc = ensure(c, c->ct_owner, (size_t)nn * sizeof(u32))) || (rc = ensure(c, c->ct_link, sb)) || (rc = ensure(c, c->ct_join, sb)) ||
+        (rc = ensure(c, c->ct_ptr[0], sb)) || (rc = ensure(c, c->ct_ptr[1], sb)) || (rc = ensure(c, c->ct_dist[0], sb)) ||
+        (rc = ensure(c, c->ct_dist[1], sb)) || (rc = ensure(c, c->ct_circ, (size_t)nn)) || (rc = ensure(c, c->c_bsum, bsum_bytes(nn))))
+        return rc;
+    const u32* owner = (const u32*)c->ct_owner.p;
+    u32 *link = (u32*)c->ct_link.p, *joined = (u32*)c->ct_join.p;
+    HIPCHK(c, hipMemsetAsync(c->ct_circ.p, 0, (size_t)nn, c->stream));
+    hipLaunchKernelGGL(kmc_contig_owner_kernel, blocks(nu), dim3(KMC_CT_THREADS), 0, c->stream, copies, node_offsets, nu, nn, (u32*)c->ct_owner.p, ctl);
+    hipLaunchKernelGGL(kmc_contig_choice_kernel, blocks(n2), dim3(KMC_CT_THREADS), 0, c->stream, g, (const kmc_ull*)c->tx_sup.p, min_support, copies, sigma,
+                       node_offsets, owner, nn, link, ctl);
+    hipLaunchKernelGGL(kmc_unitig_join_kernel, blocks(n2), dim3(KMC_U_THREADS), 0, c->stream, (const u32*)link, n2, joined, ctl + KMC_CT_UNJOINED);
+    if ((rc = read_ctl())) return rc;   // (before the ranking follows the choices)
+    tr.mark(c->stream);
+    // ranking; cycles, if there are any, are cut at the START end of their smallest node and the ranking runs again
+    const RankBufs B{joined, {(u32*)c->ct_ptr[0].p, (u32*)c->ct_ptr[1].p}, {(u32*)c->ct_dist[0].p, (u32*)c->ct_dist[1].p}, (uint8_t*)c->ct_circ.p,
+                     (u32*)(ctl + KMC_CT_CTL_WORDS)};
+    int cur = 0;
+    u32 rounds = 0, open = 0;
+    if ((rc = unitig_rank(c, B, n2, &cur, &rounds, &open)) || (rc = unitig_cut_cycles(c, what, B, nn, &cur, &rounds, open))) return rc;
+    tr.mark(c->stream);
+    // layout: start nodes and their node counts (link is free now), their scans (joined is free now)
+    const u32 *ptr = B.ptr[cur], *dist = B.dist[cur];
+    u32 *is_first = link, *first_len = link + nn, *cid_of = joined, *poff_of = joined + nn;
+    hipLaunchKernelGGL(kmc_contig_place_kernel, blocks(nn), dim3(KMC_CT_THREADS), 0, c->stream, nn, ptr, dist, is_first, first_len);
+    launch_exclusive_scan<0>(c->stream, is_first, (u32)nn, (u32*)c->c_bsum.p, cid_of, (u32*)(ctl + KMC_CT_SCAN_C));
+    launch_exclusive_scan<0>(c->stream, first_len, (u32)nn, (u32*)c->c_bsum.p, poff_of, (u32*)(ctl + KMC_CT_SCAN_P));
+    if ((rc = read_ctl())) return rc;
+    const u64 nc = w[KMC_CT_SCAN_C] & 0xFFFFFFFFull;
+    if ((w[KMC_CT_SCAN_P] & 0xFFFFFFFFull) != nn || !nc || nc > nn)
+        return fail(c, KMC_ERR_HIP, "internal error: %s laid out %llu of %llu nodes in %llu contigs", what, (unsigned long long)(w[KMC_CT_SCAN_P] & 0xFFFFFFFFull),
+                    (unsigned long long)nn, (unsigned long long)nc);
+    if ((rc = ensure(c, c->ct_poffs, (size_t)(nc + 1) * sizeof(u64))) || (rc = ensure(c, c->ct_offs, (size_t)(nc + 1) * sizeof(u64))) ||
+        (rc = ensure(c, c->ct_abund, (size_t)nc * sizeof(u64))) || (rc = ensure(c, c->ct_flags, (size_t)std::max<u64>(nc, 8))) ||
+        (rc = ensure(c, c->ct_path, (size_t)nn * sizeof(u32))) || (rc = ensure(c, c->ct_cid, (size_t)nn * sizeof(u32))) ||
+        (rc = ensure(c, c->ct_keys, (size_t)nn * sizeof(u32))) || (rc = ensure(c, c->ct_g, (size_t)nn * sizeof(u32))) ||
+        (rc = ensure(c, c->ct_start, (size_t)(nn + 1) * sizeof(u64))) || (rc = ensure(c, c->ct_src, (size_t)nn * sizeof(u64))))
+        return rc;
+    HIPCHK(c, hipMemsetAsync(c->ct_abund.p, 0, (size_t)nc * sizeof(u64), c->stream));
+    ContigSrc S;
+    S.u_offs = (const u64*)c->u_offs.p; S.u_abund = (const kmc_ull*)c->u_abund.p; S.n_unitigs = nu; S.u_bases = u_nb;
+    hipLaunchKernelGGL(kmc_contig_path_kernel, blocks(nn), dim3(KMC_CT_THREADS), 0, c->stream, nn, nc, k, ptr, dist, (const u32*)cid_of, (const u32*)poff_of,
+                       (const uint8_t*)c->ct_circ.p, owner, S, (u32*)c->ct_path.p, (u32*)c->ct_cid.p, (u32*)c->ct_keys.p, (u64*)c->ct_src.p,
+                       (u64*)c->ct_poffs.p, (kmc_ull*)c->ct_abund.p, (uint8_t*)c->ct_flags.p, ctl);
+    launch_exclusive_scan<0>(c->stream, c->ct_keys.p, (u32)nn, (u32*)c->c_bsum.p, (u32*)c->ct_g.p, (u32*)(ctl + KMC_CT_SCAN_G));
+    if ((rc = read_ctl())) return rc;
+    const u64 nk = w[KMC_CT_KEYS], nb = nk + nc * (u64)(k - 1);
+    if (nk >= (1ull << 32)) return fail(c, KMC_ERR_CAPACITY, "%s: 2^32 keys or more over the paths", what);
+    if ((w[KMC_CT_SCAN_G] & 0xFFFFFFFFull) != nk)
+        return fail(c, KMC_ERR_HIP, "internal error: %s scanned %llu of %llu keys", what, (unsigned long long)(w[KMC_CT_SCAN_G] & 0xFFFFFFFFull), (unsigned long long)nk);
+    if ((rc = ensure(c, c->ct_bases, (size_t)nb + 64))) return rc;
+    hipLaunchKernelGGL(kmc_contig_starts_kernel, blocks(nn), dim3(KMC_CT_THREADS), 0, c->stream, nn, nc, k, nb, (const u32*)c->ct_g.p, (const u32*)c->ct_cid.p,
+                       (const u64*)c->ct_poffs.p, (u64*)c->ct_start.p, (u64*)c->ct_offs.p, ctl);
+    HIPCHK(c, hipGetLastError());
+    tr.mark(c->stream);
+    // emit (d_bases is readable up to the next 16-byte boundary: the rule of kmc_add_batch_device)
+    hipLaunchKernelGGL(kmc_contig_emit_kernel, blocks((nb + 15) / 16), dim3(KMC_CT_THREADS), 0, c->stream, (const uint8_t*)c->u_bases.p, u_nb, nn, nb,
+                       (const u64*)c->ct_start.p, (const u64*)c->ct_src.p, (const u32*)c->ct_path.p, (uint8_t*)c->ct_bases.p, ctl);
+    tr.mark(c->stream);   // (as the trim call marks its gather: the kernel, not the copy of the control words and the wait)
+    if ((rc = read_ctl())) return rc;
+    h[0] = nc; h[1] = nn; h[2] = w[KMC_CT_DUP]; h[3] = w[KMC_CT_IGNORED]; h[4] = w[KMC_CT_CIRC]; h[5] = w[KMC_CT_ONE]; h[6] = w[KMC_CT_MOST]; h[7] = nb;
+    if (tr.on && tr.n_ev == 5) {
+        float ms[4] = {0, 0, 0, 0};
+        bool ok = hipEventSynchronize(tr.ev[4]) == hipSuccess;
+        for (int i = 0; ok && i < 4; ++i) ok = hipEventElapsedTime(&ms[i], tr.ev[i], tr.ev[i + 1]) == hipSuccess;
+        if (ok)
+            fprintf(stderr, "kmc_unitig_contigs: unitigs %llu nodes %llu contigs %llu bases %llu rounds %u choice_ms %.4f rank_ms %.4f layout_ms %.4f emit_ms %.4f\n",
+                    (unsigned long long)nu, (unsigned long long)nn, (unsigned long long)nc, (unsigned long long)nb, rounds, ms[0], ms[1], ms[2], ms[3]);
+    }
+    return KMC_OK;
+}
+
+// what both calls do once the state is in order: the held result (host form only) or a run that is kept
+static int contigs_result(kmc_ctx* c, const char* what, u64 min_count, u64 max_count, u64 min_reads, u64 min_support, bool may_reuse, u64* h) {
+    min_reads = std::max<u64>(min_reads, 1);
+    if (may_reuse && contigs_kept(c, min_count, max_count, min_reads, min_support)) {
+        memcpy(h, c->ct_words, sizeof(c->ct_words));
+        return KMC_OK;
+    }
+    if (int rc = contigs_run(c, what, min_reads, min_support, h)) return rc;
+    c->ct_key.keep(c->view_gen, min_count, max_count);
+    c->ct_reads = min_reads; c->ct_support = min_support;
+    memcpy(c->ct_words, h, sizeof(c->ct_words));
+    return KMC_OK;
+}
+
+static int kmc_unitig_contigs_device_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t min_reads, uint64_t min_support,
+                                          const void** d_bases, const void** d_offsets, const void** d_path_offsets, const void** d_path,
+                                          const void** d_abund, const void** d_flags, uint64_t* n_contigs, uint64_t* n_nodes, uint64_t* n_bases,
+                                          uint64_t* summary) {
+    if (!c) return KMC_ERR_ARG;
+    const char* what = "kmc_unitig_contigs_device";
+    u64 h[KMC_CONTIG_WORDS];
+    int rc;
+    if ((rc = contigs_begin(c, what, min_count, max_count)) || (rc = contigs_result(c, what, min_count, max_count, min_reads, min_support, false, h))) return rc;
+    if (d_bases) *d_bases = c->ct_bases.p;
+    if (d_offsets) *d_offsets = c->ct_offs.p;
+    if (d_path_offsets) *d_path_offsets = c->ct_poffs.p;
+    if (d_path) *d_path = c->ct_path.p;
+    if (d_abund) *d_abund = c->ct_abund.p;
+    if (d_flags) *d_flags = c->ct_flags.p;
+    if (n_contigs) *n_contigs = h[0];
+    if (n_nodes) *n_nodes = h[1];
+    if (n_bases) *n_bases = h[7];
+    if (summary) memcpy(summary, h, sizeof(h));
+    return KMC_OK;
+}
+
+static int kmc_unitig_contigs_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t min_reads, uint64_t min_support, uint8_t* bases,
+                                   uint64_t cap_bases, uint64_t* offsets, uint64_t* path_offsets, uint64_t* abund, uint8_t* flags, uint64_t cap_contigs,
+                                   uint32_t* path, uint64_t cap_nodes, uint64_t* n_contigs, uint64_t* n_nodes, uint64_t* n_bases, uint64_t* summary) {
+    if (n_contigs) *n_contigs = 0;
+    if (n_nodes) *n_nodes = 0;
+    if (n_bases) *n_bases = 0;
+    if (!c) return KMC_ERR_ARG;
+    const char* what = "kmc_unitig_contigs";
+    u64 h[KMC_CONTIG_WORDS];
+    int rc;
+    if ((rc = contigs_begin(c, what, min_count, max_count)) || (rc = contigs_result(c, what, min_count, max_count, min_reads, min_support, true, h))) return rc;
+    const u64 nc = h[0], nn = h[1], nb = h[7];
+    if (n_contigs) *n_contigs = nc;
+    if (n_nodes) *n_nodes = nn;
+    if (n_bases) *n_bases = nb;
+    if (bases && cap_bases < nb) return fail(c, KMC_ERR_ARG, "%s: capacity %llu < %llu bases", what, (unsigned long long)cap_bases, (unsigned long long)nb);
+    if ((offsets || path_offsets || abund || flags) && cap_contigs < nc)
+        return fail(c, KMC_ERR_ARG, "%s: capacity %llu < %llu contigs", what, (unsigned long long)cap_contigs, (unsigned long long)nc);
+    if (path && cap_nodes < nn) return fail(c, KMC_ERR_ARG, "%s: capacity %llu < %llu nodes", what, (unsigned long long)cap_nodes, (unsigned long long)nn);
+    if (bases && nb) HIPCHK(c, hipMemcpyAsync(bases, c->ct_bases.p, (size_t)nb, hipMemcpyDeviceToHost, c->stream));
+    if (offsets) HIPCHK(c, hipMemcpyAsync(offsets, c->ct_offs.p, (size_t)(nc + 1) * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    if (path_offsets) HIPCHK(c, hipMemcpyAsync(path_offsets, c->ct_poffs.p, (size_t)(nc + 1) * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    if (abund && nc) HIPCHK(c, hipMemcpyAsync(abund, c->ct_abund.p, (size_t)nc * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    if (flags && nc) HIPCHK(c, hipMemcpyAsync(flags, c->ct_flags.p, (size_t)nc, hipMemcpyDeviceToHost, c->stream));
+    if (path && nn) HIPCHK(c, hipMemcpyAsync(path, c->ct_path.p, (size_t)nn * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (summary) memcpy(summary, h, sizeof(h));
     return KMC_OK;
 }
 
@@ -2424,6 +2649,24 @@ extern "C" int kmc_unitig_transits(kmc_ctx* c, uint64_t min_count, uint64_t max_
     return guarded(c, [&]() -> int {
         return kmc_unitig_transits_impl(c, min_count, max_count, min_reads, flags, bases, offsets, n_reads, link_support, cap_links, transit_offsets,
                                         cap_unitigs, transit_count, cap_slots, verdict, n_unitigs, n_links, n_slots, summary);
+    });
+}
+extern "C" int kmc_unitig_contigs_device(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t min_reads, uint64_t min_support,
+                                         const void** d_bases, const void** d_offsets, const void** d_path_offsets, const void** d_path,
+                                         const void** d_abund, const void** d_flags, uint64_t* n_contigs, uint64_t* n_nodes, uint64_t* n_bases,
+                                         uint64_t* summary) {
+    return guarded(c, [&]() -> int {
+        return kmc_unitig_contigs_device_impl(c, min_count, max_count, min_reads, min_support, d_bases, d_offsets, d_path_offsets, d_path, d_abund,
+                                              d_flags, n_contigs, n_nodes, n_bases, summary);
+    });
+}
+extern "C" int kmc_unitig_contigs(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t min_reads, uint64_t min_support, uint8_t* bases,
+                                  uint64_t cap_bases, uint64_t* offsets, uint64_t* path_offsets, uint64_t* abund, uint8_t* flags,
+                                  uint64_t cap_contigs, uint32_t* path, uint64_t cap_nodes, uint64_t* n_contigs, uint64_t* n_nodes,
+                                  uint64_t* n_bases, uint64_t* summary) {
+    return guarded(c, [&]() -> int {
+        return kmc_unitig_contigs_impl(c, min_count, max_count, min_reads, min_support, bases, cap_bases, offsets, path_offsets, abund, flags,
+                                       cap_contigs, path, cap_nodes, n_contigs, n_nodes, n_bases, summary);
     });
 }
 extern "C" int kmc_correct_device(kmc_ctx* c, uint64_t min_count, uint64_t max_count, const void* d_bases, const void* d_offsets, uint64_t n_reads,

@@ -44,6 +44,8 @@ pub const KMC_TRANSIT_UNSPANNED: u8 = 1;
 pub const KMC_TRANSIT_RESOLVED: u8 = 2;
 pub const KMC_TRANSIT_AMBIGUOUS: u8 = 3;
 pub const KMC_TRANSIT_ACCUMULATE: u32 = 1;
+/// summary words of `kmc_unitig_contigs`
+pub const KMC_CONTIG_WORDS: usize = 8;
 /// summary words of `kmc_correct`, words per read of its `read_stats`, the kinds of a candidate
 pub const KMC_CORRECT_WORDS: usize = 8;
 pub const KMC_CORRECT_READ_WORDS: usize = 4;
@@ -209,6 +211,8 @@ extern "C" {
     pub fn kmc_unitig_map(ctx: *mut KmcCtx, min_count: u64, max_count: u64, bases: *const u8, offsets: *const u64, n_reads: u64, place: *mut u64, read_stats: *mut u32, seg_offsets: *mut u64, segs: *mut u32, cap_segs: u64, support: *mut u64, cap_unitigs: u64, n_segs: *mut u64, n_unitigs: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_transits_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, min_reads: u64, flags: u32, d_bases: *const c_void, d_offsets: *const c_void, n_reads: u64, n_bases: u64, d_link_support: *mut *const c_void, d_transit_offsets: *mut *const c_void, d_transit_count: *mut *const c_void, d_verdict: *mut *const c_void, n_unitigs: *mut u64, n_links: *mut u64, n_slots: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_transits(ctx: *mut KmcCtx, min_count: u64, max_count: u64, min_reads: u64, flags: u32, bases: *const u8, offsets: *const u64, n_reads: u64, link_support: *mut u64, cap_links: u64, transit_offsets: *mut u64, cap_unitigs: u64, transit_count: *mut u64, cap_slots: u64, verdict: *mut u8, n_unitigs: *mut u64, n_links: *mut u64, n_slots: *mut u64, summary: *mut u64) -> c_int;
+    pub fn kmc_unitig_contigs_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, min_reads: u64, min_support: u64, d_bases: *mut *const c_void, d_offsets: *mut *const c_void, d_path_offsets: *mut *const c_void, d_path: *mut *const c_void, d_abund: *mut *const c_void, d_flags: *mut *const c_void, n_contigs: *mut u64, n_nodes: *mut u64, n_bases: *mut u64, summary: *mut u64) -> c_int;
+    pub fn kmc_unitig_contigs(ctx: *mut KmcCtx, min_count: u64, max_count: u64, min_reads: u64, min_support: u64, bases: *mut u8, cap_bases: u64, offsets: *mut u64, path_offsets: *mut u64, abund: *mut u64, flags: *mut u8, cap_contigs: u64, path: *mut u32, cap_nodes: u64, n_contigs: *mut u64, n_nodes: *mut u64, n_bases: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_correct_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, d_bases: *const c_void, d_offsets: *const c_void, n_reads: u64, n_bases: u64, d_corrected: *mut *const c_void, d_read_stats: *mut *const c_void, d_cand_offsets: *mut *const c_void, d_cands: *mut *const c_void, n_cands: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_correct(ctx: *mut KmcCtx, min_count: u64, max_count: u64, bases: *const u8, offsets: *const u64, n_reads: u64, out_bases: *mut u8, read_stats: *mut u32, cand_offsets: *mut u64, cands: *mut u32, cap_cands: u64, n_cands: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_trim_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, mode: c_int, flags: u32, min_strong: u64, min_permille: u32, min_len: u64, d_bases: *const c_void, d_offsets: *const c_void, n_reads: u64, n_bases: u64, d_out_bases: *mut *const c_void, d_out_offsets: *mut *const c_void, d_origin: *mut *const c_void, d_read_stats: *mut *const c_void, d_verdict: *mut *const c_void, n_out: *mut u64, n_out_bases: *mut u64, summary: *mut u64) -> c_int;
@@ -565,6 +569,37 @@ impl Counter {
         })?;
         count.truncate(nsl as usize);
         Ok((support, transit_offsets, count, verdict, w))
+    }
+
+    /// The contigs of the counted walks (`kmc_unitig_contigs`): behind a `transits` call of the same range, every repeat its
+    /// counts resolve under `min_reads` has one copy per matched way through it, records below `min_support` are ignored at
+    /// the ends of single-copy unitigs (0: none is), and the chains that remain are spelled out.  Returns the bases
+    /// (concatenated), `offsets[n_contigs + 1]`, `path_offsets[n_contigs + 1]`, the path entries `2 * unitig + o` (o = 1: read
+    /// reverse-complemented), the abundance per contig (a duplicated repeat counts in full in each copy), the flags (bit 0:
+    /// circular) and the eight summary words [contigs, nodes, unitigs duplicated, records ignored, circular, one-node, most
+    /// nodes in one, bases].  A sizing call, then the copy call: the library computes once.
+    #[allow(clippy::type_complexity)]
+    pub fn contigs(&mut self, min_count: u64, max_count: u64, min_reads: u64, min_support: u64)
+                   -> Result<(Vec<u8>, Vec<u64>, Vec<u64>, Vec<u32>, Vec<u64>, Vec<u8>, [u64; KMC_CONTIG_WORDS]), KmcError> {
+        let (mut nc, mut nn, mut nb) = (0u64, 0u64, 0u64);
+        let mut w = [0u64; KMC_CONTIG_WORDS];
+        self.check(unsafe {
+            kmc_unitig_contigs(self.ctx, min_count, max_count, min_reads, min_support, std::ptr::null_mut::<u8>(), 0, std::ptr::null_mut::<u64>(),
+                               std::ptr::null_mut::<u64>(), std::ptr::null_mut::<u64>(), std::ptr::null_mut::<u8>(), 0, std::ptr::null_mut::<u32>(), 0,
+                               &mut nc, &mut nn, &mut nb, w.as_mut_ptr())
+        })?;
+        let mut bases = vec![0u8; nb as usize];
+        let mut offsets = vec![0u64; nc as usize + 1];
+        let mut path_offsets = vec![0u64; nc as usize + 1];
+        let mut path = vec![0u32; nn as usize];
+        let mut abund = vec![0u64; nc as usize];
+        let mut flags = vec![0u8; nc as usize];
+        self.check(unsafe {
+            kmc_unitig_contigs(self.ctx, min_count, max_count, min_reads, min_support, bases.as_mut_ptr(), nb, offsets.as_mut_ptr(),
+                               path_offsets.as_mut_ptr(), abund.as_mut_ptr(), flags.as_mut_ptr(), nc, path.as_mut_ptr(), nn, &mut nc, &mut nn, &mut nb,
+                               w.as_mut_ptr())
+        })?;
+        Ok((bases, offsets, path_offsets, path, abund, flags, w))
     }
 
     /// A batch of reads corrected against the solid keys of the table (`kmc_correct`; the batch is not counted): every
