@@ -34,6 +34,7 @@
  *   (addition: no equivalent in the reference)             kmc_unitig_map / kmc_unitig_map_device (reads threaded through the unitigs)
  *   (addition: no equivalent in the reference)             kmc_unitig_transits / kmc_unitig_transits_device (read walks counted per link and per unitig)
  *   (addition: no equivalent in the reference)             kmc_unitig_contigs / kmc_unitig_contigs_device (resolved repeats duplicated, unsupported links cut, contigs spelled)
+ *   (addition: no equivalent in the reference)             kmc_unitig_pairs / kmc_unitig_pairs_device (pair evidence: the ends mates connect, the bases between them, insert sizes)
  *   (addition: no equivalent in the reference)             kmc_correct / kmc_correct_device (substitution errors of reads repaired from the table)
  *   (addition: no equivalent in the reference)             kmc_trim / kmc_trim_device (reads trimmed and filtered by their solid k-mers)
  *   (addition: no equivalent in the reference)             kmc_normalize / kmc_normalize_device (read depth normalised: a per-read k-mer depth, deep reads sampled down)
@@ -189,8 +190,8 @@ int kmc_merge_pairs_device(kmc_ctx* ctx, const void* d_key_hi, const void* d_key
  * small-table way (it emptied the table into the view: tables up to some ten thousand keys, the empty one included, and
  * every view kmc_finalize_async queued): it reports the sizes of the view in place and changes nothing.  Where this header
  * says that "finalize" ends the validity of a device pointer, drops a result a ctx holds or makes a call compute again,
- * such a call is not meant: the pointers stay valid, a host form still copies what is held and KMC_TRANSIT_ACCUMULATE still
- * finds its result.  A larger table is compacted and sorted again: a new view, with everything that says. */
+ * such a call is not meant: the pointers stay valid, a host form still copies what is held and KMC_TRANSIT_ACCUMULATE or
+ * KMC_PAIR_ACCUMULATE still finds its result.  A larger table is compacted and sorted again: a new view, with everything that says. */
 int kmc_finalize(kmc_ctx* ctx, uint64_t* n_distinct, uint64_t* n_total);
 
 /* kmc_finalize for a pipeline that does not want to wait: the device work of a SMALL table's finalize (at most 131072
@@ -682,6 +683,89 @@ int kmc_unitig_contigs(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, uin
                        uint8_t* bases, uint64_t cap_bases, uint64_t* offsets, uint64_t* path_offsets, uint64_t* abund,
                        uint8_t* flags, uint64_t cap_contigs, uint32_t* path, uint64_t cap_nodes, uint64_t* n_contigs,
                        uint64_t* n_nodes, uint64_t* n_bases, uint64_t* summary);
+
+/* ---- pair evidence: which two unitig ends the mates of a pair connect, across how many bases, and the insert sizes
+ * (additions, as above).  The paired counterpart of kmc_unitig_transits: it counts and reports, exactly and
+ * deterministically; it joins nothing.  Everything refers to the unitigs of one view and one range min_count..max_count --
+ * S_u, m_u keys, L_u = m_u + k - 1 bases -- and to the segments kmc_unitig_map gives for the batch, each (start, len, uni =
+ * 2u + o, pos).  KMC_MODE_CONTIG only; every k, in a canonical or a forward ctx.  The formula is the definition.
+ * PAIR.  Reads 2i (mate A) and 2i + 1 (mate B) are pair i, n_pairs = n_reads / 2, as KMC_TRIM_PAIR_* and KMC_NORM_PAIRED
+ *   take them; an odd n_reads is KMC_ERR_ARG.  The library model is forward / reverse: the mates come from opposite strands of
+ *   one fragment and each is read from its own 5' end towards the other.  RF (mate-pair) and FF libraries are left out on
+ *   purpose: reverse-complement the mates before the call.
+ * ANCHOR of a mate.  The longest of its segments (greatest len), of equally long ones the one with the greatest segment
+ *   index.  A mate with no segment has no anchor.  With the anchor (s, len, 2u + o, pos):
+ *     out end  e = 2u + 1 - o, the end of u the mate points at;
+ *     reach    = s + (o ? pos + 1 : m_u - pos) + k - 1, the bases from the mate's first base to that end of u, extrapolated
+ *              along u (64-bit arithmetic).
+ * CLASS of a pair, one byte.  KMC_PAIR_UNPLACED: a mate has no anchor.  KMC_PAIR_SPAN: u_A != u_B.  u_A == u_B and o_A != o_B:
+ *   with R = reach_A + reach_B, KMC_PAIR_PROPER iff R > L_u, and its insert size is F = R - L_u; KMC_PAIR_EVERTED otherwise.
+ *   (With x_A = pos_A - s_A and x_B = pos_B + k - 1 + s_B as base coordinates on S_u -- the first base of the mate read
+ *   along S_u, the last base of the mate read against it -- F = x_B - x_A + 1.)  KMC_PAIR_SAME_STRAND: u_A == u_B and o_A ==
+ *   o_B.  No special case is made for circular unitigs, hairpins or palindromes.
+ * PAIR RECORD.  The SPAN pairs grouped by the unordered pair of their out ends, (a, b) = (min(e_A, e_B), max(e_A, e_B)),
+ *   listed in ascending (a, b).  One record holds count, the sum of R = reach_A + reach_B, min R and max R.  With a library
+ *   insert size F the estimated gap between the two ends is F - sum / count (host arithmetic); for two ends joined by a link
+ *   record it is -(k - 1) for error-free reads.
+ * Outputs.  Per pair: pair_class[n_pairs], uint8_t; pair_ends[2 * n_pairs], uint32_t: e_A, e_B, KMC_MAP_NONE for a mate
+ *   without an anchor; pair_value[n_pairs], uint64_t: R for SPAN, F for PROPER, else 0.  Per record: rec_ends[2 * n_records],
+ *   uint32_t: a, b; rec_count, rec_sum, rec_min, rec_max [n_records], uint64_t.  insert_hist[n_bins], uint64_t: bin
+ *   min(F, n_bins - 1) over the PROPER pairs (F >= 1, so bin 0 stays 0); 2 <= n_bins <= 2^20.
+ * summary[KMC_PAIR_WORDS]: [0] pairs, [1] UNPLACED, [2] SPAN, [3] PROPER, [4] EVERTED, [5] SAME_STRAND, [6] records, [7] the
+ *   sum of F over the PROPER pairs.  Identities, checked by the host on every call: [0] == [1] + [2] + [3] + [4] + [5]; the sum
+ *   of rec_count == [2]; the sum of insert_hist == [3]; [6] == n_records <= [2].
+ * KMC_PAIR_ACCUMULATE (flags bit 0).  Every output except the three per-pair arrays is additive, min / max included.  With
+ *   the flag the call gives exactly what one call on the concatenation of this batch behind all batches accumulated so far
+ *   would give, with the same n_bins; the per-pair arrays describe this batch alone.  The held result is keyed by view, range
+ *   and n_bins; no such result held: KMC_ERR_STATE (the first batch goes without the flag).  It is dropped where the transits
+ *   result is dropped -- finalize, reset, destroy, anything that recomputes the unitigs (a kmc_graph* call in between makes
+ *   the next pairs call one of those).  n_reads == 0 is legal and returns the held (ACCUMULATE) or zeroed result.
+ * RELATION TO THE OTHER VIEW CALLS.  A pairs call counts as a kmc_unitig_map_device call on the batch, as a transits call does
+ *   (map arrays handed out earlier are invalid): it reuses the unitigs the ctx holds under the same condition, otherwise it
+ *   computes them and keeps them.  It does not need the links.  It rewrites none of: the unitig, link, transit or contig
+ *   results, a clean, simplify, components or bubbles result, the view, a partition, a filter or set-operation result, the
+ *   query index -- a pairs call between kmc_unitig_transits and kmc_unitig_contigs leaves the contigs call working, and a
+ *   transits call leaves a held pairs result alone.  The records are grouped by the library's own radix sort; it works in
+ *   scratch of its own and touches neither the view nor the runs the view is made of.
+ * Rules: the argument, state and capacity errors of kmc_unitig_transits; an odd n_reads, unknown flag bits, n_bins outside
+ *   2..2^20: KMC_ERR_ARG; 2^32 records or more, a view of more than 2^30 unitigs (two ends share one 64-bit sort key below the
+ *   all-ones filler), 2^32 pairs and held records or more in one call: KMC_ERR_CAPACITY.  An empty view gives zeros and every
+ *   pair is UNPLACED.
+ * Diagnostic: with KMC_UNITIG_TRACE set, a call prints "kmc_unitig_pairs: unitigs U pairs N span S proper P records R
+ *   unitigs_reused 0|1 map_ms .. anchor_ms .. sort_ms .. reduce_ms .." to stderr, behind the lines of what it had to compute
+ *   (anchor_ms: the anchor and the pair pass; tools/measure_pairs.py reads it).  KMC_PAIRS_PLAIN in the environment, read per
+ *   call, makes every lane of the reduce pass issue its own atomics instead of combining per workgroup -- a diagnostic for
+ *   that tool, the result is the same.  KMC_PAIRS_GRID=N, read per call, caps the workgroups of the pair and reduce passes (a
+ *   test sends a small batch through many rounds of one workgroup with it); the result is the same. ---- */
+#define KMC_PAIR_WORDS 8
+#define KMC_PAIR_UNPLACED 0
+#define KMC_PAIR_SPAN 1
+#define KMC_PAIR_PROPER 2
+#define KMC_PAIR_EVERTED 3
+#define KMC_PAIR_SAME_STRAND 4
+#define KMC_PAIR_ACCUMULATE 1u   /* flags bit 0 */
+/* The batch in device memory by the rules of kmc_unitig_map_device.  The results in ctx-owned device arrays -- uint8_t
+ * pair_class[n_pairs], uint32_t pair_ends[2 * n_pairs], uint64_t pair_value[n_pairs], uint32_t rec_ends[2 * n_records],
+ * uint64_t rec_count / rec_sum / rec_min / rec_max [n_records], uint64_t insert_hist[n_bins] -- valid until the next
+ * kmc_unitig_pairs* call / finalize / reset / destroy (same ordering contract as kmc_export_device).  Every output pointer
+ * may be NULL. */
+int kmc_unitig_pairs_device(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, uint64_t n_bins, uint32_t flags,
+                            const void* d_bases, const void* d_offsets, uint64_t n_reads, uint64_t n_bases,
+                            const void** d_pair_class, const void** d_pair_ends, const void** d_pair_value,
+                            const void** d_rec_ends, const void** d_rec_count, const void** d_rec_sum, const void** d_rec_min,
+                            const void** d_rec_max, const void** d_insert_hist, uint64_t* n_pairs, uint64_t* n_records,
+                            uint64_t* summary);
+/* The same on host buffers (the batch as kmc_unitig_map takes it).  The three per-pair arrays share cap_pairs, the five
+ * record arrays cap_records (rec_ends has room for 2 * cap_records), insert_hist has cap_bins entries.  *n_pairs and
+ * *n_records are always set; a cap too small for an array that was given -> KMC_ERR_ARG and nothing is copied; an array that
+ * is NULL is not copied and its cap not looked at.  No sizing call is needed: n_pairs == n_reads / 2, n_records <= n_pairs
+ * plus the records held (ACCUMULATE), and insert_hist has n_bins entries.  Like kmc_unitig_map's host form it computes on
+ * EVERY call: with KMC_PAIR_ACCUMULATE a second call on the same batch adds it twice. */
+int kmc_unitig_pairs(kmc_ctx* ctx, uint64_t min_count, uint64_t max_count, uint64_t n_bins, uint32_t flags,
+                     const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads, uint8_t* pair_class, uint32_t* pair_ends,
+                     uint64_t* pair_value, uint64_t cap_pairs, uint32_t* rec_ends, uint64_t* rec_count, uint64_t* rec_sum,
+                     uint64_t* rec_min, uint64_t* rec_max, uint64_t cap_records, uint64_t* insert_hist, uint64_t cap_bins,
+                     uint64_t* n_pairs, uint64_t* n_records, uint64_t* summary);
 
 /* ---- reads corrected against the table: substitution errors repaired from the solid keys (additions, as above).
  * KMC_MODE_CONTIG only; every k, in a canonical or a forward ctx.  Reads the sorted view of the last kmc_finalize (a view

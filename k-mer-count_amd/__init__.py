@@ -99,6 +99,7 @@ ABI_SYMBOLS = [
     "kmc_unitig_map", "kmc_unitig_map_device",
     "kmc_unitig_transits", "kmc_unitig_transits_device",
     "kmc_unitig_contigs", "kmc_unitig_contigs_device",
+    "kmc_unitig_pairs", "kmc_unitig_pairs_device",
     "kmc_correct", "kmc_correct_device",
     "kmc_trim", "kmc_trim_device",
     "kmc_normalize", "kmc_normalize_device",
@@ -131,6 +132,10 @@ TRANSIT_VERDICT_NAMES = ("plain", "unspanned", "resolved", "ambiguous")
 TRANSIT_ACCUMULATE = 1  # KMC_TRANSIT_ACCUMULATE: flags bit 0, add onto the result the ctx holds
 CONTIG_WORDS = 8        # KMC_CONTIG_WORDS: contigs, nodes, unitigs duplicated, records ignored for support, circular, one-node, most nodes in one, bases
 CONTIG_CIRCULAR = 1     # bit 0 of a contig's flags byte
+PAIR_WORDS = 8          # KMC_PAIR_WORDS: pairs, UNPLACED, SPAN, PROPER, EVERTED, SAME_STRAND, records, the sum of the PROPER pairs' insert sizes
+PAIR_UNPLACED, PAIR_SPAN, PAIR_PROPER, PAIR_EVERTED, PAIR_SAME_STRAND = 0, 1, 2, 3, 4   # KMC_PAIR_*: a pair's class byte
+PAIR_CLASS_NAMES = ("unplaced", "span", "proper", "everted", "same_strand")
+PAIR_ACCUMULATE = 1     # KMC_PAIR_ACCUMULATE: flags bit 0, add onto the result the ctx holds
 CORRECT_WORDS = 8       # KMC_CORRECT_WORDS: reads, valid windows, weak windows, weak runs, candidates, corrected, ambiguous, weak windows left
 CORRECT_READ_WORDS = 4  # KMC_CORRECT_READ_WORDS: a read's valid windows, weak windows, candidates, corrected
 CORRECT_INTERIOR, CORRECT_HEAD, CORRECT_TAIL = 0, 1, 2   # KMC_CORRECT_*: a candidate's kind
@@ -236,6 +241,9 @@ def lib() -> C.CDLL:
     if "KMC_LIB_PATH" not in os.environ or hasattr(L, "kmc_unitig_contigs"):   # (as for the bubbles calls above)
         L.kmc_unitig_contigs_device.argtypes = [vp, u64, u64, u64, u64] + [C.POINTER(vp)] * 6 + [pu64, pu64, pu64, vp]
         L.kmc_unitig_contigs.argtypes = [vp, u64, u64, u64, u64, vp, u64, vp, vp, vp, vp, u64, vp, u64, pu64, pu64, pu64, vp]
+    if "KMC_LIB_PATH" not in os.environ or hasattr(L, "kmc_unitig_pairs"):   # (as for the bubbles calls above)
+        L.kmc_unitig_pairs_device.argtypes = [vp, u64, u64, u64, u32, vp, vp, u64, u64] + [C.POINTER(vp)] * 9 + [pu64, pu64, vp]
+        L.kmc_unitig_pairs.argtypes = [vp, u64, u64, u64, u32, vp, vp, u64, vp, vp, vp, u64, vp, vp, vp, vp, vp, u64, vp, u64, pu64, pu64, vp]
     L.kmc_correct_device.argtypes = [vp, u64, u64, vp, vp, u64, u64] + [C.POINTER(vp)] * 4 + [pu64, vp]
     L.kmc_correct.argtypes = [vp, u64, u64, vp, vp, u64, vp, vp, vp, vp, u64, pu64, vp]
     L.kmc_trim_device.argtypes = [vp, u64, u64, i32, u32, u64, u32, u64, vp, vp, u64, u64] + [C.POINTER(vp)] * 5 + [pu64, pu64, vp]
@@ -720,6 +728,83 @@ class Transits:
             m = self.matrix(u)
             out.append("U\t%d\t%s\t%d\t%d\n" % (u, TRANSIT_VERDICT_NAMES[int(self.verdict[u])], m.shape[0], m.shape[1]))
             out += ["T\t%d\t%d\t%d\t%d\n" % (u, p, q, int(m[p, q])) for p in range(m.shape[0]) for q in range(m.shape[1]) if m[p, q]]
+        return "".join(out)
+
+
+_PAIR_FIELDS = ("pairs", "unplaced", "span", "proper", "everted", "same_strand", "records", "insert_sum")
+
+
+@dataclass
+class PairSummary:
+    """The eight words of kmc_unitig_pairs: pairs, then those UNPLACED, SPAN, PROPER, EVERTED and SAME_STRAND, the pair
+    records, and the sum of the insert sizes of the PROPER pairs."""
+    pairs: int
+    unplaced: int
+    span: int
+    proper: int
+    everted: int
+    same_strand: int
+    records: int
+    insert_sum: int
+
+    @classmethod
+    def from_words(cls, words) -> "PairSummary":
+        return cls(*[int(w) for w in words])
+
+    def words(self) -> list:
+        return [getattr(self, f) for f in _PAIR_FIELDS]
+
+    def to_text(self) -> str:
+        """``NAME\tVALUE`` lines."""
+        return "\n".join("%s\t%d" % (f, getattr(self, f)) for f in _PAIR_FIELDS) + "\n"
+
+
+@dataclass
+class PairLinks:
+    """What KmerCounter.pair_links returns.  Per pair of the batch: ``pair_class`` uint8[n_pairs] (PAIR_*), ``pair_ends``
+    uint32[n_pairs, 2] (the out ends of mates A and B, MAP_NONE without an anchor), ``pair_value`` uint64[n_pairs] (R for a
+    SPAN pair, the insert size F for a PROPER one, else 0).  Per record, in ascending (a, b): ``rec_ends`` uint32[records, 2],
+    ``rec_count``, ``rec_sum``, ``rec_min``, ``rec_max`` uint64[records] over R of the SPAN pairs between those two ends.
+    ``insert_hist`` uint64[n_bins]: PROPER pairs per insert size, the last bin open.  With ``accumulate`` the records, the
+    histogram and the summary are totals over the batches so far."""
+    pair_class: np.ndarray
+    pair_ends: np.ndarray
+    pair_value: np.ndarray
+    rec_ends: np.ndarray
+    rec_count: np.ndarray
+    rec_sum: np.ndarray
+    rec_min: np.ndarray
+    rec_max: np.ndarray
+    insert_hist: np.ndarray
+    summary: PairSummary
+
+    def __len__(self) -> int:
+        return len(self.rec_count)
+
+    def records(self):
+        """(a, b, count, sum, min, max) per record, in array order."""
+        for (a, b), c, s, lo, hi in zip(self.rec_ends.tolist(), self.rec_count.tolist(), self.rec_sum.tolist(), self.rec_min.tolist(),
+                                        self.rec_max.tolist()):
+            yield a, b, c, s, lo, hi
+
+    def insert_median(self) -> Optional[int]:
+        """The lower median of the insert sizes in ``insert_hist`` (None without a PROPER pair; the open last bin counts as
+        its index)."""
+        total = int(self.insert_hist.sum())
+        if not total:
+            return None
+        return int(np.searchsorted(np.cumsum(self.insert_hist), (total + 1) // 2))
+
+    def gaps(self, insert: float) -> np.ndarray:
+        """float64[records]: the estimated bases between the two ends of every record under a library insert size,
+        ``insert - sum / count``; -(k - 1) where the two ends are joined by a link."""
+        return float(insert) - self.rec_sum.astype(np.float64) / self.rec_count.astype(np.float64)
+
+    def to_text(self) -> str:
+        """What ``k-mer-count --pairs`` prints: ``I F PAIRS`` per non-zero bin of the insert histogram, then ``P A B COUNT SUM
+        MIN MAX`` per record, tab-separated."""
+        out = ["I\t%d\t%d\n" % (f, int(self.insert_hist[f])) for f in np.flatnonzero(self.insert_hist).tolist()]
+        out += ["P\t%d\t%d\t%d\t%d\t%d\t%d\n" % r for r in self.records()]
         return "".join(out)
 
 
@@ -1561,6 +1646,58 @@ class KmerCounter:
             return device_view(ptr, (n_bytes + 7) // 8, dev).cpu().numpy().view(np.uint8)[:n_bytes].copy()
         got = (words(ds, 8 * nl).view(np.uint64), words(do, 8 * (nu + 1)).view(np.uint64), words(dc, 8 * nsl).view(np.uint64), words(dv, nu))
         return Transits(*got, summary, self.unitig_links(min_count, max_count))   # (the held links: copied, not computed)
+
+    # -- pair evidence: the unitig ends the mates of a pair connect, insert sizes (of the sorted view; finalize() first) --
+    def pair_links_device(self, d_bases: int, d_offsets: int, n_reads: int, n_bases: int, min_count: int = 1, max_count: int = 0,
+                          n_bins: int = 1024, accumulate: bool = False):
+        """(d_pair_class, d_pair_ends, d_pair_value, d_rec_ends, d_rec_count, d_rec_sum, d_rec_min, d_rec_max, d_insert_hist,
+        n_pairs, n_records, PairSummary) of kmc_unitig_pairs_device for a batch in device memory (raw addresses, laid out as
+        for map_reads_device, reads 2i and 2i + 1 the mates of pair i): ctx-owned device arrays.  ``accumulate`` adds onto the
+        result the ctx holds from the last pairs call of this view, range and n_bins."""
+        p = [C.c_void_p() for _ in range(9)]
+        npairs, nrec = C.c_uint64(), C.c_uint64()
+        w = (C.c_uint64 * PAIR_WORDS)()
+        self._chk(self._L.kmc_unitig_pairs_device(self._h, int(min_count), int(max_count), int(n_bins), PAIR_ACCUMULATE if accumulate else 0,
+                                                  d_bases or None, d_offsets or None, int(n_reads), int(n_bases), *[C.byref(x) for x in p],
+                                                  C.byref(npairs), C.byref(nrec), w))
+        return tuple(x.value or 0 for x in p) + (npairs.value, nrec.value, PairSummary.from_words(list(w)))
+
+    def pair_links_tensors(self, bases, offsets, min_count: int = 1, max_count: int = 0, n_bins: int = 1024, accumulate: bool = False):
+        """pair_links_device for torch tensors on this ctx's GPU (bases uint8[n_bases], padded as for add_batch_tensors;
+        offsets int64[n_reads + 1])."""
+        assert bases.is_cuda and offsets.is_cuda and bases.is_contiguous() and offsets.is_contiguous()
+        return self.pair_links_device(bases.data_ptr(), offsets.data_ptr(), max(offsets.numel() - 1, 0), bases.numel(), min_count, max_count,
+                                      n_bins, accumulate)
+
+    def pair_links(self, bases: np.ndarray, offsets: np.ndarray, min_count: int = 1, max_count: int = 0, n_bins: int = 1024,
+                   accumulate: bool = False) -> "PairLinks":
+        """kmc_unitig_pairs_device for a host batch of interleaved mates (the batch is not counted): the class of every pair
+        on the unitigs of unitigs() with the same range, the records of the pairs that span two unitigs, and the insert
+        histogram of those that lie on one.  The batch goes to the device as tensors and the result arrays are read back from
+        the ctx, so the library computes once."""
+        import torch
+        from .distributed import device_view
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n_reads, n_bases = max(int(offsets.shape[0]) - 1, 0), int(bases.shape[0])
+        if n_reads and (int(offsets[0]) != 0 or int(offsets[-1]) != n_bases or (np.diff(offsets.astype(np.int64)) < 0).any()):
+            raise ValueError("offsets must start at 0, not decrease, and end at len(bases)")
+        if n_reads and int(np.diff(offsets.astype(np.int64)).max()) >= 1 << 32:
+            raise KmcError(ERR_ARG, "a read of 2^32 bases or more")
+        dev = torch.device("cuda", self.device)
+        d_bases = torch.zeros(n_bases + 64, dtype=torch.uint8, device=dev)   # (readable past the end, 16-byte aligned)
+        d_bases[:n_bases] = torch.from_numpy(bases.copy())
+        d_offs = torch.from_numpy(offsets.view(np.int64).copy()).to(dev)
+        torch.cuda.synchronize(dev)
+        *ptr, n_pairs, n_rec, summary = self.pair_links_device(d_bases.data_ptr(), d_offs.data_ptr(), n_reads, n_bases, min_count, max_count,
+                                                               n_bins, accumulate)
+
+        def words(p, n_bytes):
+            return device_view(p, (n_bytes + 7) // 8, dev).cpu().numpy().view(np.uint8)[:n_bytes].copy()
+        u64s = lambda p, n: words(p, 8 * n).view(np.uint64)
+        return PairLinks(words(ptr[0], n_pairs), words(ptr[1], 8 * n_pairs).view(np.uint32).reshape(n_pairs, 2), u64s(ptr[2], n_pairs),
+                         words(ptr[3], 8 * n_rec).view(np.uint32).reshape(n_rec, 2), u64s(ptr[4], n_rec), u64s(ptr[5], n_rec), u64s(ptr[6], n_rec),
+                         u64s(ptr[7], n_rec), u64s(ptr[8], int(n_bins)), summary)
 
     # -- the counted walks acted on: contigs (after unitigs / unitig_links / transits of the same range) --
     def contigs(self, min_count: int = 1, max_count: int = 0, min_reads: int = 1, min_support: int = 0) -> "Contigs":

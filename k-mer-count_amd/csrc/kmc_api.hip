@@ -830,6 +830,22 @@ int msd_sort_to_run(kmc_ctx* c, u64* const hi[2], u64* const lo[2], u64* const w
     return KMC_OK;
 }
 
+}  // namespace
+// What the view layer sorts with (kmc_ctx.hip.h): one-word keys with weights into a run of the caller's.  A weighted sort
+// never updates msd_dup_heavy, a run handed out never joins c->runs, and nothing here looks at the view.
+int sort_keys_to_run(kmc_ctx* c, u64* const lo[2], u64* const w[2], u64 n, unsigned key_bits, kmc_ctx::Run* out) {
+    if (!out || !lo[0] || !lo[1] || !w[0] || !w[1] || key_bits < 1 || key_bits > 63) return fail(c, KMC_ERR_ARG, "sort_keys_to_run: bad arguments (internal error)");
+    if (n >= (1ull << 32) - KMC_MSD_RANGE) return fail(c, KMC_ERR_CAPACITY, "2^32 keys or more in one sort");
+    u64* const hi[2] = {nullptr, nullptr};
+    return msd_sort_to_run(c, hi, lo, w, n, key_bits, 1, out, true);
+}
+
+void recycle_run(kmc_ctx* c, kmc_ctx::Run* r) {
+    if (r->lo) { r->n = 0; c->run_pool.push_back(std::move(*r)); }
+    *r = kmc_ctx::Run{};
+}
+namespace {
+
 // Count the windows ending in [range_begin, n_bases) by extract -> sort -> run-length, in sub-batches
 // of at most 2^31 base positions (2 x 16-32 GiB of keys in flight).  Each sub-batch leaves one run.
 // Sort what the batches since the last flush have extracted: one run.

@@ -7,6 +7,7 @@
 //   k-mer-count [FASTA] [-k K] [--forward] [--expand] [--device N | --gpus N] [--algo auto|stream|walk|sort] [--stats]
 //               [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE | --map FILE | --correct FILE]
 //               [--transits FILE [--min-reads N]] [--contigs FILE [--min-reads N] [--min-support N]]
+//               [--pairs FILE [--insert-bins N]]
 //               [--trim FILE [--trim-mode none|ends|longest] [--min-strong N] [--strong-permille N] [--min-len N] [--invert]
 //                [--paired both|either]]
 //               [--normalize FILE --target N [--depth-permille P] [--min-depth N] [--seed S] [--norm-paired] [--norm-invert]]
@@ -55,6 +56,13 @@
 //               ">INDEX LN:i:BASES KC:i:ABUND CL:i:0|1 WK:Z:WALK" -- the abundance summed over the path, the circular flag, the
 //               path as ">U" / "<U" per unitig -- then the contig on one line.  It excludes what --transits excludes, and
 //               --transits; with --clean the reads walk the cleaned graph.
+//   --pairs FILE         (with -k K) instead of the table: the pair evidence of the reads of FILE (FASTA / FASTQ, mates adjacent as
+//               --paired takes them, forward / reverse) on the unitig graph of the counted input (kmc_unitig_pairs, which takes
+//               FILE in chunks that add up; --min-count / --max-count are the solidity range).  Output, tab-separated: "I F
+//               PAIRS" for every insert size F that pairs lying on one unitig have (--insert-bins N bins, default 1024, the last
+//               one open), then "P A B COUNT SUM MIN MAX" per pair of unitig ends A < B that pairs connect -- how many, and the
+//               sum, least and most of the bases they span up to those ends.  It excludes what --transits excludes, --transits
+//               and --contigs; with --clean the pairs lie on the cleaned graph.
 //   --correct FILE       (with -k K) instead of the table: every read of FILE (FASTA / FASTQ) corrected against the solid keys of
 //               the counted input (kmc_correct; --min-count / --max-count are the solidity range), as FASTA in file order:
 //               ">INDEX WINDOWS WEAK CANDIDATES FIXED" -- its valid K-mer windows, how many of them are not solid, the weak
@@ -182,6 +190,8 @@ int main(int argc, char** argv) {
     const char* transits_path = nullptr;
     long long min_reads = -1;   // (-1: not given)
     const char* contigs_path = nullptr;
+    const char* pairs_path = nullptr;
+    long long insert_bins = -1;   // (-1: not given)
     long long min_support = -1;   // (-1: not given)
     int trim_mode = -1, trim_invert = 0, trim_pair = 0;   // (-1: the default mode, longest)
     long long min_strong = -1, strong_permille = -1, min_len = -1;   // (-1: not given)
@@ -211,6 +221,8 @@ int main(int argc, char** argv) {
         else if (a == "--correct" && i + 1 < argc) correct_path = argv[++i];
         else if (a == "--transits" && i + 1 < argc) transits_path = argv[++i];
         else if (a == "--contigs" && i + 1 < argc) contigs_path = argv[++i];
+        else if (a == "--pairs" && i + 1 < argc) pairs_path = argv[++i];
+        else if (a == "--insert-bins" && i + 1 < argc) { if (!parse_count("--insert-bins", argv[++i], 2, 1 << 20, &insert_bins)) return 2; }
         else if (a == "--min-support" && i + 1 < argc) { if (!parse_count("--min-support", argv[++i], 0, LLONG_MAX, &min_support)) return 2; }
         else if (a == "--min-reads" && i + 1 < argc) { if (!parse_count("--min-reads", argv[++i], 0, LLONG_MAX, &min_reads)) return 2; }
         else if (a == "--trim" && i + 1 < argc) trim_path = argv[++i];
@@ -265,6 +277,7 @@ int main(int argc, char** argv) {
             fprintf(stderr, "usage: k-mer-count [FASTA] [-k K] [--forward] [--expand] [--device N | --gpus N] [--algo auto|stream|walk|sort] [--stats]\n"
                             "                   [--min-count N] [--max-count N] [--histo H] [--query-kmers FILE | --profile FILE | --map FILE | --correct FILE]\n"
                             "                   [--transits FILE [--min-reads N]] [--contigs FILE [--min-reads N] [--min-support N]]\n"
+                            "                   [--pairs FILE [--insert-bins N]]\n"
                             "                   [--trim FILE [--trim-mode none|ends|longest] [--min-strong N] [--strong-permille N] [--min-len N] [--invert]\n"
                             "                    [--paired both|either]]\n"
                             "                   [--normalize FILE --target N [--depth-permille P] [--min-depth N] [--seed S] [--norm-paired] [--norm-invert]]\n"
@@ -277,7 +290,7 @@ int main(int argc, char** argv) {
                    a == "--clean" || a == "--tip-keys" || a == "--island-keys" || a == "--bubble-keys" || a == "--component-keys" || a == "--trim" ||
                    a == "--trim-mode" || a == "--min-strong" || a == "--strong-permille" || a == "--min-len" || a == "--paired" ||
                    a == "--normalize" || a == "--target" || a == "--depth-permille" || a == "--min-depth" || a == "--seed" || a == "--transits" ||
-                   a == "--min-reads" || a == "--contigs" || a == "--min-support") {
+                   a == "--min-reads" || a == "--contigs" || a == "--min-support" || a == "--pairs" || a == "--insert-bins") {
             fprintf(stderr, "k-mer-count: %s needs a value\n", a.c_str());
             return 2;
         } else if (!a.empty() && a[0] != '-') path = argv[i];
@@ -339,6 +352,23 @@ int main(int argc, char** argv) {
         if (bad) { fprintf(stderr, "k-mer-count: --contigs %s%s\n", strncmp(bad, "needs", 5) ? "and " : "", bad); return 2; }
     } else if (min_support >= 0) {
         fprintf(stderr, "k-mer-count: --min-support needs --contigs FILE\n");
+        return 2;
+    }
+    // --pairs and its option: the same again
+    if (pairs_path) {
+        const char* bad = nullptr;
+        if (!k) bad = "needs -k K";
+        else if (transits_path || contigs_path || map_path || correct_path || trim_path || norm_path)
+            bad = "--transits / --contigs / --map / --correct / --trim / --normalize exclude each other";
+        else if (query_path || profile_path) bad = "--query-kmers / --profile exclude each other";
+        else if (histo) bad = "--histo exclude each other";
+        else if (with_path || compare || setop >= 0) bad = "--with / --compare / --setop exclude each other";
+        else if (graph || graph_stats || unitigs || gfa || components || variants)
+            bad = "--graph / --graph-stats / --unitigs / --gfa / --components / --variants exclude each other";
+        else if (expand) bad = "--expand exclude each other";
+        if (bad) { fprintf(stderr, "k-mer-count: --pairs %s%s\n", strncmp(bad, "needs", 5) ? "and " : "", bad); return 2; }
+    } else if (insert_bins >= 0) {
+        fprintf(stderr, "k-mer-count: --insert-bins needs --pairs FILE\n");
         return 2;
     }
     // --correct: the same again
@@ -410,9 +440,9 @@ int main(int argc, char** argv) {
         }
         fclose(f);
     }
-    if (profile_path || map_path || correct_path || trim_path || norm_path || transits_path || contigs_path) {
+    if (profile_path || map_path || correct_path || trim_path || norm_path || transits_path || contigs_path || pairs_path) {
         const char* reads_path = profile_path ? profile_path : map_path ? map_path : correct_path ? correct_path : trim_path ? trim_path : norm_path ? norm_path
-                                 : transits_path ? transits_path : contigs_path;
+                                 : transits_path ? transits_path : contigs_path ? contigs_path : pairs_path;
         char eb[256] = {0};
         const int prc = kmc_parse_fasta(reads_path, &prof, eb, sizeof(eb));
         if (prc) return die(reads_path, eb[0] ? eb : kmc_status_string(prc));
@@ -460,8 +490,8 @@ int main(int argc, char** argv) {
         if (!k) bad = "needs -k K";
         else if (graph || graph_stats || unitigs || gfa) bad = "--graph / --graph-stats / --unitigs / --gfa exclude each other";
         else if (histo) bad = "--histo exclude each other";
-        else if (query_path || profile_path || map_path || correct_path || trim_path || norm_path || transits_path || contigs_path)
-            bad = "--query-kmers / --profile / --map / --correct / --trim / --normalize / --transits / --contigs exclude each other";
+        else if (query_path || profile_path || map_path || correct_path || trim_path || norm_path || transits_path || contigs_path || pairs_path)
+            bad = "--query-kmers / --profile / --map / --correct / --trim / --normalize / --transits / --contigs / --pairs exclude each other";
         else if (with_path || compare || setop >= 0) bad = "--with / --compare / --setop exclude each other";
         else if (expand) bad = "--expand exclude each other";
         if (bad) { fprintf(stderr, "k-mer-count: --components %s%s\n", strncmp(bad, "needs", 5) ? "and " : "", bad); return 2; }
@@ -472,8 +502,8 @@ int main(int argc, char** argv) {
         if (!k) bad = "needs -k K";
         else if (graph || graph_stats || unitigs || gfa || components) bad = "--graph / --graph-stats / --unitigs / --gfa / --components exclude each other";
         else if (histo) bad = "--histo exclude each other";
-        else if (query_path || profile_path || map_path || correct_path || trim_path || norm_path || transits_path || contigs_path)
-            bad = "--query-kmers / --profile / --map / --correct / --trim / --normalize / --transits / --contigs exclude each other";
+        else if (query_path || profile_path || map_path || correct_path || trim_path || norm_path || transits_path || contigs_path || pairs_path)
+            bad = "--query-kmers / --profile / --map / --correct / --trim / --normalize / --transits / --contigs / --pairs exclude each other";
         else if (with_path || compare || setop >= 0) bad = "--with / --compare / --setop exclude each other";
         else if (expand) bad = "--expand exclude each other";
         if (bad) { fprintf(stderr, "k-mer-count: --variants %s%s\n", strncmp(bad, "needs", 5) ? "and " : "", bad); return 2; }
@@ -703,6 +733,39 @@ int main(int argc, char** argv) {
                     if (at < nsl && cnt[at]) printf("T\t%llu\t%llu\t%llu\t%llu\n", (unsigned long long)u, (unsigned long long)p, (unsigned long long)q, (unsigned long long)cnt[at]);
                 }
         }
+        fflush(stdout);
+        destroy_all();
+        return 0;
+    }
+    if (pairs_path) {
+        // the pairs in chunks that add up (an even number of reads each); the records and the histogram of the totals come with the last
+        const uint64_t n_rd = prof.n_reads, lo_c = (uint64_t)min_count, hi_c = (uint64_t)max_count, chunk = 1ull << 16;
+        const uint64_t bins = insert_bins < 0 ? 1024 : (uint64_t)insert_bins;
+        if (n_rd & 1) { kmc_free_reads(&prof); fprintf(stderr, "k-mer-count: --pairs %s holds an odd number of reads\n", pairs_path); destroy_all(); return 1; }
+        uint64_t np = 0, nr = 0, first = 0, held = 0;
+        std::vector<uint64_t> offs, hist((size_t)bins), rc_, rs, rn, rx;
+        std::vector<uint32_t> re;
+        do {
+            const uint64_t n = std::min<uint64_t>(chunk, n_rd - first), b0 = n_rd ? prof.offsets[first] : 0;
+            offs.assign((size_t)n + 1, 0);
+            for (uint64_t i = 0; i <= n && n_rd; ++i) offs[(size_t)i] = prof.offsets[first + i] - b0;
+            const uint64_t cap = held + n / 2;   // n_records <= the pairs of this call plus the records held
+            re.resize((size_t)2 * cap + 1); rc_.resize((size_t)cap + 1); rs.resize((size_t)cap + 1); rn.resize((size_t)cap + 1); rx.resize((size_t)cap + 1);
+            const bool last = first + n >= n_rd;
+            rc = kmc_unitig_pairs(ctx, lo_c, hi_c, bins, first ? KMC_PAIR_ACCUMULATE : 0, n_rd ? prof.bases + b0 : nullptr, offs.data(), n, nullptr, nullptr,
+                                  nullptr, 0, last ? re.data() : nullptr, last ? rc_.data() : nullptr, last ? rs.data() : nullptr, last ? rn.data() : nullptr,
+                                  last ? rx.data() : nullptr, cap, last ? hist.data() : nullptr, bins, &np, &nr, nullptr);
+            held = nr;
+            first += n;
+        } while (!rc && first < n_rd);
+        kmc_free_reads(&prof);
+        if (rc) { int r = die("kmc_unitig_pairs", kmc_last_error(ctx)); destroy_all(); return r; }
+        setvbuf(stdout, obuf.data(), _IOFBF, obuf.size());
+        for (uint64_t f = 0; f < bins; ++f)
+            if (hist[(size_t)f]) printf("I\t%llu\t%llu\n", (unsigned long long)f, (unsigned long long)hist[(size_t)f]);
+        for (uint64_t j = 0; j < nr; ++j)
+            printf("P\t%u\t%u\t%llu\t%llu\t%llu\t%llu\n", re[(size_t)2 * j], re[(size_t)2 * j + 1], (unsigned long long)rc_[(size_t)j],
+                   (unsigned long long)rs[(size_t)j], (unsigned long long)rn[(size_t)j], (unsigned long long)rx[(size_t)j]);
         fflush(stdout);
         destroy_all();
         return 0;

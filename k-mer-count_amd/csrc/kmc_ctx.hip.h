@@ -302,6 +302,19 @@ struct kmc_ctx : CtxStream {
     DevBuf ct_copies, ct_sigma, ct_pos, ct_owner, ct_link, ct_join, ct_ptr[2], ct_dist[2], ct_circ, ct_cid, ct_keys, ct_g, ct_start, ct_src, ct_ctl;
     ResultKey ct_key;
     u64 ct_reads = 0, ct_support = 0, ct_words[8] = {};
+    // kmc_unitig_pairs* (kmc_pairs.hip.h) read the unitig offsets and the segments of a map call.  Their result, in buffers
+    // of their own (a map, transits or contigs call leaves them alone, and KMC_PAIR_ACCUMULATE adds onto them): per pair of
+    // the last batch the class, the two ends and the value; the record set pr_cur of two -- sort key, ends, count, sum, min,
+    // max per record, the other set is where the next ACCUMULATE call builds its own -- and the insert histogram, with pr_key
+    // plus its parameter pr_bins and pr_words as above and pr_records records.  Whatever recomputes the unitigs drops pr_key;
+    // the links do not matter to it.  Work arrays: the anchor row per read, the sort keys and weights with the sort's
+    // scratch copies, the control words.
+    DevBuf pr_class, pr_ends, pr_value, pr_hist;
+    DevBuf pr_rkey[2], pr_rends[2], pr_rcount[2], pr_rsum[2], pr_rmin[2], pr_rmax[2];
+    DevBuf pr_anchor, pr_sk[2], pr_sw[2], pr_ctl;
+    ResultKey pr_key;
+    int pr_cur = 0;
+    u64 pr_bins = 0, pr_records = 0, pr_words[8] = {};
 };
 
 #pragma GCC visibility push(hidden)   // what follows is shared between the translation units, never exported
@@ -353,6 +366,15 @@ inline int grid_for(const kmc_ctx* c, u64 n, int threads) {
 
 // What the calls that read the view do first: a finalize queued by kmc_finalize_async counts as one (kmc_api.hip)
 int resolve_view(kmc_ctx* c);
+
+// The second thing the view layer calls of the counting side (kmc_api.hip): the MSD radix sort with run-length on n
+// one-word keys of key_bits < 64 bits in lo[0], their weights in w[0]; lo[1] / w[1] are scratch of the same size and
+// all four are overwritten.  Keys with a bit at or above key_bits are filler and dropped.  out gets the sorted distinct
+// keys (out->lo), the sums of their weights (out->cnt) and out->n / out->total; give it back with recycle_run when the
+// stream is through with it.  It works in the sort's scratch (m_*, h_ctl) and the run pool alone: the view, the live runs
+// and the keys extracted and not yet sorted stay as they are, and so does what the sort path has learned about its keys.
+int sort_keys_to_run(kmc_ctx* c, u64* const lo[2], u64* const w[2], u64 n, unsigned key_bits, kmc_ctx::Run* out);
+void recycle_run(kmc_ctx* c, kmc_ctx::Run* r);
 
 // no C++ exception leaves the library (kmc.h: "no exception or abort crosses the ABI")
 template <typename F>

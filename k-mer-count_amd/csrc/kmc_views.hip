@@ -18,6 +18,7 @@
 #include "kmc_bubbles.hip.h"
 #include "kmc_map.hip.h"
 #include "kmc_transits.hip.h"
+#include "kmc_pairs.hip.h"
 #include "kmc_correct.hip.h"
 #include "kmc_trim.hip.h"
 #include "kmc_contigs.hip.h"
@@ -755,7 +756,7 @@ static int unitig_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count
     memset(h, 0, KMC_UNITIG_WORDS * sizeof(u64));
     const u64 n = c->n_sorted, n2 = 2 * n;
     int rc;
-    c->u_key.drop(); c->l_key.drop(); c->cc_key.drop(); c->bb_key.drop(); c->tx_key.drop(); c->ct_key.drop();   // the result arrays are rewritten from here on (and the links of the old ones, their components, their bubbles and their transit counts go with them)
+    c->u_key.drop(); c->l_key.drop(); c->cc_key.drop(); c->bb_key.drop(); c->tx_key.drop(); c->ct_key.drop(); c->pr_key.drop();   // the result arrays are rewritten from here on (and the links of the old ones, their components, their bubbles, their transit counts and the pair records numbered by them go with them)
     if ((rc = ensure(c, c->u_offs, sizeof(u64))) || (rc = ensure(c, c->u_bases, 64)) || (rc = ensure(c, c->u_abund, sizeof(u64))) ||
         (rc = ensure(c, c->u_flags, 8)))
         return rc;
@@ -1374,6 +1375,215 @@ static int kmc_unitig_transits_impl(kmc_ctx* c, uint64_t min_count, uint64_t max
     if (verdict && nu) HIPCHK(c, hipMemcpyAsync(verdict, c->tx_verdict.p, (size_t)nu, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (summary) memcpy(summary, c->tx_words, sizeof(c->tx_words));
+    return KMC_OK;
+}
+
+// ---- pair evidence: the ends the mates of a pair connect, the bases between them, insert sizes (kmc_pairs.hip.h) ----
+// KMC_PAIRS_PLAIN in the environment makes every lane of the reduce kernel issue its own atomics instead of combining per
+// workgroup in LDS -- a diagnostic for tools/measure_pairs.py, the result is the same.
+static int pairs_args(kmc_ctx* c, const char* what, uint64_t n_bins, uint32_t flags, uint64_t n_reads) {
+    if (flags & ~(uint32_t)KMC_PAIR_ACCUMULATE) return fail(c, KMC_ERR_ARG, "%s: unknown flag bits 0x%x", what, flags & ~(uint32_t)KMC_PAIR_ACCUMULATE);
+    if (n_bins < 2 || n_bins > (1ull << 20)) return fail(c, KMC_ERR_ARG, "%s: n_bins %llu outside 2..2^20", what, (unsigned long long)n_bins);
+    if (n_reads & 1) return fail(c, KMC_ERR_ARG, "%s: %llu reads are no whole number of pairs", what, (unsigned long long)n_reads);
+    return KMC_OK;
+}
+
+// The pairs of the batch (device arrays) laid on the unitigs of this view and range -- those the ctx holds under map_run's
+// condition, otherwise computed and kept -- into the pr_* buffers, the summary into pr_words; finished when it returns.  The
+// map passes first, then anchor, class, sort, records, reduce.  Through map_run it shares the map buffers; through
+// sort_keys_to_run the sort's scratch and the run pool; it writes nothing else that is not its own.
+static int pairs_run(kmc_ctx* c, const char* what, u64 min_count, u64 max_count, u64 n_bins, bool accumulate, const uint8_t* d_bases,
+                     const u64* d_offsets, u64 n_reads, u64 n_bases) {
+    int rc;
+    const bool kept = c->u_live && c->u_key.holds(c->view_gen, min_count, max_count);
+    if (accumulate && !(kept && c->pr_key.holds(c->view_gen, min_count, max_count) && c->pr_bins == n_bins))
+        return fail(c, KMC_ERR_STATE, "%s: KMC_PAIR_ACCUMULATE, and the ctx holds no pairs of this view, range and n_bins to add to", what);
+    const size_t hb = (size_t)n_bins * sizeof(u64);
+    if ((rc = ensure(c, c->pr_ctl, KMC_P_CTL_WORDS * sizeof(u64))) || (rc = ensure(c, c->pr_hist, hb))) return rc;
+    if (!accumulate) {
+        c->pr_key.drop();
+        c->pr_records = 0;
+        memset(c->pr_words, 0, sizeof(c->pr_words));
+        HIPCHK(c, hipMemsetAsync(c->pr_hist.p, 0, hb, c->stream));
+    }
+    UnitigTrace tr;
+    tr.mark(c->stream);
+    // the map passes (with no read they still see to the unitigs)
+    u64 mh[KMC_MAP_WORDS] = {0}, ns = 0, nu = 0;
+    if ((rc = map_run(c, what, min_count, max_count, d_bases, d_offsets, n_reads, n_bases, mh, &ns, &nu))) return rc;
+    if (accumulate && !c->pr_key.holds(c->view_gen, min_count, max_count))
+        return fail(c, KMC_ERR_HIP, "internal error: %s computed the unitigs under a held pairs result", what);
+    if (nu > (1ull << 30)) return fail(c, KMC_ERR_CAPACITY, "%s: more than 2^30 unitigs", what);
+    if (accumulate && n_reads == 0) return KMC_OK;   // nothing to add: the held result as it stands, its pointers included
+    int end_bits = 5;   // (ten key bits at least: what the sort's first level takes)
+    while ((1ull << end_bits) < 2 * nu) ++end_bits;
+    tr.mark(c->stream);
+    const u64 n_pairs = n_reads / 2, n_old = accumulate ? c->pr_records : 0, n_sort = n_pairs + n_old;
+    if (n_sort >= (1ull << 32) - (1ull << 24)) return fail(c, KMC_ERR_CAPACITY, "%s: 2^32 pairs and held records or more", what);
+    const int cur = c->pr_cur, nxt = cur ^ 1;
+    kmc_ull* ctl = (kmc_ull*)c->pr_ctl.p;
+    u64 w[KMC_P_CTL_WORDS] = {0};
+    HIPCHK(c, hipMemsetAsync(ctl, 0, KMC_P_CTL_WORDS * sizeof(u64), c->stream));
+    const size_t sb = (size_t)std::max<u64>(n_sort, 1) * sizeof(u64), pb = (size_t)std::max<u64>(n_pairs, 1);
+    if ((rc = ensure(c, c->pr_anchor, (size_t)std::max<u64>(n_reads, 1) * 16)) || (rc = ensure(c, c->pr_class, pb)) ||
+        (rc = ensure(c, c->pr_ends, pb * 2 * sizeof(u32))) || (rc = ensure(c, c->pr_value, pb * sizeof(u64))) ||
+        (rc = ensure(c, c->pr_sk[0], sb)) || (rc = ensure(c, c->pr_sk[1], sb)) || (rc = ensure(c, c->pr_sw[0], sb)) || (rc = ensure(c, c->pr_sw[1], sb)))
+        return rc;
+    // from here on the held result is in the making (the pair pass adds to the held histogram): an error leaves none
+    auto give_up = [&](int code) { c->pr_key.drop(); return code; };
+    auto hip_ok = [&](hipError_t e, const char* step) { return e == hipSuccess ? KMC_OK : give_up(fail(c, KMC_ERR_HIP, "%s: %s: %s", what, step, hipGetErrorString(e))); };
+    // KMC_PAIRS_GRID (diagnostic, read per call): at most this many workgroups for the pair and reduce passes, so that a test
+    // sends a small batch through many rounds of one workgroup
+    u64 max_grid = ~0ull;
+    if (const char* e = getenv("KMC_PAIRS_GRID")) max_grid = std::max<u64>(1, strtoull(e, nullptr, 10));
+    if (n_pairs) {
+        hipLaunchKernelGGL(kmc_pair_anchor_kernel, dim3((u32)((n_reads + KMC_P_THREADS - 1) / KMC_P_THREADS)), dim3(KMC_P_THREADS), 0, c->stream,
+                           (const u64*)c->m_soffs.p, (const uint4*)c->m_segs.p, n_reads, ns, (const u64*)c->u_offs.p, nu, c->klen, (uint4*)c->pr_anchor.p, ctl);
+        hipLaunchKernelGGL(kmc_pair_class_kernel, dim3((u32)std::min<u64>(grid_for(c, n_pairs, KMC_P_THREADS), max_grid)), dim3(KMC_P_THREADS), 0, c->stream,
+                           (const uint4*)c->pr_anchor.p, n_pairs, (const u64*)c->u_offs.p, nu, end_bits, n_bins, (uint8_t*)c->pr_class.p, (u32*)c->pr_ends.p,
+                           (u64*)c->pr_value.p, (u64*)c->pr_sk[0].p, (u64*)c->pr_sw[0].p, (kmc_ull*)c->pr_hist.p, ctl);
+        if ((rc = hip_ok(hipGetLastError(), "the pair passes"))) return rc;
+    }
+    if (n_old) {   // the held records: keys with their counts as weights
+        if ((rc = hip_ok(hipMemcpyAsync((u64*)c->pr_sk[0].p + n_pairs, c->pr_rkey[cur].p, (size_t)n_old * sizeof(u64), hipMemcpyDeviceToDevice, c->stream), "the held keys")) ||
+            (rc = hip_ok(hipMemcpyAsync((u64*)c->pr_sw[0].p + n_pairs, c->pr_rcount[cur].p, (size_t)n_old * sizeof(u64), hipMemcpyDeviceToDevice, c->stream), "the held counts")))
+            return rc;
+    }
+    tr.mark(c->stream);
+    kmc_ctx::Run run;
+    if (n_sort) {
+        u64* const klo[2] = {(u64*)c->pr_sk[0].p, (u64*)c->pr_sk[1].p};
+        u64* const kwt[2] = {(u64*)c->pr_sw[0].p, (u64*)c->pr_sw[1].p};
+        if ((rc = sort_keys_to_run(c, klo, kwt, n_sort, 2u * (unsigned)end_bits, &run))) return give_up(rc);
+    }
+    const u64 n_rec = run.n;
+    tr.mark(c->stream);
+    const size_t rb = (size_t)std::max<u64>(n_rec, 1) * sizeof(u64);
+    if ((rc = ensure(c, c->pr_rkey[nxt], rb)) || (rc = ensure(c, c->pr_rends[nxt], rb)) || (rc = ensure(c, c->pr_rcount[nxt], rb)) ||
+        (rc = ensure(c, c->pr_rsum[nxt], rb)) || (rc = ensure(c, c->pr_rmin[nxt], rb)) || (rc = ensure(c, c->pr_rmax[nxt], rb))) {
+        recycle_run(c, &run);
+        return give_up(rc);
+    }
+    if (n_rec) {
+        hipLaunchKernelGGL(kmc_pair_records_kernel, dim3((u32)((n_rec + KMC_P_THREADS - 1) / KMC_P_THREADS)), dim3(KMC_P_THREADS), 0, c->stream,
+                           (const u64*)run.lo, (const u64*)run.cnt, n_rec, end_bits, 2 * nu, (u64*)c->pr_rkey[nxt].p, (u32*)c->pr_rends[nxt].p,
+                           (u64*)c->pr_rcount[nxt].p, (u64*)c->pr_rsum[nxt].p, (u64*)c->pr_rmin[nxt].p, (u64*)c->pr_rmax[nxt].p, ctl);
+        auto go = [&](auto TABLE) {
+            hipLaunchKernelGGL(kmc_pair_reduce_kernel<TABLE()>, dim3((u32)std::min<u64>(grid_for(c, n_sort, KMC_P_THREADS), max_grid)), dim3(KMC_P_THREADS), 0, c->stream,
+                               (const uint8_t*)c->pr_class.p, (const u32*)c->pr_ends.p, (const u64*)c->pr_value.p, n_pairs, (const u64*)c->pr_rkey[cur].p,
+                               (const u64*)c->pr_rsum[cur].p, (const u64*)c->pr_rmin[cur].p, (const u64*)c->pr_rmax[cur].p, n_old, end_bits,
+                               (const u64*)c->pr_rkey[nxt].p, n_rec, (kmc_ull*)c->pr_rsum[nxt].p, (kmc_ull*)c->pr_rmin[nxt].p, (kmc_ull*)c->pr_rmax[nxt].p, ctl);
+        };
+        if (getenv("KMC_PAIRS_PLAIN") == nullptr) go(std::true_type{}); else go(std::false_type{});
+    }
+    hipLaunchKernelGGL(kmc_pair_hist_sum_kernel, dim3((u32)((n_bins + KMC_P_THREADS - 1) / KMC_P_THREADS)), dim3(KMC_P_THREADS), 0, c->stream,
+                       (const kmc_ull*)c->pr_hist.p, n_bins, ctl);
+    const hipError_t le = hipGetLastError();
+    recycle_run(c, &run);   // (stream order: the records kernel is queued before anything can reuse it)
+    if (le != hipSuccess) return give_up(fail(c, KMC_ERR_HIP, "%s: %s", what, hipGetErrorString(le)));
+    if (hipMemcpyAsync(w, ctl, sizeof(w), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
+        return give_up(fail(c, KMC_ERR_HIP, "%s: the pair passes failed", what));
+    tr.mark(c->stream);
+    if (w[KMC_P_BAD] || w[KMC_P_MISS])
+        return give_up(fail(c, KMC_ERR_HIP, "internal error: %s met %llu indices outside their arrays and %llu keys without a record", what,
+                            (unsigned long long)w[KMC_P_BAD], (unsigned long long)w[KMC_P_MISS]));
+    u64* s = c->pr_words;
+    s[0] += n_pairs;
+    for (int j = 0; j < 5; ++j) s[1 + j] += w[KMC_P_CLASS + j];
+    s[6] = n_rec; s[7] += w[KMC_P_SUMF];
+    // the identities of include/kmc.h
+    if (s[0] != s[1] + s[2] + s[3] + s[4] + s[5] || (n_rec ? w[KMC_P_RCOUNT] : 0) != s[2] || w[KMC_P_HIST] != s[3] || n_rec > s[2] || n_rec >= (1ull << 32))
+        return give_up(fail(c, n_rec >= (1ull << 32) ? KMC_ERR_CAPACITY : KMC_ERR_HIP,
+                            "%s: %llu records; internal error unless 2^32 or more: %llu pairs in classes %llu %llu %llu %llu %llu, counts %llu, histogram %llu", what,
+                            (unsigned long long)n_rec, (unsigned long long)s[0], (unsigned long long)s[1], (unsigned long long)s[2], (unsigned long long)s[3],
+                            (unsigned long long)s[4], (unsigned long long)s[5], (unsigned long long)w[KMC_P_RCOUNT], (unsigned long long)w[KMC_P_HIST]));
+    c->pr_cur = nxt;
+    c->pr_records = n_rec;
+    c->pr_bins = n_bins;
+    c->pr_key.keep(c->view_gen, min_count, max_count);
+    if (tr.on && tr.n_ev == 5) {
+        float ms[4] = {0, 0, 0, 0};
+        bool ok = hipEventSynchronize(tr.ev[4]) == hipSuccess;
+        for (int i = 0; ok && i < 4; ++i) ok = hipEventElapsedTime(&ms[i], tr.ev[i], tr.ev[i + 1]) == hipSuccess;
+        if (ok)
+            fprintf(stderr, "kmc_unitig_pairs: unitigs %llu pairs %llu span %llu proper %llu records %llu unitigs_reused %d "
+                    "map_ms %.4f anchor_ms %.4f sort_ms %.4f reduce_ms %.4f\n", (unsigned long long)nu, (unsigned long long)n_pairs,
+                    (unsigned long long)w[KMC_P_CLASS + KMC_PAIR_SPAN], (unsigned long long)w[KMC_P_CLASS + KMC_PAIR_PROPER], (unsigned long long)n_rec,
+                    kept ? 1 : 0, ms[0], ms[1], ms[2], ms[3]);
+    }
+    return KMC_OK;
+}
+
+static int kmc_unitig_pairs_device_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t n_bins, uint32_t flags, const void* d_bases,
+                                        const void* d_offsets, uint64_t n_reads, uint64_t n_bases, const void** d_pair_class,
+                                        const void** d_pair_ends, const void** d_pair_value, const void** d_rec_ends, const void** d_rec_count,
+                                        const void** d_rec_sum, const void** d_rec_min, const void** d_rec_max, const void** d_insert_hist,
+                                        uint64_t* n_pairs, uint64_t* n_records, uint64_t* summary) {
+    if (n_pairs) *n_pairs = 0;
+    if (n_records) *n_records = 0;
+    if (!c) return KMC_ERR_ARG;
+    const char* what = "kmc_unitig_pairs_device";
+    int rc;
+    if ((rc = map_begin(c, what, min_count, max_count)) || (rc = pairs_args(c, what, n_bins, flags, n_reads))) return rc;
+    if (n_reads && (rc = check_device_batch(c, what, d_bases, d_offsets))) return rc;
+    if ((rc = pairs_run(c, what, min_count, max_count, n_bins, (flags & KMC_PAIR_ACCUMULATE) != 0, (const uint8_t*)d_bases, (const u64*)d_offsets,
+                        n_reads, n_reads ? n_bases : 0)))
+        return rc;
+    const int cur = c->pr_cur;
+    if (d_pair_class) *d_pair_class = c->pr_class.p;
+    if (d_pair_ends) *d_pair_ends = c->pr_ends.p;
+    if (d_pair_value) *d_pair_value = c->pr_value.p;
+    if (d_rec_ends) *d_rec_ends = c->pr_rends[cur].p;
+    if (d_rec_count) *d_rec_count = c->pr_rcount[cur].p;
+    if (d_rec_sum) *d_rec_sum = c->pr_rsum[cur].p;
+    if (d_rec_min) *d_rec_min = c->pr_rmin[cur].p;
+    if (d_rec_max) *d_rec_max = c->pr_rmax[cur].p;
+    if (d_insert_hist) *d_insert_hist = c->pr_hist.p;
+    if (n_pairs) *n_pairs = n_reads / 2;
+    if (n_records) *n_records = c->pr_records;
+    if (summary) memcpy(summary, c->pr_words, sizeof(c->pr_words));
+    return KMC_OK;
+}
+
+static int kmc_unitig_pairs_impl(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t n_bins, uint32_t flags, const uint8_t* bases,
+                                 const uint64_t* offsets, uint64_t n_reads, uint8_t* pair_class, uint32_t* pair_ends, uint64_t* pair_value,
+                                 uint64_t cap_pairs, uint32_t* rec_ends, uint64_t* rec_count, uint64_t* rec_sum, uint64_t* rec_min, uint64_t* rec_max,
+                                 uint64_t cap_records, uint64_t* insert_hist, uint64_t cap_bins, uint64_t* n_pairs, uint64_t* n_records,
+                                 uint64_t* summary) {
+    if (n_pairs) *n_pairs = 0;
+    if (n_records) *n_records = 0;
+    if (!c) return KMC_ERR_ARG;
+    const char* what = "kmc_unitig_pairs";
+    int rc;
+    if ((rc = map_begin(c, what, min_count, max_count)) || (rc = pairs_args(c, what, n_bins, flags, n_reads))) return rc;
+    u64 n_bases = 0;
+    if (n_reads && (rc = stage_batch(c, what, bases, offsets, n_reads, true, &n_bases))) return rc;
+    if ((rc = pairs_run(c, what, min_count, max_count, n_bins, (flags & KMC_PAIR_ACCUMULATE) != 0, (const uint8_t*)c->q_bases.p,
+                        (const u64*)c->q_offs.p, n_reads, n_bases)))
+        return rc;
+    const u64 np = n_reads / 2, nr = c->pr_records;
+    const int cur = c->pr_cur;
+    if (n_pairs) *n_pairs = np;
+    if (n_records) *n_records = nr;
+    if ((pair_class || pair_ends || pair_value) && cap_pairs < np)
+        return fail(c, KMC_ERR_ARG, "%s: capacity %llu < %llu pairs", what, (unsigned long long)cap_pairs, (unsigned long long)np);
+    if ((rec_ends || rec_count || rec_sum || rec_min || rec_max) && cap_records < nr)
+        return fail(c, KMC_ERR_ARG, "%s: capacity %llu < %llu records", what, (unsigned long long)cap_records, (unsigned long long)nr);
+    if (insert_hist && cap_bins < n_bins) return fail(c, KMC_ERR_ARG, "%s: capacity %llu < %llu bins", what, (unsigned long long)cap_bins, (unsigned long long)n_bins);
+    auto down = [&](void* dst, const DevBuf& src, size_t bytes) {
+        return dst && bytes ? hipMemcpyAsync(dst, src.p, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+    };
+    HIPCHK(c, down(pair_class, c->pr_class, (size_t)np));
+    HIPCHK(c, down(pair_ends, c->pr_ends, (size_t)np * 2 * sizeof(u32)));
+    HIPCHK(c, down(pair_value, c->pr_value, (size_t)np * sizeof(u64)));
+    HIPCHK(c, down(rec_ends, c->pr_rends[cur], (size_t)nr * 2 * sizeof(u32)));
+    HIPCHK(c, down(rec_count, c->pr_rcount[cur], (size_t)nr * sizeof(u64)));
+    HIPCHK(c, down(rec_sum, c->pr_rsum[cur], (size_t)nr * sizeof(u64)));
+    HIPCHK(c, down(rec_min, c->pr_rmin[cur], (size_t)nr * sizeof(u64)));
+    HIPCHK(c, down(rec_max, c->pr_rmax[cur], (size_t)nr * sizeof(u64)));
+    HIPCHK(c, down(insert_hist, c->pr_hist, (size_t)n_bins * sizeof(u64)));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (summary) memcpy(summary, c->pr_words, sizeof(c->pr_words));
     return KMC_OK;
 }
 
@@ -2640,6 +2850,26 @@ extern "C" int kmc_unitig_transits_device(kmc_ctx* c, uint64_t min_count, uint64
     return guarded(c, [&]() -> int {
         return kmc_unitig_transits_device_impl(c, min_count, max_count, min_reads, flags, d_bases, d_offsets, n_reads, n_bases, d_link_support,
                                                d_transit_offsets, d_transit_count, d_verdict, n_unitigs, n_links, n_slots, summary);
+    });
+}
+extern "C" int kmc_unitig_pairs_device(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t n_bins, uint32_t flags, const void* d_bases,
+                                       const void* d_offsets, uint64_t n_reads, uint64_t n_bases, const void** d_pair_class, const void** d_pair_ends,
+                                       const void** d_pair_value, const void** d_rec_ends, const void** d_rec_count, const void** d_rec_sum,
+                                       const void** d_rec_min, const void** d_rec_max, const void** d_insert_hist, uint64_t* n_pairs,
+                                       uint64_t* n_records, uint64_t* summary) {
+    return guarded(c, [&] {
+        return kmc_unitig_pairs_device_impl(c, min_count, max_count, n_bins, flags, d_bases, d_offsets, n_reads, n_bases, d_pair_class, d_pair_ends,
+                                            d_pair_value, d_rec_ends, d_rec_count, d_rec_sum, d_rec_min, d_rec_max, d_insert_hist, n_pairs, n_records, summary);
+    });
+}
+extern "C" int kmc_unitig_pairs(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t n_bins, uint32_t flags, const uint8_t* bases,
+                                const uint64_t* offsets, uint64_t n_reads, uint8_t* pair_class, uint32_t* pair_ends, uint64_t* pair_value,
+                                uint64_t cap_pairs, uint32_t* rec_ends, uint64_t* rec_count, uint64_t* rec_sum, uint64_t* rec_min, uint64_t* rec_max,
+                                uint64_t cap_records, uint64_t* insert_hist, uint64_t cap_bins, uint64_t* n_pairs, uint64_t* n_records,
+                                uint64_t* summary) {
+    return guarded(c, [&] {
+        return kmc_unitig_pairs_impl(c, min_count, max_count, n_bins, flags, bases, offsets, n_reads, pair_class, pair_ends, pair_value, cap_pairs,
+                                     rec_ends, rec_count, rec_sum, rec_min, rec_max, cap_records, insert_hist, cap_bins, n_pairs, n_records, summary);
     });
 }
 extern "C" int kmc_unitig_transits(kmc_ctx* c, uint64_t min_count, uint64_t max_count, uint64_t min_reads, uint32_t flags, const uint8_t* bases,

@@ -44,6 +44,14 @@ pub const KMC_TRANSIT_UNSPANNED: u8 = 1;
 pub const KMC_TRANSIT_RESOLVED: u8 = 2;
 pub const KMC_TRANSIT_AMBIGUOUS: u8 = 3;
 pub const KMC_TRANSIT_ACCUMULATE: u32 = 1;
+/// summary words of `kmc_unitig_pairs`, a pair's class byte, the flag that adds onto the held result
+pub const KMC_PAIR_WORDS: usize = 8;
+pub const KMC_PAIR_UNPLACED: u8 = 0;
+pub const KMC_PAIR_SPAN: u8 = 1;
+pub const KMC_PAIR_PROPER: u8 = 2;
+pub const KMC_PAIR_EVERTED: u8 = 3;
+pub const KMC_PAIR_SAME_STRAND: u8 = 4;
+pub const KMC_PAIR_ACCUMULATE: u32 = 1;
 /// summary words of `kmc_unitig_contigs`
 pub const KMC_CONTIG_WORDS: usize = 8;
 /// summary words of `kmc_correct`, words per read of its `read_stats`, the kinds of a candidate
@@ -211,6 +219,8 @@ extern "C" {
     pub fn kmc_unitig_map(ctx: *mut KmcCtx, min_count: u64, max_count: u64, bases: *const u8, offsets: *const u64, n_reads: u64, place: *mut u64, read_stats: *mut u32, seg_offsets: *mut u64, segs: *mut u32, cap_segs: u64, support: *mut u64, cap_unitigs: u64, n_segs: *mut u64, n_unitigs: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_transits_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, min_reads: u64, flags: u32, d_bases: *const c_void, d_offsets: *const c_void, n_reads: u64, n_bases: u64, d_link_support: *mut *const c_void, d_transit_offsets: *mut *const c_void, d_transit_count: *mut *const c_void, d_verdict: *mut *const c_void, n_unitigs: *mut u64, n_links: *mut u64, n_slots: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_transits(ctx: *mut KmcCtx, min_count: u64, max_count: u64, min_reads: u64, flags: u32, bases: *const u8, offsets: *const u64, n_reads: u64, link_support: *mut u64, cap_links: u64, transit_offsets: *mut u64, cap_unitigs: u64, transit_count: *mut u64, cap_slots: u64, verdict: *mut u8, n_unitigs: *mut u64, n_links: *mut u64, n_slots: *mut u64, summary: *mut u64) -> c_int;
+    pub fn kmc_unitig_pairs_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, n_bins: u64, flags: u32, d_bases: *const c_void, d_offsets: *const c_void, n_reads: u64, n_bases: u64, d_pair_class: *mut *const c_void, d_pair_ends: *mut *const c_void, d_pair_value: *mut *const c_void, d_rec_ends: *mut *const c_void, d_rec_count: *mut *const c_void, d_rec_sum: *mut *const c_void, d_rec_min: *mut *const c_void, d_rec_max: *mut *const c_void, d_insert_hist: *mut *const c_void, n_pairs: *mut u64, n_records: *mut u64, summary: *mut u64) -> c_int;
+    pub fn kmc_unitig_pairs(ctx: *mut KmcCtx, min_count: u64, max_count: u64, n_bins: u64, flags: u32, bases: *const u8, offsets: *const u64, n_reads: u64, pair_class: *mut u8, pair_ends: *mut u32, pair_value: *mut u64, cap_pairs: u64, rec_ends: *mut u32, rec_count: *mut u64, rec_sum: *mut u64, rec_min: *mut u64, rec_max: *mut u64, cap_records: u64, insert_hist: *mut u64, cap_bins: u64, n_pairs: *mut u64, n_records: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_contigs_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, min_reads: u64, min_support: u64, d_bases: *mut *const c_void, d_offsets: *mut *const c_void, d_path_offsets: *mut *const c_void, d_path: *mut *const c_void, d_abund: *mut *const c_void, d_flags: *mut *const c_void, n_contigs: *mut u64, n_nodes: *mut u64, n_bases: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_unitig_contigs(ctx: *mut KmcCtx, min_count: u64, max_count: u64, min_reads: u64, min_support: u64, bases: *mut u8, cap_bases: u64, offsets: *mut u64, path_offsets: *mut u64, abund: *mut u64, flags: *mut u8, cap_contigs: u64, path: *mut u32, cap_nodes: u64, n_contigs: *mut u64, n_nodes: *mut u64, n_bases: *mut u64, summary: *mut u64) -> c_int;
     pub fn kmc_correct_device(ctx: *mut KmcCtx, min_count: u64, max_count: u64, d_bases: *const c_void, d_offsets: *const c_void, n_reads: u64, n_bases: u64, d_corrected: *mut *const c_void, d_read_stats: *mut *const c_void, d_cand_offsets: *mut *const c_void, d_cands: *mut *const c_void, n_cands: *mut u64, summary: *mut u64) -> c_int;
@@ -569,6 +579,46 @@ impl Counter {
         })?;
         count.truncate(nsl as usize);
         Ok((support, transit_offsets, count, verdict, w))
+    }
+
+    /// The pair evidence of a batch of interleaved mates (`kmc_unitig_pairs`; reads 2i and 2i + 1 are pair i, forward /
+    /// reverse; the batch is not counted).  Returns per pair the class (`KMC_PAIR_*`), the two out ends and the value (R of a
+    /// SPAN pair, the insert size of a PROPER one), per record in ascending (a, b) the two ends, count, sum, min and max of R,
+    /// the insert histogram of `n_bins` bins (the last one open) and the eight summary words [pairs, unplaced, span, proper,
+    /// everted, same strand, records, sum of the insert sizes].  `accumulate` adds the records, the histogram and the words
+    /// onto the result of the last call for this range and `n_bins` (the first batch goes without it).  `held_records` is the
+    /// number of records the last call returned (0 without `accumulate`): there are at most that many more than pairs.
+    #[allow(clippy::type_complexity)]
+    pub fn pairs(&mut self, bases: &[u8], offsets: &[u64], min_count: u64, max_count: u64, n_bins: u64, accumulate: bool, held_records: u64)
+                 -> Result<(Vec<u8>, Vec<u32>, Vec<u64>, Vec<u32>, Vec<u64>, Vec<u64>, Vec<u64>, Vec<u64>, Vec<u64>, [u64; KMC_PAIR_WORDS]), KmcError> {
+        let (mut nd, mut nt) = (0u64, 0u64);
+        self.check(unsafe { kmc_finalize(self.ctx, &mut nd, &mut nt) })?;
+        let n_reads = offsets.len().saturating_sub(1);
+        if n_reads > 0 && offsets[n_reads] as usize != bases.len() {
+            return Err(KmcError(-1, "offsets do not end at the number of bases".into()));
+        }
+        let cap_pairs = (n_reads / 2) as u64;
+        let cap_records = cap_pairs + if accumulate { held_records } else { 0 };
+        let mut class = vec![0u8; cap_pairs as usize];
+        let mut ends = vec![0u32; 2 * cap_pairs as usize];
+        let mut value = vec![0u64; cap_pairs as usize];
+        let mut rec_ends = vec![0u32; 2 * cap_records as usize];
+        let mut rec = [vec![0u64; cap_records as usize], vec![0u64; cap_records as usize], vec![0u64; cap_records as usize], vec![0u64; cap_records as usize]];
+        let mut hist = vec![0u64; n_bins as usize];
+        let (mut np, mut nr) = (0u64, 0u64);
+        let mut w = [0u64; KMC_PAIR_WORDS];
+        let [rc, rs, rn, rx] = &mut rec;
+        self.check(unsafe {
+            kmc_unitig_pairs(self.ctx, min_count, max_count, n_bins, if accumulate { KMC_PAIR_ACCUMULATE } else { 0 }, bases.as_ptr(), offsets.as_ptr(),
+                             n_reads as u64, class.as_mut_ptr(), ends.as_mut_ptr(), value.as_mut_ptr(), cap_pairs, rec_ends.as_mut_ptr(), rc.as_mut_ptr(),
+                             rs.as_mut_ptr(), rn.as_mut_ptr(), rx.as_mut_ptr(), cap_records, hist.as_mut_ptr(), n_bins, &mut np, &mut nr, w.as_mut_ptr())
+        })?;
+        rec_ends.truncate(2 * nr as usize);
+        let [mut rc, mut rs, mut rn, mut rx] = rec;
+        for v in [&mut rc, &mut rs, &mut rn, &mut rx] {
+            v.truncate(nr as usize);
+        }
+        Ok((class, ends, value, rec_ends, rc, rs, rn, rx, hist, w))
     }
 
     /// The contigs of the counted walks (`kmc_unitig_contigs`): behind a `transits` call of the same range, every repeat its
